@@ -15,6 +15,12 @@ Workload = configs[1] (configs[2] when N > 1, same job sharded): 1M synthetic pr
 value = 64-bit Hamming comparisons/s over the whole step (8 x 10^12 comparisons per step; the
 build time is inside the denominator); images hashed/s is reported next to it.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the --steps steps and prints the line (with the per-kernel figures of the
+timed steps' own events).  --full adds everything else beside the line: the configs[3] / configs[4] legs, the
+popcount kernel and the bucketed join on the same sweep, the single-process sharded leg, the indexer stages, the
+CPU baseline with the identity checks, the expected-result tables and the per-rank residency.
+--dump-outputs DIR writes what the last timed step computed as DIR/*.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -69,6 +75,11 @@ def parse():
                     help="skip the single-process leg (ONE DctHashIndex handle over all GPUs: cbh_idx64_create_sharded)")
     ap.add_argument("--no-features", action="store_true",
                     help="skip the indexer-stage leg (ORB, ColorDescriptor::create; reported beside the contract line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs, baselines and checks beside the contract line "
+                         "(the --no-* options pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (float64, <= 64 MB)")
     return ap.parse_args()
 
 
@@ -224,6 +235,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if share else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:  # (every rank holds all hashes and the results of all needles)
+        dump_outputs(args.dump_outputs, torch, state, dhts, n, args.topk)
 
     # ---- per-kernel figures from the events recorded inside the timed region (this rank) --------
     torch.cuda.synchronize()
@@ -360,11 +373,11 @@ def main():
         except Exception:
             pass
 
-    if not args.no_video:
+    if args.full and not args.no_video:
         result["configs4_video"] = video_leg(args, torch, dist, dev, local_rank, rank, world, share)
-    if not args.no_orb:
+    if args.full and not args.no_orb:
         result["configs3_cvfeatures"] = cvfeatures_leg(args, torch, dist, dev, local_rank, rank, world, share)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # outside the timed region, for the record: the same launches on the popcount (VALU) kernel
         # k_hamm64_scan that the matrix-core kernel replaced (identical records; tests/test_gpu_hamm.py)
         import ctypes as C
@@ -384,7 +397,7 @@ def main():
         finally:
             ops.L.cbh_set_tuning(b"scan_mfma", 1)
         result["popcount_kernel_scan_ms"] = pop
-    if world == 1 and all(1 <= d <= 8 for d in dhts) and float(n) * float(n) * 8.8e-12 >= 1.0:  # (the join is only asked where
+    if args.full and world == 1 and all(1 <= d <= 8 for d in dhts) and float(n) * float(n) * 8.8e-12 >= 1.0:  # (the join is only asked where
         # a scan takes >= 1 ms)
         # Beside the contract line, never part of `value`: the same sweep with "scan_mfma" 3 -- thresholds <= 8 answered by the
         # bucketed join (hamm64_join.hip: multi-index hashing; only pairs that share one of max(4, dht) chunk values are
@@ -421,18 +434,19 @@ def main():
         finally:
             ops.L.cbh_set_tuning(b"scan_mfma", 1)
         result["bucketed_join"] = jl
-    exp = EXPECTED_MATCHES.get((n, args.seed))
-    got_matches = {s_["dht"]: s_["matches"] for s_ in sweep}
-    result["matches_expected"] = None if exp is None or any(d not in exp for d in dhts) else \
-        all(got_matches[d] == exp[d] for d in dhts)
-    if exp is not None and result["matches_expected"] is False:
-        result["matches_expected_table"] = {str(d): exp.get(d) for d in dhts}
-    if rank == 0 and (n, args.seed) in EXPECTED_HASH_SHA256:  # every rank holds all hashes (gather_hashes)
+    if args.full:
+        exp = EXPECTED_MATCHES.get((n, args.seed))
+        got_matches = {s_["dht"]: s_["matches"] for s_ in sweep}
+        result["matches_expected"] = None if exp is None or any(d not in exp for d in dhts) else \
+            all(got_matches[d] == exp[d] for d in dhts)
+        if exp is not None and result["matches_expected"] is False:
+            result["matches_expected_table"] = {str(d): exp.get(d) for d in dhts}
+    if args.full and rank == 0 and (n, args.seed) in EXPECTED_HASH_SHA256:  # every rank holds all hashes (gather_hashes)
         import hashlib
 
         result["hashes_expected"] = hashlib.sha256(
             state["hashes"].cpu().numpy().tobytes()).hexdigest() == EXPECTED_HASH_SHA256[(n, args.seed)]
-    if dist.is_initialized():
+    if args.full and dist.is_initialized():
         # the transport's own view of the job: how many ranks the communicator spans (a sum of ones through it) and
         # which library carried it
         ones = torch.ones(1, dtype=torch.int32, device="cpu" if share else dev)
@@ -445,7 +459,7 @@ def main():
                 result["collective"]["rccl_version"] = ".".join(str(x) for x in torch.cuda.nccl.version())
             except Exception as e:  # the version query is informative only
                 result["collective"]["rccl_version"] = repr(e)[:80]
-    if world > 1:
+    if args.full and world > 1:
         # what every rank actually holds: its share of the images / index slots / descriptor rows, never another's
         mine = {"rank": rank, "device": local_rank, "images": b - a, "image_bytes": int(imgs.numel()),
                 "index_slots": int(ops.index.count()),
@@ -454,11 +468,11 @@ def main():
         parts = [None] * world
         dist.all_gather_object(parts, mine)
         result["per_rank_residency"] = parts
-    if rank == 0 and not args.no_sharded_leg:
+    if args.full and rank == 0 and not args.no_sharded_leg:
         result["single_process_sharded"] = sharded_leg(args, world, local_rank, share)
-    if rank == 0 and world == 1 and not args.no_features:
+    if args.full and rank == 0 and world == 1 and not args.no_features:
         result["indexer_stages"] = features_leg(torch, dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args, torch, imgs, state, n, dhts, sh, ops)
         # north_star's acceptance line, as fields of the contract line: every needle's full (mediaId, distance) list
         # equal to the real VP-tree's, every hash equal to the CPU port's
@@ -494,6 +508,42 @@ def _flush_c_stdio():
         ctypes.CDLL(None).fflush(None)
     except Exception:
         pass
+
+
+def dump_outputs(path, torch, state, dhts, n, k):
+    """--dump-outputs: what the timed path hands its caller in the last timed step, as float64 .npy files (every value
+    exact), 64 MB at most.  Beyond 2^20 images or 32768 needles the rows are a fixed sample, the same for the same
+    arguments:
+        images.npy         [mh]      indices of the images whose hashes follow
+        hashes.npy         [mh, 2]   their dctHash64 as (high 32 bits, low 32 bits)
+        needles.npy        [m]       indices of the needles whose find results follow
+        dht<d>_ids.npy     [m, k]    per threshold d: mediaIds of the first k matches, in (distance, mediaId) order,
+        dht<d>_scores.npy  [m, k]    and their distances; -1 past the needle's count
+        dht<d>_counts.npy  [m]       matches of the needle before the cut at k"""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(20241016)
+    dev = state["hashes"].device
+
+    def rows(m):
+        return np.arange(n) if m >= n else np.sort(rng.choice(n, m, replace=False))
+
+    img = rows(min(n, 1 << 20))
+    h = state["hashes"][torch.from_numpy(img).to(dev)].cpu().numpy().view(np.uint64)
+    per_needle = 8 + len(dhts) * (8 + 16 * k)
+    m = min(n, 32768, max(1, (63_000_000 - 24 * len(img)) // per_needle))
+    ndl = rows(m)
+    out = {"images": img, "hashes": np.stack([h >> np.uint64(32), h & np.uint64(0xFFFFFFFF)], 1), "needles": ndl}
+    sel = torch.from_numpy(ndl).to(dev)
+    for d in dhts:
+        ids, scores, counts = (t[sel].contiguous().cpu().numpy() for t in state[d])
+        past = np.arange(ids.shape[1]).reshape(1, -1) >= counts.reshape(-1, 1)
+        out[f"dht{d}_ids"] = np.where(past, -1, ids.view(np.uint32).astype(np.int64))
+        out[f"dht{d}_scores"] = np.where(past, -1, scores)
+        out[f"dht{d}_counts"] = counts
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, np.float64))
 
 
 def sharded_leg(args, world, local_rank, share):

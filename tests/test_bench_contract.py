@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_keys(gpu):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--images", "40000", "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--images", "40000", "--steps", "2",
                           "--warmup", "1", "--cpu-seconds", "2", "--orb-images", "4000"], capture_output=True, text=True,
                          timeout=600,
                          cwd=ROOT)
@@ -53,7 +53,7 @@ def test_bench_two_ranks_sharing_the_gpu(gpu):
     import json
 
     env = dict(os.environ, CBH_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    args = ["--images", "60000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--dht", "2,5,8", "--orb-images",
+    args = ["--full", "--images", "60000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--dht", "2,5,8", "--orb-images",
             "3000", "--video-clips", "2000"]
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True,
                          timeout=600, env=env)
@@ -81,7 +81,7 @@ def test_bench_eight_ranks_preflight(gpu):
     rank holds another rank's data (its images, index slots and descriptor rows are exactly its shard_range share)."""
     env = dict(os.environ, CBH_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     n, orb = 80001, 4001  # ragged on purpose: 80001 = 8 * 10000 + 1
-    args = ["--images", str(n), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-features", "--no-sharded-leg",
+    args = ["--full", "--images", str(n), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-features", "--no-sharded-leg",
             "--dht", "2,5,8", "--orb-images", str(orb), "--video-clips", "2000"]
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True,
                          timeout=600, env=env)
@@ -109,3 +109,56 @@ def test_bench_eight_ranks_preflight(gpu):
         # images + hashes + exchange blocks + leg scratch: nowhere near a second rank's 655 MB of images
         assert p["device_bytes_allocated_by_torch"] < 1.6 * p["image_bytes"] + (256 << 20)
     assert sum(p["images"] for p in res) == n and sum(p["orb_rows"] for p in res) == orb * 500
+
+
+def test_bench_options():
+    """--full (the legs beside the contract line) and --dump-outputs are options of bench.py"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                         timeout=60, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert "--full" in out.stdout and "--dump-outputs DIR" in out.stdout
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(gpu, orc, tmp_path):
+    """A plain run prints the contract line without the legs and checks of --full; --dump-outputs writes the hashes and
+    the find results of the last timed step, the same for any --steps, equal to the oracle's on a sample of needles"""
+    import numpy as np
+
+    n, dhts, k = 30000, (2, 5, 8), 8  # (n <= 32768: every image and every needle is in the dump)
+    lines, dumps = [], []
+    for steps in (1, 3):
+        d = tmp_path / f"steps{steps}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--images", str(n), "--steps", str(steps),
+                              "--warmup", "1", "--dht", ",".join(map(str, dhts)), "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        found = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(found) == 1
+        lines.append(json.loads(found[0]))
+        dumps.append({f.name[:-4]: np.load(f) for f in d.iterdir()})
+    for steps, r in zip((1, 3), lines):
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in r, key
+        assert r["steps"] == steps and r["higher_is_better"] is True
+        assert abs(r["value"] - float(n) ** 2 * len(dhts) / (r["ms_per_step"] * 1e-3)) / r["value"] < 1e-6
+        for key in ("cpu_baseline", "full_identity", "hash_identity", "configs3_cvfeatures", "configs4_video",
+                    "popcount_kernel_scan_ms", "bucketed_join", "single_process_sharded", "indexer_stages",
+                    "matches_expected", "hashes_expected"):
+            assert key not in r, key
+    a, b = dumps
+    names = ["images", "hashes", "needles"] + [f"dht{d}_{x}" for d in dhts for x in ("ids", "scores", "counts")]
+    assert sorted(a) == sorted(b) == sorted(names)
+    assert all(v.dtype == np.float64 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64e6
+    assert all(np.array_equal(a[x], b[x]) for x in names)
+    assert (a["images"] == np.arange(n)).all() and (a["needles"] == np.arange(n)).all()
+    h = (a["hashes"][:, 0].astype(np.uint64) << np.uint64(32)) | a["hashes"][:, 1].astype(np.uint64)
+    ids = np.arange(1, n + 1, dtype=np.uint32)
+    sample = np.random.default_rng(0).choice(n, 512, replace=False)
+    for d, s in zip(dhts, lines[1]["dht_sweep"]):
+        assert s["dht"] == d and a[f"dht{d}_counts"].sum() == s["matches"]
+        wi, ws, wc = orc.find64_batch(h, ids, h[sample], d, k)
+        past = np.arange(k).reshape(1, -1) >= wc.reshape(-1, 1)
+        assert (a[f"dht{d}_counts"][sample] == wc).all()
+        assert (a[f"dht{d}_ids"][sample] == np.where(past, -1, wi.astype(np.int64))).all()
+        assert (a[f"dht{d}_scores"][sample] == np.where(past, -1, ws)).all()

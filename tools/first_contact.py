@@ -116,7 +116,7 @@ def main():
         if not multi:
             e["CBH_BENCH_SHARE_GPU"] = "1"  # ranks share the one GPU over gloo: a rehearsal of the launch only
         cmd = [py, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
-               "--master-port", str(29600 + n), "bench.py", "--gpus", str(n), "--images", "80000", "--steps", "2",
+               "--master-port", str(29600 + n), "bench.py", "--full", "--gpus", str(n), "--images", "80000", "--steps", "2",
                "--warmup", "1", "--no-video", "--no-orb", "--no-sharded-leg"]
         rc, out, err, dt = run(cmd, 420, e)
         j = last_json(out) or {}
