@@ -8,6 +8,8 @@
 //   sizeLongestSide(cvGray, 400)                              prestage.hip (Lanczos-4)           (:876)
 //   makeKeyPoints / makeKeyPointDescriptors                   orb.hip                            (:878-884)
 //   makeKeyPointHashes on the keypoints compute() left        dcthash.hip (k_kp_hashes)          (:886-889)
+// With mirror_mask (cbh_index_images_views) the grey step is mirror.hip's k_gray_views, which writes the views of each
+// uploaded image, and the stages after it run on those V planes per image.
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -21,7 +23,7 @@
 #include "cbh_index.h"
 
 static int index_images_one(const uint8_t* imgs, size_t n, int w, int h, size_t row_stride, size_t img_stride,
-                            int channels, const cbh_index_params* p, uint64_t* dct_hashes, int32_t* rects,
+                            int channels, int mirror_mask, const cbh_index_params* p, uint64_t* dct_hashes, int32_t* rects,
                             int32_t* resized_dims, uint32_t* kp_counts, cbh_keypoint* kp, uint8_t* desc,
                             uint32_t* kph_counts, uint64_t* kp_hashes, uint8_t* color_descs, uint8_t* color_ok,
                             int device);
@@ -42,7 +44,7 @@ extern "C" int cbh_index_images(const uint8_t* imgs, size_t n, int w, int h, siz
   const bool split_ok = p && n >= 1024 && !(p->algos & 8) && (p->algos & 6) && imgs && img_stride > 0;
   const size_t T = split_ok ? std::min<size_t>((size_t)max_threads, n / 512) : 1;
   if (T <= 1)
-    return index_images_one(imgs, n, w, h, row_stride, img_stride, channels, p, dct_hashes, rects, resized_dims,
+    return index_images_one(imgs, n, w, h, row_stride, img_stride, channels, 0, p, dct_hashes, rects, resized_dims,
                             kp_counts, kp, desc, kph_counts, kp_hashes, color_descs, color_ok, device);
   std::vector<int> rc(T, CBH_OK);
   std::vector<std::thread> th;
@@ -50,7 +52,7 @@ extern "C" int cbh_index_images(const uint8_t* imgs, size_t n, int w, int h, siz
   for (size_t t = 0; t < T; ++t) {
     const size_t a = t * n / T, b = (t + 1) * n / T;
     th.emplace_back([&, t, a, b]() {
-      rc[t] = index_images_one(imgs + a * img_stride, b - a, w, h, row_stride, img_stride, channels, p,
+      rc[t] = index_images_one(imgs + a * img_stride, b - a, w, h, row_stride, img_stride, channels, 0, p,
                                dct_hashes ? dct_hashes + a : nullptr, rects ? rects + 4 * a : nullptr,
                                resized_dims ? resized_dims + 2 * a : nullptr, kp_counts ? kp_counts + a : nullptr,
                                kp ? kp + a * cap : nullptr, desc ? desc + a * cap * 32 : nullptr,
@@ -64,13 +66,25 @@ extern "C" int cbh_index_images(const uint8_t* imgs, size_t n, int w, int h, siz
   return CBH_OK;
 }
 
+// Engine::query's reflection search (src/engine.cpp:423-436): processImage of the needle and of Engine::mirrored(needle,
+// h, v) (:357-365) for the bits of mirrorMask, from one upload per chunk.  Runs whole (no threaded split): its results
+// are the same either way, and the colour leg would keep it whole anyway.
+extern "C" int cbh_index_images_views(const uint8_t* imgs, size_t n, int w, int h, size_t row_stride, size_t img_stride,
+                                      int channels, int mirror_mask, const cbh_index_params* p, uint64_t* dct_hashes,
+                                      int32_t* rects, int32_t* resized_dims, uint32_t* kp_counts, cbh_keypoint* kp,
+                                      uint8_t* desc, uint32_t* kph_counts, uint64_t* kp_hashes, uint8_t* color_descs,
+                                      uint8_t* color_ok, int device) {
+  return index_images_one(imgs, n, w, h, row_stride, img_stride, channels, mirror_mask, p, dct_hashes, rects,
+                          resized_dims, kp_counts, kp, desc, kph_counts, kp_hashes, color_descs, color_ok, device);
+}
+
 static int index_images_one(const uint8_t* imgs, size_t n, int w, int h, size_t row_stride, size_t img_stride,
-                            int channels, const cbh_index_params* p, uint64_t* dct_hashes, int32_t* rects,
+                            int channels, int mirror_mask, const cbh_index_params* p, uint64_t* dct_hashes, int32_t* rects,
                             int32_t* resized_dims, uint32_t* kp_counts, cbh_keypoint* kp, uint8_t* desc,
                             uint32_t* kph_counts, uint64_t* kp_hashes, uint8_t* color_descs, uint8_t* color_ok,
                             int device) {
   if (!cbh::device_usable(device)) return CBH_E_NODEVICE;
-  if (!p) return CBH_E_INVAL;
+  if (!p || mirror_mask < 0 || mirror_mask > 7) return CBH_E_INVAL;
   const bool a_dct = p->algos & 1, a_fdct = p->algos & 2, a_orb = p->algos & 4, a_color = p->algos & 8;
   const bool feats = a_fdct || a_orb;
   const int rs = p->resize_longest_side, cap = p->kp_cap;
@@ -85,7 +99,16 @@ static int index_images_one(const uint8_t* imgs, size_t n, int w, int h, size_t 
   // chunks of up to 8 GB of input (16384 images): the colour leg runs one lane per image, so its rate grows with the
   // chunk (0.43 s for anything up to 4096 images, 0.48 s for 16384)
   size_t per_chunk = std::max<size_t>(1, ((size_t)8192 << 20) / std::max(img_stride, span1));
-  per_chunk = std::min<size_t>(std::min(per_chunk, n), 16384);
+  // A reflection search (mirror_mask != 0) runs every stage on the V views of each uploaded image: result i*V + v.  The
+  // chunk shrinks by V so that the per-result buffers stay the size they have without views.
+  const size_t V = 1 + (size_t)__builtin_popcount((unsigned)mirror_mask);
+  const bool views = V > 1, color_views = views && a_color && channels != 1;
+  per_chunk = std::min<size_t>(std::min(std::max<size_t>(1, per_chunk / V), n), 16384 / V);
+  const size_t per_out = per_chunk * V;  // results per chunk
+  const size_t src_bytes = (per_chunk - 1) * img_stride + span1;
+  // the reflected colour images follow the upload in the same buffer: the colour leg takes one base and per-image offsets
+  const size_t cview_off = color_views ? (src_bytes + 255) & ~(size_t)255 : src_bytes;
+  const size_t cview_bytes = (size_t)w * h * channels;
   const size_t slot = feats ? (size_t)rs * rs + 16 : 0;  // room per image in the packed resize buffer
   uint8_t *d_src = nullptr, *d_gray = nullptr, *d_res = nullptr, *d_desc = nullptr, *d_cdesc = nullptr, *d_cok = nullptr;
   uint64_t *d_out = nullptr, *d_kph = nullptr;
@@ -119,23 +142,23 @@ static int index_images_one(const uint8_t* imgs, size_t n, int w, int h, size_t 
   CBH_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   CBH_TRY(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
   CBH_TRY(hipEventCreateWithFlags(&ev_up, hipEventDisableTiming));
-  CBH_TRY(cbh::malloc_async((void**)&d_src, (per_chunk - 1) * img_stride + span1, s));
-  if (channels != 1) CBH_TRY(cbh::malloc_async((void**)&d_gray, per_chunk * (size_t)w * h, s));
-  CBH_TRY(cbh::malloc_async((void**)&d_out, per_chunk * sizeof(uint64_t), s));
-  CBH_TRY(cbh::malloc_async((void**)&d_rects, per_chunk * 4 * sizeof(int), s));
+  CBH_TRY(cbh::malloc_async((void**)&d_src, cview_off + (color_views ? per_chunk * (V - 1) * cview_bytes : 0), s));
+  if (channels != 1 || views) CBH_TRY(cbh::malloc_async((void**)&d_gray, per_out * (size_t)w * h, s));
+  CBH_TRY(cbh::malloc_async((void**)&d_out, per_out * sizeof(uint64_t), s));
+  CBH_TRY(cbh::malloc_async((void**)&d_rects, per_out * 4 * sizeof(int), s));
   if (feats) {
-    CBH_TRY(cbh::malloc_async((void**)&d_res, 2 * per_chunk * slot, s));  // the chunk-wide pass + the odd images redone
-    CBH_TRY(cbh::malloc_async((void**)&d_kp, per_chunk * (size_t)cap * sizeof(cbh_keypoint), s));
-    CBH_TRY(cbh::malloc_async((void**)&d_cnt, per_chunk * sizeof(uint32_t), s));
+    CBH_TRY(cbh::malloc_async((void**)&d_res, 2 * per_out * slot, s));  // the chunk-wide pass + the odd images redone
+    CBH_TRY(cbh::malloc_async((void**)&d_kp, per_out * (size_t)cap * sizeof(cbh_keypoint), s));
+    CBH_TRY(cbh::malloc_async((void**)&d_cnt, per_out * sizeof(uint32_t), s));
     if (a_orb) {
-      CBH_TRY(cbh::malloc_async((void**)&d_after, per_chunk * (size_t)cap * 2 * sizeof(float), s));
-      CBH_TRY(cbh::malloc_async((void**)&d_desc, per_chunk * (size_t)cap * 32, s));
+      CBH_TRY(cbh::malloc_async((void**)&d_after, per_out * (size_t)cap * 2 * sizeof(float), s));
+      CBH_TRY(cbh::malloc_async((void**)&d_desc, per_out * (size_t)cap * 32, s));
     }
-    if (a_fdct) CBH_TRY(cbh::malloc_async((void**)&d_kph, per_chunk * (size_t)cap * sizeof(uint64_t), s));
+    if (a_fdct) CBH_TRY(cbh::malloc_async((void**)&d_kph, per_out * (size_t)cap * sizeof(uint64_t), s));
   }
   if (a_color && channels != 1) {
-    CBH_TRY(cbh::malloc_async((void**)&d_cdesc, per_chunk * 258, s));
-    CBH_TRY(cbh::malloc_async((void**)&d_cok, per_chunk, s));
+    CBH_TRY(cbh::malloc_async((void**)&d_cdesc, per_out * 258, s));
+    CBH_TRY(cbh::malloc_async((void**)&d_cok, per_out, s));
   }
   const bool trace = getenv("CBH_PIPELINE_TRACE") != nullptr;  // stage times of each chunk on stderr
   auto now = [] { return std::chrono::steady_clock::now(); };
@@ -147,20 +170,26 @@ static int index_images_one(const uint8_t* imgs, size_t n, int w, int h, size_t 
     fprintf(stderr, "[cbh_index_images] %-18s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t - t_last).count());
     t_last = t;
   };
-  std::vector<int> hr(per_chunk * 4);
-  std::vector<uint64_t> off(per_chunk), coff(per_chunk);
-  std::vector<uint32_t> ws(per_chunk), hs(per_chunk), cw(per_chunk, (uint32_t)w), chh(per_chunk, (uint32_t)h),
-      cst(per_chunk, (uint32_t)row_stride), cnt(per_chunk), kp_first(per_chunk + 1), out_first(per_chunk + 1);
+  std::vector<int> hr(per_out * 4);
+  std::vector<uint64_t> off(per_out), coff(per_out);
+  std::vector<uint32_t> ws(per_out), hs(per_out), cw(per_out, (uint32_t)w), chh(per_out, (uint32_t)h),
+      cst(per_out, (uint32_t)row_stride), cnt(per_out), kp_first(per_out + 1), out_first(per_out + 1);
   std::vector<cbh_keypoint> hkp;
   std::vector<float> hafter, tri;
   for (size_t i0 = 0; rc == CBH_OK && i0 < n; i0 += per_chunk) {
-    const size_t m = std::min(per_chunk, n - i0);
+    const size_t mu = std::min(per_chunk, n - i0);  // images uploaded
+    const size_t m = mu * V, o0 = i0 * V;            // results of the chunk, index of its first
     lap("(setup)");
-    CBH_TRY(hipMemcpyAsync(d_src, imgs + i0 * img_stride, (m - 1) * img_stride + span1, hipMemcpyHostToDevice, s));
+    CBH_TRY(hipMemcpyAsync(d_src, imgs + i0 * img_stride, (mu - 1) * img_stride + span1, hipMemcpyHostToDevice, s));
     lap("upload");
     const uint8_t* gray = d_src;
     size_t gs = row_stride, gi = img_stride;
-    if (channels != 1) {
+    if (views) {
+      rc = cbh_gray_views_dev(d_src, mu, w, h, row_stride, img_stride, channels, mirror_mask, d_gray,
+                              color_views ? d_src + cview_off : nullptr, device, s);
+      if (rc) break;
+      gray = d_gray, gs = (size_t)w, gi = (size_t)w * h;
+    } else if (channels != 1) {
       rc = cbh_bgr2gray_dev(d_src, m, w, h, row_stride, img_stride, channels, d_gray, device, s);
       if (rc) break;
       gray = d_gray, gs = (size_t)w, gi = (size_t)w * h;
@@ -173,20 +202,24 @@ static int index_images_one(const uint8_t* imgs, size_t n, int w, int h, size_t 
     color_rc = CBH_OK;
     if (a_color) {
       if (channels == 1) {
-        memset(color_descs + i0 * 258, 0, m * 258);
-        memset(color_ok + i0, 0, m);
+        memset(color_descs + o0 * 258, 0, m * 258);
+        memset(color_ok + o0, 0, m);
       } else {
         CBH_TRY(hipEventRecord(ev_up, s));
-        for (size_t i = 0; i < m; ++i) coff[i] = i * img_stride;
-        color_thread = std::thread([&, m, i0] {
+        for (size_t i = 0; i < mu; ++i)
+          for (size_t v = 0; v < V; ++v) {  // view 0 is the upload itself, the reflections were written behind it
+            coff[i * V + v] = v == 0 ? i * img_stride : cview_off + (i * (V - 1) + v - 1) * cview_bytes;
+            cst[i * V + v] = (uint32_t)(v == 0 ? row_stride : (size_t)w * channels);
+          }
+        color_thread = std::thread([&, m, o0] {
           cbh::DeviceGuard tg(device);
           hipError_t e = hipStreamWaitEvent(s2, ev_up, 0);
           if (e == hipSuccess)
             color_rc = cbh_color_descriptors_dev(d_src, m, coff.data(), cw.data(), chh.data(), cst.data(), channels, d_cdesc,
                                                  d_cok, device, s2);
           if (e == hipSuccess && color_rc == CBH_OK &&
-              ((e = hipMemcpyAsync(color_descs + i0 * 258, d_cdesc, m * 258, hipMemcpyDeviceToHost, s2)) != hipSuccess ||
-               (e = hipMemcpyAsync(color_ok + i0, d_cok, m, hipMemcpyDeviceToHost, s2)) != hipSuccess ||
+              ((e = hipMemcpyAsync(color_descs + o0 * 258, d_cdesc, m * 258, hipMemcpyDeviceToHost, s2)) != hipSuccess ||
+               (e = hipMemcpyAsync(color_ok + o0, d_cok, m, hipMemcpyDeviceToHost, s2)) != hipSuccess ||
                (e = hipStreamSynchronize(s2)) != hipSuccess))
             ;
           if (e != hipSuccess) {
@@ -207,7 +240,7 @@ static int index_images_one(const uint8_t* imgs, size_t n, int w, int h, size_t 
     } else {
       for (size_t i = 0; i < m; ++i) hr[i * 4] = hr[i * 4 + 1] = 0, hr[i * 4 + 2] = w, hr[i * 4 + 3] = h;
     }
-    if (rects) memcpy(rects + i0 * 4, hr.data(), m * 4 * sizeof(int));
+    if (rects) memcpy(rects + o0 * 4, hr.data(), m * 4 * sizeof(int));
     lap("gray + autocrop");
     // Launch plan for the per-geometry stages (hash, resize).  Runs of equal kept regions take one launch each; when
     // a few odd regions are scattered among images that share one region (photos: almost all keep the whole frame),
@@ -249,7 +282,7 @@ static int index_images_one(const uint8_t* imgs, size_t n, int w, int h, size_t 
         }
       }
       if (rc) break;
-      CBH_TRY(hipMemcpyAsync(dct_hashes + i0, d_out, m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+      CBH_TRY(hipMemcpyAsync(dct_hashes + o0, d_out, m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     }
     lap("dct hash");
     if (!feats) {
@@ -290,7 +323,7 @@ static int index_images_one(const uint8_t* imgs, size_t n, int w, int h, size_t 
     if (rc) break;
     lap("resize");
     if (resized_dims)
-      for (size_t i = 0; i < m; ++i) resized_dims[2 * (i0 + i)] = (int)ws[i], resized_dims[2 * (i0 + i) + 1] = (int)hs[i];
+      for (size_t i = 0; i < m; ++i) resized_dims[2 * (o0 + i)] = (int)ws[i], resized_dims[2 * (o0 + i) + 1] = (int)hs[i];
     // images the resize rejected get a 1x1 stand-in geometry: no pyramid level, no keypoints
     std::vector<uint32_t> ow(ws.begin(), ws.begin() + m), oh(hs.begin(), hs.begin() + m);
     for (size_t i = 0; i < m; ++i)
@@ -305,18 +338,18 @@ static int index_images_one(const uint8_t* imgs, size_t n, int w, int h, size_t 
     if (a_orb) {
       hafter.resize(m * (size_t)cap * 2);
       CBH_TRY(hipMemcpyAsync(hafter.data(), d_after, m * (size_t)cap * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
-      CBH_TRY(hipMemcpyAsync(desc + i0 * (size_t)cap * 32, d_desc, m * (size_t)cap * 32, hipMemcpyDeviceToHost, s));
+      CBH_TRY(hipMemcpyAsync(desc + o0 * (size_t)cap * 32, d_desc, m * (size_t)cap * 32, hipMemcpyDeviceToHost, s));
     }
     CBH_TRY(hipStreamSynchronize(s));
     lap("orb download");
     // the keypoint list as processImage holds it after makeKeyPointDescriptors (which rewrites pt) -- or as detected
     for (size_t i = 0; i < m; ++i) {
-      kp_counts[i0 + i] = cnt[i];
+      kp_counts[o0 + i] = cnt[i];
       const size_t c = std::min<size_t>(cnt[i], (size_t)cap);
       for (size_t j = 0; j < c; ++j) {
         cbh_keypoint k = hkp[i * cap + j];
         if (a_orb) k.x = hafter[2 * (i * cap + j)], k.y = hafter[2 * (i * cap + j) + 1];
-        kp[(i0 + i) * cap + j] = k;
+        kp[(o0 + i) * cap + j] = k;
       }
     }
     lap("keypoint lists");
@@ -326,7 +359,7 @@ static int index_images_one(const uint8_t* imgs, size_t n, int w, int h, size_t 
       for (size_t i = 0; i < m; ++i) {
         const size_t c = std::min<size_t>(cnt[i], (size_t)cap);
         for (size_t j = 0; j < c; ++j) {
-          const cbh_keypoint& k = kp[(i0 + i) * cap + j];
+          const cbh_keypoint& k = kp[(o0 + i) * cap + j];
           tri.push_back(k.x), tri.push_back(k.y), tri.push_back(k.size);
         }
         kp_first[i + 1] = (uint32_t)(tri.size() / 3);
@@ -342,8 +375,8 @@ static int index_images_one(const uint8_t* imgs, size_t n, int w, int h, size_t 
       CBH_TRY(hipStreamSynchronize(s));
       for (size_t i = 0; i < m; ++i) {
         const uint32_t c = out_first[i + 1] - out_first[i];
-        kph_counts[i0 + i] = c;
-        memcpy(kp_hashes + (i0 + i) * cap, hh.data() + out_first[i], (size_t)c * sizeof(uint64_t));
+        kph_counts[o0 + i] = c;
+        memcpy(kp_hashes + (o0 + i) * cap, hh.data() + out_first[i], (size_t)c * sizeof(uint64_t));
       }
     }
     if (color_thread.joinable()) color_thread.join();

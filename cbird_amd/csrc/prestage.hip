@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "cbh_index.h"
+#include "gray_px.h"
 
 namespace {
 
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(256) void k_bgr2gray(const unsigned char* __restric
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int y = (int)(i / w), x = (int)(i - (size_t)y * w);
     const unsigned char* p = s + (size_t)y * row_stride + (size_t)x * channels;
-    d[i] = (unsigned char)((p[0] * 1868 + p[1] * 9617 + p[2] * 4899 + 8192) >> 14);
+    d[i] = cbh_gray_px(p[0], p[1], p[2]);
   }
 }
 

@@ -306,6 +306,83 @@ def filter_groups_c_abi(params, needle_ids, pairs, counts, media, db_path: str =
                 for g in range(ng.value)]
 
 
+def similar_to(index, needle, params: SearchParams, id_map: dict, db_path: str = ""):
+    """Database::similarTo (src/database.cpp:1468-1536; the inSet slice is not here): searchIndex, then filterMatch on
+    [needle, match...] -- which clears the list when it keeps no more than minMatches entries -- and the needle dropped"""
+    return _filtered(needle, search_index(index, needle, params, id_map), params, db_path)
+
+
+def _filtered(needle, group, params, db_path):
+    """similarTo's tail (:1494-1502) on searchIndex's result"""
+    result = [needle] + list(group)
+    if filter_match(params, result, db_path):
+        result = []
+    return result[1:]
+
+
+_MIRROR_FLAGS = (SearchParams.MirrorHorizontal, SearchParams.MirrorVertical, SearchParams.MirrorBoth)
+
+
+def mirrored(needle, view):
+    """Engine::mirrored (src/engine.cpp:357-365): the Media processImage makes of the reflected image, here from its
+    IndexResult (scanner.process_images_views).  processImage builds a new Media (scanner.cpp:864) with the needle's path
+    and no database id -- Media::setDefaults sets id 0 (media.cpp:105) -- so searchIndex's filterSelf (database.cpp:1736)
+    never drops the needle's own id from a mirrored list, while the path filters see the needle's path."""
+    m = copy.copy(needle)
+    m.id = 0
+    m.dctHash = int(view.dctHash)
+    m.keyPointHashes = [int(x) for x in view.keyPointHashes]
+    m.keyPointDescriptors = view.keyPointDescriptors
+    m.colorDescriptor = view.colorDescriptor
+    return m
+
+
+def _needle_views(needle, params, views):
+    """the needle and its reflections in the order Engine::query searches them (engine.cpp:429-436)"""
+    out = [needle]
+    for flag in _MIRROR_FLAGS:
+        if params.mirrorMask & flag:
+            if views is None or views.get(flag) is None:
+                raise ValueError(f"mirrorMask has bit {flag} but no view {flag} of {needle.path!r} was given")
+            out.append(mirrored(needle, views[flag]))
+    return out
+
+
+def _compose(lists):
+    """matches.append(...) of every list, then std::sort(matches) (engine.cpp:438): Media::operator< (media.h:231-234)
+    compares scores only (no match flags are set here) and std::sort is unstable; ties are fixed as in _sorted_matches,
+    by mediaId, then by the list (view) they came from.  Duplicates across the lists are kept."""
+    tagged = [(m.score, m.id, v, t, m) for v, lst in enumerate(lists) for t, m in enumerate(lst)]
+    return [x[-1] for x in sorted(tagged, key=lambda x: x[:4])]
+
+
+def query(index, needle, params: SearchParams, id_map: dict, views=None, db_path: str = ""):
+    """Engine::query from similarTo on (src/engine.cpp:421-438), without the template matcher: similarTo of the needle,
+    then for each bit of params.mirrorMask (1 left-right, 2 top-bottom, 4 both, in that order) similarTo of the mirrored
+    needle appended, each list filtered on its own; the whole sorted by score.  views = the {flag: IndexResult} that
+    scanner.process_images_views returned for this needle; a set bit without its view raises ValueError."""
+    needles = _needle_views(needle, params, views)
+    return _compose([similar_to(index, m, params, id_map, db_path) for m in needles])
+
+
+def query_batch(index, needles, views, params: SearchParams, id_map: dict, db_path: str = ""):
+    """query() for many needles: the needles and all their reflections go through ONE search_index_batch call, the lists
+    are then filtered and composed per needle.  views[i] is the {flag: IndexResult} of needles[i] (may be None with
+    mirrorMask 0).  Returns [query(index, n, params, id_map, v, db_path) for n, v in zip(needles, views)]."""
+    needles = list(needles)
+    views = list(views) if views is not None else [None] * len(needles)
+    if len(views) != len(needles):
+        raise ValueError("one views dict per needle")
+    per = [_needle_views(n, params, v) for n, v in zip(needles, views)]
+    flat = [m for ms in per for m in ms]
+    groups = search_index_batch(index, flat, params, id_map) if flat else []
+    out, k = [], 0
+    for ms in per:
+        out.append(_compose([_filtered(m, groups[k + j], params, db_path) for j, m in enumerate(ms)]))
+        k += len(ms)
+    return out
+
+
 def similar(index, haystack, params: SearchParams, batched: bool = True, db_path: str = ""):
     """Database::similar for an in-memory haystack (list of Media with unique ids): every item is searched
     as a needle; returns the accepted groups [needle, match1, ...].
@@ -313,6 +390,8 @@ def similar(index, haystack, params: SearchParams, batched: bool = True, db_path
     batched (DctHashIndex): the whole job behind the C-ABI -- cbh_search_index_batch (scans, escalation and the
     per-needle cut on the device, no per-needle loop here) and cbh_filter_groups_ex (path / parent filters, acceptance,
     duplicate groups, merge / expand, order); this function only turns the surviving rows back into Media objects."""
+    if getattr(params, "mirrorMask", 0):
+        warnings.warn("reflected images unsupported, use -similar-to")  # database.cpp:1283; ignored, as there
     id_map = {m.id: m for m in haystack}
     if batched and hasattr(index, "search_index_batch") and params.algo == SearchParams.AlgoDCT:
         import ctypes as C

@@ -67,6 +67,11 @@ class SearchParams:
     AlgoCVFeatures = 2
     AlgoColor = 3
     AlgoVideo = 4
+    # reflection search, Engine::query (src/index.h:51-59)
+    MirrorNone = 0
+    MirrorHorizontal = 1
+    MirrorVertical = 2
+    MirrorBoth = 4
 
     algo: int = 0
     dctThresh: int = 5
@@ -83,6 +88,7 @@ class SearchParams:
     filterParent: bool = False
     expandGroups: bool = False
     mergeGroups: int = 0
+    mirrorMask: int = 0       # Mirror* flags: also search the needle's reflections (-p.refl; database.query)
 
 
 def _as_u64(a) -> np.ndarray:

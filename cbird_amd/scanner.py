@@ -41,8 +41,31 @@ class IndexResult:
     colorDescriptor: np.ndarray | None = None
 
 
+MirrorFlags = (1, 2, 4)  # SearchParams::MirrorHorizontal, MirrorVertical, MirrorBoth (src/index.h:51-59)
+
+
 def process_images(imgs: np.ndarray, params: IndexParams | None = None, device: int = 0) -> list[IndexResult]:
     """imgs: uint8 [n, h, w] (grey) or [n, h, w, 3 | 4] (BGR / BGRA), one geometry.  One IndexResult per image."""
+    return _index(imgs, None, params, device)
+
+
+def process_images_views(imgs: np.ndarray, mirror_mask: int, params: IndexParams | None = None,
+                         device: int = 0) -> list[dict]:
+    """processImage of each image and of its reflections for a reflection search (Engine::mirrored / Engine::query,
+    src/engine.cpp:357-365, 423-436) over cbh_index_images_views: one upload per image feeds every view.  Returns one
+    {flag: IndexResult} per image: 0 = the image as given, 1 / 2 / 4 = mirrored left-right / top-bottom / both, for the
+    bits of mirror_mask (SearchParams.mirrorMask); rects and keypoints are in the coordinates of their own view."""
+    mirror_mask = int(mirror_mask)
+    if not 0 <= mirror_mask <= 7:
+        raise ValueError(f"mirror_mask {mirror_mask}: expected 0..7")
+    flags = [0] + [f for f in MirrorFlags if mirror_mask & f]
+    res = _index(imgs, mirror_mask, params, device)
+    V = len(flags)
+    return [dict(zip(flags, res[i * V:(i + 1) * V])) for i in range(len(res) // V)]
+
+
+def _index(imgs, mirror_mask, params, device):
+    """cbh_index_images (mirror_mask None) or cbh_index_images_views: one IndexResult per result row"""
     p = params or IndexParams()
     imgs = np.asarray(imgs)
     if imgs.dtype != np.uint8 or imgs.ndim not in (3, 4):
@@ -52,6 +75,8 @@ def process_images(imgs: np.ndarray, params: IndexParams | None = None, device: 
     ch = 1 if imgs.ndim == 3 else imgs.shape[3]
     if n == 0:
         return []
+    V = 1 if mirror_mask is None else 1 + bin(mirror_mask).count("1")  # results per image
+    nr = n * V
     # room per image: ties in retainBest can exceed numFeatures; a call that found more is repeated, and the size that
     # worked is remembered (equal buffer sizes from call to call also keep the device's scratch pool reusable)
     cap = max(p.numFeatures + 64, getattr(process_images, "_cap_hint", {}).get(p.numFeatures, 0))
@@ -60,28 +85,33 @@ def process_images(imgs: np.ndarray, params: IndexParams | None = None, device: 
         cp = _Params(20 if (p.algos and p.autocrop) else -1, p.algos, p.resizeLongestSide, p.numFeatures, cap)
         # output buffers are kept between calls (an indexer calls this in a loop): fresh numpy arrays are untouched
         # pages, and a device-to-host copy into untouched pageable memory pays a page fault per 4 KB
-        key = (n, cap)
+        key = (nr, cap)
         bufs = getattr(process_images, "_bufs", None)
         if bufs is None or bufs[0] != key:
-            bufs = (key, np.zeros(n, np.uint64), np.zeros((n, 4), np.int32), np.zeros((n, 2), np.int32),
-                    np.zeros(n, np.uint32), np.zeros((n, cap), KP_DTYPE), np.zeros((n, cap, 32), np.uint8),
-                    np.zeros(n, np.uint32), np.zeros((n, cap), np.uint64), np.zeros(n, COLOR_DTYPE), np.zeros(n, np.uint8))
+            bufs = (key, np.zeros(nr, np.uint64), np.zeros((nr, 4), np.int32), np.zeros((nr, 2), np.int32),
+                    np.zeros(nr, np.uint32), np.zeros((nr, cap), KP_DTYPE), np.zeros((nr, cap, 32), np.uint8),
+                    np.zeros(nr, np.uint32), np.zeros((nr, cap), np.uint64), np.zeros(nr, COLOR_DTYPE),
+                    np.zeros(nr, np.uint8))
             for a in bufs[1:]:
                 a.fill(0)  # touch
             process_images._bufs = bufs
         _, hashes, rects, dims, kpc, kp, desc, khc, kh, cd, cok = bufs
         hashes.fill(0), kpc.fill(0), khc.fill(0), cok.fill(0)
         t0 = time.perf_counter()
-        check(L.cbh_index_images(imgs.ctypes.data, n, w, h, w * ch, w * h * ch, ch, C.byref(cp), hashes.ctypes.data,
-                                 rects.ctypes.data, dims.ctypes.data, kpc.ctypes.data, kp.ctypes.data, desc.ctypes.data,
-                                 khc.ctypes.data, kh.ctypes.data, cd.ctypes.data, cok.ctypes.data, device), "index_images")
+        outs = (hashes.ctypes.data, rects.ctypes.data, dims.ctypes.data, kpc.ctypes.data, kp.ctypes.data,
+                desc.ctypes.data, khc.ctypes.data, kh.ctypes.data, cd.ctypes.data, cok.ctypes.data, device)
+        if mirror_mask is None:
+            check(L.cbh_index_images(imgs.ctypes.data, n, w, h, w * ch, w * h * ch, ch, C.byref(cp), *outs), "index_images")
+        else:
+            check(L.cbh_index_images_views(imgs.ctypes.data, n, w, h, w * ch, w * h * ch, ch, mirror_mask, C.byref(cp),
+                                           *outs), "index_images_views")
         process_images.last_call_seconds = time.perf_counter() - t0  # the C call alone (the rest is Python unpacking)
         if int(kpc.max()) <= cap:
             break
         cap = (int(kpc.max()) + 63) // 64 * 64
     process_images._cap_hint = {**getattr(process_images, "_cap_hint", {}), p.numFeatures: cap}
     out = []
-    for i in range(n):
+    for i in range(nr):
         c = int(kpc[i])
         r = IndexResult(dctHash=int(hashes[i]), cropRect=tuple(int(v) for v in rects[i]),
                         resizedDims=(int(dims[i, 0]), int(dims[i, 1])), keyPoints=kp[i, :c].copy(),

@@ -210,6 +210,15 @@ int cbh_color_descriptors_dev(const void* d_imgs, size_t n, const uint64_t* img_
  * n*w*h bytes. */
 int cbh_bgr2gray_dev(const void* d_src, size_t n, int w, int h, size_t row_stride, size_t img_stride,
                      int channels, void* d_gray, int device, void* stream);
+/* The grey planes of the reflected images a reflection search processes (SearchParams::mirrorMask, src/index.h:51-59;
+ * Engine::mirrored, src/engine.cpp:357-365: QImage::mirrored(h, v)), all from one read of each image.  mirror_mask: bit
+ * 1 left-right, 2 top-bottom, 4 both (0..7, else CBH_E_INVAL); V = 1 + popcount(mirror_mask).  d_gray: n*V packed
+ * planes of w*h, plane i*V + v, the views of image i in the order identity, 1, 2, 4 (the set bits); each plane equals
+ * cbh_bgr2gray_dev of the reflected image (channels 1: the reflected bytes).  d_color: NULL, or n*(V-1) packed images of
+ * w*h*channels bytes (row stride w*channels), image i*(V-1) + v-1 = the reflected colour image of view v >= 1 -- what
+ * ColorDescriptor::create reads for that view; the identity view is the input itself.  Channels 1 / 3 / 4. */
+int cbh_gray_views_dev(const void* d_src, size_t n, int w, int h, size_t row_stride, size_t img_stride, int channels,
+                       int mirror_mask, void* d_gray, void* d_color, int device, void* stream);
 /* autocrop(gray, range) (src/cvutil.cpp:1285-1402): d_rects[i] = {left, top, right, bottom} (int32 x4) of the
  * region kept (the whole image when nothing is cropped). */
 int cbh_autocrop_dev(const void* d_gray, size_t n, int w, int h, size_t row_stride, size_t img_stride, int range,
@@ -249,6 +258,16 @@ int cbh_index_images(const uint8_t* imgs, size_t n, int w, int h, size_t row_str
                      const cbh_index_params* p, uint64_t* dct_hashes, int32_t* rects, int32_t* resized_dims,
                      uint32_t* kp_counts, cbh_keypoint* kp, uint8_t* desc, uint32_t* kph_counts, uint64_t* kp_hashes,
                      uint8_t* color_descs, uint8_t* color_ok, int device);
+/* cbh_index_images for a reflection search: Engine::query (src/engine.cpp:423-436) runs processImage again on the needle
+ * mirrored left-right, top-bottom and both ways (Engine::mirrored, :357-365) for the bits of SearchParams::mirrorMask.
+ * Each chunk of images is uploaded once; cbh_gray_views_dev makes the grey (and, with the colour leg, colour) images of
+ * the V = 1 + popcount(mirror_mask) views and the stages run on all of them.  Every output array is sized for n*V results,
+ * result i*V + v = view v of image i (views in the order identity, 1, 2, 4), each exactly what cbh_index_images gives for
+ * the reflected image (rects and keypoints in the coordinates of that view).  mirror_mask 0..7, else CBH_E_INVAL. */
+int cbh_index_images_views(const uint8_t* imgs, size_t n, int w, int h, size_t row_stride, size_t img_stride,
+                           int channels, int mirror_mask, const cbh_index_params* p, uint64_t* dct_hashes, int32_t* rects,
+                           int32_t* resized_dims, uint32_t* kp_counts, cbh_keypoint* kp, uint8_t* desc,
+                           uint32_t* kph_counts, uint64_t* kp_hashes, uint8_t* color_descs, uint8_t* color_ok, int device);
 
 /* sizeLongestSide(cv::Mat& img, int size, int filter = INTER_LANCZOS4) -- src/cvutil.cpp:1932-1950, the resize in
  * front of ORB detection (src/scanner.cpp:876, size = IndexParams::resizeLongestSide = 400): target size from the
