@@ -165,7 +165,7 @@ int launch_hamm64_join(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n
                        unsigned flags, bool force, double scan_ms_estimate);
 unsigned scan_pre_flags(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
                         hipStream_t stream);  // SCAN_PRE_GIVEN | SCAN_PRE_VALUE, probed once for a sharded call
-void set_scan_mfma(int on);  // <0 = keep; 2 = force for any size
+void set_scan_mfma(int on);  // 0..4 (get_scan_mfma); anything else leaves the knob unchanged
 void set_scan_pre_max(int t);   // -1 = prefilter or three-field kernel by the launch's candidate rate (default), 0 = never the
                                 // prefilter, t > 0 = thresholds <= t take it whatever the data
 void set_scan_pre_rate(int e9); // candidate rate x 1e9 up to which the prefilter kernel is taken ("scan_pre_rate_e9")

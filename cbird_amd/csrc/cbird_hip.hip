@@ -1348,6 +1348,7 @@ int cbh_set_tuning(const char* key, int value) {
       {"fault_rccl", [](int v) { set_fault_rccl(v); }},
   };
   if (!strcmp(key, "orb_retain_order") && value != 0 && value != 1) return CBH_E_INVAL;
+  if (!strcmp(key, "scan_mfma") && (value < 0 || value > 4)) return CBH_E_INVAL;
   for (const auto& k : kKnobs)
     if (!strcmp(key, k.name)) {
       k.set(value);
@@ -1362,6 +1363,7 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strcmp(key, "fault_fired")) return *value = (long long)get_fault_fired(), CBH_OK;
   if (!strcmp(key, "alloc_calls")) return *value = (long long)get_alloc_calls(), CBH_OK;
   if (!strncmp(key, "arena_", 6)) return arena_counter(key + 6, value);
+  if (!strcmp(key, "scan_mfma")) return *value = get_scan_mfma(), CBH_OK;
   if (!strcmp(key, "scan_pre_mask")) return *value = get_scan_pre_mask(), CBH_OK;
   if (!strcmp(key, "scan_probes")) return *value = get_scan_probes(), CBH_OK;
   if (!strcmp(key, "scan_joins")) return *value = get_scan_joins(), CBH_OK;

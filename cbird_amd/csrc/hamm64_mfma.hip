@@ -245,8 +245,13 @@ __device__ __forceinline__ void handle_tile2(const v16f& c, uint32_t row0, uint3
 // The wave's 2048 words: pending list (2 words per descriptor) | record buffer | parking area.
 constexpr uint32_t kParkLanes = 16;  // hit lanes parked at a time (a denser group takes several rounds)
 constexpr uint32_t kPark = kQueue - kParkLanes * 32u;  // word offset of the parking area
-constexpr uint32_t kOutOff = kPark - 2u * kOutCap;     // ... of the record buffer; pending: < 64 + 16 * 32 <= kOutOff / 2 descriptors
-static_assert(kOutOff / 2u >= 64u + kParkLanes * 32u, "pending list");
+constexpr uint32_t kOutOff = kPark - 2u * kOutCap;     // ... of the record buffer; the pending list holds kOutOff / 2
+// Pending descriptors.  A drain keeps npend & 63.  A step starts with <= 63, and so does every group behind a multi-lane
+// group (which drains once it is done); a one-lane group adds <= 32 without draining, so one-lane groups alone reach at most
+// 63 + 4 x 32.  A multi-lane group drains before each chunk of kParkLanes x 32 that would not fit behind what is pending
+// (up to 63 + 3 x 32 from one-lane groups before it): after that drain the chunk lands on <= 63.
+static_assert(kOutOff / 2u >= 63u + (kHT / kG) * 32u, "pending list: one-lane groups of a step");
+static_assert(kOutOff / 2u >= 63u + kParkLanes * 32u, "pending list: a chunk of hit lanes");
 
 // OR of accumulator registers [A, B) of a group (register r = tile r / 16, element r % 16), three and then two per
 // v_or3_b32
@@ -447,14 +452,20 @@ __global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(
             wave_order();
             list(kPark, (uint32_t)__builtin_ctzll(hm), ok);
             wave_order();
-            // (drained at the end of the step: a one-lane event adds at most 32 descriptors, four groups cannot overflow the
-            //  list -- and the drain's code sits once per step instead of once per group: 4.3k instead of 5.5k instructions,
-            //  threshold 6 1.5 % faster, profiles/r06_pre_drain_sites_ab.json)
+            // (drained at the end of the step: a one-lane event adds at most 32 descriptors, so the step's one-lane groups
+            //  add at most 4 x 32 to the <= 63 a step or a multi-lane group leaves -- and the drain's code sits once per step
+            //  instead of once per group: 4.3k instead of 5.5k instructions, threshold 6 1.5 % faster,
+            //  profiles/r06_pre_drain_sites_ab.json)
           } else {
             // several hit lanes, in chunks of kParkLanes (one chunk unless the group is dense: duplicates, video frames);
-            // the k-th hit lane of a chunk parks all its registers at kPark + 32 k
+            // the k-th hit lane of a chunk parks all its registers at kPark + 32 k.  A chunk lists up to kParkLanes x 32
+            // descriptors: the list is drained before a chunk that might not fit behind the pending ones (up to 63 + 3 x 32
+            // from earlier one-lane groups of the step), and once the group is done, so that one-lane groups behind it
+            // start from <= 63 -- otherwise descriptors would run into the record buffer.  (One drain site for both.)
             uint64_t rest = hm;
-            do {
+            for (;;) {
+              if (rest ? npend + kParkLanes * 32u > kOutOff / 2u : npend >= 64u) drain(false);
+              if (!rest) break;
               uint64_t cm = rest;
               if ((uint32_t)__popcll(rest) > kParkLanes) {
                 uint64_t rem = rest;
@@ -468,8 +479,7 @@ __global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(
               uint32_t at = kPark;
               for (uint64_t m = cm; m; m &= m - 1, at += 32u) list(at, (uint32_t)__builtin_ctzll(m), 0xffffffffu);
               wave_order();
-              if (npend >= 64u) drain(false);
-            } while (rest);
+            }
           }
         }
       } else {
@@ -848,7 +858,7 @@ uint32_t g_mfma_min_nq = 256;  // below this the needle expansion + tile padding
 }  // namespace
 
 void set_scan_mfma(int on) {
-  if (on >= 0) g_scan_mfma = on;
+  if (on >= 0 && on <= 4) g_scan_mfma = on;  // (cbh_set_tuning refuses the rest: an unknown mode would scan like 1)
 }
 int get_scan_mfma() { return g_scan_mfma; }
 void set_scan_pre_max(int t) {
