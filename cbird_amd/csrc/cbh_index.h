@@ -287,7 +287,7 @@ namespace cbh {
 // per-shard { count, records } blocks are exchanged (device-to-device copies inside one device, RCCL all-gather
 // between devices) and end up as ONE block in the root workspace (sharded.hip)
 int sharded_scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t nq, int thresh, hipStream_t stream,
-                     unsigned long long* total, unsigned flags, const uint64_t* d_qmask, size_t max_records);
+                     unsigned long long* total, const ScanOpts& opts, size_t max_records);
 int sharded_download(const cbh_idx64* idx, uint64_t* hashes, uint32_t* ids, size_t cap);
 }  // namespace cbh
 
@@ -296,16 +296,16 @@ int sharded_download(const cbh_idx64* idx, uint64_t* hashes, uint32_t* ids, size
 // max_records: a result larger than this is not materialised -- CBH_E_OVERFLOW with *total set, and the workspace is
 // never grown past it (the self-join cache asks before it commits a GB-sized buffer).
 inline int scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t nq, int thresh,
-                    hipStream_t stream, unsigned long long* total, unsigned flags = 0,
-                    const uint64_t* d_qmask = nullptr, size_t max_records = ~(size_t)0) {
-  if (idx->shards) return sharded_scan_all(idx, ws, d_q, nq, thresh, stream, total, flags, d_qmask, max_records);
+                    hipStream_t stream, unsigned long long* total, const ScanOpts& opts = {},
+                    size_t max_records = ~(size_t)0) {
+  if (idx->shards) return sharded_scan_all(idx, ws, d_q, nq, thresh, stream, total, opts, max_records);
   int rc = ws->ensure_records(std::min(std::max<size_t>(idx->rec_cap_default, 1024), std::max<size_t>(max_records, 1024)));
   if (rc) return rc;
   for (int attempt = 0; attempt < 3; ++attempt) {
     CBH_HIP(hipMemsetAsync(ws->d_total, 0, sizeof(unsigned long long), stream));
     CBH_HIP(hipEventRecord(ws->ev0, stream));
     rc = launch_hamm64_scan(idx->d_hashes, idx->d_ids, idx->n, d_q, nq, thresh, ws->d_rec,
-                            ws->rec_cap, ws->d_total, stream, flags, d_qmask);
+                            ws->rec_cap, ws->d_total, stream, opts);
     if (rc) return rc;
     CBH_HIP(hipEventRecord(ws->ev1, stream));
     CBH_HIP(hipMemcpyAsync(ws->h_total, ws->d_total, sizeof(unsigned long long),
@@ -329,4 +329,18 @@ inline int scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t n
     if (rc) return rc == CBH_E_NOMEM ? CBH_E_OVERFLOW : rc;
   }
   return CBH_E_OVERFLOW;
+}
+
+// K4 counting select (topk.hip) on the workspace's { count, records } block as scan_all left it (total records): the
+// first k by (distance, id) of each of the nq needles into d_out / d_counts
+inline int records_topk(Workspace* ws, size_t nq, int k, unsigned long long total, cbh_match* d_out, uint32_t* d_counts,
+                        hipStream_t s) {
+  void* scratch = nullptr;
+  const size_t ncap = std::min<size_t>(ws->rec_cap, (size_t)total + 1);  // slots past the count are never read
+  CBH_HIP(cbh::malloc_async(&scratch, topk_scratch_bytes(nq, ncap) + 16, s));
+  unsigned* d_status = (unsigned*)((char*)scratch + topk_scratch_bytes(nq, ncap));
+  int rc = topk_scratch_init(scratch, nq, s);
+  if (!rc) rc = launch_records_topk(ws->d_total, 1, 0, ncap, nq, k, d_out, d_counts, d_status, scratch, s);
+  (void)cbh::free_async(scratch, s);
+  return rc;
 }

@@ -1,4 +1,6 @@
 // cbh_internal.h -- shared declarations between the host shim and the kernel launchers.
+// 64-bit threshold searches: every caller goes through launch_hamm64_scan (hamm64_scan.hip), the one place that decides
+// between the bucketed join, the popcount kernel and the matrix-core kernels; those modules launch what they are told.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -111,20 +113,38 @@ static inline hipError_t gated_host_malloc(T** p, size_t bytes, unsigned flags =
     }                                          \
   } while (0)
 
-// ---- hamm64_scan.hip ------------------------------------------------------------------
+// ---- the 64-bit threshold search: hamm64_scan.hip decides, hamm64_join.hip / hamm64_mfma.hip launch what they are told --
+// What a caller says about a search besides its shape.
+struct ScanOpts {
+  bool keep_id0 = false;              // also emit slots whose id is 0 (DctFeaturesIndex top-10 cut)
+  // one u64 per needle: also require ((q[j] ^ hashes[i]) & qmask[j]) == 0 -- the reference's approximate structures only
+  // compare a needle with the entries that share its low bits (HammingTree leaf, src/tree/hammingtree.h:244-252; RadixMap
+  const uint64_t* d_qmask = nullptr;  // bucket, src/tree/radix.h:135-141)
+  // a call made of several launches against the same needles (the shards of a sharded handle):
+  int pre = -1;                       // the prefilter choice made once for the whole call (scan_pick_pre); -1: the launch's own
+  unsigned siblings = 1;              // launches running side by side on this device
+  const uint4* qx = nullptr;          // the needles expanded once on this device (expand_needles_for_scan)
+};
 // Appends one record per (query j, slot i) with popc(q[j]^hashes[i]) < thresh, ids[i] != 0,
 // q[j] != 0.  *d_total += number of such pairs; records with slot index >= cap are dropped.
-// d_qmask (optional, one u64 per query): additionally require ((q[j] ^ hashes[i]) & qmask[j]) == 0 -- the
-// reference's approximate structures only compare a needle with the entries that share its low bits
-// (HammingTree leaf, src/tree/hammingtree.h:244-252; RadixMap bucket, src/tree/radix.h:135-141).
+// Runs the bucketed join, the popcount kernel or the matrix-core scan: the route at the end of hamm64_scan.hip.
 int launch_hamm64_scan(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n,
                        const uint64_t* d_q, size_t nq, int thresh, cbh_record* d_rec, size_t cap,
-                       unsigned long long* d_total, hipStream_t stream, unsigned flags = 0,
-                       const uint64_t* d_qmask = nullptr, const void* qx_given = nullptr);
-enum { SCAN_KEEP_ID0 = 1u,    // also emit slots whose id is 0 (DctFeaturesIndex top-10 cut)
-       SCAN_PRE_GIVEN = 2u,   // matrix-core scan: the prefilter / three-field choice was made by the caller (a sharded
-       SCAN_PRE_VALUE = 4u,   // handle probes once for all its shards) -- SCAN_PRE_VALUE says which
-       SCAN_SIBLINGS_SHIFT = 8 }; // bits 8..15: launches against the same needles running side by side on the device (0 = alone)
+                       unsigned long long* d_total, hipStream_t stream, const ScanOpts& opts = {});
+// For a call made of several launches: would a launch of n slots run the matrix-core scan; and the prefilter choice for
+// the whole call, probed on one launch's n slots of the call's n_total (ScanOpts::pre)
+bool scan_takes_mfma(size_t n, size_t nq, int thresh);
+bool scan_pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
+                   hipStream_t stream);
+// the knobs and read-backs behind cbh_set_tuning / cbh_get_tuning (include/cbird_hip.h documents each)
+int set_scan_mfma(int mode);  // 0..4; CBH_E_INVAL (knob unchanged) for anything else
+int get_scan_mfma();
+void set_scan_pre_max(int t);
+void set_scan_pre_rate(int e9);
+long long get_scan_pre_mask();
+long long get_scan_probes();
+long long get_scan_probe_rate_e9();
+long long get_scan_probe_true_e9();
 
 // ---- the lone needle (Engine::query / -similar-to: one find() at a time) ---------------------------------------------
 // One kernel launch and no copies: the needle travels as a kernel argument, matches go straight into a pinned, coherent
@@ -140,39 +160,33 @@ struct LoneBlock {
 // d_state: two zeroed words of device memory owned by the caller's workspace (the kernel leaves them zeroed)
 int launch_find_one(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, uint64_t q, int thresh, unsigned* d_state,
                     LoneBlock* h_block, unsigned long long seq, hipStream_t stream);
-// spin until the block carries `seq` (falls back to a stream synchronisation after ~2 s); CBH_OK / CBH_E_HIP
+// spin until the block carries `seq`, with no time limit; every 4096 polls ask whether the stream is still busy: once it
+// is idle without `seq`, or the query fails, CBH_E_HIP (only the failed query sets an error text).  CBH_OK / CBH_E_HIP
 int wait_find_one(const LoneBlock* h_block, unsigned long long seq, hipStream_t stream);
 
 // ---- hamm64_mfma.hip: the same scan on the matrix cores (FP4 sign dot products) --------
-int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n,
-                            const uint64_t* d_q, size_t nq, int thresh, cbh_record* d_rec,
-                            size_t cap, unsigned long long* d_total, hipStream_t stream,
-                            unsigned flags = 0, const uint64_t* d_qmask = nullptr, const void* qx_given = nullptr);
+// pre: the prefilter kernel (thresholds <= 32), else the three-field kernel (<= 64) or the two-field one (65)
+int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
+                            int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
+                            bool pre, const ScanOpts& opts);
 // the needles of a call in the matrix-core kernels' operand layout, made ONCE for several launches against the same needles
-// on one device (the shards of a sharded handle): *qx = malloc_async on `stream`, to be handed to every launch as qx_given
-// (launches on other streams wait for an event of `stream`) and given back with free_async once they have all finished
-int expand_needles_for_scan(const uint64_t* d_q, size_t nq, hipStream_t stream, void** qx);
-bool scan_mfma_wanted(size_t n, size_t nq, int thresh);
-int get_scan_mfma();  // the "scan_mfma" knob: 0 popcount kernel, 1 as shipped, 2 matrix-core scan forced, 3 + the bucketed join where
-                      // its candidate count says so, 4 the join forced wherever it can represent the call
-// ---- hamm64_join.hip: the same search as a bucketed join (multi-index hashing), thresholds <= 8 ----------------------
-bool scan_join_possible(size_t n, size_t nq, int thresh, unsigned flags, const uint64_t* d_qmask);
+// on one device (the shards of a sharded handle): *qx = malloc_async on `stream`, to be handed to every launch as
+// ScanOpts::qx (launches on other streams wait for an event of `stream`) and given back with free_async once they have
+// all finished
+int expand_needles_for_scan(const uint64_t* d_q, size_t nq, hipStream_t stream, uint4** qx);
+// k_fold_probe: the rates of fold-distance candidates and of true matches under `thresh` (<= kProbeMaxThresh) among a
+// sample of the launch's pairs -- one host round trip; false if it could not run
+constexpr int kProbeMaxThresh = 8;
+bool probe_fold_rates(const uint64_t* d_hashes, size_t n, const uint64_t* d_q, size_t nq, int thresh, hipStream_t stream,
+                      double* r_cand, double* r_true);
+// ---- hamm64_join.hip: the same search as a bucketed join (multi-index hashing), thresholds <= kJoinMaxThresh -----------
+constexpr int kJoinMaxThresh = 8;
 long long get_scan_joins();  // calls the join has answered so far (cbh_get_tuning "scan_joins")
 // CBH_OK = done; CBH_E_UNSUPPORTED = the scan is cheaper for this call (decided from the exact candidate count against
-// scan_ms_estimate unless `force`): nothing written, the caller scans
+// scan_ms_estimate unless `force`), or its jobs do not fit a grid: nothing written, the caller may scan.  No needle masks.
 int launch_hamm64_join(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
                        int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
-                       unsigned flags, bool force, double scan_ms_estimate);
-unsigned scan_pre_flags(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
-                        hipStream_t stream);  // SCAN_PRE_GIVEN | SCAN_PRE_VALUE, probed once for a sharded call
-void set_scan_mfma(int on);  // 0..4 (get_scan_mfma); anything else leaves the knob unchanged
-void set_scan_pre_max(int t);   // -1 = prefilter or three-field kernel by the launch's candidate rate (default), 0 = never the
-                                // prefilter, t > 0 = thresholds <= t take it whatever the data
-void set_scan_pre_rate(int e9); // candidate rate x 1e9 up to which the prefilter kernel is taken ("scan_pre_rate_e9")
-long long get_scan_pre_mask();  // bit t = the most recent matrix-core launch at threshold t took the prefilter kernel
-long long get_scan_probes();    // candidate-rate probes run so far
-long long get_scan_probe_rate_e9();  // what the last one found for its threshold, x 1e9 (-1: none yet): candidates ...
-long long get_scan_probe_true_e9();  // ... and true matches
+                       bool keep_id0, bool force, double scan_ms_estimate);
 
 // ---- hamm256_mfma.hip: 256-bit threshold scan on the matrix cores -----------------------
 int launch_scan256_mfma(const uint8_t* d_rows, size_t n, const uint8_t* d_q, size_t nq, int thresh,

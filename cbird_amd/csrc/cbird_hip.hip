@@ -1145,23 +1145,12 @@ static int find_batch_core(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, s
   int rc = ws->ensure_records(std::max<size_t>(idx->rec_cap_default, 1024));  // (d_total must exist when n == 0)
   if (rc) return rc;
   if (idx->n && thresh > 0) {
-    rc = scan_all(idx, ws, d_q, nq, thresh, s, total, 0, d_qmask);
+    rc = scan_all(idx, ws, d_q, nq, thresh, s, total, ScanOpts{false, d_qmask});
     if (rc) return rc;
   } else {
     CBH_HIP(hipMemsetAsync(ws->d_total, 0, sizeof(unsigned long long), s));
   }
-  if (k <= kTopkMaxK && *total < ((unsigned long long)1 << 32)) {
-    // K4 counting select (topk.hip): the workspace's { count, records } block is its input as it stands
-    void* scratch = nullptr;
-    unsigned* d_status = nullptr;
-    const size_t ncap = std::min<size_t>(ws->rec_cap, (size_t)*total + 1);  // slots past the count are never read
-    CBH_HIP(cbh::malloc_async(&scratch, topk_scratch_bytes(nq, ncap) + 16, s));
-    d_status = (unsigned*)((char*)scratch + topk_scratch_bytes(nq, ncap));
-    rc = topk_scratch_init(scratch, nq, s);
-    if (!rc) rc = launch_records_topk(ws->d_total, 1, 0, ncap, nq, k, d_out, d_counts, d_status, scratch, s);
-    (void)cbh::free_async(scratch, s);
-    return rc;
-  }
+  if (k <= kTopkMaxK && *total < ((unsigned long long)1 << 32)) return records_topk(ws, nq, k, *total, d_out, d_counts, s);
   if ((rc = ws->ensure_sort())) return rc;
   rc = launch_sort_records(ws->d_rec, ws->d_alt, (size_t)*total, nq, ws->d_tmp, ws->tmp_bytes, s);
   if (rc) return rc;
@@ -1321,7 +1310,6 @@ int cbh_set_tuning(const char* key, int value) {
     const char* name;
     void (*set)(int);
   } kKnobs[] = {
-      {"scan_mfma", [](int v) { set_scan_mfma(v); }},
       {"scan_mfma_pre_max", [](int v) { set_scan_pre_max(v); }},
       {"scan_pre_rate_e9", [](int v) { set_scan_pre_rate(v); }},
       {"scan256_mfma", [](int v) { set_scan256_mfma(v); }},
@@ -1348,7 +1336,7 @@ int cbh_set_tuning(const char* key, int value) {
       {"fault_rccl", [](int v) { set_fault_rccl(v); }},
   };
   if (!strcmp(key, "orb_retain_order") && value != 0 && value != 1) return CBH_E_INVAL;
-  if (!strcmp(key, "scan_mfma") && (value < 0 || value > 4)) return CBH_E_INVAL;
+  if (!strcmp(key, "scan_mfma")) return set_scan_mfma(value);
   for (const auto& k : kKnobs)
     if (!strcmp(key, k.name)) {
       k.set(value);

@@ -185,8 +185,7 @@ int serve_by_scan(cbh_idx64* idx, Coalescer* co, Workspace* ws, std::vector<Req*
     }
   } else {
     CBH_HIP(hipMemsetAsync(ws->d_total, 0, sizeof(unsigned long long), s));
-    rc = launch_hamm64_scan(idx->d_hashes, idx->d_ids, idx->n, ws->d_q, nq, thresh, ws->d_rec, ws->rec_cap, ws->d_total,
-                            s, 0, nullptr);
+    rc = launch_hamm64_scan(idx->d_hashes, idx->d_ids, idx->n, ws->d_q, nq, thresh, ws->d_rec, ws->rec_cap, ws->d_total, s);
     if (rc) return rc;
     CBH_HIP(hipMemcpyAsync(co->h_total, ws->d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     CBH_HIP(hipMemcpyAsync(co->h_spec, ws->d_rec, spec * sizeof(cbh_record), hipMemcpyDeviceToHost, s));
@@ -248,7 +247,7 @@ int build_self_join(cbh_idx64* idx, const Snapshot* base, Workspace* ws, int thr
   }
   // bounded: an index full of near-duplicates (1e5 equal hashes = 1e10 pairs) must not make one find() ask for tens
   // of GB -- scan_all learns the count from its first pass and gives up before it grows anything past the limit
-  rc = scan_all(idx, ws, d_needles, n, thresh, s, &total, 0, nullptr, kJoinMaxRecords);
+  rc = scan_all(idx, ws, d_needles, n, thresh, s, &total, {}, kJoinMaxRecords);
   if (rc == CBH_E_OVERFLOW || (!rc && total > kJoinMaxRecords)) {
     *too_big = true;
     return CBH_OK;

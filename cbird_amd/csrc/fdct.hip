@@ -132,21 +132,11 @@ int fdct_core(cbh_idx64* idx, const uint64_t* hashes, const std::vector<Needle>&
     CBH_HIP(hipMemcpyAsync(ws->d_qmask, masks.data(), nq * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
   }
   unsigned long long total = 0;
-  rc = scan_all(idx, ws, ws->d_q, nq, thresh, ws->stream, &total, SCAN_KEEP_ID0,
-                tree_compat ? ws->d_qmask : nullptr);
+  rc = scan_all(idx, ws, ws->d_q, nq, thresh, ws->stream, &total, ScanOpts{true, tree_compat ? ws->d_qmask : nullptr});
   if (rc) return rc;
   hipStream_t s = ws->stream;
   // per needle hash: the first 10 candidates by (distance, id) -- K4 counting select on the workspace block
-  {
-    void* scratch = nullptr;
-    const size_t ncap = std::min<size_t>(ws->rec_cap, (size_t)total + 1);
-    CBH_HIP(cbh::malloc_async(&scratch, topk_scratch_bytes(nq, ncap) + 16, s));
-    unsigned* d_status = (unsigned*)((char*)scratch + topk_scratch_bytes(nq, ncap));
-    rc = topk_scratch_init(scratch, nq, s);
-    if (!rc) rc = launch_records_topk(ws->d_total, 1, 0, ncap, nq, k, ws->d_out, ws->d_counts, d_status, scratch, s);
-    (void)cbh::free_async(scratch, s);
-    if (rc) return rc;
-  }
+  if ((rc = records_topk(ws, nq, k, total, ws->d_out, ws->d_counts, s))) return rc;
   if (g_fdct_host_vote == 1 || (g_fdct_host_vote == 0 && needles.size() == 1)) {  // host reduction
     std::vector<cbh_match> top(nq * (size_t)k);
     std::vector<uint32_t> counts(nq);

@@ -32,7 +32,7 @@ namespace {
 constexpr int kJT = 256;        // threads
 constexpr uint32_t kJH = 2 * kJT;  // slots per job of the wide join (two per lane)
 constexpr uint32_t kJQ = 2048;  // needles per job (a value's needles beyond that make further jobs)
-constexpr int kMaxChunks = 8;
+constexpr int kMaxChunks = kJoinMaxThresh;  // chunks: max(4, thresh)
 constexpr uint32_t kOutCap = 96;  // records a wave parks before it appends them
 
 struct JoinPlan {
@@ -347,17 +347,11 @@ std::atomic<long long> g_n_join{0};
 
 long long get_scan_joins() { return g_n_join.load(); }
 
-bool scan_join_possible(size_t n, size_t nq, int thresh, unsigned flags, const uint64_t* d_qmask) {
-  (void)flags;
-  return thresh >= 1 && thresh <= kMaxChunks && d_qmask == nullptr && n >= 1 && nq >= 1 && n < 0xfffffff0ull &&
-         nq <= CBH_MAX_QUERIES_PER_CALL;
-}
-
 // CBH_OK: done (records appended, *d_total advanced like the scans do); CBH_E_UNSUPPORTED: the caller's scan is cheaper
 // (or `force` is false and the call is too small to be worth the bookkeeping) -- nothing has been written.
 int launch_hamm64_join(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
                        int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
-                       unsigned flags, bool force, double scan_ms_estimate) {
+                       bool keep_id0, bool force, double scan_ms_estimate) {
   JoinPlan P;
   memset(&P, 0, sizeof P);
   P.m = std::max(4, thresh);
@@ -431,7 +425,7 @@ int launch_hamm64_join(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n
                        start_h, hist_h, hx, hid);
     hipLaunchKernelGGL(k_join_by_needle, dim3((unsigned)((nq + kJT - 1) / kJT)), dim3(kJT), 0, stream, P, (uint32_t)n,
                        (uint32_t)nq, hx, hid, d_q, start_h, (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total,
-                       (uint32_t)(flags & 1u));
+                       (uint32_t)keep_id0);
     CBH_HIP(hipGetLastError());
     g_n_join++;
     return CBH_OK;
@@ -466,11 +460,11 @@ int launch_hamm64_join(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n
     if (P.lo[j + 1] - P.lo[j] >= 12)
       hipLaunchKernelGGL(k_join_narrow, dim3((unsigned)((n + kJT - 1) / kJT)), dim3(kJT), 0, stream, j, P, (uint32_t)n,
                          (uint32_t)nq, hx, hid, qx, qidx, start_q, (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total,
-                         (uint32_t)(flags & 1u));
+                         (uint32_t)keep_id0);
     else
       hipLaunchKernelGGL(k_join_pairs, dim3((unsigned)h_stats[2 * j]), dim3(kJT), 0, stream, j, P, (uint32_t)n, (uint32_t)nq,
                          hx, hid, qx, qidx, start_h, start_q, jobstart, (uint32_t)thresh, d_rec, (unsigned long long)cap,
-                         d_total, (uint32_t)(flags & 1u));
+                         d_total, (uint32_t)keep_id0);
   }
   CBH_HIP(hipGetLastError());
   g_n_join++;

@@ -24,17 +24,18 @@
 //   * both halves are positive normal f16 bit patterns, so v_pk_maximum3_f16 (new on gfx950) takes
 //     the per-half maximum of three registers at once: 4 ops per MFMA instead of 8.
 //
-// Three variants (all exact), chosen by the launcher (pick_pre below: per launch, from the candidate rate of the data):
+// Three variants (all exact).  Which one runs is decided in hamm64_scan.hip (the prefilter from the candidate rates the
+// probe below measures) and handed to launch_hamm64_scan_mfma:
 //   FULL3 (k_hamm64_mfma3, thresholds up to 64 that the prefilter does not take) three needle tiles per accumulator,
 //         detection by OR of flag bits -- described at the kernel below.
 //   FULL2 (thresh 65 only) K = the 64 bits of one hash; tile B is a second MFMA accumulated
 //         onto tile A's.  hi16 = 0x4B40 - distB, lo16 = 0x4080 - 2*distA.  Hits are real matches.
 //   PRE   (small thresholds while candidates are rare) 32-bit prefilter at twice the pair rate.  The 32-bit word is the FOLD
 //         f(x) = lo(x) ^ hi(x): bit i of f(a) ^ f(b) is the XOR of bits i and i + 32 of a ^ b, so
-//         popc(f(a) ^ f(b)) <= popc(a ^ b) -- a lower bound on the distance that looks at all 64 bits.  (Round 1-4
-//         used the low word alone: also a lower bound, but the low-frequency coefficients of images agree far more
-//         often than chance; on image-derived hashes the fold passes 2-3x fewer false candidates -- exactly the rate
-//         of uniform random words -- NOTES 11.)  The block scale is per lane and K block, so lanes 0-31 (K 0..31)
+//         popc(f(a) ^ f(b)) <= popc(a ^ b) -- a lower bound on the distance that looks at all 64 bits.  (The low word
+//         alone is also a lower bound, but the low-frequency coefficients of images agree far more often than chance;
+//         on image-derived hashes the fold passes 2-3x fewer false candidates -- exactly the rate of uniform random
+//         words -- NOTES 11.)  The block scale is per lane and K block, so lanes 0-31 (K 0..31)
 //         carry the folds of one needle tile and lanes 32-63 (K 32..63) the folds of the next, against the
 //         haystack's folds in both K blocks: ONE MFMA = 2048 fold distances.  Two such MFMAs are chained into one
 //         accumulator with block scales 2^-1 | 2^5 and 2^11 | 2^17: four 6-bit flag-bit fields per register (the
@@ -52,10 +53,9 @@
 // Layout.  A workgroup is 4 waves; each wave keeps HT haystack tiles (32 rows each) expanded
 // to FP4 in VGPRs (4 VGPRs per tile: lane (r, half) holds word `half` of row r; PRE: the fold
 // lo ^ hi in both halves) and streams needle tiles -- pre-expanded once per call by
-// k_expand_needles into a 32-byte-per-needle scratch -- through 16-byte loads that the 4 waves
+// k_expand_needles (expand_needles_for_scan) into a 48-byte-per-needle scratch -- through 16-byte loads that the 4 waves
 // share in L1/L2.
 #include <algorithm>
-#include <atomic>
 #include <mutex>
 #include <vector>
 
@@ -707,28 +707,11 @@ __global__ __launch_bounds__(kThreads, 2) void k_hamm64_mfma3(
   out_flush(s_out, nout, hp);
 }
 
-// ---- which kernel: the candidate rate of THIS launch's data ---------------------------------------------------------
-// The prefilter kernel is twice as fast as the three-field kernel while its candidates are rare and loses to it when
-// they are not: every candidate costs a park / list / re-check (~110 SIMD cycles per event).  How many there are is a
-// property of the data -- r_cand(t) = P[popc(fold(a) ^ fold(b)) < t] over the launch's needle x slot pairs: 5.7e-5 at
-// t = 6 and 2.7e-4 at t = 7 for unrelated hashes, but anything for a library of scans of one form, blank frames or a video
-// against itself.  The three-field kernel in turn pays for every TRUE match (a flagged group goes through three passes
-// of sixteen ballots): ~4x what a candidate costs the prefilter, so where the candidates are mostly true matches -- a
-// dense cluster of near-identical hashes -- the prefilter wins again, at any rate.  Measured per 10^12 pairs
-// (tools/ab/adaptive_ab.py, profiles/r06_adaptive_ab*.jsonl):  T_pre = 8.8 ms + 6e4 ms x r_cand,  T_full = 16.3 ms +
-// 2.5e5 ms x r_true.  k_fold_probe counts both rates on kProbeS x kProbeS evenly spaced (slot, needle) samples -- a few
-// microseconds and one host round trip, against launches of milliseconds -- and pick_pre takes the prefilter while
-//   r_cand - kTrueWeight x r_true <= kPreRateMax          (the rate at which the two kernels tie: 1.25e-4).
-// Launches too small to pay for the round trip, and a probe that cannot allocate, take the fixed rule of round 5
-// (thresholds <= 6).
+// ---- the probe: candidate and true-match rates of THIS launch's data (the route in hamm64_scan.hip weighs them) --------
+// k_fold_probe counts, on kProbeS x kProbeS (slot, needle) samples, the pairs whose fold distance and whose 64-bit distance
+// are under each threshold up to kProbeT.
 constexpr uint32_t kProbeS = 2048;     // samples per side
-constexpr int kProbeT = 8;             // thresholds 1..8 are counted (the prefilter never pays beyond: 1e-3 per pair at 8)
-constexpr int kPreStatic = 6;          // the fixed rule
-int g_pre_max_thresh = -1;             // "scan_mfma_pre_max": -1 = by candidate rate (default), 0 = never the prefilter,
-                                       // t > 0 = thresholds <= t take it whatever the data (tests, A/B)
-int g_pre_rate_max_e9 = 125000;        // "scan_pre_rate_e9": kPreRateMax x 1e9
-constexpr double kTrueWeight = 4.0;
-constexpr uint64_t kProbeMinPairs = 1ull << 31;  // ~20 us of scan: below this the probe's round trip is not worth it
+constexpr int kProbeT = kProbeMaxThresh;  // thresholds 1..8 are counted (the prefilter never pays beyond: 1e-3 per pair at 8)
 
 // grid (sq / 256, sh / 64): thread = one needle sample against 64 slot samples; counts[t - 1] += pairs with fold
 // distance < t, counts[kProbeT + t - 1] += pairs with 64-bit distance < t.  The samples are pseudo-random rows / needles
@@ -804,23 +787,14 @@ void probe_slot_put(uint32_t* p) {
   g_probe_free.push_back(p);
 }
 
-std::atomic<uint64_t> g_pre_mask{0};          // bit t: the most recent matrix-core launch at threshold t took the prefilter
-std::atomic<uint64_t> g_n_probe{0};           // probes run
-std::atomic<long long> g_last_rate_e9{-1};    // candidate rate x 1e9 the last probe found for its threshold
-std::atomic<long long> g_last_true_e9{-1};    // ... and the rate of true (64-bit) matches
+}  // namespace
 
-// true = this launch takes the prefilter kernel.  n_total = the slots the call scans in all (a sharded handle probes one
-// shard's slots on behalf of all of them)
-bool pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
-              hipStream_t stream) {
-  if (thresh > 32) return false;
-  if (g_pre_max_thresh >= 0) return thresh <= g_pre_max_thresh;
-  if (thresh > kProbeT) return false;
-  if ((uint64_t)n_total * (uint64_t)nq < kProbeMinPairs) return thresh <= kPreStatic;
+bool probe_fold_rates(const uint64_t* d_hashes, size_t n, const uint64_t* d_q, size_t nq, int thresh, hipStream_t stream,
+                      double* r_cand, double* r_true) {
   uint32_t* d_cnt = nullptr;
   if (cbh::malloc_async((void**)&d_cnt, 2 * kProbeT * sizeof(uint32_t), stream) != hipSuccess) {
     (void)hipGetLastError();
-    return thresh <= kPreStatic;
+    return false;
   }
   uint32_t* h_cnt = probe_slot_get();
   bool ok = h_cnt != nullptr;
@@ -837,57 +811,20 @@ bool pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t
     }
   }
   (void)cbh::free_async(d_cnt, stream);
-  bool pre = thresh <= kPreStatic;
   if (ok) {
     const double pairs = (double)sh * (double)sq;
-    const double r_cand = (double)h_cnt[thresh - 1] / pairs, r_true = (double)h_cnt[kProbeT + thresh - 1] / pairs;
-    g_last_rate_e9 = (long long)(r_cand * 1e9);
-    g_last_true_e9 = (long long)(r_true * 1e9);
-    g_n_probe++;
-    pre = (r_cand - kTrueWeight * r_true) * 1e9 <= (double)g_pre_rate_max_e9;
+    *r_cand = (double)h_cnt[thresh - 1] / pairs;
+    *r_true = (double)h_cnt[kProbeT + thresh - 1] / pairs;
   } else {
     (void)hipGetLastError();
   }
   if (h_cnt) probe_slot_put(h_cnt);
-  return pre;
-}
-
-int g_scan_mfma = 1;           // use the matrix-core scan when the batch is large enough
-uint32_t g_mfma_min_nq = 256;  // below this the needle expansion + tile padding is not worth it
-
-}  // namespace
-
-void set_scan_mfma(int on) {
-  if (on >= 0 && on <= 4) g_scan_mfma = on;  // (cbh_set_tuning refuses the rest: an unknown mode would scan like 1)
-}
-int get_scan_mfma() { return g_scan_mfma; }
-void set_scan_pre_max(int t) {
-  if (t >= -1 && t <= 32) g_pre_max_thresh = t;
-}
-void set_scan_pre_rate(int e9) {
-  if (e9 >= 0) g_pre_rate_max_e9 = e9;
-}
-// read-backs (cbh_get_tuning): "scan_pre_mask", "scan_probes", "scan_probe_rate_e9"
-long long get_scan_pre_mask() { return (long long)g_pre_mask.load(); }
-long long get_scan_probes() { return (long long)g_n_probe.load(); }
-long long get_scan_probe_rate_e9() { return g_last_rate_e9.load(); }
-long long get_scan_probe_true_e9() { return g_last_true_e9.load(); }
-
-// the choice for a call that scans n_total slots in several launches (sharded.hip), made once on one shard's slots:
-// SCAN_PRE_GIVEN | SCAN_PRE_VALUE bits for launch_hamm64_scan's flags
-unsigned scan_pre_flags(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
-                        hipStream_t stream) {
-  return SCAN_PRE_GIVEN | (pick_pre(d_hashes, n, n_total, d_q, nq, thresh, stream) ? SCAN_PRE_VALUE : 0u);
-}
-
-bool scan_mfma_wanted(size_t n, size_t nq, int thresh) {
-  if (g_scan_mfma == 2 || g_scan_mfma == 4) return thresh >= 1 && thresh <= 65;  // forced (tests); 3 sizes like 1
-  return g_scan_mfma && nq >= g_mfma_min_nq && n >= 4096 && thresh >= 1 && thresh <= 65;
+  return ok;
 }
 
 static uint32_t padded_needles(size_t nq) { return (uint32_t)((nq + 191) / 192) * 192u; }  // whole pairs (64) and triples (96)
 
-int expand_needles_for_scan(const uint64_t* d_q, size_t nq, hipStream_t stream, void** qx_out) {
+int expand_needles_for_scan(const uint64_t* d_q, size_t nq, hipStream_t stream, uint4** qx_out) {
   *qx_out = nullptr;
   if (nq == 0 || nq > CBH_MAX_QUERIES_PER_CALL) return CBH_OK;
   const uint32_t nq_pad = padded_needles(nq);
@@ -904,32 +841,25 @@ int expand_needles_for_scan(const uint64_t* d_q, size_t nq, hipStream_t stream, 
   return CBH_OK;
 }
 
-int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n,
-                            const uint64_t* d_q, size_t nq, int thresh, cbh_record* d_rec,
-                            size_t cap, unsigned long long* d_total, hipStream_t stream,
-                            unsigned flags, const uint64_t* d_qmask, const void* qx_given) {
-  if (n == 0 || nq == 0 || thresh <= 0) return CBH_OK;
-  if (n > 0xfffffff0ull || nq > CBH_MAX_QUERIES_PER_CALL || thresh > 65) return CBH_E_INVAL;
-  const bool pre = (flags & SCAN_PRE_GIVEN) ? (flags & SCAN_PRE_VALUE) != 0 : pick_pre(d_hashes, n, n, d_q, nq, thresh, stream);
-  if (thresh < 64) {
-    if (pre) g_pre_mask |= 1ull << thresh; else g_pre_mask &= ~(1ull << thresh);
-  }
+int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
+                            int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
+                            bool pre, const ScanOpts& o) {
   const uint32_t n_pairs = (uint32_t)((nq + 63) / 64);
   const uint32_t n_triples = (uint32_t)((nq + 95) / 96);
   const uint32_t nq_pad = padded_needles(nq);
-  const uint4* qx = reinterpret_cast<const uint4*>(qx_given);
-  void* qx_own = nullptr;
+  const uint4* qx = o.qx;
+  uint4* qx_own = nullptr;
   if (!qx) {
     int rc = expand_needles_for_scan(d_q, nq, stream, &qx_own);
     if (rc) return rc;
-    qx = reinterpret_cast<const uint4*>(qx_own);
+    qx = qx_own;
   }
   const uint4* qf = qx + 2u * (size_t)nq_pad;
   const uint32_t rows_per_wg = 32u * kHT * kWaves;
   // launches that run side by side on this device (the shards of a sharded handle): the workgroups that fill the machine are
   // theirs together -- a shard of 125 000 slots alone cut its needles into chunks of 128 pairs to reach 8192 workgroups and
   // paid the shorter chunks' per-chunk costs (3 % of the sweep) for parallelism its seven siblings already supplied
-  const uint32_t sib = std::max(1u, (flags >> SCAN_SIBLINGS_SHIFT) & 0xffu);
+  const uint32_t sib = std::max(1u, o.siblings);
   const uint32_t wgs = (uint32_t)((n + rows_per_wg - 1) / rows_per_wg);
   if (!pre && thresh <= 64) {
     // needle chunk: >= 8192 workgroups in flight when there is that much work, but each wave amortises its tile expansion
@@ -944,8 +874,8 @@ int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, siz
     }
     hipLaunchKernelGGL(k_hamm64_mfma3, dim3(wgs, ch3), dim3(kThreads), 0, stream,
                        reinterpret_cast<const uint2*>(d_hashes), d_ids, (uint32_t)n, d_q, qx, (uint32_t)nq, n_triples, tpc,
-                       (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total, (uint32_t)(flags & 1u),
-                       reinterpret_cast<const uint2*>(d_qmask));
+                       (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total, (uint32_t)o.keep_id0,
+                       reinterpret_cast<const uint2*>(o.d_qmask));
   } else {
     // (prefilter: 512 pairs = 32768 needles per chunk -- a wave drains its pending candidates at the end of its chunk,
     // mostly a short list: at threshold 6 chunks of 512 / 1024 pairs run 12.63 ms against 12.98 with 256 and 13.35 with 64)
@@ -959,8 +889,8 @@ int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, siz
 #define CBH_MFMA(PRE)                                                                                                 \
   hipLaunchKernelGGL((k_hamm64_mfma<PRE>), dim3(wgs, chunks), dim3(kThreads), 0, stream,                              \
                      reinterpret_cast<const uint2*>(d_hashes), d_ids, (uint32_t)n, d_q, qx, (uint32_t)nq, n_pairs, ppc, \
-                     (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total, (uint32_t)(flags & 1u),               \
-                     reinterpret_cast<const uint2*>(d_qmask), qf)
+                     (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total, (uint32_t)o.keep_id0,                 \
+                     reinterpret_cast<const uint2*>(o.d_qmask), qf)
     if (pre) CBH_MFMA(true); else CBH_MFMA(false);
 #undef CBH_MFMA
   }

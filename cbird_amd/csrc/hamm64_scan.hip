@@ -20,6 +20,10 @@
 //    every block; FULL is used otherwise.
 //  * grid = (slot tiles) x (needle chunks); consecutive blockIdx.x share a needle chunk, so the
 //    workgroups resident at one time stream the same few needle chunks out of L2.
+// The end of the file: launch_hamm64_scan, the entry of every 64-bit threshold search, and the one place that decides
+// which path a search takes.
+#include <atomic>
+
 #include "cbh_internal.h"
 
 namespace cbh {
@@ -111,7 +115,7 @@ __device__ __forceinline__ void refine_block(const uint2 (&h)[H], const uint32_t
 
 enum { MODE_PRE = 0, MODE_FULL = 1, MODE_EQ = 2 };
 
-template <int H, int QB, int MODE, bool GROUP>
+template <int H, int QB, int MODE>
 __global__ __launch_bounds__(kThreads) void k_hamm64_scan(
     const uint2* __restrict__ hay, const uint32_t* __restrict__ ids, uint32_t n,
     const uint64_t* __restrict__ q, uint32_t nq, uint32_t q_chunk, uint32_t thresh,
@@ -164,67 +168,49 @@ __global__ __launch_bounds__(kThreads) void k_hamm64_scan(
       uint32_t acc[H];
 #pragma unroll
       for (int j = 0; j < H; ++j) acc[j] = 0xffu;
-      if (GROUP) {
-        // Issue-rate shaping (tools/ubench/valu_rate.hip): VGPR-only v_xor_b32 runs at 32 lanes/clk
-        // only inside long runs of such ops, while v_bcnt/v_min3 (and any op with an SGPR source)
-        // run at 16 lanes/clk and cost a ~25-cycle mode switch when interleaved.  So: broadcast
-        // the needles into VGPRs, do all QB*H xors back to back, then all the popcounts/minima.
-        uint32_t ql[QB], qh[QB];
+      // Issue-rate shaping (tools/ubench/valu_rate.hip): VGPR-only v_xor_b32 runs at 32 lanes/clk
+      // only inside long runs of such ops, while v_bcnt/v_min3 (and any op with an SGPR source)
+      // run at 16 lanes/clk and cost a ~25-cycle mode switch when interleaved.  So: broadcast
+      // the needles into VGPRs, do all QB*H xors back to back, then all the popcounts/minima.
+      uint32_t ql[QB], qh[QB];
 #pragma unroll
-        for (int i = 0; i < QB; ++i) {
-          asm volatile("v_mov_b32 %0, %1" : "=v"(ql[i]) : "s"(cur[i].x));
-          if (MODE == MODE_FULL) asm volatile("v_mov_b32 %0, %1" : "=v"(qh[i]) : "s"(cur[i].y));
-        }
-        uint32_t x[QB][H];
+      for (int i = 0; i < QB; ++i) {
+        asm volatile("v_mov_b32 %0, %1" : "=v"(ql[i]) : "s"(cur[i].x));
+        if (MODE == MODE_FULL) asm volatile("v_mov_b32 %0, %1" : "=v"(qh[i]) : "s"(cur[i].y));
+      }
+      uint32_t x[QB][H];
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < QB; ++i)
+#pragma unroll
+        for (int j = 0; j < H; ++j) x[i][j] = h[j].x ^ ql[i];
+      __builtin_amdgcn_sched_barrier(0);
+      if (MODE == MODE_FULL) {
+#pragma unroll
+        for (int i = 0; i < QB; ++i)
+#pragma unroll
+          for (int j = 0; j < H; ++j) x[i][j] = (uint32_t)__popc(x[i][j]);
+        uint32_t y[QB][H];
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < QB; ++i)
 #pragma unroll
-          for (int j = 0; j < H; ++j) x[i][j] = h[j].x ^ ql[i];
+          for (int j = 0; j < H; ++j) y[i][j] = h[j].y ^ qh[i];
         __builtin_amdgcn_sched_barrier(0);
-        if (MODE == MODE_FULL) {
 #pragma unroll
-          for (int i = 0; i < QB; ++i)
+        for (int i = 0; i < QB; i += 2)
 #pragma unroll
-            for (int j = 0; j < H; ++j) x[i][j] = (uint32_t)__popc(x[i][j]);
-          uint32_t y[QB][H];
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 0; i < QB; ++i)
-#pragma unroll
-            for (int j = 0; j < H; ++j) y[i][j] = h[j].y ^ qh[i];
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 0; i < QB; i += 2)
-#pragma unroll
-            for (int j = 0; j < H; ++j)
-              acc[j] = min3u(acc[j], x[i][j] + (uint32_t)__popc(y[i][j]),
-                             x[i + 1][j] + (uint32_t)__popc(y[i + 1][j]));
-        } else {
-#pragma unroll
-          for (int i = 0; i < QB; i += 2)
-#pragma unroll
-            for (int j = 0; j < H; ++j)
-              acc[j] = min3u(acc[j], (uint32_t)__popc(x[i][j]), (uint32_t)__popc(x[i + 1][j]));
-        }
-        __builtin_amdgcn_sched_barrier(0);
+          for (int j = 0; j < H; ++j)
+            acc[j] = min3u(acc[j], x[i][j] + (uint32_t)__popc(y[i][j]),
+                           x[i + 1][j] + (uint32_t)__popc(y[i + 1][j]));
       } else {
 #pragma unroll
-      for (int i = 0; i < QB; i += 2) {
-        const uint2 qa = cur[i];
-        const uint2 qc = cur[i + 1];
+        for (int i = 0; i < QB; i += 2)
 #pragma unroll
-        for (int j = 0; j < H; ++j) {
-          uint32_t c0 = __popc(h[j].x ^ qa.x);
-          uint32_t c1 = __popc(h[j].x ^ qc.x);
-          if (MODE == MODE_FULL) {
-            c0 += __popc(h[j].y ^ qa.y);
-            c1 += __popc(h[j].y ^ qc.y);
-          }
-          acc[j] = min3u(acc[j], c0, c1);
-        }
+          for (int j = 0; j < H; ++j)
+            acc[j] = min3u(acc[j], (uint32_t)__popc(x[i][j]), (uint32_t)__popc(x[i + 1][j]));
       }
-      }
+      __builtin_amdgcn_sched_barrier(0);
       uint32_t m = acc[0];
 #pragma unroll
       for (int j = 1; j + 1 < H; j += 2) m = min3u(m, acc[j], acc[j + 1]);
@@ -276,8 +262,6 @@ __global__ __launch_bounds__(256) void k_find_one(const uint2* __restrict__ hay,
   }
 }
 
-constexpr int kPreMax = 7;  // largest threshold served by the low-word prefilter variant (r01: wins up to 7 on this kernel)
-
 }  // namespace
 
 int launch_find_one(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, uint64_t q, int thresh, unsigned* d_state,
@@ -311,30 +295,66 @@ int wait_find_one(const LoneBlock* h_block, unsigned long long seq, hipStream_t 
   }
 }
 
-int launch_hamm64_scan(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n,
-                       const uint64_t* d_q, size_t nq, int thresh, cbh_record* d_rec, size_t cap,
-                       unsigned long long* d_total, hipStream_t stream, unsigned flags,
-                       const uint64_t* d_qmask, const void* qx_given) {
-  if (n == 0 || nq == 0 || thresh <= 0) return CBH_OK;
-  if (n > 0xfffffff0ull || nq > CBH_MAX_QUERIES_PER_CALL) return CBH_E_INVAL;
-  // thresholds <= 8, "scan_mfma" 3: the bucketed join (hamm64_join.hip) when its candidate count says it is cheaper than
-  // looking at every pair (only asked where a scan would take >= 1 ms); 4: whenever it can represent the call (the parity
-  // suite).  As shipped (1) every pair is compared: the join avoids comparisons, it does not make them faster.
-  {
-    const int mode = get_scan_mfma();
-    const double scan_ms = (double)n * (double)nq * (thresh <= 6 ? 8.8e-12 : 16.3e-12);  // (prefilter / three-field kernel)
-    if ((mode == 4 || (mode == 3 && scan_ms >= 1.0)) && scan_join_possible(n, nq, thresh, flags, d_qmask)) {
-      const int rc = launch_hamm64_join(d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, flags, mode == 4,
-                                        scan_ms);
-      if (rc == CBH_OK || mode == 4 || (rc != CBH_E_UNSUPPORTED && rc != CBH_E_NOMEM)) return rc;
-      // (its scratch is all taken before the first record is written: a join that could not get it, like one whose count
-      // said no, leaves the call to the scan)
-      if (rc == CBH_E_NOMEM) cbh_clear_error();
-    }
-  }
-  if (scan_mfma_wanted(n, nq, thresh))
-    return launch_hamm64_scan_mfma(d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream,
-                                   flags, d_qmask, qx_given);
+// ---- which path a 64-bit search takes: the bucketed join, the popcount kernel above (EQ / PRE / FULL) or the matrix-core
+// scan (prefilter / three-field / two-field).  The knobs and constants below are read nowhere else; the data enter only
+// through the probe's rates and the join's own candidate count, which can still hand a call back.
+namespace {
+
+constexpr int kPreMax = 7;            // largest threshold served by the popcount kernel's low-word PRE form (r01: wins up to 7)
+constexpr size_t kMfmaMinNq = 256;    // below this the needle expansion + tile padding is not worth it
+constexpr size_t kMfmaMinN = 4096;
+// The prefilter kernel is twice as fast as the three-field kernel while its candidates are rare and loses to it when
+// they are not: every candidate costs a park / list / re-check (~110 SIMD cycles per event).  How many there are is a
+// property of the data -- r_cand(t) = P[popc(fold(a) ^ fold(b)) < t] over the launch's needle x slot pairs: 5.7e-5 at
+// t = 6 and 2.7e-4 at t = 7 for unrelated hashes, but anything for a library of scans of one form, blank frames or a video
+// against itself.  The three-field kernel in turn pays for every TRUE match (a flagged group goes through three passes
+// of sixteen ballots): ~4x what a candidate costs the prefilter, so where the candidates are mostly true matches -- a
+// dense cluster of near-identical hashes -- the prefilter wins again, at any rate.  Measured per 10^12 pairs
+// (tools/ab/adaptive_ab.py, profiles/r06_adaptive_ab*.jsonl):  T_pre = 8.8 ms + 6e4 ms x r_cand,  T_full = 16.3 ms +
+// 2.5e5 ms x r_true.  The probe counts both rates on a sample of the launch's pairs -- a few microseconds and one host
+// round trip, against launches of milliseconds -- and the prefilter is taken while
+//   r_cand - kTrueWeight x r_true <= "scan_pre_rate_e9" x 1e-9      (the rate at which the two kernels tie: 1.25e-4).
+// Launches too small to pay for the round trip, and a probe that cannot run, take the fixed rule (thresholds <= 6).
+constexpr int kPreStatic = 6;
+constexpr double kTrueWeight = 4.0;
+constexpr uint64_t kProbeMinPairs = 1ull << 31;  // ~20 us of scan: below this the probe's round trip is not worth it
+
+int g_scan_mfma = 1;             // "scan_mfma"
+int g_pre_max_thresh = -1;       // "scan_mfma_pre_max"
+int g_pre_rate_max_e9 = 125000;  // "scan_pre_rate_e9"
+std::atomic<uint64_t> g_pre_mask{0};        // bit t: the most recent matrix-core launch at threshold t took the prefilter
+std::atomic<uint64_t> g_n_probe{0};         // probes run
+std::atomic<long long> g_last_rate_e9{-1};  // candidate rate x 1e9 the last probe found for its threshold
+std::atomic<long long> g_last_true_e9{-1};  // ... and the rate of true (64-bit) matches
+
+enum class Join { None, IfCheaper, Forced };
+enum class Kernel { PopcEq, PopcPre, PopcFull, Mfma };
+struct Route {
+  Join join;
+  Kernel kernel;   // the scan: the whole call, or what a join that hands the call back leaves
+  double scan_ms;  // the scan's modelled time, which the join has to beat
+};
+
+// the route of one launch of n slots x nq needles (n, nq >= 1, n <= 0xfffffff0, thresh >= 1)
+Route route(size_t n, size_t nq, int thresh, bool masked) {
+  Route r;
+  r.scan_ms = (double)n * (double)nq * (thresh <= 6 ? 8.8e-12 : 16.3e-12);  // (prefilter / three-field kernel)
+  // thresholds <= 8, "scan_mfma" 3: the join when its candidate count says it is cheaper than looking at every pair (only
+  // asked where a scan would take >= 1 ms); 4: whenever it can represent the call (the parity suite).  As shipped (1)
+  // every pair is compared: the join avoids comparisons, it does not make them faster.
+  const bool joinable = thresh <= kJoinMaxThresh && !masked && n < 0xfffffff0ull;
+  r.join = !joinable ? Join::None : g_scan_mfma == 4 ? Join::Forced
+           : g_scan_mfma == 3 && r.scan_ms >= 1.0 ? Join::IfCheaper : Join::None;
+  // "scan_mfma" 2 and 4 force the matrix cores for any size (tests); 3 sizes like 1
+  const bool mfma = thresh <= 65 && (g_scan_mfma == 2 || g_scan_mfma == 4 ||
+                                     (g_scan_mfma != 0 && nq >= kMfmaMinNq && n >= kMfmaMinN));
+  r.kernel = mfma ? Kernel::Mfma : thresh == 1 ? Kernel::PopcEq : thresh <= kPreMax ? Kernel::PopcPre : Kernel::PopcFull;
+  return r;
+}
+
+int launch_popc(Kernel kernel, const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
+                int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
+                const ScanOpts& o) {
   const uint32_t tile = kThreads * kH;
   const uint32_t tiles = (uint32_t)((n + tile - 1) / tile);
   // needle chunk: enough workgroups to fill 256 CUs x 8 waves/SIMD several times over, but each
@@ -349,21 +369,76 @@ int launch_hamm64_scan(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n
   }
   dim3 grid(tiles, chunks), block(kThreads);
   const uint2* hay = reinterpret_cast<const uint2*>(d_hashes);
-#define CBH_SCAN(MODE, GROUP)                                                                 \
-  hipLaunchKernelGGL((k_hamm64_scan<kH, kQB, MODE, GROUP>), grid, block, 0, stream, hay,      \
-                     d_ids, (uint32_t)n, d_q, (uint32_t)nq, q_chunk, (uint32_t)thresh, d_rec, \
-                     (unsigned long long)cap, d_total, (uint32_t)(flags & 1u),                \
-                     reinterpret_cast<const uint2*>(d_qmask))
-  // (issue-rate-shaped variants only: GROUP; thresholds of 1 compare for equality)
-  if (thresh == 1)
-    CBH_SCAN(MODE_EQ, false);
-  else if (thresh <= kPreMax)
-    CBH_SCAN(MODE_PRE, true);
-  else
-    CBH_SCAN(MODE_FULL, true);
+#define CBH_SCAN(MODE)                                                                                                  \
+  hipLaunchKernelGGL((k_hamm64_scan<kH, kQB, MODE>), grid, block, 0, stream, hay, d_ids, (uint32_t)n, d_q, (uint32_t)nq, \
+                     q_chunk, (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total, (uint32_t)o.keep_id0,            \
+                     reinterpret_cast<const uint2*>(o.d_qmask))
+  if (kernel == Kernel::PopcEq) CBH_SCAN(MODE_EQ);
+  else if (kernel == Kernel::PopcPre) CBH_SCAN(MODE_PRE);
+  else CBH_SCAN(MODE_FULL);
 #undef CBH_SCAN
   CBH_HIP(hipGetLastError());
   return CBH_OK;
 }
+
+}  // namespace
+
+bool scan_takes_mfma(size_t n, size_t nq, int thresh) {
+  return thresh >= 1 && route(n, nq, thresh, false).kernel == Kernel::Mfma;
+}
+
+bool scan_pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
+                   hipStream_t stream) {
+  if (thresh > 32) return false;  // (the prefilter kernel's flag fields)
+  if (g_pre_max_thresh >= 0) return thresh <= g_pre_max_thresh;
+  if (thresh > kProbeMaxThresh) return false;
+  if ((uint64_t)n_total * (uint64_t)nq < kProbeMinPairs) return thresh <= kPreStatic;
+  double r_cand = 0, r_true = 0;
+  if (!probe_fold_rates(d_hashes, n, d_q, nq, thresh, stream, &r_cand, &r_true)) return thresh <= kPreStatic;
+  g_last_rate_e9 = (long long)(r_cand * 1e9);
+  g_last_true_e9 = (long long)(r_true * 1e9);
+  g_n_probe++;
+  return (r_cand - kTrueWeight * r_true) * 1e9 <= (double)g_pre_rate_max_e9;
+}
+
+int launch_hamm64_scan(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
+                       int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
+                       const ScanOpts& o) {
+  if (n == 0 || nq == 0 || thresh <= 0) return CBH_OK;
+  if (n > 0xfffffff0ull || nq > CBH_MAX_QUERIES_PER_CALL) return CBH_E_INVAL;
+  const Route r = route(n, nq, thresh, o.d_qmask != nullptr);
+  if (r.join != Join::None) {
+    const bool force = r.join == Join::Forced;
+    const int rc = launch_hamm64_join(d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, o.keep_id0, force,
+                                      r.scan_ms);
+    if (rc == CBH_OK || force || (rc != CBH_E_UNSUPPORTED && rc != CBH_E_NOMEM)) return rc;
+    // (its scratch is all taken before the first record is written: a join that could not get it, like one whose count
+    // said no, leaves the call to the scan)
+    if (rc == CBH_E_NOMEM) cbh_clear_error();
+  }
+  if (r.kernel != Kernel::Mfma) return launch_popc(r.kernel, d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, o);
+  const bool pre = o.pre >= 0 ? o.pre != 0 : scan_pick_pre(d_hashes, n, n, d_q, nq, thresh, stream);
+  if (thresh < 64) {
+    if (pre) g_pre_mask |= 1ull << thresh; else g_pre_mask &= ~(1ull << thresh);
+  }
+  return launch_hamm64_scan_mfma(d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, pre, o);
+}
+
+int set_scan_mfma(int mode) {
+  if (mode < 0 || mode > 4) return CBH_E_INVAL;
+  g_scan_mfma = mode;
+  return CBH_OK;
+}
+int get_scan_mfma() { return g_scan_mfma; }
+void set_scan_pre_max(int t) {
+  if (t >= -1 && t <= 32) g_pre_max_thresh = t;
+}
+void set_scan_pre_rate(int e9) {
+  if (e9 >= 0) g_pre_rate_max_e9 = e9;
+}
+long long get_scan_pre_mask() { return (long long)g_pre_mask.load(); }
+long long get_scan_probes() { return (long long)g_n_probe.load(); }
+long long get_scan_probe_rate_e9() { return g_last_rate_e9.load(); }
+long long get_scan_probe_true_e9() { return g_last_true_e9.load(); }
 
 }  // namespace cbh

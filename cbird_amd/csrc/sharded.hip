@@ -327,7 +327,7 @@ struct ShardLeases {
 }  // namespace
 
 int sharded_scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t nq, int thresh, hipStream_t stream,
-                     unsigned long long* total, unsigned flags, const uint64_t* d_qmask, size_t max_records) {
+                     unsigned long long* total, const ScanOpts& opts, size_t max_records) {
   ShardSet* S = idx->shards;
   ShardComm& C = S->comm;
   const size_t R = S->child.size();
@@ -343,9 +343,9 @@ int sharded_scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t 
   }
   // (declared ahead of the leases: given back after their destructor has drained every shard stream that may still read it
   // -- on the paths that succeed the root stream has waited for those shards and nothing is synchronised again)
-  void* qx_root = nullptr;
+  uint4* qx_root = nullptr;
   struct QxFree {
-    void*& p;
+    uint4*& p;
     hipStream_t st;
     int dev;
     ~QxFree() {
@@ -358,7 +358,7 @@ int sharded_scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t 
   ShardLeases L(S);
   if ((rc = L.acquire_all())) return rc;
   // ---- scan: every shard, its own device and stream ----
-  std::vector<const uint64_t*> q_of(R, d_q), mask_of(R, d_qmask);
+  std::vector<const uint64_t*> q_of(R, d_q), mask_of(R, opts.d_qmask);
   std::vector<unsigned long long> count(R, 0);
   std::vector<char> todo(R, 1);
   for (size_t s = 0; s < R; ++s) todo[s] = S->child[s]->n != 0;
@@ -383,11 +383,13 @@ int sharded_scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t 
   // are (every shard probing for itself cost a stream synchronisation per shard and threshold); and ONE expansion of the
   // needles into the matrix-core operand layout for all the shards of the root device (48 bytes per needle: eight of them
   // per threshold were 3.9 ms of kernel time beside the scans)
+  ScanOpts shard_opts = opts;
+  shard_opts.siblings = (unsigned)C.per_device;
   for (size_t s = 0; s < R; ++s) {
     cbh_idx64* c = S->child[s];
-    if (c->device == root && c->n != 0 && scan_mfma_wanted(c->n, nq, thresh)) {
+    if (c->device == root && c->n != 0 && scan_takes_mfma(c->n, nq, thresh)) {
       DeviceGuard g(root);
-      flags |= scan_pre_flags(c->d_hashes, c->n, idx->n, d_q, nq, thresh, stream);
+      shard_opts.pre = scan_pick_pre(c->d_hashes, c->n, idx->n, d_q, nq, thresh, stream);
       if ((rc = expand_needles_for_scan(d_q, nq, stream, &qx_root))) return rc;
       break;
     }
@@ -415,9 +417,9 @@ int sharded_scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t 
           if ((rc = Workspace::grow(&cw->d_q, &cw->q_cap, nq))) return rc;
           CBH_HIP(hipMemcpyPeerAsync(cw->d_q, c->device, d_q, root, nq * sizeof(uint64_t), cs));
           q_of[s] = cw->d_q;
-          if (d_qmask) {
+          if (opts.d_qmask) {
             if ((rc = Workspace::grow(&cw->d_qmask, &cw->qmask_cap, nq))) return rc;
-            CBH_HIP(hipMemcpyPeerAsync(cw->d_qmask, c->device, d_qmask, root, nq * sizeof(uint64_t), cs));
+            CBH_HIP(hipMemcpyPeerAsync(cw->d_qmask, c->device, opts.d_qmask, root, nq * sizeof(uint64_t), cs));
             mask_of[s] = cw->d_qmask;
           }
           C.n_peer_copies++;
@@ -426,10 +428,11 @@ int sharded_scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t 
       }
       if (!direct[s]) CBH_HIP(hipMemsetAsync(cw->d_total, 0, sizeof(unsigned long long), cs));
       if (timed) CBH_HIP(hipEventRecord(cw->ev0, cs));
+      ScanOpts o = shard_opts;
+      o.d_qmask = mask_of[s];
+      o.qx = c->device == root ? qx_root : nullptr;
       rc = launch_hamm64_scan(c->d_hashes, c->d_ids, c->n, q_of[s], nq, thresh, direct[s] ? ws->d_rec : cw->d_rec,
-                              direct[s] ? ws->rec_cap : cw->rec_cap, direct[s] ? ws->d_total : cw->d_total, cs,
-                              flags | ((unsigned)std::min(C.per_device, 255) << SCAN_SIBLINGS_SHIFT), mask_of[s],
-                              c->device == root ? qx_root : nullptr);
+                              direct[s] ? ws->rec_cap : cw->rec_cap, direct[s] ? ws->d_total : cw->d_total, cs, o);
       if (rc) return rc;
       if (timed || direct[s]) CBH_HIP(hipEventRecord(cw->ev1, cs));
       if (!direct[s])

@@ -121,7 +121,7 @@ int scan_to_host(cbh_vidx* v, const uint64_t* q, size_t nq, int thresh, std::vec
     CBH_HIP(hipMemcpyAsync(ws->d_qmask, masks.data(), nq * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
   }
   unsigned long long total = 0;
-  rc = scan_all(idx, ws, ws->d_q, nq, thresh, ws->stream, &total, 0, v->radix ? ws->d_qmask : nullptr);
+  rc = scan_all(idx, ws, ws->d_q, nq, thresh, ws->stream, &total, ScanOpts{false, v->radix ? ws->d_qmask : nullptr});
   if (rc) return rc;
   if ((rc = ws->ensure_sort())) return rc;
   rc = launch_sort_records(ws->d_rec, ws->d_alt, (size_t)total, nq, ws->d_tmp, ws->tmp_bytes, ws->stream);
@@ -194,7 +194,7 @@ int reduce_on_device(cbh_vidx* v, const std::vector<uint64_t>& q, const std::vec
     CBH_HIP(hipMemcpyAsync(ws->d_qmask, masks.data(), nq * sizeof(uint64_t), hipMemcpyHostToDevice, s));
   }
   unsigned long long total = 0;
-  rc = scan_all(idx, ws, ws->d_q, nq, thresh, s, &total, 0, v->radix ? ws->d_qmask : nullptr);
+  rc = scan_all(idx, ws, ws->d_q, nq, thresh, s, &total, ScanOpts{false, v->radix ? ws->d_qmask : nullptr});
   if (rc) return rc;
   if (total == 0) return CBH_OK;
   if (total >= (1ull << 32)) return CBH_E_OVERFLOW;

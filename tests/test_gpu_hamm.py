@@ -448,3 +448,51 @@ def test_bucketed_join_equals_the_scan_and_steps_aside_on_skewed_data(gpu, orc, 
             del idx
     finally:
         L.cbh_set_tuning(b"scan_mfma", 1)
+
+
+def test_scan_route_counters_on_plain_and_sharded_handles(gpu, scan_path):
+    """Which path a 64-bit search takes, read through the counters behind cbh_get_tuning, on a plain handle and on five
+    shards of one device: at "scan_mfma" 1 a batch of 4096 needles on 2^20 slots at threshold 6 runs ONE candidate-rate
+    probe (a sharded call probes once for all its shards); a batch of fewer than 256 needles takes the popcount kernel --
+    no probe, "scan_pre_mask" untouched whatever "scan_mfma_pre_max" says; "scan_mfma" 4 at thresholds <= 8 runs the join
+    once per launch that has slots (one per non-empty shard), and not at all above 8."""
+    from cbird_amd import _lib, synth
+
+    if scan_path != "mfma":
+        pytest.skip("sets the routing knobs itself: once is enough")
+    L = _lib.lib()
+
+    def get(key):
+        v = C.c_longlong(0)
+        assert L.cbh_get_tuning(key, C.byref(v)) == 0
+        return v.value
+
+    h, ids = synth.make_hashes(1 << 20, seed=99)
+    try:
+        for shape in (None, (1, 5)):
+            _lib.set_default_sharding(shape)
+            idx, tiny = gpu.DctHashIndex(), gpu.DctHashIndex()
+            idx.load(h, ids)
+            tiny.load(h[:100], ids[:100])
+            L.cbh_set_tuning(b"scan_mfma", 1)
+            L.cbh_set_tuning(b"scan_mfma_pre_max", -1)
+            p0 = get(b"scan_probes")
+            idx.find_batch(h[:4096], 6, 4)
+            assert get(b"scan_probes") == p0 + 1, shape
+            mask = get(b"scan_pre_mask")
+            for pre_max in (0, 32, -1):  # (one of the first two would flip bit 6 if the call reached the matrix cores)
+                L.cbh_set_tuning(b"scan_mfma_pre_max", pre_max)
+                idx.find_batch(h[:200], 6, 4)
+                assert get(b"scan_probes") == p0 + 1 and get(b"scan_pre_mask") == mask, (shape, pre_max)
+            L.cbh_set_tuning(b"scan_mfma", 4)
+            for ix in (idx, tiny):
+                launches = sum(1 for c in ix.shard_counts() if c)
+                for dht in (1, 5, 8, 9):
+                    j0 = get(b"scan_joins")
+                    ix.find_batch(h[:2048], dht, 4)
+                    assert get(b"scan_joins") - j0 == (launches if dht <= 8 else 0), (shape, ix.shard_counts(), dht)
+            del idx, tiny
+    finally:
+        _lib.set_default_sharding(None)
+        L.cbh_set_tuning(b"scan_mfma", 2)
+        L.cbh_set_tuning(b"scan_mfma_pre_max", -1)
