@@ -291,6 +291,23 @@ int sharded_scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t 
 int sharded_download(const cbh_idx64* idx, uint64_t* hashes, uint32_t* ids, size_t cap);
 }  // namespace cbh
 
+// what scan_all and sharded_scan_all share: the size of the first record block of a call, ...
+inline size_t first_record_block(const cbh_idx64* idx, size_t max_records) {
+  return std::min(std::max<size_t>(idx->rec_cap_default, 1024), std::max<size_t>(max_records, 1024));
+}
+// ... growing a block for a counted result (no memory for it: the result does not fit, CBH_E_OVERFLOW), ...
+inline int grow_for_result(Workspace* ws, unsigned long long records) {
+  const int rc = ws->ensure_records((size_t)records + 1024);
+  return rc == CBH_E_NOMEM ? CBH_E_OVERFLOW : rc;
+}
+// ... and the entry of one scan over the whole index in cbh_idx64_get_stats
+inline void count_scan(cbh_idx64* idx, size_t nq, float ms) {
+  std::lock_guard<std::mutex> lk(idx->stats_mu);
+  idx->stats.scan_launches += 1;
+  idx->stats.scan_pairs += (uint64_t)idx->n * (uint64_t)nq;
+  idx->stats.scan_ms += (double)ms;
+}
+
 // scan into the workspace record buffer, growing it until every record fits.
 // On return *total = number of matching pairs, all of them present in ws->d_rec.
 // max_records: a result larger than this is not materialised -- CBH_E_OVERFLOW with *total set, and the workspace is
@@ -299,7 +316,7 @@ inline int scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t n
                     hipStream_t stream, unsigned long long* total, const ScanOpts& opts = {},
                     size_t max_records = ~(size_t)0) {
   if (idx->shards) return sharded_scan_all(idx, ws, d_q, nq, thresh, stream, total, opts, max_records);
-  int rc = ws->ensure_records(std::min(std::max<size_t>(idx->rec_cap_default, 1024), std::max<size_t>(max_records, 1024)));
+  int rc = ws->ensure_records(first_record_block(idx, max_records));
   if (rc) return rc;
   for (int attempt = 0; attempt < 3; ++attempt) {
     CBH_HIP(hipMemsetAsync(ws->d_total, 0, sizeof(unsigned long long), stream));
@@ -312,21 +329,13 @@ inline int scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t n
                            hipMemcpyDeviceToHost, stream));
     CBH_HIP(hipStreamSynchronize(stream));
     *total = *ws->h_total;
-    {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, ws->ev0, ws->ev1) == hipSuccess) {
-        std::lock_guard<std::mutex> lk(idx->stats_mu);
-        idx->stats.scan_launches += 1;
-        idx->stats.scan_pairs += (uint64_t)idx->n * (uint64_t)nq;
-        idx->stats.scan_ms += (double)ms;
-      }
-    }
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ws->ev0, ws->ev1) == hipSuccess) count_scan(idx, nq, ms);
     if (*total <= ws->rec_cap) return CBH_OK;
     if (*total > max_records) return CBH_E_OVERFLOW;  // the caller does not want a result of this size
     // every match must be materialised to be ordered: grow and rescan
     CBH_HIP(hipStreamSynchronize(stream));
-    rc = ws->ensure_records((size_t)*total + 1024);
-    if (rc) return rc == CBH_E_NOMEM ? CBH_E_OVERFLOW : rc;
+    if ((rc = grow_for_result(ws, *total))) return rc;
   }
   return CBH_E_OVERFLOW;
 }

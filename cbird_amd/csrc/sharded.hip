@@ -12,10 +12,16 @@
 // block".  Everything above it (the K4 cut, fdct votes, video reduce, searchIndex escalation, the coalescer's self-join)
 // runs unchanged on the root device over the merged block.
 //
-//   scan      every shard scans its slots for all needles on its own device and stream, into its own block
-//             { u64 count; records[cap] } (needles reach the other devices by peer copies behind an event);
-//             the host reads the R counts (the one synchronisation scan_all always had); only a shard whose block
-//             overflowed grows it and scans again
+//   scan      in phases over one ShardRun per shard; sharded_scan_all is the loop that calls them:
+//             plan       once per call.  The shards of the root device are DIRECT: they append straight into the root block
+//                        through its one counter -- no block, count read-back, synchronisation or copy of their own --
+//                        unless the exchange is the collective, whose send buffers are the devices' own blocks
+//             launch     every shard that has to run scans on its own device and stream behind an event of the root stream;
+//                        a shard that is not direct fills its own block { u64 count; records[cap] }
+//             collect    the direct shards share one wait on the root stream and one read of its counter; any other shard
+//                        synchronises and reads its own, and if its block overflowed it alone grows it and runs again
+//             settle     a root block too small for the sum grows, and the direct shards run again
+//             finish     statistics, the exchange below for the shards that are not direct, word 0 = total
 //   exchange  ShardComm::exchange (cbh_shard.h; shared with the sharded CvFeaturesIndex, idx256.hip) --
 //             inside a device: device-to-device copies of exactly count_s records behind each other;
 //             between devices: ONE grouped ncclAllGather of the per-device blocks, sized to the fullest device
@@ -292,261 +298,260 @@ namespace {
 constexpr size_t kKeepXBufBytes = (size_t)64 << 20;  // exchange buffers above this go back after the call
 constexpr size_t kKeepShardRecs = (size_t)1 << 22;   // a shard's record block above this (32 MB) likewise
 
-// leases of one call: a workspace per shard, given back (idle) at the end
+// One shard for the length of one call.  `drained`: nothing this call put on the shard's stream can still be running.  Two
+// operations touch it: work(), through which every enqueue goes, clears it; saw_drained(), where the host saw that, sets it.
+struct ShardRun {
+  cbh_idx64* c = nullptr;        // the child index
+  Workspace* ws = nullptr;       // leased from it
+  bool direct = false;           // lives on the root device: appends into the root block through the root counter
+  bool todo = false;             // has to scan in the next round (a lone find: launched, not yet collected)
+  unsigned long long count = 0;  // records in its own block (the direct shards' are ScanCall::direct_count)
+  const uint64_t *q = nullptr, *qmask = nullptr;  // needles and masks on its own device
+  bool drained = true;           // (a workspace is idle when it is leased)
+  hipStream_t work() { return drained = false, ws->stream; }
+  void saw_drained() { drained = true; }
+};
+
+// what one call holds: a workspace per shard, and the needles expanded for the root device's shards (scans only)
 struct ShardLeases {
-  ShardSet* S;
-  std::vector<Workspace*> ws;
-  std::vector<char> idle;  // the call has already seen this shard's stream drained (see sharded_scan_all's end)
-  explicit ShardLeases(ShardSet* s) : S(s), ws(s->child.size(), nullptr), idle(s->child.size(), 0) {}
+  std::vector<ShardRun> run;
+  uint4* qx_root = nullptr;  // the shards read it on their own streams; allocated on the root stream
+  hipStream_t root_stream;
+  int root;
+  ShardLeases(cbh_idx64* idx, hipStream_t st) : run(idx->shards->child.size()), root_stream(st), root(idx->device) {
+    for (size_t s = 0; s < run.size(); ++s) run[s].c = idx->shards->child[s];
+  }
   int acquire_all() {
-    for (size_t s = 0; s < ws.size(); ++s) {
-      DeviceGuard g(S->child[s]->device);
+    for (ShardRun& r : run) {
+      DeviceGuard g(r.c->device);
       if (!g.ok) return CBH_E_NODEVICE;
       int rc = CBH_OK;
-      ws[s] = S->child[s]->acquire(&rc);
-      if (!ws[s]) return rc ? rc : CBH_E_NOMEM;
+      r.ws = r.c->acquire(&rc);
+      if (!r.ws) return rc ? rc : CBH_E_NOMEM;
     }
     return CBH_OK;
   }
+  // In this order: every shard stream not known drained is synchronised, so that its workspace, shrunk, goes back idle to
+  // its pool; only then qx_root, which those streams may have been reading, is freed on the root stream.  (On the paths
+  // that succeed the root stream has waited for the shards and nothing is synchronised here.)
   ~ShardLeases() {
-    for (size_t s = 0; s < ws.size(); ++s)
-      if (ws[s]) {
-        DeviceGuard g(S->child[s]->device);
-        // its buffers must be idle when the next call takes it (6.5 us per synchronisation even on a drained stream: a
-        // lone find() on 8 shards spent 52 of its 230 us here)
-        if (!idle[s]) (void)hipStreamSynchronize(ws[s]->stream);
+    for (ShardRun& r : run)
+      if (r.ws) {
+        DeviceGuard g(r.c->device);
+        // (6.5 us per synchronisation even on a drained stream: a lone find() on 8 shards spent 52 of its 230 us here)
+        if (!r.drained) (void)hipStreamSynchronize(r.ws->stream);
         // one large result (a self-join attempt) must not leave every shard holding a block of that size for good
-        ws[s]->shrink_records(std::max<size_t>(S->child[s]->rec_cap_default, kKeepShardRecs));
-        for (XBuf& x : ws[s]->x)
+        r.ws->shrink_records(std::max<size_t>(r.c->rec_cap_default, kKeepShardRecs));
+        for (XBuf& x : r.ws->x)
           if (x.bytes > kKeepXBufBytes) x.release();
-        S->child[s]->give_back(ws[s]);
+        r.c->give_back(r.ws);
       }
+    if (qx_root) {
+      DeviceGuard g(root);
+      (void)free_async(qx_root, root_stream);
+    }
   }
 };
+
+// the arguments of one sharded_scan_all, what plan_scan decides once for it, and the tallies of its rounds
+struct ScanCall {
+  cbh_idx64* idx;
+  Workspace* ws;  // the root workspace: the merged block ends up in it
+  const uint64_t* d_q;
+  size_t nq, max_records;
+  int thresh;
+  hipStream_t stream;
+  unsigned long long* total;
+  ScanOpts opts;  // the caller's; plan_scan adds the siblings and the prefilter choice
+  ShardLeases L;
+  ShardComm& C;  // (an aggregate: sharded_scan_all fills it down to here)
+  bool timed = false, any_direct = false;
+  unsigned long long direct_count = 0;  // records the direct shards have appended to the root block
+  float scan_ms = 0.f;
+  bool pending(bool direct_only = false) const {
+    return std::any_of(L.run.begin(), L.run.end(), [=](const ShardRun& r) { return r.todo && (r.direct || !direct_only); });
+  }
+  unsigned long long sum() const {  // as far as the shards have reported
+    unsigned long long t = direct_count;
+    for (const ShardRun& r : L.run) t += r.count;
+    return t;
+  }
+};
+
+// plan: what is decided once per call
+int plan_scan(ScanCall& K) {
+  const bool collective = g_exchange == 0 && (K.C.devices.size() > 1 || g_force_rccl);
+  for (ShardRun& r : K.L.run) {
+    r.todo = r.c->n != 0;
+    r.direct = !collective && r.todo && r.c->device == K.L.root;
+    K.any_direct = K.any_direct || r.direct;
+    r.q = K.d_q, r.qmask = K.opts.d_qmask;
+  }
+  // kernel timing (cbh_idx64_get_stats) only where it can matter: a handful of needles is launch-bound, every HIP call counts
+  K.timed = K.nq >= 256;
+  // prefilter or three-field kernel: one probe for the whole call, on the slots of a shard that lives where the needles
+  // are (every shard probing for itself cost a stream synchronisation per shard and threshold); and ONE expansion of the
+  // needles into the matrix-core operand layout for all the shards of the root device (48 bytes per needle)
+  K.opts.siblings = (unsigned)K.C.per_device;
+  for (const ShardRun& r : K.L.run)
+    if (r.c->device == K.L.root && r.c->n != 0 && scan_takes_mfma(r.c->n, K.nq, K.thresh)) {
+      DeviceGuard g(K.L.root);
+      K.opts.pre = scan_pick_pre(r.c->d_hashes, r.c->n, K.idx->n, K.d_q, K.nq, K.thresh, K.stream);
+      return expand_needles_for_scan(K.d_q, K.nq, K.stream, &K.L.qx_root);
+    }
+  return CBH_OK;
+}
+
+// launch a round
+int launch_round(ScanCall& K, int attempt) {
+  const bool direct_now = K.pending(true);
+  DeviceGuard on_root(K.L.root);
+  if (direct_now) CBH_HIP(hipMemsetAsync(K.ws->d_total, 0, sizeof(unsigned long long), K.stream));
+  // the needles (and masks, the expansion, the zeroed counter) are complete on the root device
+  if (attempt == 0 || direct_now) CBH_HIP(hipEventRecord(K.ws->ev0, K.stream));
+  for (ShardRun& r : K.L.run) {
+    if (!r.todo) continue;
+    cbh_idx64* c = r.c;
+    Workspace* cw = r.ws;
+    DeviceGuard g(c->device);
+    if (!g.ok) return CBH_E_NODEVICE;
+    hipStream_t cs = r.work();
+    int rc;
+    if (attempt == 0 || r.direct) CBH_HIP(hipStreamWaitEvent(cs, K.ws->ev0, 0));
+    if (attempt == 0) {         // the shard's first run
+      if (c->device != K.L.root) {  // replicate the needles: one peer copy per shard and call (8 B per needle)
+        if ((rc = Workspace::grow(&cw->d_q, &cw->q_cap, K.nq))) return rc;
+        CBH_HIP(hipMemcpyPeerAsync(cw->d_q, c->device, K.d_q, K.L.root, K.nq * sizeof(uint64_t), cs));
+        r.q = cw->d_q;
+        if (r.qmask) {
+          if ((rc = Workspace::grow(&cw->d_qmask, &cw->qmask_cap, K.nq))) return rc;
+          CBH_HIP(hipMemcpyPeerAsync(cw->d_qmask, c->device, r.qmask, K.L.root, K.nq * sizeof(uint64_t), cs));
+          r.qmask = cw->d_qmask;
+        }
+        K.C.n_peer_copies++;
+      }
+      if (!r.direct && (rc = cw->ensure_records(std::max<size_t>(c->rec_cap_default, 1024)))) return rc;
+    }
+    if (!r.direct) CBH_HIP(hipMemsetAsync(cw->d_total, 0, sizeof(unsigned long long), cs));
+    if (K.timed) CBH_HIP(hipEventRecord(cw->ev0, cs));
+    Workspace* into = r.direct ? K.ws : cw;
+    ScanOpts o = K.opts;
+    o.d_qmask = r.qmask;
+    o.qx = c->device == K.L.root ? K.L.qx_root : nullptr;
+    rc = launch_hamm64_scan(c->d_hashes, c->d_ids, c->n, r.q, K.nq, K.thresh, into->d_rec, into->rec_cap, into->d_total, cs, o);
+    if (rc) return rc;
+    if (K.timed || r.direct) CBH_HIP(hipEventRecord(cw->ev1, cs));
+    if (!r.direct)
+      CBH_HIP(hipMemcpyAsync(cw->h_total, cw->d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
+    K.C.n_scans++;
+    if (attempt) K.C.n_rescans++;
+  }
+  return CBH_OK;
+}
+
+// collect a round; *worst = the slowest kernel of the round
+int collect_round(ScanCall& K, float* worst) {
+  float ms = 0.f;
+  if (K.pending(true)) {
+    DeviceGuard g(K.L.root);
+    for (const ShardRun& r : K.L.run)
+      if (r.todo && r.direct) CBH_HIP(hipStreamWaitEvent(K.stream, r.ws->ev1, 0));
+    CBH_HIP(hipMemcpyAsync(K.ws->h_total, K.ws->d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, K.stream));
+    CBH_HIP(hipStreamSynchronize(K.stream));
+    K.direct_count = *K.ws->h_total;
+    for (ShardRun& r : K.L.run) {
+      if (!r.todo || !r.direct) continue;
+      if (K.timed && hipEventElapsedTime(&ms, r.ws->ev0, r.ws->ev1) == hipSuccess) *worst = std::max(*worst, ms);
+      r.todo = false;
+      r.saw_drained();  // its stream's last operation is the event the root stream waited for, and that stream is drained
+    }
+  }
+  for (ShardRun& r : K.L.run) {
+    if (!r.todo) continue;
+    Workspace* cw = r.ws;
+    DeviceGuard g(r.c->device);
+    CBH_HIP(hipStreamSynchronize(cw->stream));
+    r.saw_drained();
+    r.count = *cw->h_total;
+    if (K.timed && hipEventElapsedTime(&ms, cw->ev0, cw->ev1) == hipSuccess) *worst = std::max(*worst, ms);
+    r.todo = false;
+    if (r.count > cw->rec_cap) {
+      if (K.sum() > K.max_records && K.sum() > K.ws->rec_cap) {  // the merged result cannot fit anyway
+        *K.total = K.sum();
+        return CBH_E_OVERFLOW;
+      }
+      if (int rc = grow_for_result(cw, r.count)) return rc;
+      r.todo = true;
+    }
+  }
+  return CBH_OK;
+}
+
+// settle the root block, once every shard has reported
+int settle_root_block(ScanCall& K) {
+  const unsigned long long sum = K.sum();
+  if (sum <= K.ws->rec_cap) return CBH_OK;
+  *K.total = sum;
+  if (sum > K.max_records) return CBH_E_OVERFLOW;  // nobody grows for it
+  DeviceGuard g(K.L.root);
+  CBH_HIP(hipStreamSynchronize(K.stream));
+  if (int rc = grow_for_result(K.ws, sum)) return rc;  // (a new block: what the direct shards appended is gone)
+  for (ShardRun& r : K.L.run) r.todo = r.direct;
+  K.direct_count = 0;
+  return CBH_OK;
+}
+
+// finish
+int finish_scan(ScanCall& K) {
+  count_scan(K.idx, K.nq, K.scan_ms);
+  const unsigned long long sum = K.sum(), remote = sum - K.direct_count;
+  *K.total = sum;
+  if (sum > K.ws->rec_cap) return CBH_E_OVERFLOW;
+  // all of it is in place, the counter holds the sum, and every shard that ran has been seen drained
+  if (!remote && K.any_direct) return CBH_OK;
+  std::vector<ShardPart> parts(K.L.run.size());
+  for (size_t s = 0; s < parts.size(); ++s) {
+    ShardRun& r = K.L.run[s];
+    Workspace* w = r.ws;  // (its d_total heads the shard's own block { count, records[rec_cap] })
+    parts[s] = ShardPart{K.C.dev_pos_of_shard(s), r.work(), reinterpret_cast<const unsigned long long*>(w->d_rec), r.count,
+                         w->d_total, w->rec_cap, w->ev1, w->x, w->h_total};
+  }
+  bool by_collective = true;
+  int rc = K.C.exchange(parts, K.stream, reinterpret_cast<unsigned long long*>(K.ws->d_rec), &by_collective, K.direct_count);
+  if (rc) return rc;
+  DeviceGuard g(K.L.root);
+  *K.ws->h_total = sum;
+  CBH_HIP(hipMemcpyAsync(K.ws->d_total, K.ws->h_total, sizeof(unsigned long long), hipMemcpyHostToDevice, K.stream));
+  CBH_HIP(hipStreamSynchronize(K.stream));  // scan_all's contract: the block is complete on return
+  // Copies: a shard stream's last operation is its record copy + event, which `stream` waited for before the synchronisation
+  // just done.  (A collective may leave the peers' halves of the all-gather in flight: synchronised when the leases end.)
+  if (!by_collective)
+    for (ShardRun& r : K.L.run) r.saw_drained();
+  return CBH_OK;
+}
 
 }  // namespace
 
 int sharded_scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t nq, int thresh, hipStream_t stream,
                      unsigned long long* total, const ScanOpts& opts, size_t max_records) {
-  ShardSet* S = idx->shards;
-  ShardComm& C = S->comm;
-  const size_t R = S->child.size();
-  const int root = idx->device;
   *total = 0;
   // the root block must exist whatever happens (consumers read word 0)
-  int rc = ws->ensure_records(std::min(std::max<size_t>(idx->rec_cap_default, 1024), std::max<size_t>(max_records, 1024)));
+  int rc = ws->ensure_records(first_record_block(idx, max_records));
   if (rc) return rc;
   if (nq == 0 || idx->n == 0 || thresh <= 0) {
     CBH_HIP(hipMemsetAsync(ws->d_total, 0, sizeof(unsigned long long), stream));
     CBH_HIP(hipStreamSynchronize(stream));
     return CBH_OK;
   }
-  // (declared ahead of the leases: given back after their destructor has drained every shard stream that may still read it
-  // -- on the paths that succeed the root stream has waited for those shards and nothing is synchronised again)
-  uint4* qx_root = nullptr;
-  struct QxFree {
-    uint4*& p;
-    hipStream_t st;
-    int dev;
-    ~QxFree() {
-      if (p) {
-        DeviceGuard g(dev);
-        (void)free_async(p, st);
-      }
-    }
-  } qx_free{qx_root, stream, root};
-  ShardLeases L(S);
-  if ((rc = L.acquire_all())) return rc;
-  // ---- scan: every shard, its own device and stream ----
-  std::vector<const uint64_t*> q_of(R, d_q), mask_of(R, opts.d_qmask);
-  std::vector<unsigned long long> count(R, 0);
-  std::vector<char> todo(R, 1);
-  for (size_t s = 0; s < R; ++s) todo[s] = S->child[s]->n != 0;
-  // Shards that live on the root device append STRAIGHT into the root block through its one counter (the scan kernels
-  // append with one atomic per wave and flush: eight kernels on a counter cost what one does): no block of their own, no
-  // count read-back and stream synchronisation per shard, no copy into place -- per threshold a handle over 8 shards of one
-  // device spent ~140 us between its scans and its cut on exactly those (tools/ab/sharded_trace.py).  Not under the
-  // collective exchange, whose send buffers are the devices' own blocks.
-  const bool collective_mode = g_exchange == 0 && (C.devices.size() > 1 || g_force_rccl);
-  std::vector<char> direct(R, 0);
-  bool any_direct = false;
-  for (size_t s = 0; s < R; ++s) {
-    direct[s] = !collective_mode && todo[s] && S->child[s]->device == root;
-    any_direct = any_direct || direct[s];
-  }
-  unsigned long long direct_count = 0;
-  float scan_ms = 0.f;
-  // kernel timing for cbh_idx64_get_stats only where it can matter: a handful of needles is launch-bound, and every
-  // HIP call counts there (a lone find() on 8 shards: ~12 calls per shard from this one thread)
-  const bool timed = nq >= 256;
-  // prefilter or three-field kernel: one probe for the whole call, on the slots of a shard that lives where the needles
-  // are (every shard probing for itself cost a stream synchronisation per shard and threshold); and ONE expansion of the
-  // needles into the matrix-core operand layout for all the shards of the root device (48 bytes per needle: eight of them
-  // per threshold were 3.9 ms of kernel time beside the scans)
-  ScanOpts shard_opts = opts;
-  shard_opts.siblings = (unsigned)C.per_device;
-  for (size_t s = 0; s < R; ++s) {
-    cbh_idx64* c = S->child[s];
-    if (c->device == root && c->n != 0 && scan_takes_mfma(c->n, nq, thresh)) {
-      DeviceGuard g(root);
-      shard_opts.pre = scan_pick_pre(c->d_hashes, c->n, idx->n, d_q, nq, thresh, stream);
-      if ((rc = expand_needles_for_scan(d_q, nq, stream, &qx_root))) return rc;
-      break;
-    }
-  }
-  for (int attempt = 0; attempt < 4; ++attempt) {
-    bool any = false, any_direct_now = false;
-    for (size_t s = 0; s < R; ++s) any_direct_now = any_direct_now || (todo[s] && direct[s]);
-    {
-      DeviceGuard g(root);
-      if (any_direct_now) CBH_HIP(hipMemsetAsync(ws->d_total, 0, sizeof(unsigned long long), stream));
-      // the needles (and masks, the expansion, the zeroed counter) are complete on the root device
-      if (attempt == 0 || any_direct_now) CBH_HIP(hipEventRecord(ws->ev0, stream));
-    }
-    for (size_t s = 0; s < R; ++s) {
-      if (!todo[s]) continue;
-      any = true;
-      cbh_idx64* c = S->child[s];
-      Workspace* cw = L.ws[s];
-      DeviceGuard g(c->device);
-      if (!g.ok) return CBH_E_NODEVICE;
-      hipStream_t cs = cw->stream;
-      if (attempt == 0 || direct[s]) CBH_HIP(hipStreamWaitEvent(cs, ws->ev0, 0));
-      if (attempt == 0) {
-        if (c->device != root) {  // replicate the needles: one peer copy per shard and call (8 B per needle)
-          if ((rc = Workspace::grow(&cw->d_q, &cw->q_cap, nq))) return rc;
-          CBH_HIP(hipMemcpyPeerAsync(cw->d_q, c->device, d_q, root, nq * sizeof(uint64_t), cs));
-          q_of[s] = cw->d_q;
-          if (opts.d_qmask) {
-            if ((rc = Workspace::grow(&cw->d_qmask, &cw->qmask_cap, nq))) return rc;
-            CBH_HIP(hipMemcpyPeerAsync(cw->d_qmask, c->device, opts.d_qmask, root, nq * sizeof(uint64_t), cs));
-            mask_of[s] = cw->d_qmask;
-          }
-          C.n_peer_copies++;
-        }
-        if (!direct[s] && (rc = cw->ensure_records(std::max<size_t>(c->rec_cap_default, 1024)))) return rc;
-      }
-      if (!direct[s]) CBH_HIP(hipMemsetAsync(cw->d_total, 0, sizeof(unsigned long long), cs));
-      if (timed) CBH_HIP(hipEventRecord(cw->ev0, cs));
-      ScanOpts o = shard_opts;
-      o.d_qmask = mask_of[s];
-      o.qx = c->device == root ? qx_root : nullptr;
-      rc = launch_hamm64_scan(c->d_hashes, c->d_ids, c->n, q_of[s], nq, thresh, direct[s] ? ws->d_rec : cw->d_rec,
-                              direct[s] ? ws->rec_cap : cw->rec_cap, direct[s] ? ws->d_total : cw->d_total, cs, o);
-      if (rc) return rc;
-      if (timed || direct[s]) CBH_HIP(hipEventRecord(cw->ev1, cs));
-      if (!direct[s])
-        CBH_HIP(hipMemcpyAsync(cw->h_total, cw->d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
-      C.n_scans++;
-      if (attempt) C.n_rescans++;
-    }
-    if (!any) break;
+  ScanCall K{idx, ws, d_q, nq, max_records, thresh, stream, total, opts, ShardLeases(idx, stream), idx->shards->comm};
+  if ((rc = K.L.acquire_all()) || (rc = plan_scan(K))) return rc;
+  for (int attempt = 0; attempt < 4 && K.pending(); ++attempt) {
     float worst = 0.f;
-    if (any_direct_now) {  // one wait for all of them, on the root stream
-      DeviceGuard g(root);
-      for (size_t s = 0; s < R; ++s)
-        if (todo[s] && direct[s]) CBH_HIP(hipStreamWaitEvent(stream, L.ws[s]->ev1, 0));
-      CBH_HIP(hipMemcpyAsync(ws->h_total, ws->d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-      CBH_HIP(hipStreamSynchronize(stream));
-      direct_count = *ws->h_total;
-      for (size_t s = 0; s < R; ++s) {
-        if (!todo[s] || !direct[s]) continue;
-        float ms = 0.f;
-        if (timed && hipEventElapsedTime(&ms, L.ws[s]->ev0, L.ws[s]->ev1) == hipSuccess) worst = std::max(worst, ms);
-        todo[s] = 0;
-        L.idle[s] = 1;  // (its stream's last operation is the event the root stream waited for, and that stream is drained)
-      }
-    }
-    for (size_t s = 0; s < R; ++s) {
-      if (!todo[s]) continue;
-      cbh_idx64* c = S->child[s];
-      Workspace* cw = L.ws[s];
-      DeviceGuard g(c->device);
-      CBH_HIP(hipStreamSynchronize(cw->stream));
-      count[s] = *cw->h_total;
-      float ms = 0.f;
-      if (timed && hipEventElapsedTime(&ms, cw->ev0, cw->ev1) == hipSuccess) worst = std::max(worst, ms);
-      todo[s] = 0;
-      if (count[s] > cw->rec_cap) {  // this shard alone grows its block and scans again
-        unsigned long long others = direct_count;
-        for (size_t o = 0; o < R; ++o)
-          if (o != s) others += count[o];
-        if (others + count[s] > max_records && others + count[s] > ws->rec_cap) {  // the merged result cannot fit anyway
-          *total = others + count[s];
-          return CBH_E_OVERFLOW;
-        }
-        rc = cw->ensure_records((size_t)count[s] + 1024);
-        if (rc) return rc == CBH_E_NOMEM ? CBH_E_OVERFLOW : rc;
-        todo[s] = 1;
-      }
-    }
-    scan_ms += worst;  // the shards run side by side: a round costs what its slowest shard costs
-    bool pending = false;
-    for (size_t s = 0; s < R; ++s) pending = pending || todo[s];
-    if (pending) continue;
-    // every shard has reported: does the root block hold the whole result?
-    unsigned long long sum = direct_count;
-    for (size_t s = 0; s < R; ++s) sum += count[s];
-    if (sum <= ws->rec_cap) break;
-    *total = sum;
-    if (sum > max_records) return CBH_E_OVERFLOW;  // nobody grows for it
-    {
-      DeviceGuard g(root);
-      CBH_HIP(hipStreamSynchronize(stream));
-      rc = ws->ensure_records((size_t)sum + 1024);  // (a new block: what the root device's shards appended is gone)
-      if (rc) return rc == CBH_E_NOMEM ? CBH_E_OVERFLOW : rc;
-    }
-    if (!any_direct) break;
-    for (size_t s = 0; s < R; ++s) todo[s] = direct[s];
-    direct_count = 0;
+    if ((rc = launch_round(K, attempt)) || (rc = collect_round(K, &worst))) return rc;
+    K.scan_ms += worst;  // the shards run side by side: a round costs what its slowest shard costs
+    if (!K.pending() && (rc = settle_root_block(K))) return rc;
   }
-  for (size_t s = 0; s < R; ++s)
-    if (todo[s]) return CBH_E_OVERFLOW;
-  {
-    std::lock_guard<std::mutex> lk(idx->stats_mu);
-    idx->stats.scan_launches += 1;
-    idx->stats.scan_pairs += (uint64_t)idx->n * (uint64_t)nq;
-    idx->stats.scan_ms += (double)scan_ms;
-  }
-  unsigned long long sum = direct_count, remote = 0;
-  for (size_t s = 0; s < R; ++s) remote += count[s];
-  sum += remote;
-  *total = sum;
-  if (sum > ws->rec_cap) return CBH_E_OVERFLOW;
-  if (!remote && any_direct) {
-    // all of it is in place, the counter holds the sum, and the root stream was drained when the count was read
-    for (size_t s = 0; s < R; ++s) L.idle[s] = 1;
-    return CBH_OK;
-  }
-  // ---- exchange: the other shards' records into the root block, behind what the root device's appended ----
-  std::vector<ShardPart> parts(R);
-  for (size_t s = 0; s < R; ++s) {
-    Workspace* cw = L.ws[s];
-    parts[s].dev_pos = C.dev_pos_of_shard(s);
-    parts[s].stream = cw->stream;
-    parts[s].d_rec = reinterpret_cast<const unsigned long long*>(cw->d_rec);
-    parts[s].count = count[s];
-    parts[s].own_block = cw->d_total;  // { count, records[rec_cap] }
-    parts[s].own_cap = cw->rec_cap;
-    parts[s].ev = cw->ev1;
-    parts[s].x = cw->x;
-    parts[s].h_word = cw->h_total;
-  }
-  bool by_collective = true;
-  if ((rc = C.exchange(parts, stream, reinterpret_cast<unsigned long long*>(ws->d_rec), &by_collective, direct_count)))
-    return rc;
-  {
-    DeviceGuard g(root);
-    *ws->h_total = sum;
-    CBH_HIP(hipMemcpyAsync(ws->d_total, ws->h_total, sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-    CBH_HIP(hipStreamSynchronize(stream));  // scan_all's contract: the block is complete on return
-  }
-  // Copies as the exchange: a shard stream's last operation is its count read-back (synchronised above) or its record copy
-  // + event, which `stream` waited for before the synchronisation just done -- every shard stream is drained.  (A collective
-  // leaves the peers' halves of the all-gather possibly in flight: those streams are synchronised when the leases end.)
-  if (!by_collective)
-    for (size_t s = 0; s < R; ++s) L.idle[s] = 1;
-  return CBH_OK;
+  return K.pending() ? CBH_E_OVERFLOW : finish_scan(K);
 }
 
 // The lone needle on a sharded handle (cbh_idx64_find): one launch_find_one per shard, issued back to back from this thread,
@@ -554,35 +559,30 @@ int sharded_scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t 
 // (what made a find() on 8 shards cost 203 us against 26 on the plain index).  *fits = every shard's matches fitted its
 // LoneBlock (then *recs holds them all, unordered); otherwise the caller takes the general path.
 int sharded_find_one(cbh_idx64* idx, uint64_t q, int thresh, std::vector<cbh_record>* recs, bool* fits) {
-  ShardSet* S = idx->shards;
-  const size_t R = S->child.size();
   *fits = false;
   recs->clear();
-  ShardLeases L(S);
+  ShardLeases L(idx, nullptr);
   int rc = L.acquire_all();
   if (rc) return rc;
-  std::vector<unsigned long long> seq(R, 0);
-  for (size_t s = 0; s < R; ++s) {
-    cbh_idx64* c = S->child[s];
-    if (c->n == 0) continue;
-    DeviceGuard g(c->device);
+  for (ShardRun& r : L.run) {
+    if (r.c->n == 0) continue;
+    DeviceGuard g(r.c->device);
     if (!g.ok) return CBH_E_NODEVICE;
-    Workspace* cw = L.ws[s];
+    Workspace* cw = r.ws;
+    hipStream_t cs = r.work();  // (ensure_lone's first call already puts a memset there)
     if ((rc = cw->ensure_lone())) return rc;
-    seq[s] = ++cw->lone_seq;
-    if ((rc = launch_find_one(c->d_hashes, c->d_ids, c->n, q, thresh, cw->d_lone, cw->h_lone, seq[s], cw->stream))) return rc;
-    S->comm.n_scans++;
+    rc = launch_find_one(r.c->d_hashes, r.c->d_ids, r.c->n, q, thresh, cw->d_lone, cw->h_lone, ++cw->lone_seq, cs);
+    if (rc) return rc;
+    r.todo = true;
+    idx->shards->comm.n_scans++;
   }
   bool all_fit = true;
-  for (size_t s = 0; s < R; ++s) {
-    if (!seq[s]) {
-      L.idle[s] = 1;
-      continue;
-    }
-    Workspace* cw = L.ws[s];
-    DeviceGuard g(S->child[s]->device);
-    if ((rc = wait_find_one(cw->h_lone, seq[s], cw->stream))) return rc;
-    L.idle[s] = 1;  // its kernel has published its result: nothing of this call is left on the stream
+  for (ShardRun& r : L.run) {
+    if (!r.todo) continue;
+    Workspace* cw = r.ws;  // (leased to this call alone: lone_seq is still this call's number)
+    DeviceGuard g(r.c->device);
+    if ((rc = wait_find_one(cw->h_lone, cw->lone_seq, cw->stream))) return rc;
+    r.saw_drained();  // its kernel has published its result: nothing of this call is left on the stream
     const unsigned long long t = cw->h_lone->count;
     if (t > LoneBlock::kRecs) all_fit = false;
     else if (all_fit) recs->insert(recs->end(), cw->h_lone->recs, cw->h_lone->recs + t);

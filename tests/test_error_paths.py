@@ -88,10 +88,12 @@ def _cases(gpu):
     cases["dcthash_general"] = lambda: hashing.dct_hash64_batch(photos)
     cases["process_images"] = lambda: tuple(np.asarray(x) for x in hashing.process_images(photos, autocrop=20))
 
-    def idx64(shards=None, thresh=5, nq=2048):
+    def idx64(shards=None, thresh=5, nq=2048, record_capacity=None):
         def run():
             idx = gpu.DctHashIndex(shards=shards)
             idx.load(h, ids)
+            if record_capacity:
+                idx.set_record_capacity(record_capacity)
             a = idx.find_batch(h[:nq], thresh, 6)
             m = idx.find(gpu.Media(id=1, dctHash=int(h[7])), SearchParams(dctThresh=9))
             sl = idx.slice(ids[100:400].tolist())
@@ -102,6 +104,9 @@ def _cases(gpu):
     cases["idx64_mfma_pre"] = idx64(thresh=3)
     cases["idx64_valu"] = idx64(nq=40)
     cases["idx64_sharded"] = idx64(shards=(1, 3))
+    # the grow-and-run-again route: 3095 matching pairs against a root block of 1024 records, so the three shards of the
+    # root device fill it, it grows, and they run again -- every allocation of that second round fails once too
+    cases["idx64_sharded_regrow"] = idx64(shards=(1, 3), record_capacity=1024)
 
     def search_index():
         idx = gpu.DctHashIndex()
@@ -210,7 +215,7 @@ def _cases(gpu):
 
 
 _CASE_NAMES = ["dcthash_256", "dcthash_general", "process_images", "idx64_mfma_full", "idx64_mfma_pre", "idx64_valu",
-               "idx64_sharded", "search_index_batch", "fdct_find_batch", "video_find_batch", "idx256_knn_small",
+               "idx64_sharded", "idx64_sharded_regrow", "search_index_batch", "fdct_find_batch", "video_find_batch", "idx256_knn_small",
                "idx256_knn_batch", "color_find_batch", "orb", "color_descriptor_create", "keypoint_hashes",
                "video_indexer"]
 
