@@ -74,7 +74,7 @@ constexpr int kG = 2;   // tiles per accumulator group
 // 2^23 + 0x4040 + 64 * 2^15
 constexpr float kC0 = 8388608.0f + 16448.0f + 2097152.0f;
 constexpr int kScale15 = 0x8e8e8e8e;  // E8M0 142 = 2^15
-constexpr uint32_t kQueue = 2048;     // words of wave-private LDS behind the prefilter / two-field kernels
+constexpr uint32_t kQueue = 2048;     // words of wave-private LDS behind the two-field kernel (the prefilter: kPreQueue)
 // PRE keeps FOUR prefilter-word distances per accumulator register as 6-bit fields at bits 0, 6, 12, 18 (two chained
 // MFMAs; see the kernel), biased so that "under the threshold" is bit 5 of the field; the top field's flag is the carry
 // into the f32 exponent (bit 23 of the pattern).  OR-ing accumulators preserves "some flag is set".
@@ -228,30 +228,30 @@ __device__ __forceinline__ void handle_tile2(const v16f& c, uint32_t row0, uint3
   wave_order();
 }
 
-// PRE, the candidate path (hit lanes in rounds of kParkLanes; one round and one lane is the common case while candidates
-// are rare: 8192 pairs per group x 1e-5 .. 6e-5 per pair).  A candidate costs the matrix pipe nothing but a handful of VALU
-// slots when it is FOUND and is re-checked LATER, 64 at a time:
-//   * each lane that holds a flag parks its accumulators in LDS (ds_write_b128 straight from the MFMA result registers,
-//     under the lanes' own exec mask: LDS issue, no VALU); hit lane by hit lane, lane r reads register r back, ONE
-//     ballot names the flagged registers, and those lanes append a descriptor {register pattern, register | tile |
-//     lane | step} to the wave's pending list -- ~10 VALU instructions per hit lane, no global memory access, so the
-//     wave is back at its MFMAs after two LDS round trips;
-//   * when 64 descriptors are pending (and at the end of the wave's needle chunk) the wave drains the list, one
-//     descriptor per lane: haystack hash from LDS, the needles of the flagged fields from global memory (64 lanes'
-//     loads in flight together), popcount; real matches go to the wave's record buffer.
+// PRE, the candidate path.  A candidate costs the matrix pipe nothing but a handful of VALU slots when it is FOUND and
+// is re-checked LATER, 64 at a time:
+//   * the event: every lane whose OR of a group's flags is not clear appends ONE descriptor {flag bits of the two
+//     reduction chains, lane | group | step} to the wave's pending list -- a ballot, an mbcnt and one ds_write_b64 for
+//     all hit lanes of the group at once, no global memory access, no difference between one hit lane and sixty-four.
+//     The lane does NOT find out which of its 32 accumulator registers held the flag (that took parking them in LDS and
+//     reading them back -- most of what a candidate used to cost, NOTES 11);
+//   * when 64 descriptors are pending at the end of a step (and at the end of the wave's needle chunk) the wave drains
+//     the list, one descriptor per lane: the needles of the flagged fields from global memory (64 lanes' loads in flight
+//     together), then ALL 17 or 15 haystack rows of a flagged chain from LDS against them, popcount on 64 bits; real
+//     matches go to the wave's record buffer.  Every (row, needle) pair belongs to one (lane, group, step) and one
+//     chain, so a match is emitted once.
 // (An immediate scalar re-check -- s_load + s_bcnt1 per candidate -- was built first: no VALU at all, but every event
-//  stalled the wave for a scalar-cache miss, 15.9 ms at threshold 6 where this form takes ~11; NOTES 11.  The per-tile
-//  queue path of rounds 1-4 -- ~750 cycles per candidate group -- is in the history: r05's "scan_pre_lean" 0.)
-// The wave's 2048 words: pending list (2 words per descriptor) | record buffer | parking area.
-constexpr uint32_t kParkLanes = 16;  // hit lanes parked at a time (a denser group takes several rounds)
-constexpr uint32_t kPark = kQueue - kParkLanes * 32u;  // word offset of the parking area
-constexpr uint32_t kOutOff = kPark - 2u * kOutCap;     // ... of the record buffer; the pending list holds kOutOff / 2
-// Pending descriptors.  A drain keeps npend & 63.  A step starts with <= 63, and so does every group behind a multi-lane
-// group (which drains once it is done); a one-lane group adds <= 32 without draining, so one-lane groups alone reach at most
-// 63 + 4 x 32.  A multi-lane group drains before each chunk of kParkLanes x 32 that would not fit behind what is pending
-// (up to 63 + 3 x 32 from one-lane groups before it): after that drain the chunk lands on <= 63.
-static_assert(kOutOff / 2u >= 63u + (kHT / kG) * 32u, "pending list: one-lane groups of a step");
-static_assert(kOutOff / 2u >= 63u + kParkLanes * 32u, "pending list: a chunk of hit lanes");
+//  stalled the wave for a scalar-cache miss, 15.9 ms at threshold 6; NOTES 11.  The per-tile queue path of rounds 1-4
+//  -- ~750 cycles per candidate group -- and the parking path of rounds 5-6 are in the history.)
+// The wave's words: pending list (2 words per descriptor) | record buffer.
+// Pending descriptors.  A group adds at most one per lane, a step has kHT / kG groups, a drain keeps npend & 63: a step
+// that starts with <= 63 ends with <= 63 + 4 x 64 = 319, so the list is drained between steps only.
+constexpr uint32_t kPendCap = 320;                          // descriptors the pending list holds
+constexpr uint32_t kOutOff = 2u * kPendCap;                 // word offset of the record buffer
+constexpr uint32_t kPreQueue = kOutOff + 2u * kOutCap;      // the prefilter kernel's words per wave
+static_assert(kPendCap >= 63u + (kHT / kG) * 64u, "pending list: every lane of every group of a step");
+static_assert(kPreQueue <= kQueue, "the prefilter kernel's LDS must not grow");
+static_assert(kG == 2, "a descriptor names the two reduction chains of a group of 32 registers");
 
 // OR of accumulator registers [A, B) of a group (register r = tile r / 16, element r % 16), three and then two per
 // v_or3_b32
@@ -275,8 +275,8 @@ __global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(
     unsigned long long cap, unsigned long long* __restrict__ total, uint32_t keep0,
     const uint2* __restrict__ qmask, const uint4* __restrict__ qf) {
   constexpr int HT = kHT, G = kG;
-  __shared__ uint32_t s_queue_[kWaves][kQueue];
-  __shared__ uint2 s_hay_[PRE ? kWaves : 1][PRE ? HT * 32 : 1];  // PRE: raw hashes for the re-check
+  __shared__ __attribute__((aligned(16))) uint32_t s_queue_[kWaves][PRE ? kPreQueue : kQueue];
+  __shared__ __attribute__((aligned(16))) uint2 s_hay_[PRE ? kWaves : 1][PRE ? HT * 32 : 1];  // PRE: raw hashes for the re-check
   __shared__ uint32_t s_out2_[PRE ? 1 : kWaves][PRE ? 1 : 2 * kOutCap];  // FULL2: the record buffer (PRE: inside s_queue)
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform, and known to be
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(
   const HitParams hp = {lo_key, hi_key, lo_zero, hi_zero, thresh, n, nq, keep0, q, ids, rec, cap, total, hay, qmask};
 
   uint32_t npend = 0;  // PRE: descriptors waiting in s_queue (wave-uniform)
-  // one descriptor per lane: the flagged fields of a parked register against all 64 bits
+  // one descriptor per lane: every row of its flagged chains against the needles of its flagged fields, on all 64 bits
   // (whole passes of 64 only -- the newest descriptors; the < 64 oldest wait for company, and for the chunk's end: a pass
   // costs its global-memory round trip whether one lane works in it or all of them)
   auto drain = [&](bool all) {
@@ -341,31 +341,73 @@ __global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(
     const uint32_t keep = all ? 0u : (npend & 63u);
     for (uint32_t k0 = keep; k0 < npend; k0 += 64u) {
       const uint32_t k = min(k0 + lane, npend - 1u);
-      const uint32_t bits = s_queue[2u * k], w1 = s_queue[2u * k + 1u];
-      const uint32_t g = w1 & 15u, tile = (w1 >> 4) & 7u, L = (w1 >> 7) & 63u, pp = p0 + 2u * (w1 >> 13);
-      const uint32_t rit = (g & 3u) + 8u * (g >> 2) + 4u * (L >> 5);  // C/D layout, see handle_tile2
-      const uint32_t row = (tile0 + tile) * 32u + rit;
-      // a carry into the exponent (top field flagged) leaves the lower fields unreadable: all four are candidates
-      uint32_t fields = ((bits >> 23) & 1u) ? 0xfu
-                                            : (((bits >> 5) & 1u) | (((bits >> 11) & 1u) << 1) | (((bits >> 17) & 1u) << 2));
-      if (row >= hp.n || k0 + lane >= npend) fields = 0;
-      const uint2 hv = s_hay[tile * 32u + rit];
-      // every lane takes its lowest flagged field per round (nearly always one round: one field per descriptor); the
-      // loop is uniform -- the record buffer ballots
-      while (__builtin_amdgcn_ballot_w64(fields != 0) != 0) {
-        const uint32_t qi = pp * 64u + (uint32_t)__builtin_ctz(fields | 16u) * 32u + (L & 31u);
-        bool has = false;
-        uint32_t d = 0, id = 0;
-        if (fields != 0 && qi < hp.nq) {
-          const uint64_t nv = hp.q[qi];
-          d = __popc(hv.x ^ (uint32_t)nv) + __popc(hv.y ^ (uint32_t)(nv >> 32));
-          if (nv != 0 && d < hp.thresh && mask_ok(hp, row, qi, nv)) {
+      const uint2 e = *reinterpret_cast<const uint2*>(&s_queue[2u * k]);
+      const uint32_t L = e.y & 63u, pp = p0 + 2u * (e.y >> 8);
+      // register 16 t + g of the group is wave row  64 group + 32 t + (g & 3) + 8 (g >> 2) + 4 (L >> 5)  (C/D layout, see
+      // handle_tile2)  =  base + 8 (register >> 2) + (register & 3): a quad of registers is four rows in a row
+      const uint32_t base = ((e.y >> 6) & 3u) * 64u + 4u * (L >> 5);
+      const uint32_t col = pp * 64u + (L & 31u);  // needle of field f: col + 32 f
+      // candidates: bit 4 c + f = field f in the rows of chain c (flag bits of chain c at 5 + c, 11 + c, 17 + c, 23 + c).
+      // A carry into the exponent (top field flagged) leaves the lower fields of that register unreadable, and the OR
+      // cannot say which register it was: all four fields are candidates in that chain's rows.
+      uint32_t cm = 0;
+#pragma unroll
+      for (uint32_t c = 0; c < 2; ++c) {
+        const uint32_t w = e.x >> c;
+        cm |= (((w >> 23) & 1u) ? 0xfu : (((w >> 5) & 1u) | (((w >> 11) & 1u) << 1) | (((w >> 17) & 1u) << 2))) << (4u * c);
+      }
+      if (k0 + lane >= npend) cm = 0;
+      // the needles of the candidate fields, all loads in flight together; a null needle (and one past nq: the padding,
+      // the partner of a lone last pair) matches nothing
+      uint32_t nlo[4], nhi[4];
+#pragma unroll
+      for (uint32_t f = 0; f < 4; ++f) {
+        const uint64_t nv = (((cm | (cm >> 4)) >> f) & 1u) != 0 && col + 32u * f < hp.nq ? hp.q[col + 32u * f] : 0;
+        nlo[f] = (uint32_t)nv;
+        nhi[f] = (uint32_t)(nv >> 32);
+      }
+#pragma unroll
+      for (uint32_t f = 0; f < 4; ++f)
+        if ((nlo[f] | nhi[f]) == 0) cm &= ~(0x11u << f);
+      // every lane takes its lowest candidate per round (one round while candidates are rare and the top field is not
+      // among them); the loops are uniform -- the record buffer ballots
+      while (__builtin_amdgcn_ballot_w64(cm != 0) != 0) {
+        const uint32_t b = (uint32_t)__builtin_ctz(cm | 0x100u), f = b & 3u, ch = (b >> 2) & 1u;
+        const uint32_t qlo = f == 0 ? nlo[0] : f == 1 ? nlo[1] : f == 2 ? nlo[2] : nlo[3];
+        const uint32_t qhi = f == 0 ? nhi[0] : f == 1 ? nhi[1] : f == 2 ? nhi[2] : nhi[3];
+        // chain 0 = registers 0..16 (quads 0..3 and the first of quad 4), chain 1 = 17..31 (the rest of quad 4, quads 5..7)
+        const uint32_t rows = cm == 0 ? 0u : ch ? 0xfffe0000u : 0x0001ffffu;
+        const uint2* hq = s_hay + base + 32u * ch;
+        uint32_t hit = 0;
+#pragma unroll 1
+        for (uint32_t i = 0; i < 5u; ++i) {
+          const uint32_t qd = 4u * ch + i;  // chain 1 at i = 4: quad 8, masked below; clamped to stay inside s_hay
+          const uint4* h4 = reinterpret_cast<const uint4*>(hq + 8u * min(i, 4u - ch));
+          const uint4 x = h4[0], y = h4[1];
+          const uint32_t d0 = __popc(x.x ^ qlo) + __popc(x.y ^ qhi), d1 = __popc(x.z ^ qlo) + __popc(x.w ^ qhi);
+          const uint32_t d2 = __popc(y.x ^ qlo) + __popc(y.y ^ qhi), d3 = __popc(y.z ^ qlo) + __popc(y.w ^ qhi);
+          const uint32_t m4 = (d0 < hp.thresh ? 1u : 0u) | (d1 < hp.thresh ? 2u : 0u) | (d2 < hp.thresh ? 4u : 0u) |
+                              (d3 < hp.thresh ? 8u : 0u);
+          hit |= qd < 8u ? m4 << (4u * qd) : 0u;
+        }
+        hit &= rows;
+        // a needle can match several rows of a chain (duplicates): one record per lane and round
+        const uint32_t qi = col + 32u * f;
+        while (__builtin_amdgcn_ballot_w64(hit != 0) != 0) {
+          const uint32_t rr = (uint32_t)__builtin_ctz(hit | 0x80000000u);
+          const uint32_t wr = base + 8u * (rr >> 2) + (rr & 3u), row = tile0 * 32u + wr;
+          const uint2 hv = s_hay[wr];
+          const uint32_t d = __popc(hv.x ^ qlo) + __popc(hv.y ^ qhi);
+          bool has = false;
+          uint32_t id = 0;
+          if (hit != 0 && row < hp.n && mask_ok(hp, row, qi, ((uint64_t)qhi << 32) | qlo)) {
             id = hp.ids[row];
             has = id != 0 || hp.keep0;
           }
+          out_push(s_out, nout, has, qi, d, id, hp);
+          hit &= hit - 1u;
         }
-        out_push(s_out, nout, has, qi, d, id, hp);
-        fields &= fields - 1u;
+        cm &= cm - 1u;
       }
     }
     wave_order();
@@ -398,89 +440,22 @@ __global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(
         const uint32_t flags = (half0 | half1) & kFlagMaskPre;
         const uint64_t hm = __builtin_amdgcn_ballot_w64(flags != 0);
         if (hm != 0) {
-          // wave-uniform from here: some lane holds a candidate (one group in ~10 at threshold 5, every other at 6)
-          static_assert(R == 32, "the parking slots below are 32 registers");
-          auto park4 = [&](uint32_t at, int t, int k) {  // registers 16 t + 4 k .. + 3 of the lane: one ds_write_b128
-            *reinterpret_cast<float4*>(&s_queue[at + (uint32_t)(t * 16 + 4 * k)]) =
-                make_float4(c[t][4 * k], c[t][4 * k + 1], c[t][4 * k + 2], c[t][4 * k + 3]);
-          };
-          auto park = [&](uint32_t at) {
-#pragma unroll
-            for (int t = 0; t < G; ++t)
-#pragma unroll
-              for (int k = 0; k < 4; ++k) park4(at, t, k);
-          };
-          const uint32_t w1c = ((uint32_t)t0 << 4) | (((p - p0) >> 1) << 13);  // tile of register 0, step
-          // lane r < 32 reads register r of a hit lane back (the lanes above read on into the next slot, or the first words
-          // behind the wave's queue: inside the workgroup's LDS, and discarded by the mask / lane < 32); `ok` = the registers
-          // whose parking slot was written.  Appends {pattern, register | tile | hit lane | step} for every flagged one.
-          auto list = [&](uint32_t at, uint32_t L, uint32_t ok) {
-            // (the lane id through an opaque copy: the compiler otherwise hoists this path's lane-derived values -- the
-            // parking area's address, 1 << lane -- out of the chunk loop, runs out of its 128 registers and SPILLS them:
-            // two scratch loads + a wait in front of every list(), i.e. in every other group at threshold 6)
-            uint32_t ln = lane;
-            asm volatile("" : "+v"(ln));
-            const uint32_t v = s_queue[at + ln];
-            const bool pred = (v & kFlagMaskPre) != 0 && ((ok >> (ln & 31u)) & 1u) != 0u;
-            const uint32_t bm = (uint32_t)(__builtin_amdgcn_ballot_w64(pred) & 0xffffffffull);
-            if (pred && ln < (uint32_t)R) {
-              // lane = 16 t + g: bits 0-3 the register, bits 4-6 (t0 + t) the wave's tile; bits 7-12 the hit lane
-              *reinterpret_cast<uint2*>(&s_queue[2u * (npend + __builtin_amdgcn_mbcnt_lo(bm, 0u))]) =
-                  make_uint2(v, ln | (w1c | (L << 7)));
-            }
-            npend += (uint32_t)__popc(bm);
-          };
-          if ((hm & (hm - 1)) == 0) {
-            // ONE hit lane (nine events in ten), a fixed address -- and nearly always one flagged register: only the
-            // registers of the reduction chain(s) that hold a flag are parked -- 0..16 (five ds_write_b128) or 17..31
-            // (four) instead of all eight; a ds_write_b128 moves 1 KB whatever its exec mask.  (Masks, not bools: a
-            // uniform bool comes back as v_cndmask + v_cmp.)
-            const uint64_t b0 = __builtin_amdgcn_ballot_w64((half0 & kFlagMaskPre) != 0);
-            const uint64_t b1 = __builtin_amdgcn_ballot_w64((half1 & kFlagMaskPre) != 0);
-            if (flags != 0) {
-              if (b0) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) park4(kPark, 0, k);
-              }
-              park4(kPark, 1, 0);
-              if (b1) {
-#pragma unroll
-                for (int k = 1; k < 4; ++k) park4(kPark, 1, k);
-              }
-            }
-            const uint32_t ok = (b0 ? 0x000fffffu : 0u) | (b1 ? 0xffff0000u : 0u);
-            wave_order();
-            list(kPark, (uint32_t)__builtin_ctzll(hm), ok);
-            wave_order();
-            // (drained at the end of the step: a one-lane event adds at most 32 descriptors, so the step's one-lane groups
-            //  add at most 4 x 32 to the <= 63 a step or a multi-lane group leaves -- and the drain's code sits once per step
-            //  instead of once per group: 4.3k instead of 5.5k instructions, threshold 6 1.5 % faster,
-            //  profiles/r06_pre_drain_sites_ab.json)
-          } else {
-            // several hit lanes, in chunks of kParkLanes (one chunk unless the group is dense: duplicates, video frames);
-            // the k-th hit lane of a chunk parks all its registers at kPark + 32 k.  A chunk lists up to kParkLanes x 32
-            // descriptors: the list is drained before a chunk that might not fit behind the pending ones (up to 63 + 3 x 32
-            // from earlier one-lane groups of the step), and once the group is done, so that one-lane groups behind it
-            // start from <= 63 -- otherwise descriptors would run into the record buffer.  (One drain site for both.)
-            uint64_t rest = hm;
-            for (;;) {
-              if (rest ? npend + kParkLanes * 32u > kOutOff / 2u : npend >= 64u) drain(false);
-              if (!rest) break;
-              uint64_t cm = rest;
-              if ((uint32_t)__popcll(rest) > kParkLanes) {
-                uint64_t rem = rest;
-                for (uint32_t i = 0; i < kParkLanes; ++i) rem &= rem - 1;
-                cm = rest ^ rem;  // the lowest kParkLanes hit lanes
-              }
-              rest ^= cm;
-              if ((cm >> lane) & 1ull)
-                park(kPark + 32u * __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u)));
-              wave_order();
-              uint32_t at = kPark;
-              for (uint64_t m = cm; m; m &= m - 1, at += 32u) list(at, (uint32_t)__builtin_ctzll(m), 0xffffffffu);
-              wave_order();
-            }
+          // wave-uniform from here: some lane holds a candidate (one group in ~10 at threshold 5, every other at 6).
+          // Every hit lane appends {flag bits of chain 0 | those of chain 1 one bit higher, lane | group | step}.
+          // (the lane id through an opaque copy: the compiler otherwise hoists this path's lane-derived values out of the
+          // chunk loop, runs out of its 128 registers and SPILLS them)
+          static_assert(R == 32, "two chains of 17 and 15 registers");
+          uint32_t ln = lane;
+          asm volatile("" : "+v"(ln));
+          if (flags != 0) {
+            const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, npend));
+            *reinterpret_cast<uint2*>(&s_queue[2u * at]) =
+                make_uint2((half0 & kFlagMaskPre) | ((half1 & kFlagMaskPre) << 1),
+                           ln | ((uint32_t)(t0 / G) << 6) | (((p - p0) >> 1) << 8));
           }
+          npend += (uint32_t)__popcll(hm);
+          // (drained at the end of the step: 4 x 64 descriptors fit behind the <= 63 a drain leaves, and the drain's code
+          //  sits once per step instead of once per group, profiles/r06_pre_drain_sites_ab.json)
         }
       } else {
         // packed per-half maximum of the group's G*16 results: 8 v_pk_maximum3_f16 per tile

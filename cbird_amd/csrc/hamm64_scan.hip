@@ -304,24 +304,29 @@ constexpr int kPreMax = 7;            // largest threshold served by the popcoun
 constexpr size_t kMfmaMinNq = 256;    // below this the needle expansion + tile padding is not worth it
 constexpr size_t kMfmaMinN = 4096;
 // The prefilter kernel is twice as fast as the three-field kernel while its candidates are rare and loses to it when
-// they are not: every candidate costs a park / list / re-check (~110 SIMD cycles per event).  How many there are is a
-// property of the data -- r_cand(t) = P[popc(fold(a) ^ fold(b)) < t] over the launch's needle x slot pairs: 5.7e-5 at
-// t = 6 and 2.7e-4 at t = 7 for unrelated hashes, but anything for a library of scans of one form, blank frames or a video
-// against itself.  The three-field kernel in turn pays for every TRUE match (a flagged group goes through three passes
-// of sixteen ballots): ~4x what a candidate costs the prefilter, so where the candidates are mostly true matches -- a
-// dense cluster of near-identical hashes -- the prefilter wins again, at any rate.  Measured per 10^12 pairs
-// (tools/ab/adaptive_ab.py, profiles/r06_adaptive_ab*.jsonl):  T_pre = 8.8 ms + 6e4 ms x r_cand,  T_full = 16.3 ms +
-// 2.5e5 ms x r_true.  The probe counts both rates on a sample of the launch's pairs -- a few microseconds and one host
-// round trip, against launches of milliseconds -- and the prefilter is taken while
-//   r_cand - kTrueWeight x r_true <= "scan_pre_rate_e9" x 1e-9      (the rate at which the two kernels tie: 1.25e-4).
-// Launches too small to pay for the round trip, and a probe that cannot run, take the fixed rule (thresholds <= 6).
+// they are not: every candidate costs a descriptor and a share of a re-check of its chain's rows (~40 SIMD cycles).
+// How many there are is a property of the data -- r_cand(t) = P[popc(fold(a) ^ fold(b)) < t] over the launch's
+// needle x slot pairs: 5.8e-5 at t = 6, 2.7e-4 at t = 7 and 1.04e-3 at t = 8 for unrelated hashes, but anything for a
+// library of scans of one form, blank frames or a video against itself.  The three-field kernel in turn pays for every
+// TRUE match (a flagged group goes through three passes of sixteen ballots, 2.7e5 ms per unit of r_true against the
+// prefilter's 0.7e5): where the candidates are mostly true matches -- a dense cluster of near-identical hashes -- the
+// prefilter wins again, at any rate.  Measured per 10^12 pairs (tools/ab/adaptive_ab.py, profiles/r07_adaptive_ab_*.jsonl):
+//   T_pre = 8.55 ms + 2.4e4 ms x r_cand  (8.6 / 8.7 / 10.0 / 14.7 / 33.9 ms at thresholds 4..8 of image hashes),
+//   T_full = 15.75 ms + 2.7e5 ms x r_true.
+// The probe counts both rates on a sample of the launch's pairs -- a few microseconds and one host round trip, against
+// launches of milliseconds -- and the prefilter is taken while
+//   r_cand - kTrueWeight x r_true <= "scan_pre_rate_e9" x 1e-9      (the rate at which the two kernels tie: 3.0e-4;
+//   kTrueWeight = (2.7e5 - 0.7e5) / 2.4e4),
+// which puts threshold 7 of unrelated hashes on the prefilter (14.6-14.8 ms against 15.75-17.0) and leaves 8 to the
+// three-field kernel.  Launches too small to pay for the round trip, and a probe that cannot run, take the fixed rule
+// (thresholds <= 6: at 7 the prefilter's margin is 7 % on unrelated hashes and gone on anything denser).
 constexpr int kPreStatic = 6;
-constexpr double kTrueWeight = 4.0;
+constexpr double kTrueWeight = 8.0;
 constexpr uint64_t kProbeMinPairs = 1ull << 31;  // ~20 us of scan: below this the probe's round trip is not worth it
 
 int g_scan_mfma = 1;             // "scan_mfma"
 int g_pre_max_thresh = -1;       // "scan_mfma_pre_max"
-int g_pre_rate_max_e9 = 125000;  // "scan_pre_rate_e9"
+int g_pre_rate_max_e9 = 300000;  // "scan_pre_rate_e9"
 std::atomic<uint64_t> g_pre_mask{0};        // bit t: the most recent matrix-core launch at threshold t took the prefilter
 std::atomic<uint64_t> g_n_probe{0};         // probes run
 std::atomic<long long> g_last_rate_e9{-1};  // candidate rate x 1e9 the last probe found for its threshold
@@ -338,7 +343,8 @@ struct Route {
 // the route of one launch of n slots x nq needles (n, nq >= 1, n <= 0xfffffff0, thresh >= 1)
 Route route(size_t n, size_t nq, int thresh, bool masked) {
   Route r;
-  r.scan_ms = (double)n * (double)nq * (thresh <= 6 ? 8.8e-12 : 16.3e-12);  // (prefilter / three-field kernel)
+  // (the prefilter at thresholds <= 5, at 6 and at 7 on unrelated hashes; the three-field kernel)
+  r.scan_ms = (double)n * (double)nq * (thresh <= 5 ? 8.7e-12 : thresh == 6 ? 10.0e-12 : thresh == 7 ? 14.7e-12 : 15.8e-12);
   // thresholds <= 8, "scan_mfma" 3: the join when its candidate count says it is cheaper than looking at every pair (only
   // asked where a scan would take >= 1 ms); 4: whenever it can represent the call (the parity suite).  As shipped (1)
   // every pair is compared: the join avoids comparisons, it does not make them faster.

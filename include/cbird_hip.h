@@ -737,11 +737,11 @@ int cbh_color_find_batch(cbh_color*, const void* needle_descs, size_t nq, int k,
  *                   Other values return CBH_E_INVAL and leave the knob as it was
  *   "scan_mfma_pre_max" prefilter kernel or three-field 64-bit kernel: -1 (default) = per launch, by the candidate rate of the
  *                   launch's own data -- r_cand = P[popc(fold(a) ^ fold(b)) < thresh] and r_true = P[hamm64(a, b) < thresh], counted
- *                   on 2048 x 2048 sampled (slot, needle) pairs by k_fold_probe; the prefilter while r_cand - 4 r_true <=
+ *                   on 2048 x 2048 sampled (slot, needle) pairs by k_fold_probe; the prefilter while r_cand - 8 r_true <=
  *                   "scan_pre_rate_e9" (a candidate costs the prefilter a re-check, a true match costs the three-field kernel
- *                   four times that); launches of < 2^31 pairs: thresholds <= 6 -- 0 = never the prefilter, t > 0 =
+ *                   eight times that more than it costs the prefilter); launches of < 2^31 pairs: thresholds <= 6 -- 0 = never the prefilter, t > 0 =
  *                   thresholds <= t (<= 32) take it whatever the data
- *   "scan_pre_rate_e9" that bound x 1e9 (default 125000 = 1.25e-4: where the two kernels tie, profiles/r06_adaptive_ab*.jsonl)
+ *   "scan_pre_rate_e9" that bound x 1e9 (default 300000 = 3.0e-4: where the two kernels tie, profiles/r07_adaptive_ab_*.jsonl)
  *   "scan256_mfma"  256-bit scan on the matrix cores (k_hamm256_*): 0 = never (k_hamm256_scan), 1 = calls with >= 64 needle
  *                   descriptors and >= 4096 rows (default), 2 = always
  *   "scan256_small" 1 = searches with <= 512 needle descriptors (one ORB needle image) and thresholds <= 40 use the
