@@ -193,8 +193,24 @@ int launch_scan256_mfma(const uint8_t* d_rows, size_t n, const uint8_t* d_q, siz
                         unsigned long long* d_rec, size_t cap, unsigned long long* d_total,
                         hipStream_t stream);
 bool scan256_mfma_wanted(size_t n, size_t nq, int thresh);
-void set_scan256_small(int v);  // stationary-needle kernel for <= 512 needle descriptors: 0 / 1
-void set_scan256_mfma(int on);  // <0 = keep; 2 = force for any size
+int set_scan256_small(int v);  // stationary-needle kernel for <= 512 needle descriptors: 0 / 1; else CBH_E_INVAL, knob unchanged
+int set_scan256_mfma(int v);   // 0..2 (2 = force for any size); else CBH_E_INVAL, knob unchanged
+int get_scan256_small();
+int get_scan256_mfma();
+// "scan256_kernels": which kernels 256-bit launches have used since the mask was last cleared (cbh_set_tuning(.., 0)).
+// Noted by launch_scan256 (idx256.hip) and launch_scan256_mfma and nowhere else.
+enum Scan256Kernel : int {
+  kS256Scan = 1 << 0,     // k_hamm256_scan<8,4>
+  kS256Mfma2 = 1 << 1,    // k_hamm256_mfma<6,3,2>
+  kS256Mfma4 = 1 << 2,    // k_hamm256_mfma<6,3,4>
+  kS256Mfma3 = 1 << 3,    // k_hamm256_mfma3<12,2>
+  kS256Small4 = 1 << 4,   // k_hamm256_small<4>
+  kS256Small8 = 1 << 5,   // k_hamm256_small<8>
+  kS256Small16 = 1 << 6,  // k_hamm256_small<16>
+};
+void note_scan256_kernel(int bit);
+long long get_scan256_kernels();
+void clear_scan256_kernels();
 
 
 

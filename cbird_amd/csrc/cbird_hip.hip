@@ -1312,8 +1312,6 @@ int cbh_set_tuning(const char* key, int value) {
   } kKnobs[] = {
       {"scan_mfma_pre_max", [](int v) { set_scan_pre_max(v); }},
       {"scan_pre_rate_e9", [](int v) { set_scan_pre_rate(v); }},
-      {"scan256_mfma", [](int v) { set_scan256_mfma(v); }},
-      {"scan256_small", [](int v) { set_scan256_small(v); }},
       {"hash_mfma", [](int v) { (void)g_hash_mfma_set(v); }},
       {"hash_band_area", [](int v) { set_hash_band_area(v); }},
       {"hash_fuse", [](int v) { set_hash_fuse(v); }},
@@ -1337,6 +1335,13 @@ int cbh_set_tuning(const char* key, int value) {
   };
   if (!strcmp(key, "orb_retain_order") && value != 0 && value != 1) return CBH_E_INVAL;
   if (!strcmp(key, "scan_mfma")) return set_scan_mfma(value);
+  if (!strcmp(key, "scan256_mfma")) return set_scan256_mfma(value);
+  if (!strcmp(key, "scan256_small")) return set_scan256_small(value);
+  if (!strcmp(key, "scan256_kernels")) {  // a read-back, not a knob: writing 0 clears it, nothing else can be written
+    if (value != 0) return CBH_E_INVAL;
+    clear_scan256_kernels();
+    return CBH_OK;
+  }
   for (const auto& k : kKnobs)
     if (!strcmp(key, k.name)) {
       k.set(value);
@@ -1353,6 +1358,9 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strncmp(key, "arena_", 6)) return arena_counter(key + 6, value);
   if (!strcmp(key, "scan_mfma")) return *value = get_scan_mfma(), CBH_OK;
   if (!strcmp(key, "scan_pre_mask")) return *value = get_scan_pre_mask(), CBH_OK;
+  if (!strcmp(key, "scan256_mfma")) return *value = get_scan256_mfma(), CBH_OK;
+  if (!strcmp(key, "scan256_small")) return *value = get_scan256_small(), CBH_OK;
+  if (!strcmp(key, "scan256_kernels")) return *value = get_scan256_kernels(), CBH_OK;
   if (!strcmp(key, "scan_probes")) return *value = get_scan_probes(), CBH_OK;
   if (!strcmp(key, "scan_joins")) return *value = get_scan_joins(), CBH_OK;
   if (!strcmp(key, "scan_probe_rate_e9")) return *value = get_scan_probe_rate_e9(), CBH_OK;

@@ -12,6 +12,7 @@
 // hit parks the accumulators in LDS and decodes them in a rolled loop.  VALU work is 2 ops per
 // MFMA, so the kernel runs at the matrix-core rate: 4 x ~43 cycles per 1024 pairs.
 #include <algorithm>
+#include <atomic>
 
 #include "cbh_internal.h"
 #include "fp4_sign.h"
@@ -151,7 +152,9 @@ __global__ __launch_bounds__(kThreads) void k_hamm256_mfma(
 // three 8-bit fields in [b, 128 + b] (no borrow, no carry for b <= 127), and  d_i <= b  <=>  bit 7 of field i = bits 7,
 // 15 of the f32 pattern and, for the top field, the carry out of the mantissa = bit 23 (exponent 150 -> 151; the ulp is
 // then 2: the lowest bit of the sum is rounded away, which can only turn an odd field 0 into a neighbouring even one --
-// a field of exactly 128 is even and stays, so no pair under the threshold is lost).  The +-0.5 products are exact
+// a field of exactly 128 is even and stays, so no pair under the threshold is lost; tests/test_scan256_layout.py runs it:
+// the excursion_mfma / excursion_block fixtures take the sum over 2^24 and back between and inside MFMAs, carry_hidden
+// ends there).  The +-0.5 products are exact
 // because the hardware adds the 32 products of a K block (an integer) before it meets the accumulator
 // (tools/ubench/mfma_half_exact.hip).  OR keeps "some flag is set": 16 result registers per SIX MFMAs, 1.33 v_or3_b32
 // per MFMA.  A flagged register's candidates (all three fields when the exponent moved, else the flagged ones) are
@@ -410,15 +413,25 @@ __global__ __launch_bounds__(kThreads, 2) void k_hamm256_small(  // (2: accumula
 int g_scan256_small = 1;   // "scan256_small": the stationary-needle kernel for <= 512 needle descriptors (default on)
 int g_scan256_mfma = 1;
 constexpr int kPre128MaxThresh = 40;  // thresholds up to this take a first-128-bit prefilter variant
+std::atomic<long long> g_scan256_kernels{0};  // "scan256_kernels": Scan256Kernel bits of the launches since the last clear
 
 }  // namespace
 
-void set_scan256_mfma(int on) {
-  if (on >= 0) g_scan256_mfma = on;
+int set_scan256_mfma(int v) {
+  if (v < 0 || v > 2) return CBH_E_INVAL;
+  g_scan256_mfma = v;
+  return CBH_OK;
 }
-void set_scan256_small(int v) {
-  if (v == 0 || v == 1) g_scan256_small = v;
+int set_scan256_small(int v) {
+  if (v != 0 && v != 1) return CBH_E_INVAL;
+  g_scan256_small = v;
+  return CBH_OK;
 }
+int get_scan256_mfma() { return g_scan256_mfma; }
+int get_scan256_small() { return g_scan256_small; }
+void note_scan256_kernel(int bit) { g_scan256_kernels.fetch_or((long long)bit); }
+long long get_scan256_kernels() { return g_scan256_kernels.load(); }
+void clear_scan256_kernels() { g_scan256_kernels.store(0); }
 
 bool scan256_mfma_wanted(size_t n, size_t nq, int thresh) {
   if (thresh < 1 || thresh > 257) return false;
@@ -458,6 +471,7 @@ int launch_scan256_mfma(const uint8_t* d_rows, size_t n, const uint8_t* d_q, siz
                      (uint32_t)nq, (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total)
     if (nt == 4) CBH_SMALL(4); else if (nt == 8) CBH_SMALL(8); else CBH_SMALL(16);
 #undef CBH_SMALL
+    note_scan256_kernel(nt == 4 ? kS256Small4 : nt == 8 ? kS256Small8 : kS256Small16);
     hipError_t es = hipGetLastError();
     (void)cbh::free_async(qx, stream);
     CBH_HIP(es);
@@ -491,6 +505,7 @@ int launch_scan256_mfma(const uint8_t* d_rows, size_t n, const uint8_t* d_q, siz
                      (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total)
     CBH_256F3(12, 2);
 #undef CBH_256F3
+    note_scan256_kernel(kS256Mfma3);
     hipError_t e3 = hipGetLastError();
     (void)cbh::free_async(qx, stream);
     CBH_HIP(e3);
@@ -515,6 +530,7 @@ int launch_scan256_mfma(const uint8_t* d_rows, size_t n, const uint8_t* d_q, siz
                      (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total)
   if (pre128) CBH_256(6, 3, 2); else CBH_256(6, 3, 4);
 #undef CBH_256
+  note_scan256_kernel(pre128 ? kS256Mfma2 : kS256Mfma4);
   hipError_t e = hipGetLastError();
   (void)cbh::free_async(qx, stream);
   CBH_HIP(e);

@@ -219,6 +219,7 @@ int launch_scan256(cbh_idx256* ix, const uint8_t* d_q, size_t nq, int thresh) {
                      reinterpret_cast<const uint4*>(d_q), (uint32_t)nq, q_chunk, (uint32_t)thresh, ix->d_rec,
                      (unsigned long long)ix->rec_cap, ix->d_total);
   CBH_HIP(hipGetLastError());
+  cbh::note_scan256_kernel(cbh::kS256Scan);
   return CBH_OK;
 }
 

@@ -743,9 +743,11 @@ int cbh_color_find_batch(cbh_color*, const void* needle_descs, size_t nq, int k,
  *                   thresholds <= t (<= 32) take it whatever the data
  *   "scan_pre_rate_e9" that bound x 1e9 (default 300000 = 3.0e-4: where the two kernels tie, profiles/r07_adaptive_ab_*.jsonl)
  *   "scan256_mfma"  256-bit scan on the matrix cores (k_hamm256_*): 0 = never (k_hamm256_scan), 1 = calls with >= 64 needle
- *                   descriptors and >= 4096 rows (default), 2 = always
+ *                   descriptors and >= 4096 rows (default), 2 = always.  Other values return CBH_E_INVAL and leave the knob
+ *                   as it was
  *   "scan256_small" 1 = searches with <= 512 needle descriptors (one ORB needle image) and thresholds <= 40 use the
- *                   stationary-needle kernel k_hamm256_small (default), 0 = the row-stationary kernels
+ *                   stationary-needle kernel k_hamm256_small (default), 0 = the row-stationary kernels.  Other values return
+ *                   CBH_E_INVAL and leave the knob as it was
  *   "hash_mfma"     256 x 256 tiles: non-zero (default 2) = k_dcthash_256_band (the 7 x 7 box filter as i8 MFMAs, its vertical
  *                   sum kept in their accumulators; rows must be 16-byte aligned, otherwise 0 is taken), 0 = k_dcthash_256
  *                   (all VALU; also what runs if the band table cannot be made)
@@ -800,7 +802,11 @@ int cbh_set_tuning(const char* key, int value);
  * knob's value); "scan_pre_mask"
  * (bit t = the most recent matrix-core launch at threshold t took the prefilter kernel), "scan_joins" (calls the bucketed join has answered), "scan_probes" (candidate-rate
  * probes run so far), "scan_probe_rate_e9" / "scan_probe_true_e9" (the candidate and true-match rates the last one found for its threshold,
- * x 1e9; -1 = none yet). */
+ * x 1e9; -1 = none yet); "scan256_mfma", "scan256_small" (the knobs' values); "scan256_kernels" (a bit mask of the kernels
+ * that 256-bit scan launches have used since it was last cleared -- cbh_set_tuning("scan256_kernels", 0) clears it, any
+ * other value written is CBH_E_INVAL; bit 0 k_hamm256_scan, 1 k_hamm256_mfma<6,3,2> (first-128-bit prefilter, one needle
+ * tile per accumulator), 2 k_hamm256_mfma<6,3,4> (all 256 bits), 3 k_hamm256_mfma3, 4 / 5 / 6 k_hamm256_small<4 / 8 / 16>;
+ * a sharded handle notes one launch per shard, a buffer that had to grow one per attempt). */
 int cbh_get_tuning(const char* key, long long* value);
 
 /* ---- measurement support ---------------------------------------------------------------- */

@@ -2,7 +2,8 @@
 k_hamm256_small / k_hamm256_mfma3 / k_hamm256_mfma / k_hamm256_scan on the same random index and queries must give the
 same list, and that list must equal numpy's brute force on a sample of the queries.  Index rows are random; queries are
 rows with a random number of flipped bits around the threshold (so that there are hits just under, at and just over
-it), rows of zeros / ones, and unrelated descriptors.  Prints one JSON line.
+it), rows of zeros / ones, and unrelated descriptors (tests/scan256_layout.py: soak_case, which a short seeded GPU test
+runs too, with every query checked).  Prints one JSON line.
 
     python tools/fuzz_scan256.py [--cases 40] [--seed 1]
 """
@@ -14,6 +15,9 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+
+from scan256_layout import soak_case  # noqa: E402  (the case generator, shared with tests/test_scan256_layout.py)
 
 PATHS = {"shipped": {b"scan256_mfma": 2, b"scan256_small": 1},
          "rows": {b"scan256_mfma": 2, b"scan256_small": 0},  # k_hamm256_mfma3 / k_hamm256_mfma without k_hamm256_small
@@ -32,32 +36,12 @@ def main():
     rng = np.random.default_rng(args.seed)
     bad, total_matches, checked = [], 0, 0
     for c in range(args.cases):
-        n_img = int(rng.integers(8, 400))
-        per = int(rng.integers(20, 700))
+        case = soak_case(rng)
+        n_img, per, rows, n = case["n_img"], case["per"], case["rows"], case["n"]
+        max_dist, nq, q, bits = case["max_dist"], case["nq"], case["queries"], case["bits"]
         idx = CvFeaturesIndex()
-        rows = rng.integers(0, 256, (n_img * per, 32), dtype=np.uint8)
         for i in range(n_img):
             _lib.check(L.cbh_idx256_add(idx.handle, i + 1, rows[i * per:(i + 1) * per].ctypes.data, per), "add")
-        n = len(rows)
-        max_dist = int(rng.choice([0, 1, 5, 24, 25, 29, 39, 40, 41, 60, 90]))
-        nq = int(rng.choice([1, 31, 32, 33, 95, 96, 97, 500, 512, 513, 1200, int(rng.integers(1, 2000))]))
-        q = rows[rng.integers(0, n, nq)].copy()
-        bits = np.unpackbits(q, axis=1)
-        for j in range(nq):
-            kind = rng.integers(0, 10)
-            if kind < 7:  # flips around the threshold, anywhere in the 256 bits
-                k = int(np.clip(max_dist + rng.integers(-3, 4), 0, 256))
-                pos = rng.choice(256, k, replace=False)
-                bits[j, pos] ^= 1
-            elif kind == 7:
-                bits[j] = rng.integers(0, 2, 256)
-            elif kind == 8:
-                bits[j] = 0
-            else:  # all flips in the first 128 bits / in the last 128 bits
-                k = int(np.clip(max_dist + rng.integers(-2, 3), 0, 128))
-                pos = rng.choice(128, k, replace=False) + (128 if rng.integers(0, 2) else 0)
-                bits[j, pos] ^= 1
-        q = np.packbits(bits, axis=1)
         got = {}
         for name, knobs in PATHS.items():
             for k, v in knobs.items():
