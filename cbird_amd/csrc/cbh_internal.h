@@ -188,17 +188,9 @@ int launch_hamm64_join(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n
                        int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
                        bool keep_id0, bool force, double scan_ms_estimate);
 
-// ---- hamm256_mfma.hip: 256-bit threshold scan on the matrix cores -----------------------
-int launch_scan256_mfma(const uint8_t* d_rows, size_t n, const uint8_t* d_q, size_t nq, int thresh,
-                        unsigned long long* d_rec, size_t cap, unsigned long long* d_total,
-                        hipStream_t stream);
-bool scan256_mfma_wanted(size_t n, size_t nq, int thresh);
-int set_scan256_small(int v);  // stationary-needle kernel for <= 512 needle descriptors: 0 / 1; else CBH_E_INVAL, knob unchanged
-int set_scan256_mfma(int v);   // 0..2 (2 = force for any size); else CBH_E_INVAL, knob unchanged
-int get_scan256_small();
-int get_scan256_mfma();
+// ---- the 256-bit threshold scan: hamm256_scan.hip decides, hamm256_mfma.hip launches what it is told -------------------
 // "scan256_kernels": which kernels 256-bit launches have used since the mask was last cleared (cbh_set_tuning(.., 0)).
-// Noted by launch_scan256 (idx256.hip) and launch_scan256_mfma and nowhere else.
+// Noted by launch_hamm256_scan and nowhere else.
 enum Scan256Kernel : int {
   kS256Scan = 1 << 0,     // k_hamm256_scan<8,4>
   kS256Mfma2 = 1 << 1,    // k_hamm256_mfma<6,3,2>
@@ -208,11 +200,29 @@ enum Scan256Kernel : int {
   kS256Small8 = 1 << 5,   // k_hamm256_small<8>
   kS256Small16 = 1 << 6,  // k_hamm256_small<16>
 };
-void note_scan256_kernel(int bit);
+// the kernel of a launch of n rows x nq needle descriptors, and the descriptor count its expanded needles are padded to
+// (0: k_hamm256_scan reads the needles as they are)
+struct Route256 {
+  Scan256Kernel kernel;
+  uint32_t nq_pad;
+};
+Route256 route256(size_t n, size_t nq, int thresh);
+// Appends one record q << 41 | dist << 32 | row per (needle descriptor q, row) with popcount(xor of the 32 bytes) < thresh.
+// *d_total += number of such pairs; records with slot index >= cap are dropped.
+int launch_hamm256_scan(const uint8_t* d_rows, size_t n, const uint8_t* d_q, size_t nq, int thresh,
+                        unsigned long long* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream);
+int set_scan256_small(int v);  // stationary-needle kernel for <= 512 needle descriptors: 0 / 1; else CBH_E_INVAL, knob unchanged
+int set_scan256_mfma(int v);   // 0..2 (2 = force for any size); else CBH_E_INVAL, knob unchanged
+int get_scan256_small();
+int get_scan256_mfma();
 long long get_scan256_kernels();
 void clear_scan256_kernels();
-
-
+// hamm256_mfma.hip: the needles in the matrix-core kernels' operand layout (qx: nq_pad x 128 bytes), and one of its kernels
+// on them
+void expand_needles256(const uint8_t* d_q, size_t nq, uint32_t nq_pad, uint4* qx, hipStream_t stream);
+int launch_hamm256_mfma(Scan256Kernel kernel, const uint8_t* d_rows, size_t n, const uint4* qx, const uint8_t* d_q,
+                        size_t nq, int thresh, unsigned long long* d_rec, size_t cap, unsigned long long* d_total,
+                        hipStream_t stream);
 
 // ---- setters behind cbh_set_tuning (include/cbird_hip.h documents every knob) ---------------------------------------
 int g_hash_mfma_set(int v);        // dcthash.hip "hash_mfma": 256 x 256 tiles on k_dcthash_256_band (non-zero) or k_dcthash_256 (0)

@@ -1,7 +1,7 @@
 // hamm256_mfma.hip -- K6m: 256-bit Hamming threshold scan (CvFeaturesIndex brute force,
 // src/cvfeaturesindex.cpp:497-518: the exact search FLANN-LSH approximates) on the matrix cores.
 //
-// Same records as k_hamm256_scan (idx256.hip): one  q<<41 | dist<<32 | row  per (needle descriptor,
+// Same records as k_hamm256_scan (hamm256_scan.hip): one  q<<41 | dist<<32 | row  per (needle descriptor,
 // index row) with popcount(xor of the 32 bytes) < thresh.
 //
 // A 256-bit distance is four chained FP4 sign-dot-product MFMAs (fp4_sign.h) on one accumulator:
@@ -12,7 +12,6 @@
 // hit parks the accumulators in LDS and decodes them in a rolled loop.  VALU work is 2 ops per
 // MFMA, so the kernel runs at the matrix-core rate: 4 x ~43 cycles per 1024 pairs.
 #include <algorithm>
-#include <atomic>
 
 #include "cbh_internal.h"
 #include "fp4_sign.h"
@@ -410,111 +409,52 @@ __global__ __launch_bounds__(kThreads, 2) void k_hamm256_small(  // (2: accumula
   }
 }
 
-int g_scan256_small = 1;   // "scan256_small": the stationary-needle kernel for <= 512 needle descriptors (default on)
-int g_scan256_mfma = 1;
-constexpr int kPre128MaxThresh = 40;  // thresholds up to this take a first-128-bit prefilter variant
-std::atomic<long long> g_scan256_kernels{0};  // "scan256_kernels": Scan256Kernel bits of the launches since the last clear
+// the launch geometry of each kernel, with its measured constants; qx: the needles expanded by expand_needles256
+struct Scan256Args {
+  const uint32_t* rows;
+  uint32_t n;
+  const uint4* qx;
+  const uint32_t* qraw;
+  uint32_t nq, thresh;
+  unsigned long long* rec;
+  unsigned long long cap;
+  unsigned long long* total;
+  hipStream_t stream;
+};
 
-}  // namespace
-
-int set_scan256_mfma(int v) {
-  if (v < 0 || v > 2) return CBH_E_INVAL;
-  g_scan256_mfma = v;
-  return CBH_OK;
-}
-int set_scan256_small(int v) {
-  if (v != 0 && v != 1) return CBH_E_INVAL;
-  g_scan256_small = v;
-  return CBH_OK;
-}
-int get_scan256_mfma() { return g_scan256_mfma; }
-int get_scan256_small() { return g_scan256_small; }
-void note_scan256_kernel(int bit) { g_scan256_kernels.fetch_or((long long)bit); }
-long long get_scan256_kernels() { return g_scan256_kernels.load(); }
-void clear_scan256_kernels() { g_scan256_kernels.store(0); }
-
-bool scan256_mfma_wanted(size_t n, size_t nq, int thresh) {
-  if (thresh < 1 || thresh > 257) return false;
-  if (g_scan256_mfma == 2) return true;  // forced (tests)
-  return g_scan256_mfma && nq >= 64 && n >= 4096;
+template <int NT>
+void launch_small(const Scan256Args& a) {
+  const uint32_t row_tiles = (a.n + 31u) / 32u;
+  uint32_t wgs_s = 2048u;  // workgroups of the persistent grid; measured: 512 / 1024 / 2048 / 8192 = 1.22 / 1.10 / 1.07 / 1.07 ms
+  wgs_s = std::min(wgs_s, (row_tiles + kWaves - 1) / kWaves);
+  hipLaunchKernelGGL((k_hamm256_small<NT>), dim3(wgs_s), dim3(kThreads), 0, a.stream, a.rows, a.n, a.qx, a.qraw, a.nq,
+                     a.thresh, a.rec, a.cap, a.total);
 }
 
-int launch_scan256_mfma(const uint8_t* d_rows, size_t n, const uint8_t* d_q, size_t nq, int thresh,
-                        unsigned long long* d_rec, size_t cap, unsigned long long* d_total,
-                        hipStream_t stream) {
-  if (n == 0 || nq == 0 || thresh <= 0) return CBH_OK;
-  if (n > 0xfffffff0ull || nq >= (1u << 23) || thresh > 257) return CBH_E_INVAL;
-  const uint32_t n_tiles = (uint32_t)((nq + 31) / 32);
-  const uint32_t nq_pad = n_tiles * 32u;
-  uint4* qx = nullptr;
-  CBH_HIP(cbh::malloc_async((void**)&qx, (size_t)nq_pad * 128u, stream));
-  hipLaunchKernelGGL(k_expand_needles256, dim3((8u * nq_pad + 255u) / 256u), dim3(256), 0, stream,
-                     reinterpret_cast<const uint32_t*>(d_q), (uint32_t)nq, nq_pad, qx);
-  if (g_scan256_small && thresh <= kPre128MaxThresh && n_tiles <= 16 && (n >= 4096 || g_scan256_mfma == 2) &&
-      n <= ((size_t)1 << 27) - 64) {  // (its buffer descriptor spans n * 32 bytes)
-    // needle tiles padded to the template's count read zero descriptors from the scratch (rows of zero bits never pass:
-    // qi >= nq is dropped in the hit path)
-    const uint32_t nt = n_tiles <= 4 ? 4 : n_tiles <= 8 ? 8 : 16;
-    if (nt != n_tiles) {  // the scratch must hold nt tiles
-      (void)cbh::free_async(qx, stream);
-      qx = nullptr;
-      CBH_HIP(cbh::malloc_async((void**)&qx, (size_t)nt * 32u * 128u, stream));
-      hipLaunchKernelGGL(k_expand_needles256, dim3((8u * nt * 32u + 255u) / 256u), dim3(256), 0, stream,
-                         reinterpret_cast<const uint32_t*>(d_q), (uint32_t)nq, nt * 32u, qx);
-    }
-    const uint32_t row_tiles = (uint32_t)((n + 31) / 32);
-    uint32_t wgs_s = 2048u;  // workgroups of the persistent grid; measured: 512 / 1024 / 2048 / 8192 = 1.22 / 1.10 / 1.07 / 1.07 ms
-    wgs_s = std::min(wgs_s, (row_tiles + kWaves - 1) / kWaves);
-#define CBH_SMALL(NTT)                                                                                               \
-  hipLaunchKernelGGL((k_hamm256_small<NTT>), dim3(wgs_s), dim3(kThreads), 0, stream,                                   \
-                     reinterpret_cast<const uint32_t*>(d_rows), (uint32_t)n, qx, reinterpret_cast<const uint32_t*>(d_q), \
-                     (uint32_t)nq, (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total)
-    if (nt == 4) CBH_SMALL(4); else if (nt == 8) CBH_SMALL(8); else CBH_SMALL(16);
-#undef CBH_SMALL
-    note_scan256_kernel(nt == 4 ? kS256Small4 : nt == 8 ? kS256Small8 : kS256Small16);
-    hipError_t es = hipGetLastError();
-    (void)cbh::free_async(qx, stream);
-    CBH_HIP(es);
-    return CBH_OK;
+void launch_mfma3(const Scan256Args& a) {
+  const uint32_t n_triples = ((a.nq + 31u) / 32u + 2u) / 3u;
+  // shape: 12 row tiles per wave, groups of 2 (measured, 1e7 rows x 32 000 needles: 6/2, 6/3, 8/2, 12/2, 12/3 =
+  // 12.2 / 11.6 / 11.3 / 10.9 / 10.9 ms; one tile per accumulator 13.4)
+  constexpr int ht3 = 12;
+  const uint32_t rows_per_wg3 = 32u * (uint32_t)ht3 * kWaves;
+  const uint32_t wgs3 = (uint32_t)(((size_t)a.n + rows_per_wg3 - 1) / rows_per_wg3);
+  uint32_t tpc3 = 43;  // needle triples per chunk (4128 descriptors)
+  while (tpc3 > 2 && (uint64_t)wgs3 * ((n_triples + tpc3 - 1) / tpc3) < 8192) tpc3 = (tpc3 + 1) >> 1;
+  uint32_t chunks3 = (n_triples + tpc3 - 1) / tpc3;
+  if (chunks3 > 65535) {
+    tpc3 = (n_triples + 65534) / 65535;
+    chunks3 = (n_triples + tpc3 - 1) / tpc3;
   }
-  if (thresh <= kPre128MaxThresh && n_tiles >= 3) {
-    const uint32_t n_triples = (n_tiles + 2u) / 3u;
-    if (n_triples * 3u != n_tiles) {  // the scratch must hold whole triples (zero descriptors: dropped at qi >= nq)
-      (void)cbh::free_async(qx, stream);
-      qx = nullptr;
-      CBH_HIP(cbh::malloc_async((void**)&qx, (size_t)n_triples * 96u * 128u, stream));
-      hipLaunchKernelGGL(k_expand_needles256, dim3((8u * n_triples * 96u + 255u) / 256u), dim3(256), 0, stream,
-                         reinterpret_cast<const uint32_t*>(d_q), (uint32_t)nq, n_triples * 96u, qx);
-    }
-    // shape: 12 row tiles per wave, groups of 2 (measured, 1e7 rows x 32 000 needles: 6/2, 6/3, 8/2, 12/2, 12/3 =
-    // 12.2 / 11.6 / 11.3 / 10.9 / 10.9 ms; one tile per accumulator 13.4)
-    constexpr int ht3 = 12;
-    const uint32_t rows_per_wg3 = 32u * (uint32_t)ht3 * kWaves;
-    const uint32_t wgs3 = (uint32_t)((n + rows_per_wg3 - 1) / rows_per_wg3);
-    uint32_t tpc3 = 43;  // needle triples per chunk (4128 descriptors)
-    while (tpc3 > 2 && (uint64_t)wgs3 * ((n_triples + tpc3 - 1) / tpc3) < 8192) tpc3 = (tpc3 + 1) >> 1;
-    uint32_t chunks3 = (n_triples + tpc3 - 1) / tpc3;
-    if (chunks3 > 65535) {
-      tpc3 = (n_triples + 65534) / 65535;
-      chunks3 = (n_triples + tpc3 - 1) / tpc3;
-    }
-#define CBH_256F3(HT, GG)                                                                               \
-  hipLaunchKernelGGL((k_hamm256_mfma3<HT, GG>), dim3(wgs3, chunks3), dim3(kThreads), 0, stream,         \
-                     reinterpret_cast<const uint32_t*>(d_rows), (uint32_t)n, qx,                        \
-                     reinterpret_cast<const uint32_t*>(d_q), (uint32_t)nq, n_triples, tpc3,             \
-                     (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total)
-    CBH_256F3(12, 2);
-#undef CBH_256F3
-    note_scan256_kernel(kS256Mfma3);
-    hipError_t e3 = hipGetLastError();
-    (void)cbh::free_async(qx, stream);
-    CBH_HIP(e3);
-    return CBH_OK;
-  }
-  // fewer than three needle tiles, or thresholds beyond the prefilter's range: one tile per accumulator
+  hipLaunchKernelGGL((k_hamm256_mfma3<ht3, 2>), dim3(wgs3, chunks3), dim3(kThreads), 0, a.stream, a.rows, a.n, a.qx,
+                     a.qraw, a.nq, n_triples, tpc3, a.thresh, a.rec, a.cap, a.total);
+}
+
+template <int KCH>
+void launch_mfma(const Scan256Args& a) {
+  const uint32_t n_tiles = (a.nq + 31u) / 32u;
   constexpr int ht = 6;
   const uint32_t rows_per_wg = 32u * (uint32_t)ht * kWaves;
-  const uint32_t wgs = (uint32_t)((n + rows_per_wg - 1) / rows_per_wg);
+  const uint32_t wgs = (uint32_t)(((size_t)a.n + rows_per_wg - 1) / rows_per_wg);
   uint32_t tpc = 128;  // needle tiles per chunk (4096 descriptors)
   while (tpc > 4 && (uint64_t)wgs * ((n_tiles + tpc - 1) / tpc) < 8192) tpc >>= 1;
   uint32_t chunks = (n_tiles + tpc - 1) / tpc;
@@ -522,18 +462,33 @@ int launch_scan256_mfma(const uint8_t* d_rows, size_t n, const uint8_t* d_q, siz
     tpc = (n_tiles + 65534) / 65535;
     chunks = (n_tiles + tpc - 1) / tpc;
   }
-  const bool pre128 = thresh <= kPre128MaxThresh;
-#define CBH_256(HT, GG, KC)                                                                       \
-  hipLaunchKernelGGL((k_hamm256_mfma<HT, GG, KC>), dim3(wgs, chunks), dim3(kThreads), 0, stream,  \
-                     reinterpret_cast<const uint32_t*>(d_rows), (uint32_t)n, qx,                  \
-                     reinterpret_cast<const uint32_t*>(d_q), (uint32_t)nq, n_tiles, tpc,          \
-                     (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total)
-  if (pre128) CBH_256(6, 3, 2); else CBH_256(6, 3, 4);
-#undef CBH_256
-  note_scan256_kernel(pre128 ? kS256Mfma2 : kS256Mfma4);
-  hipError_t e = hipGetLastError();
-  (void)cbh::free_async(qx, stream);
-  CBH_HIP(e);
+  hipLaunchKernelGGL((k_hamm256_mfma<ht, 3, KCH>), dim3(wgs, chunks), dim3(kThreads), 0, a.stream, a.rows, a.n, a.qx,
+                     a.qraw, a.nq, n_tiles, tpc, a.thresh, a.rec, a.cap, a.total);
+}
+
+}  // namespace
+
+// nq needle descriptors into qx, which has room for nq_pad (a multiple of 32); the padding is zero descriptors
+void expand_needles256(const uint8_t* d_q, size_t nq, uint32_t nq_pad, uint4* qx, hipStream_t stream) {
+  hipLaunchKernelGGL(k_expand_needles256, dim3((8u * nq_pad + 255u) / 256u), dim3(256), 0, stream,
+                     reinterpret_cast<const uint32_t*>(d_q), (uint32_t)nq, nq_pad, qx);
+}
+
+int launch_hamm256_mfma(Scan256Kernel kernel, const uint8_t* d_rows, size_t n, const uint4* qx, const uint8_t* d_q,
+                        size_t nq, int thresh, unsigned long long* d_rec, size_t cap, unsigned long long* d_total,
+                        hipStream_t stream) {
+  const Scan256Args a{reinterpret_cast<const uint32_t*>(d_rows), (uint32_t)n, qx, reinterpret_cast<const uint32_t*>(d_q),
+                      (uint32_t)nq, (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total, stream};
+  switch (kernel) {
+    case kS256Small4: launch_small<4>(a); break;
+    case kS256Small8: launch_small<8>(a); break;
+    case kS256Small16: launch_small<16>(a); break;
+    case kS256Mfma3: launch_mfma3(a); break;
+    case kS256Mfma2: launch_mfma<2>(a); break;
+    case kS256Mfma4: launch_mfma<4>(a); break;
+    default: return CBH_E_INVAL;  // (k_hamm256_scan is hamm256_scan.hip's own)
+  }
+  CBH_HIP(hipGetLastError());
   return CBH_OK;
 }
 

@@ -7,79 +7,23 @@
 // skipped AFTER the knn cut, :518), and scores each media by median distance * 1000 / votes (:564-596).
 // LSH is approximate; this is the exact search it approximates (results are a superset).
 //
-// k_hamm256_scan has the shape of k_hamm64_scan: each lane keeps H rows (first 128 bits, 4 VGPRs per row) in
-// registers, needles are wave-uniform SGPR operands.  Since the k nearest are only ever used below a threshold,
-// it is a threshold scan: the first 128 bits give a sound lower bound (4 xor + 4 bcnt per pair, min3 over
-// pairs), and only slots whose bound drops under the threshold load their second half and evaluate all 256 bits.
-// Records q<<41 | dist<<32 | row are then ordered and cut at k per needle descriptor.
+// Since the k nearest are only ever used below a threshold, the search is a threshold scan (launch_hamm256_scan,
+// hamm256_scan.hip: the popcount kernel or the matrix cores).  Records q<<41 | dist<<32 | row are then ordered and cut
+// at k per needle descriptor.
+//
+//   rows   Rows256: rows on one device and what a scan of them needs.  A plain handle has one; a sharded handle one per
+//          shard, and its own holds no rows but receives the shards' records.
+//   call   Call256 owns one search: the handle's device and mutex, and a Run256 per Rows256 it puts work on.
+//   scan   rounds over the runs that have to scan (launch_round, collect_round), the same for both handle kinds;
+//          gather_shards is the sharded-only finish.
+//   cut    sorted_records leaves the ordered records in the handle's own block; knn256 cuts them at k, radius256 downloads them.
 
 #include <map>
+#include <optional>
 
 #include "cbh_index.h"
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kH = 8;
-constexpr int kQB = 4;
-
-__device__ __forceinline__ uint32_t min3u(uint32_t a, uint32_t b, uint32_t c) { return min(min(a, b), c); }
-
-__device__ __forceinline__ uint32_t popc128(uint4 a, uint4 b) {
-  return __popc(a.x ^ b.x) + __popc(a.y ^ b.y) + __popc(a.z ^ b.z) + __popc(a.w ^ b.w);
-}
-
-template <int H, int QB>
-__global__ __launch_bounds__(kThreads) void k_hamm256_scan(
-    const uint4* __restrict__ rows /* 2 x uint4 per row */, uint32_t n, const uint4* __restrict__ q, uint32_t nq,
-    uint32_t q_chunk, uint32_t thresh, unsigned long long* __restrict__ rec, unsigned long long cap,
-    unsigned long long* __restrict__ total) {
-  const uint32_t base_idx = blockIdx.x * (uint32_t)(kThreads * H) + threadIdx.x;
-  uint4 h[H];
-#pragma unroll
-  for (int j = 0; j < H; ++j) {
-    const uint32_t idx = base_idx + (uint32_t)j * kThreads;
-    h[j] = idx < n ? rows[(size_t)idx * 2] : make_uint4(0u, 0u, 0u, 0u);
-  }
-  const uint32_t q0 = blockIdx.y * q_chunk;
-  const uint32_t q1 = min(nq, q0 + q_chunk);
-  for (uint32_t qb = q0; qb < q1; qb += QB) {
-    uint4 cur[QB];
-#pragma unroll
-    for (int i = 0; i < QB; ++i) cur[i] = q[(size_t)min(qb + i, q1 - 1) * 2];  // wave-uniform -> SMEM
-    uint32_t acc[H];
-#pragma unroll
-    for (int j = 0; j < H; ++j) acc[j] = 0xffffu;
-#pragma unroll
-    for (int i = 0; i < QB; i += 2) {
-#pragma unroll
-      for (int j = 0; j < H; ++j) acc[j] = min3u(acc[j], popc128(h[j], cur[i]), popc128(h[j], cur[i + 1]));
-    }
-    uint32_t m = acc[0];
-#pragma unroll
-    for (int j = 1; j < H; ++j) m = min(m, acc[j]);
-    if (m < thresh) {
-#pragma unroll
-      for (int j = 0; j < H; ++j) {
-        if (acc[j] < thresh) {
-          const uint32_t idx = base_idx + (uint32_t)j * kThreads;
-          if (idx < n) {
-            const uint4 h2 = rows[(size_t)idx * 2 + 1];
-#pragma unroll 1
-            for (uint32_t qi = qb; qi < min(qb + QB, q1); ++qi) {
-              const uint32_t d = popc128(h[j], q[(size_t)qi * 2]) + popc128(h2, q[(size_t)qi * 2 + 1]);
-              if (d < thresh) {
-                const unsigned long long slot = atomicAdd(total, 1ull);
-                if (slot < cap)
-                  rec[slot] = ((unsigned long long)qi << 41) | ((unsigned long long)d << 32) | idx;
-              }
-            }
-          }
-        }
-      }
-    }
-  }
-}
 
 // first k records of every needle descriptor from the sorted list: (row, dist)
 __global__ __launch_bounds__(256) void k_select256(const unsigned long long* __restrict__ rec, size_t n,
@@ -116,33 +60,88 @@ int sig_bits256(size_t nq) {
   return 41 + b;
 }
 
+// a grow-only device array of `need` elements of `each` bytes (what it held is not kept)
+template <class T>
+int regrow(T** p, size_t* cap, size_t need, size_t each) {
+  if (need <= *cap) return CBH_OK;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  CBH_HIP(hipMalloc(p, need * each));
+  *cap = need;
+  return CBH_OK;
+}
+
+// rows on one device and what a scan of them needs (every function: on `device`, the caller has made it current)
+struct Rows256 {
+  int device = 0;
+  uint8_t* d_rows = nullptr;  // n x 32 B
+  size_t n = 0, cap = 0;
+  hipStream_t stream = nullptr;
+  uint8_t* d_q = nullptr;  // the needles of a call
+  size_t q_cap = 0;
+  unsigned long long* d_rec = nullptr;
+  size_t rec_cap = 0;
+  unsigned long long *d_total = nullptr, *h_total = nullptr;  // h_total: pinned
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  cbh::XBuf x[2];  // exchange buffers of a shard (cbh_shard.h)
+
+  int ensure_scan(size_t nq, size_t rec_need) {
+    if (!stream) {
+      CBH_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+      CBH_HIP(hipMalloc(&d_total, 8));
+      CBH_HIP(hipHostMalloc(&h_total, 8));
+      CBH_HIP(hipEventCreate(&ev0));
+      CBH_HIP(hipEventCreate(&ev1));
+    }
+    const int rc = regrow(&d_rec, &rec_cap, rec_need, 8);
+    return rc ? rc : regrow(&d_q, &q_cap, nq, 32);
+  }
+  int append(const uint8_t* rows, size_t n_rows) {
+    if (n + n_rows > cap) {
+      size_t ncap = std::max<size_t>(n + n_rows, cap + cap / 2 + 65536);
+      uint8_t* nr = nullptr;
+      CBH_HIP(hipMalloc(&nr, ncap * 32));
+      if (n) CBH_HIP(hipMemcpy(nr, d_rows, n * 32, hipMemcpyDeviceToDevice));
+      if (d_rows) (void)hipFree(d_rows);
+      d_rows = nr;
+      cap = ncap;
+    }
+    CBH_HIP(hipMemcpy(d_rows + n * 32, rows, n_rows * 32, hipMemcpyHostToDevice));
+    n += n_rows;
+    return CBH_OK;
+  }
+  void release() {
+    for (cbh::XBuf& b : x) b.release();
+    for (void* p : {(void*)d_rows, (void*)d_rec, (void*)d_total, (void*)d_q})
+      if (p) (void)hipFree(p);
+    if (h_total) (void)hipHostFree(h_total);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (stream) cbh::stream_destroy(stream);
+  }
+};
+
 }  // namespace
 
-struct Shards256;  // below: the children of a CvFeaturesIndex that spans several shards / devices
-
+struct Shards256;  // below: the shards of a CvFeaturesIndex that spans several shards / devices
 struct cbh_idx256 {
-  int device = 0;
   bool loaded = false;
-  Shards256* shards = nullptr;  // cbh_idx256_create_sharded: this handle keeps the maps, its children the rows
-  cbh::XBuf x[2];               // exchange buffers of a child (cbh_shard.h)
-  uint8_t* d_rows = nullptr;  // N x 32 B
-  size_t n = 0, cap = 0;
+  Shards256* shards = nullptr;  // cbh_idx256_create_sharded: this handle keeps the maps, the shards the rows
+  Rows256 own;                  // a plain handle: the rows.  A sharded one: no rows, the block that receives the shards' records
+  size_t n = 0;                 // rows in all (a plain handle: own.n)
   // _indexMap (cvfeaturesindex.h:77): first row -> mediaId (0 = removed), ascending; sentinel (n, 0)
-  std::vector<uint32_t> first_row;
-  std::vector<uint32_t> media_id;
+  std::vector<uint32_t> first_row{0};
+  std::vector<uint32_t> media_id{0};
   std::map<uint32_t, uint32_t> id_to_first;  // _idMap
-  // scratch (one search at a time per index; guarded)
-  std::mutex mu;
-  hipStream_t stream = nullptr;
-  unsigned long long *d_rec = nullptr, *d_alt = nullptr, *d_total = nullptr, *h_total = nullptr;
+  std::mutex mu;                             // one search at a time per index
+  // sort and cut scratch beside own.d_rec
+  unsigned long long* d_alt = nullptr;
   void* d_tmp = nullptr;
-  size_t rec_cap = 0, tmp_bytes = 0;
-  uint8_t* d_q = nullptr;
-  size_t q_cap = 0;
-  uint32_t *d_out_row = nullptr, *d_counts = nullptr;
+  size_t alt_cap = 0, tmp_bytes = 0;
+  uint32_t *d_out_row = nullptr, *d_counts = nullptr;  // k_select256's outputs
   uint16_t* d_out_dist = nullptr;
-  size_t out_cap = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  size_t row_cap = 0, dist_cap = 0, counts_cap = 0;
   double scan_ms = 0;
   uint64_t scan_pairs = 0, scan_launches = 0;
 
@@ -151,123 +150,33 @@ struct cbh_idx256 {
     if (it == first_row.begin()) return 0;
     return media_id[(size_t)(it - first_row.begin()) - 1];
   }
+  // the ping-pong buffer and radix scratch for own.rec_cap records; nq x k places for the cut (a radius search: none)
+  int ensure_cut(size_t nq, int k) {
+    const size_t places = nq * (size_t)k;
+    int rc = CBH_OK;
+    if (alt_cap < own.rec_cap) {  // (the two grow together)
+      tmp_bytes = 0;
+      rc = regrow(&d_tmp, &tmp_bytes, std::max<size_t>(cbh::sort_records_scratch_bytes(own.rec_cap), 16), 1);
+      if (!rc) rc = regrow(&d_alt, &alt_cap, own.rec_cap, 8);
+    }
+    if (!rc) rc = regrow(&d_out_row, &row_cap, places, 4);
+    if (!rc) rc = regrow(&d_out_dist, &dist_cap, places, 2);
+    return rc ? rc : regrow(&d_counts, &counts_cap, nq, 4);
+  }
 };
 
-namespace {
-
-int ensure_scratch(cbh_idx256* ix, size_t nq, size_t rec_cap, int k, bool scan_only = false) {
-  if (!ix->stream) {
-    CBH_HIP(hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking));
-    CBH_HIP(hipMalloc(&ix->d_total, 8));
-    CBH_HIP(hipHostMalloc(&ix->h_total, 8));
-    CBH_HIP(hipEventCreate(&ix->ev0));
-    CBH_HIP(hipEventCreate(&ix->ev1));
-  }
-  if (rec_cap > ix->rec_cap) {
-    if (ix->d_rec) (void)hipFree(ix->d_rec);
-    if (ix->d_alt) (void)hipFree(ix->d_alt);
-    if (ix->d_tmp) (void)hipFree(ix->d_tmp);
-    ix->d_rec = ix->d_alt = nullptr;
-    ix->d_tmp = nullptr;
-    ix->rec_cap = 0;
-    CBH_HIP(hipMalloc(&ix->d_rec, rec_cap * 8));
-    if (!scan_only) {  // (a shard only scans: the sort and the cut run on the parent)
-      CBH_HIP(hipMalloc(&ix->d_alt, rec_cap * 8));
-      ix->tmp_bytes = cbh::sort_records_scratch_bytes(rec_cap);
-      CBH_HIP(hipMalloc(&ix->d_tmp, ix->tmp_bytes ? ix->tmp_bytes : 16));
-    }
-    ix->rec_cap = rec_cap;
-  }
-  if (nq > ix->q_cap) {
-    if (ix->d_q) (void)hipFree(ix->d_q);
-    ix->d_q = nullptr;
-    ix->q_cap = 0;
-    CBH_HIP(hipMalloc(&ix->d_q, nq * 32));
-    ix->q_cap = nq;
-  }
-  if (!scan_only && nq * (size_t)k > ix->out_cap) {
-    if (ix->d_out_row) (void)hipFree(ix->d_out_row);
-    if (ix->d_out_dist) (void)hipFree(ix->d_out_dist);
-    if (ix->d_counts) (void)hipFree(ix->d_counts);
-    ix->d_out_row = ix->d_counts = nullptr;
-    ix->d_out_dist = nullptr;
-    ix->out_cap = 0;
-    CBH_HIP(hipMalloc(&ix->d_out_row, nq * (size_t)k * 4));
-    CBH_HIP(hipMalloc(&ix->d_out_dist, nq * (size_t)k * 2));
-    CBH_HIP(hipMalloc(&ix->d_counts, nq * 4));
-    ix->out_cap = nq * (size_t)k;
-  }
-  return CBH_OK;
-}
-
-int launch_scan256(cbh_idx256* ix, const uint8_t* d_q, size_t nq, int thresh) {
-  if (cbh::scan256_mfma_wanted(ix->n, nq, thresh))
-    return cbh::launch_scan256_mfma(ix->d_rows, ix->n, d_q, nq, thresh, ix->d_rec, ix->rec_cap, ix->d_total,
-                                    ix->stream);
-  const uint32_t tile = kThreads * kH;
-  const uint32_t tiles = (uint32_t)((ix->n + tile - 1) / tile);
-  uint32_t q_chunk = 4096;
-  while (q_chunk > 256 && (uint64_t)tiles * ((nq + q_chunk - 1) / q_chunk) < 8192) q_chunk >>= 1;
-  uint32_t chunks = (uint32_t)((nq + q_chunk - 1) / q_chunk);
-  if (chunks > 65535) {
-    q_chunk = (uint32_t)((nq + 65534) / 65535);
-    q_chunk = (q_chunk + kQB - 1) / kQB * kQB;
-    chunks = (uint32_t)((nq + q_chunk - 1) / q_chunk);
-  }
-  hipLaunchKernelGGL((k_hamm256_scan<kH, kQB>), dim3(tiles, chunks), dim3(kThreads), 0, ix->stream,
-                     reinterpret_cast<const uint4*>(ix->d_rows), (uint32_t)ix->n,
-                     reinterpret_cast<const uint4*>(d_q), (uint32_t)nq, q_chunk, (uint32_t)thresh, ix->d_rec,
-                     (unsigned long long)ix->rec_cap, ix->d_total);
-  CBH_HIP(hipGetLastError());
-  cbh::note_scan256_kernel(cbh::kS256Scan);
-  return CBH_OK;
-}
-
-// every record of nq needle rows (host memory) against the rows of ONE device-resident index, in ix->d_rec on
-// ix->stream; the buffer grows until all of them fit
-int scan_records(cbh_idx256* ix, const uint8_t* needles, size_t nq, int k, int thresh, unsigned long long* total_out,
-                 bool scan_only = false) {
-  int rc;
-  CBH_HIP(hipMemcpyAsync(ix->d_q, needles, nq * 32, hipMemcpyHostToDevice, ix->stream));
-  unsigned long long total = 0;
-  for (int attempt = 0;; ++attempt) {
-    CBH_HIP(hipMemsetAsync(ix->d_total, 0, 8, ix->stream));
-    CBH_HIP(hipEventRecord(ix->ev0, ix->stream));
-    rc = launch_scan256(ix, ix->d_q, nq, thresh);
-    if (rc) return rc;
-    CBH_HIP(hipEventRecord(ix->ev1, ix->stream));
-    CBH_HIP(hipMemcpyAsync(ix->h_total, ix->d_total, 8, hipMemcpyDeviceToHost, ix->stream));
-    CBH_HIP(hipStreamSynchronize(ix->stream));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ix->ev0, ix->ev1) == hipSuccess) {
-      ix->scan_ms += ms;
-      ix->scan_pairs += (uint64_t)ix->n * nq;
-      ix->scan_launches++;
-    }
-    total = *ix->h_total;
-    if (total <= ix->rec_cap) break;
-    if (attempt >= 2) return CBH_E_OVERFLOW;
-    rc = ensure_scratch(ix, nq, (size_t)total + 1024, k, scan_only);
-    if (rc) return rc == CBH_E_NOMEM ? CBH_E_OVERFLOW : rc;
-  }
-  *total_out = total;
-  return CBH_OK;
-}
-
-}  // namespace
-
 // ---- one CvFeaturesIndex over several shards / GPUs (cbh_idx256_create_sharded) ------------------------------------
-// Sharded BY IMAGE: a media's descriptor rows stay together on one shard; the parent keeps the
-// first-row -> mediaId maps in GLOBAL row numbers exactly as the one-device index does, the children hold rows only.
+// Sharded BY IMAGE: a media's descriptor rows stay together on one shard; the handle keeps the
+// first-row -> mediaId maps in GLOBAL row numbers exactly as the one-device index does, the shards hold rows only.
 // Rows arrive media by media (add), so a shard takes media until it has received kShardRun rows, then the emptiest
 // shard takes over: the global row order is the add order, a shard's rows are runs of it (a segment table per shard).
 // A search scans every shard on its own device and stream, rewrites the LOCAL row of every record to the global one
 // (k_rows_to_global: the tie-break of the knn is (distance, global row), and the maps are global), brings the records
-// to the parent with ShardComm::exchange (cbh_shard.h: copies inside a device, ncclAllGather between devices) and
-// sorts / cuts / scores there as the one-device index does.
+// to the handle's own block with ShardComm::exchange (cbh_shard.h: copies inside a device, ncclAllGather between devices)
+// and sorts / cuts / scores there as the one-device index does.
 struct Shards256 {
   cbh::ShardComm comm;
-  std::vector<cbh_idx256*> child;
+  std::vector<Rows256> shard;
   struct Seg {
     uint32_t shard;
     size_t local, global, len;
@@ -280,6 +189,28 @@ struct Shards256 {
   std::vector<long long*> d_seg_delta;
   std::vector<uint32_t> n_seg;
   bool dirty = true;
+
+  // the shard the next media goes to: the current one until it has had its run, then the emptiest
+  size_t next_shard() {
+    if (cur_run >= kShardRun) {
+      size_t best = 0;
+      for (size_t s = 1; s < shard.size(); ++s)
+        if (shard[s].n < shard[best].n) best = s;
+      cur = best;
+      cur_run = 0;
+    }
+    return cur;
+  }
+  // n_rows rows went to shard `cur` at its row `local`, as global rows from `global`
+  void note_rows(size_t local, size_t global, size_t n_rows) {
+    if (!segs.empty() && segs.back().shard == cur && segs.back().local + segs.back().len == local &&
+        segs.back().global + segs.back().len == global)
+      segs.back().len += n_rows;
+    else
+      segs.push_back(Seg{(uint32_t)cur, local, global, n_rows});
+    cur_run += n_rows;
+    dirty = true;
+  }
 };
 
 namespace {
@@ -302,11 +233,17 @@ __global__ __launch_bounds__(256) void k_rows_to_global(unsigned long long* __re
   rec[i] = (r & 0xffffffff00000000ull) | (uint32_t)((long long)row + seg_delta[lo]);
 }
 
-int upload_segments(cbh_idx256* ix) {
-  Shards256* S = ix->shards;
+// a block for a counted result and, beside the handle's own block, its sort scratch (no memory for it: the result does
+// not fit, CBH_E_OVERFLOW)
+int grow_for_result(cbh_idx256* ix, Rows256* r, unsigned long long records) {
+  int rc = r->ensure_scan(0, (size_t)records + 1024);
+  if (!rc && r == &ix->own) rc = ix->ensure_cut(0, 0);
+  return rc == CBH_E_NOMEM ? CBH_E_OVERFLOW : rc;
+}
+
+int upload_segments(Shards256* S) {
   if (!S->dirty) return CBH_OK;
-  const size_t R = S->child.size();
-  for (size_t s = 0; s < R; ++s) {
+  for (size_t s = 0; s < S->shard.size(); ++s) {
     std::vector<uint32_t> loc;
     std::vector<long long> delta;
     for (const Shards256::Seg& g : S->segs)
@@ -314,7 +251,7 @@ int upload_segments(cbh_idx256* ix) {
         loc.push_back((uint32_t)g.local);
         delta.push_back((long long)g.global - (long long)g.local);
       }
-    cbh::DeviceGuard dg(S->child[s]->device);
+    cbh::DeviceGuard dg(S->shard[s].device);
     if (!dg.ok) return CBH_E_NODEVICE;
     if (S->d_seg_local[s]) (void)hipFree(S->d_seg_local[s]);
     if (S->d_seg_delta[s]) (void)hipFree(S->d_seg_delta[s]);
@@ -330,150 +267,251 @@ int upload_segments(cbh_idx256* ix) {
   return CBH_OK;
 }
 
-// as scan_records, over the shards: all records, rows global, in the parent's d_rec on the parent's stream
-int scan_records_sharded(cbh_idx256* ix, const uint8_t* needles, size_t nq, int k, int thresh,
-                         unsigned long long* total_out) {
-  Shards256* S = ix->shards;
-  const size_t R = S->child.size();
-  int rc = upload_segments(ix);
-  if (rc) return rc;
-  std::vector<unsigned long long> count(R, 0);
-  std::vector<char> todo(R, 0);
-  // needles to every shard's device, first scans
-  for (size_t s = 0; s < R; ++s) {
-    cbh_idx256* c = S->child[s];
-    if (!c->n) continue;
-    cbh::DeviceGuard dg(c->device);
-    if (!dg.ok) return CBH_E_NODEVICE;
-    if ((rc = ensure_scratch(c, nq, std::max<size_t>(c->rec_cap, std::max<size_t>(65536, ((size_t)1 << 22) / R)), k, true)))
-      return rc;
-    CBH_HIP(hipMemcpyAsync(c->d_q, needles, nq * 32, hipMemcpyHostToDevice, c->stream));
-    todo[s] = 1;
+// One Rows256 for the length of one call.  `drained`: nothing this call put on its stream can still be running.  Two
+// operations touch it: work(), through which every enqueue goes, clears it; saw_drained(), where the host saw that, sets it.
+struct Run256 {
+  Rows256* r = nullptr;
+  bool todo = false;             // has to scan in the next round
+  unsigned long long count = 0;  // records its last scan counted
+  bool drained = true;           // (the index's streams are idle when its mutex is taken)
+  hipStream_t work() { return drained = false, r->stream; }
+  void saw_drained() { drained = true; }
+};
+
+// What one search holds: the handle's device and mutex, and the runs.  run[0 .. n_scan) scan: the shards, or a plain
+// handle's own rows; root() is the handle's own block, where the records end up (a plain handle: the same run).
+struct Call256 {
+  cbh_idx256* ix;
+  Shards256* S;
+  const uint8_t* needles;  // host memory
+  size_t nq;
+  int thresh;
+  cbh::DeviceGuard g;
+  std::lock_guard<std::mutex> lk;
+  std::vector<Run256> run;
+  size_t n_scan;
+  Call256(cbh_idx256* i, const uint8_t* q, size_t nq_, int t)
+      : ix(i), S(i->shards), needles(q), nq(nq_), thresh(t), g(i->own.device), lk(i->mu),
+        run(S ? S->shard.size() + 1 : 1), n_scan(S ? S->shard.size() : 1) {
+    for (size_t s = 0; S && s < n_scan; ++s) run[s].r = &S->shard[s];
+    run.back().r = &ix->own;
   }
-  float scan_ms = 0;
-  for (int attempt = 0; attempt < 3; ++attempt) {
-    bool any = false;
-    for (size_t s = 0; s < R; ++s) {
-      if (!todo[s]) continue;
-      any = true;
-      cbh_idx256* c = S->child[s];
-      cbh::DeviceGuard dg(c->device);
-      CBH_HIP(hipMemsetAsync(c->d_total, 0, 8, c->stream));
-      CBH_HIP(hipEventRecord(c->ev0, c->stream));
-      if ((rc = launch_scan256(c, c->d_q, nq, thresh))) return rc;
-      CBH_HIP(hipEventRecord(c->ev1, c->stream));
-      CBH_HIP(hipMemcpyAsync(c->h_total, c->d_total, 8, hipMemcpyDeviceToHost, c->stream));
-      S->comm.n_scans++;
-      if (attempt) S->comm.n_rescans++;
-    }
-    if (!any) break;
-    float worst = 0;
-    for (size_t s = 0; s < R; ++s) {
-      if (!todo[s]) continue;
-      cbh_idx256* c = S->child[s];
-      cbh::DeviceGuard dg(c->device);
-      CBH_HIP(hipStreamSynchronize(c->stream));
-      count[s] = *c->h_total;
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) worst = std::max(worst, ms);
-      todo[s] = 0;
-      if (count[s] > c->rec_cap) {  // this shard alone grows its buffer and scans again
-        rc = ensure_scratch(c, nq, (size_t)count[s] + 1024, k, true);
-        if (rc) return rc == CBH_E_NOMEM ? CBH_E_OVERFLOW : rc;
-        todo[s] = 1;
+  Run256& root() { return run.back(); }
+  // Every stream not known drained is synchronised; only then the members go: the mutex is released, and the caller's
+  // host buffers may follow.  (On the paths that succeed everything has been seen drained and nothing is synchronised here.)
+  ~Call256() {
+    for (Run256& u : run)
+      if (!u.drained) {
+        cbh::DeviceGuard dg(u.r->device);
+        (void)hipStreamSynchronize(u.r->stream);
       }
-    }
-    scan_ms += worst;
   }
-  for (size_t s = 0; s < R; ++s)
-    if (todo[s]) return CBH_E_OVERFLOW;
-  ix->scan_ms += scan_ms;
-  ix->scan_pairs += (uint64_t)ix->n * nq;
-  ix->scan_launches++;
-  unsigned long long sum = 0;
-  for (size_t s = 0; s < R; ++s) sum += count[s];
-  if (sum > ix->rec_cap) {
-    cbh::DeviceGuard dg(ix->device);
-    rc = ensure_scratch(ix, nq, (size_t)sum + 1024, k);
-    if (rc) return rc == CBH_E_NOMEM ? CBH_E_OVERFLOW : rc;
+};
+
+// the device of a scanning run for a scope: a shard's own; a plain handle's rows are on the device the call holds already
+struct RunDevice {
+  std::optional<cbh::DeviceGuard> g;
+  RunDevice(const Call256& K, const Run256& u) { if (K.S) g.emplace(u.r->device); }
+  bool ok() const { return !g || g->ok; }
+};
+
+// the handle's own block and cut scratch, the segment tables, and on every run with rows: room for the needles and a first
+// record block (2^22 records, split over the shards), the needles, todo
+int begin_scan(Call256& K, size_t out_nq, int out_k) {
+  cbh_idx256* ix = K.ix;
+  int rc = ix->own.ensure_scan(K.nq, std::max<size_t>(ix->own.rec_cap, (size_t)1 << 22));
+  if (!rc) rc = ix->ensure_cut(out_nq, out_k);
+  if (!rc && K.S) rc = upload_segments(K.S);
+  if (rc) return rc;
+  const size_t first_block = std::max<size_t>(65536, ((size_t)1 << 22) / K.n_scan);
+  for (size_t s = 0; s < K.n_scan; ++s) {
+    Run256& u = K.run[s];
+    if (!u.r->n) continue;
+    RunDevice dev(K, u);
+    if (!dev.ok()) return CBH_E_NODEVICE;
+    if (K.S && (rc = u.r->ensure_scan(K.nq, std::max(u.r->rec_cap, first_block)))) return rc;
+    CBH_HIP(hipMemcpyAsync(u.r->d_q, K.needles, K.nq * 32, hipMemcpyHostToDevice, u.work()));
+    u.todo = true;
   }
-  // local rows -> global rows, then the exchange
-  std::vector<cbh::ShardPart> parts(R);
-  for (size_t s = 0; s < R; ++s) {
-    cbh_idx256* c = S->child[s];
-    cbh::DeviceGuard dg(c->device);
-    if (count[s]) {
-      hipLaunchKernelGGL(k_rows_to_global, dim3((unsigned)((count[s] + 255) / 256)), dim3(256), 0, c->stream, c->d_rec,
-                         count[s], S->d_seg_local[s], S->d_seg_delta[s], S->n_seg[s]);
-      CBH_HIP(hipGetLastError());
-    }
-    if (!c->stream) {  // an empty shard that never scanned still takes part in a collective
-      if ((rc = ensure_scratch(c, 1, 1024, k, true))) return rc;
-    }
-    parts[s].dev_pos = S->comm.dev_pos_of_shard(s);
-    parts[s].stream = c->stream;
-    parts[s].d_rec = c->d_rec;
-    parts[s].count = count[s];
-    parts[s].ev = c->ev1;
-    parts[s].x = c->x;
-    parts[s].h_word = c->h_total;
-  }
-  cbh::DeviceGuard dg(ix->device);
-  if ((rc = S->comm.exchange(parts, ix->stream, ix->d_rec))) return rc;
-  CBH_HIP(hipStreamSynchronize(ix->stream));
-  for (size_t s = 0; s < R; ++s) {  // the shards' side of a collective has finished too before their buffers are reused
-    cbh_idx256* c = S->child[s];
-    cbh::DeviceGuard dg2(c->device);
-    if (c->stream) CBH_HIP(hipStreamSynchronize(c->stream));
-  }
-  *total_out = sum;
   return CBH_OK;
 }
 
-// knn (k per needle descriptor, below thresh) for nq needle rows on the host side of the index;
-// out_row/out_dist [nq*k], counts[nq] (full number under thresh)
-int knn_core(cbh_idx256* ix, const uint8_t* needles, size_t nq, int k, int thresh, std::vector<uint32_t>* row,
-             std::vector<uint16_t>* dist, std::vector<uint32_t>* counts,
-             std::vector<unsigned long long>* all_records = nullptr) {
-  if (!all_records) {
-    row->assign(nq * (size_t)k, 0);
-    dist->assign(nq * (size_t)k, 0);
-    counts->assign(nq, 0);
-  } else {
-    all_records->clear();
+// every run that has to scan: counter, scan, count back, on its own stream
+int launch_round(Call256& K, int attempt) {
+  for (size_t s = 0; s < K.n_scan; ++s) {
+    Run256& u = K.run[s];
+    if (!u.todo) continue;
+    Rows256* r = u.r;
+    RunDevice dev(K, u);
+    if (!dev.ok()) return CBH_E_NODEVICE;
+    hipStream_t st = u.work();
+    CBH_HIP(hipMemsetAsync(r->d_total, 0, 8, st));
+    CBH_HIP(hipEventRecord(r->ev0, st));
+    const int rc = cbh::launch_hamm256_scan(r->d_rows, r->n, r->d_q, K.nq, K.thresh, r->d_rec, r->rec_cap, r->d_total, st);
+    if (rc) return rc;
+    CBH_HIP(hipEventRecord(r->ev1, st));
+    CBH_HIP(hipMemcpyAsync(r->h_total, r->d_total, 8, hipMemcpyDeviceToHost, st));
+    if (K.S) K.S->comm.n_scans++, K.S->comm.n_rescans += attempt ? 1 : 0;
   }
-  if (nq == 0 || ix->n == 0 || thresh <= 0 || k <= 0) return CBH_OK;
-  if (nq >= (1u << 23)) return CBH_E_INVAL;
-  cbh::DeviceGuard g(ix->device);
-  if (!g.ok) return CBH_E_NODEVICE;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  int rc = ensure_scratch(ix, nq, std::max<size_t>(ix->rec_cap, (size_t)1 << 22), k);
+  return CBH_OK;
+}
+
+// waits for the round; a run whose count outgrew its block grows the block (the count plus 1024) and has to scan again,
+// up to three attempts.  *slowest: the longest kernel time of the round in ms, < 0 if none could be read.
+int collect_round(Call256& K, int attempt, float* slowest) {
+  *slowest = -1.f;
+  for (size_t s = 0; s < K.n_scan; ++s) {
+    Run256& u = K.run[s];
+    if (!u.todo) continue;
+    Rows256* r = u.r;
+    RunDevice dev(K, u);
+    if (!dev.ok()) return CBH_E_NODEVICE;
+    CBH_HIP(hipStreamSynchronize(r->stream));
+    u.saw_drained();
+    u.count = *r->h_total;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, r->ev0, r->ev1) == hipSuccess) *slowest = std::max(*slowest, ms);
+    u.todo = false;
+    if (u.count <= r->rec_cap) continue;
+    if (attempt >= 2) return CBH_E_OVERFLOW;
+    const int rc = grow_for_result(K.ix, r, u.count);
+    if (rc) return rc;
+    u.todo = true;
+  }
+  return CBH_OK;
+}
+
+// The rounds, and what cbh_idx256_get_stats counts of them.  A plain handle counts every attempt as a scan of its own: its
+// kernel time (when it could be read), n * nq pairs, one launch.  A sharded handle counts the call once: the sum over the
+// rounds of the slowest shard, n * nq pairs, one launch (the shards' launches are cbh_shard_stats' scans / rescans).
+int scan_rounds(Call256& K) {
+  cbh_idx256* ix = K.ix;
+  float call_ms = 0;
+  auto count_scan = [&](float ms) { ix->scan_ms += ms, ix->scan_pairs += (uint64_t)ix->n * K.nq, ix->scan_launches++; };
+  auto any_todo = [&] { return std::any_of(K.run.begin(), K.run.begin() + K.n_scan, [](const Run256& u) { return u.todo; }); };
+  for (int attempt = 0; any_todo(); ++attempt) {  // (collect_round ends the third)
+    float ms = 0;
+    int rc = launch_round(K, attempt);
+    if (!rc) rc = collect_round(K, attempt, &ms);
+    if (rc) return rc;
+    if (K.S)
+      call_ms += std::max(ms, 0.f);
+    else if (ms >= 0)
+      count_scan(ms);
+  }
+  if (K.S) count_scan(call_ms);
+  return CBH_OK;
+}
+
+// sharded only: local rows -> global rows on every shard, then the exchange into the handle's own block (grown to the sum
+// of the counts), and both sides of it finished
+int gather_shards(Call256& K, unsigned long long* total) {
+  cbh_idx256* ix = K.ix;
+  Shards256* S = K.S;
+  unsigned long long sum = 0;
+  for (size_t s = 0; s < K.n_scan; ++s) sum += K.run[s].count;
+  if (sum > ix->own.rec_cap) {
+    cbh::DeviceGuard dg(ix->own.device);
+    if (!dg.ok) return CBH_E_NODEVICE;
+    const int rc = grow_for_result(ix, &ix->own, sum);
+    if (rc) return rc;
+  }
+  std::vector<cbh::ShardPart> parts(K.n_scan);
+  for (size_t s = 0; s < K.n_scan; ++s) {
+    Run256& u = K.run[s];
+    Rows256* r = u.r;
+    cbh::DeviceGuard dg(r->device);
+    if (!dg.ok) return CBH_E_NODEVICE;
+    if (u.count) {
+      hipLaunchKernelGGL(k_rows_to_global, dim3((unsigned)((u.count + 255) / 256)), dim3(256), 0, u.work(), r->d_rec, u.count,
+                         S->d_seg_local[s], S->d_seg_delta[s], S->n_seg[s]);
+      CBH_HIP(hipGetLastError());
+    }
+    if (!r->stream) {  // an empty shard that never scanned still takes part in a collective
+      const int rc = r->ensure_scan(1, 1024);
+      if (rc) return rc;
+    }
+    parts[s] = cbh::ShardPart{S->comm.dev_pos_of_shard(s), u.work(), r->d_rec, u.count, nullptr, 0, r->ev1, r->x, r->h_total};
+  }
+  cbh::DeviceGuard dg(ix->own.device);
+  if (!dg.ok) return CBH_E_NODEVICE;
+  const int rc = S->comm.exchange(parts, K.root().work(), ix->own.d_rec);
   if (rc) return rc;
-  unsigned long long total = 0;
-  if ((rc = ix->shards ? scan_records_sharded(ix, needles, nq, k, thresh, &total) : scan_records(ix, needles, nq, k, thresh, &total)))
-    return rc;
-  if (total > 1) {
+  CBH_HIP(hipStreamSynchronize(ix->own.stream));
+  K.root().saw_drained();
+  for (size_t s = 0; s < K.n_scan; ++s) {  // the shards' side of a collective has finished too before their buffers are reused
+    cbh::DeviceGuard dg2(K.run[s].r->device);
+    if (!dg2.ok) return CBH_E_NODEVICE;
+    CBH_HIP(hipStreamSynchronize(K.run[s].r->stream));
+    K.run[s].saw_drained();
+  }
+  *total = sum;
+  return CBH_OK;
+}
+
+// Every record of the call's needles under its threshold, in (needle, distance, row) order, in the handle's own block, on
+// its stream; *total of them.  out_nq x out_k: the places the caller's cut needs (ensure_cut).
+int sorted_records(Call256& K, size_t out_nq, int out_k, unsigned long long* total) {
+  cbh_idx256* ix = K.ix;
+  if (!K.g.ok) return CBH_E_NODEVICE;
+  int rc = begin_scan(K, out_nq, out_k);
+  if (!rc) rc = scan_rounds(K);
+  if (rc) return rc;
+  *total = K.run[0].count;
+  if (K.S && (rc = gather_shards(K, total))) return rc;
+  if (*total > 1) {
     unsigned long long* sorted = nullptr;
-    if ((rc = cbh::sort_keys64_db(ix->d_rec, ix->d_alt, (size_t)total, (unsigned)sig_bits256(nq), ix->d_tmp, ix->tmp_bytes,
-                                  ix->stream, &sorted)))
+    hipStream_t st = K.root().work();
+    if ((rc = cbh::sort_keys64_db(ix->own.d_rec, ix->d_alt, (size_t)*total, (unsigned)sig_bits256(K.nq), ix->d_tmp,
+                                  ix->tmp_bytes, st, &sorted)))
       return rc;
-    if (sorted != ix->d_rec)
-      CBH_HIP(hipMemcpyAsync(ix->d_rec, sorted, total * 8, hipMemcpyDeviceToDevice, ix->stream));
+    if (sorted != ix->own.d_rec)
+      CBH_HIP(hipMemcpyAsync(ix->own.d_rec, sorted, *total * 8, hipMemcpyDeviceToDevice, st));
   }
-  if (all_records) {  // radius search: every record, already in (needle, distance, row) order
-    all_records->resize((size_t)total);
-    if (total)
-      CBH_HIP(hipMemcpyAsync(all_records->data(), ix->d_rec, total * 8, hipMemcpyDeviceToHost, ix->stream));
-    CBH_HIP(hipStreamSynchronize(ix->stream));
-    return CBH_OK;
+  return CBH_OK;
+}
+
+// knn (k per needle descriptor, below thresh) for nq needle rows in host memory: row/dist [nq*k] in (distance, row) order,
+// zero past the count; counts[nq] (full number under thresh)
+int knn256(cbh_idx256* ix, const uint8_t* needles, size_t nq, int k, int thresh, uint32_t* row, uint16_t* dist,
+           uint32_t* counts) {
+  if (k > 0 && nq) {
+    memset(row, 0, nq * (size_t)k * 4);
+    memset(dist, 0, nq * (size_t)k * 2);
   }
-  hipLaunchKernelGGL(k_select256, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ix->stream, ix->d_rec,
-                     (size_t)total, (uint32_t)nq, k, ix->d_out_row, ix->d_out_dist, ix->d_counts);
+  if (nq) memset(counts, 0, nq * 4);
+  if (nq == 0 || ix->n == 0 || thresh <= 0 || k <= 0) return CBH_OK;  // (nothing to scan: the zeros are the answer)
+  if (nq >= (1u << 23)) return CBH_E_INVAL;
+  Call256 K(ix, needles, nq, thresh);
+  unsigned long long total = 0;
+  const int rc = sorted_records(K, nq, k, &total);
+  if (rc) return rc;
+  hipStream_t st = K.root().work();
+  hipLaunchKernelGGL(k_select256, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, ix->own.d_rec, (size_t)total,
+                     (uint32_t)nq, k, ix->d_out_row, ix->d_out_dist, ix->d_counts);
   CBH_HIP(hipGetLastError());
-  CBH_HIP(hipMemcpyAsync(row->data(), ix->d_out_row, nq * (size_t)k * 4, hipMemcpyDeviceToHost, ix->stream));
-  CBH_HIP(hipMemcpyAsync(dist->data(), ix->d_out_dist, nq * (size_t)k * 2, hipMemcpyDeviceToHost, ix->stream));
-  CBH_HIP(hipMemcpyAsync(counts->data(), ix->d_counts, nq * 4, hipMemcpyDeviceToHost, ix->stream));
-  CBH_HIP(hipStreamSynchronize(ix->stream));
+  CBH_HIP(hipMemcpyAsync(row, ix->d_out_row, nq * (size_t)k * 4, hipMemcpyDeviceToHost, st));
+  CBH_HIP(hipMemcpyAsync(dist, ix->d_out_dist, nq * (size_t)k * 2, hipMemcpyDeviceToHost, st));
+  CBH_HIP(hipMemcpyAsync(counts, ix->d_counts, nq * 4, hipMemcpyDeviceToHost, st));
+  CBH_HIP(hipStreamSynchronize(st));
+  K.root().saw_drained();
+  return CBH_OK;
+}
+
+// radius search: every record, in (needle, distance, row) order.  `rec` is the caller's: it outlives the call's copies.
+int radius256(cbh_idx256* ix, const uint8_t* needles, size_t nq, int thresh, std::vector<unsigned long long>* rec) {
+  rec->clear();
+  if (nq == 0 || ix->n == 0 || thresh <= 0) return CBH_OK;
+  if (nq >= (1u << 23)) return CBH_E_INVAL;
+  Call256 K(ix, needles, nq, thresh);
+  unsigned long long total = 0;
+  const int rc = sorted_records(K, 0, 0, &total);
+  if (rc) return rc;
+  rec->resize((size_t)total);
+  hipStream_t st = K.root().work();
+  if (total) CBH_HIP(hipMemcpyAsync(rec->data(), ix->own.d_rec, total * 8, hipMemcpyDeviceToHost, st));
+  CBH_HIP(hipStreamSynchronize(st));
+  K.root().saw_drained();
   return CBH_OK;
 }
 
@@ -516,6 +554,23 @@ void score256(const cbh_idx256* ix, const uint32_t* row, const uint16_t* dist, c
   score_media(media.data(), dist + d0 * (size_t)k, counts + d0, 0, d1 - d0, k, out);
 }
 
+// per-needle results, score(i, &res) for needle i, packed into out (cap places) and out_offsets (n_needles + 1 entries)
+template <class Score>
+int pack_matches(size_t n_needles, Score score, cbh_match* out, size_t cap, uint64_t* out_offsets) {
+  uint64_t pos = 0;
+  for (size_t i = 0; i < n_needles; ++i) {
+    out_offsets[i] = pos;
+    std::vector<cbh_match> res;
+    score(i, &res);
+    for (auto& m : res) {
+      if (pos < cap) out[pos] = m;
+      ++pos;
+    }
+  }
+  out_offsets[n_needles] = pos;
+  return pos > cap ? CBH_E_OVERFLOW : CBH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -525,9 +580,7 @@ cbh_idx256* cbh_idx256_create(int device) {
   if (!cbh::device_usable(device)) return (cbh_idx256*)cbh::fail_handle(CBH_E_NODEVICE, "cbh_idx256_create: no usable gfx950 device at that ordinal");
   cbh_idx256* ix = new (std::nothrow) cbh_idx256;
   if (!ix) return (cbh_idx256*)cbh::fail_handle(CBH_E_NOMEM, "cbh_idx256_create: host allocation failed");
-  ix->device = device;
-  ix->first_row.push_back(0);
-  ix->media_id.push_back(0);
+  ix->own.device = device;
   return ix;
 }
 
@@ -539,33 +592,28 @@ cbh_idx256* cbh_idx256_create_sharded(uint32_t device_mask, int shards_per_devic
     delete S;
     return (cbh_idx256*)cbh::fail_handle(CBH_E_INVAL, "cbh_idx256_create_sharded: empty mask, a device of the mask is not usable, or shards_per_device out of range");
   }
-  cbh_idx256* ix = cbh_idx256_create(S->comm.devices[0]);
+  cbh_idx256* ix = new (std::nothrow) cbh_idx256;
   if (!ix) {
     delete S;
-    return nullptr;  // (cbh_idx256_create has set the code)
+    return (cbh_idx256*)cbh::fail_handle(CBH_E_NOMEM, "cbh_idx256_create_sharded: host allocation failed");
   }
+  ix->own.device = S->comm.devices[0];
   ix->shards = S;
   const size_t R = S->comm.shard_count();
-  for (size_t s = 0; s < R; ++s) {
-    cbh_idx256* c = cbh_idx256_create(S->comm.device_of_shard(s));
-    if (!c) {
-      cbh_idx256_destroy(ix);
-      return nullptr;
-    }
-    S->child.push_back(c);
-  }
+  S->shard.resize(R);
+  for (size_t s = 0; s < R; ++s) S->shard[s].device = S->comm.device_of_shard(s);
   S->d_seg_local.assign(R, nullptr);
   S->d_seg_delta.assign(R, nullptr);
   S->n_seg.assign(R, 0);
   return ix;
 }
 
-int cbh_idx256_shard_count(const cbh_idx256* ix) { return !ix ? 0 : ix->shards ? (int)ix->shards->child.size() : 1; }
+int cbh_idx256_shard_count(const cbh_idx256* ix) { return !ix ? 0 : ix->shards ? (int)ix->shards->shard.size() : 1; }
 
 size_t cbh_idx256_shard_rows(const cbh_idx256* ix, int i) {
   if (!ix) return 0;
   if (!ix->shards) return i == 0 ? ix->n : 0;
-  return i >= 0 && (size_t)i < ix->shards->child.size() ? ix->shards->child[(size_t)i]->n : 0;
+  return i >= 0 && (size_t)i < ix->shards->shard.size() ? ix->shards->shard[(size_t)i].n : 0;
 }
 
 int cbh_idx256_shard_stats(const cbh_idx256* ix, cbh_shard_stats* out) {
@@ -574,7 +622,7 @@ int cbh_idx256_shard_stats(const cbh_idx256* ix, cbh_shard_stats* out) {
   out->shards = 1, out->devices = 1;
   if (!ix->shards) return CBH_OK;
   const Shards256* S = ix->shards;
-  out->shards = (uint32_t)S->child.size();
+  out->shards = (uint32_t)S->shard.size();
   out->devices = (uint32_t)S->comm.devices.size();
   out->device_mask = S->comm.mask;
   out->segments = S->segs.size();
@@ -589,27 +637,20 @@ int cbh_idx256_shard_stats(const cbh_idx256* ix, cbh_shard_stats* out) {
 void cbh_idx256_destroy(cbh_idx256* ix) {
   if (!ix) return;
   cbh::combiner_drop(ix);  // combine.hip: the queue of cbh_*_find_coalesced callers
-  if (ix->shards) {
-    Shards256* S = ix->shards;
+  if (Shards256* S = ix->shards) {
     S->comm.destroy_comms();
-    for (size_t s = 0; s < S->child.size(); ++s) {
-      cbh::DeviceGuard g(S->child[s]->device);
-      if (s < S->d_seg_local.size() && S->d_seg_local[s]) (void)hipFree(S->d_seg_local[s]);
-      if (s < S->d_seg_delta.size() && S->d_seg_delta[s]) (void)hipFree(S->d_seg_delta[s]);
-      cbh_idx256_destroy(S->child[s]);
+    for (size_t s = 0; s < S->shard.size(); ++s) {
+      cbh::DeviceGuard g(S->shard[s].device);
+      if (S->d_seg_local[s]) (void)hipFree(S->d_seg_local[s]);
+      if (S->d_seg_delta[s]) (void)hipFree(S->d_seg_delta[s]);
+      S->shard[s].release();
     }
     delete S;
-    ix->shards = nullptr;
   }
-  cbh::DeviceGuard g(ix->device);
-  for (cbh::XBuf& b : ix->x) b.release();
-  for (void* p : {(void*)ix->d_rows, (void*)ix->d_rec, (void*)ix->d_alt, (void*)ix->d_tmp, (void*)ix->d_total,
-                  (void*)ix->d_q, (void*)ix->d_out_row, (void*)ix->d_out_dist, (void*)ix->d_counts})
+  cbh::DeviceGuard g(ix->own.device);
+  ix->own.release();
+  for (void* p : {(void*)ix->d_alt, (void*)ix->d_tmp, (void*)ix->d_out_row, (void*)ix->d_out_dist, (void*)ix->d_counts})
     if (p) (void)hipFree(p);
-  if (ix->h_total) (void)hipHostFree(ix->h_total);
-  if (ix->ev0) (void)hipEventDestroy(ix->ev0);
-  if (ix->ev1) (void)hipEventDestroy(ix->ev1);
-  if (ix->stream) cbh::stream_destroy(ix->stream);
   delete ix;
 }
 
@@ -621,39 +662,15 @@ int cbh_idx256_add(cbh_idx256* ix, uint32_t media_id, const uint8_t* rows, size_
   if (n_rows == 0) return CBH_OK;
   if (!rows) return CBH_E_INVAL;
   if (ix->n + n_rows > 0xfffffff0ull) return CBH_E_INVAL;
-  cbh::DeviceGuard g(ix->device);
-  if (!g.ok) return CBH_E_NODEVICE;
   std::lock_guard<std::mutex> lk(ix->mu);
-  if (ix->shards) {  // the rows go to a shard, the maps stay here in global row numbers
-    Shards256* S = ix->shards;
-    if (S->cur_run >= Shards256::kShardRun) {  // the current shard has had its run: the emptiest one takes over
-      size_t best = 0;
-      for (size_t s = 1; s < S->child.size(); ++s)
-        if (S->child[s]->n < S->child[best]->n) best = s;
-      S->cur = best;
-      S->cur_run = 0;
-    }
-    cbh_idx256* c = S->child[S->cur];
-    const size_t local = c->n;
-    int rc = cbh_idx256_add(c, media_id, rows, n_rows);
-    if (rc) return rc;
-    if (!S->segs.empty() && S->segs.back().shard == S->cur && S->segs.back().local + S->segs.back().len == local &&
-        S->segs.back().global + S->segs.back().len == ix->n)
-      S->segs.back().len += n_rows;
-    else
-      S->segs.push_back(Shards256::Seg{(uint32_t)S->cur, local, ix->n, n_rows});
-    S->cur_run += n_rows;
-    S->dirty = true;
-  } else if (ix->n + n_rows > ix->cap) {
-    size_t ncap = std::max<size_t>(ix->n + n_rows, ix->cap + ix->cap / 2 + 65536);
-    uint8_t* nr = nullptr;
-    CBH_HIP(hipMalloc(&nr, ncap * 32));
-    if (ix->n) CBH_HIP(hipMemcpy(nr, ix->d_rows, ix->n * 32, hipMemcpyDeviceToDevice));
-    if (ix->d_rows) (void)hipFree(ix->d_rows);
-    ix->d_rows = nr;
-    ix->cap = ncap;
-  }
-  if (!ix->shards) CBH_HIP(hipMemcpy(ix->d_rows + ix->n * 32, rows, n_rows * 32, hipMemcpyHostToDevice));
+  Shards256* S = ix->shards;  // the rows go to a shard, the maps stay here in global row numbers
+  Rows256& dst = S ? S->shard[S->next_shard()] : ix->own;
+  const size_t local = dst.n;
+  cbh::DeviceGuard g(dst.device);
+  if (!g.ok) return CBH_E_NODEVICE;
+  const int rc = dst.append(rows, n_rows);
+  if (rc) return rc;
+  if (S) S->note_rows(local, ix->n, n_rows);
   // _idMap[mid] = numDesc; _indexMap[numDesc] = mid; sentinel (numDesc + rows) -> 0
   ix->first_row.back() = (uint32_t)ix->n;
   ix->media_id.back() = media_id;
@@ -700,17 +717,17 @@ int cbh_idx256_download_rows(const cbh_idx256* ix, size_t first, size_t count, u
     for (const Shards256::Seg& sg : ix->shards->segs) {
       const size_t a = std::max(first, sg.global), b = std::min(first + count, sg.global + sg.len);
       if (a >= b) continue;
-      const cbh_idx256* c = ix->shards->child[sg.shard];
-      cbh::DeviceGuard g(c->device);
+      const Rows256& c = ix->shards->shard[sg.shard];
+      cbh::DeviceGuard g(c.device);
       if (!g.ok) return CBH_E_NODEVICE;
-      CBH_HIP(hipMemcpy(out + (a - first) * 32, c->d_rows + (sg.local + (a - sg.global)) * 32, (b - a) * 32,
+      CBH_HIP(hipMemcpy(out + (a - first) * 32, c.d_rows + (sg.local + (a - sg.global)) * 32, (b - a) * 32,
                         hipMemcpyDeviceToHost));
     }
     return CBH_OK;
   }
-  cbh::DeviceGuard g(ix->device);
+  cbh::DeviceGuard g(ix->own.device);
   if (!g.ok) return CBH_E_NODEVICE;
-  CBH_HIP(hipMemcpy(out, ix->d_rows + first * 32, count * 32, hipMemcpyDeviceToHost));
+  CBH_HIP(hipMemcpy(out, ix->own.d_rows + first * 32, count * 32, hipMemcpyDeviceToHost));
   return CBH_OK;
 }
 
@@ -719,14 +736,7 @@ int cbh_idx256_download_rows(const cbh_idx256* ix, size_t first, size_t count, u
 int cbh_idx256_knn(cbh_idx256* ix, const uint8_t* needles, size_t nq, int k, int thresh, uint32_t* out_row,
                    uint16_t* out_dist, uint32_t* counts) {
   if (!ix || (nq && (!needles || !out_row || !out_dist || !counts))) return CBH_E_INVAL;
-  std::vector<uint32_t> row, cnt;
-  std::vector<uint16_t> dist;
-  int rc = knn_core(ix, needles, nq, k, thresh, &row, &dist, &cnt);
-  if (rc) return rc;
-  memcpy(out_row, row.data(), row.size() * 4);
-  memcpy(out_dist, dist.data(), dist.size() * 2);
-  memcpy(counts, cnt.data(), cnt.size() * 4);
-  return CBH_OK;
+  return knn256(ix, needles, nq, k, thresh, out_row, out_dist, counts);
 }
 
 /* knn + the mediaId of every candidate row (0 = removed): the shard-local step of the multi-GPU path, where the
@@ -750,18 +760,10 @@ int cbh_cvfeatures_score(const uint32_t* media, const uint16_t* dist, const uint
                          size_t n_needles, int k, cbh_match* out, size_t cap, uint64_t* out_offsets) {
   if (!offsets || !out_offsets || (cap && !out) || k <= 0) return CBH_E_INVAL;
   if (n_needles && offsets[n_needles] && (!media || !dist || !counts)) return CBH_E_INVAL;
-  uint64_t pos = 0;
-  for (size_t i = 0; i < n_needles; ++i) {
-    out_offsets[i] = pos;
-    std::vector<cbh_match> res;
-    score_media(media, dist, counts, (size_t)offsets[i], (size_t)offsets[i + 1], k, &res);
-    for (auto& m : res) {
-      if (pos < cap) out[pos] = m;
-      ++pos;
-    }
-  }
-  out_offsets[n_needles] = pos;
-  return pos > cap ? CBH_E_OVERFLOW : CBH_OK;
+  auto score = [&](size_t i, std::vector<cbh_match>* res) {
+    score_media(media, dist, counts, (size_t)offsets[i], (size_t)offsets[i + 1], k, res);
+  };
+  return pack_matches(n_needles, score, out, cap, out_offsets);
 }
 
 /* CvFeaturesIndex::find (:438-604) for one needle with n_desc descriptor rows */
@@ -769,9 +771,10 @@ int cbh_idx256_find(cbh_idx256* ix, const uint8_t* needle_rows, size_t n_desc, i
                     size_t cap, size_t* n_out) {
   if (!ix || !n_out || (cap && !out) || (n_desc && !needle_rows)) return CBH_E_INVAL;
   *n_out = 0;
-  std::vector<uint32_t> row, cnt;
-  std::vector<uint16_t> dist;
-  int rc = knn_core(ix, needle_rows, n_desc, k, thresh, &row, &dist, &cnt);
+  const size_t places = n_desc * (size_t)std::max(k, 0);
+  std::vector<uint32_t> row(places), cnt(n_desc);
+  std::vector<uint16_t> dist(places);
+  int rc = knn256(ix, needle_rows, n_desc, k, thresh, row.data(), dist.data(), cnt.data());
   if (rc) return rc;
   std::vector<cbh_match> res;
   score256(ix, row.data(), dist.data(), cnt.data(), 0, n_desc, k, &res);
@@ -784,22 +787,15 @@ int cbh_idx256_find_batch(cbh_idx256* ix, const uint8_t* needle_rows, const uint
                           int thresh, int k, cbh_match* out, size_t cap, uint64_t* out_offsets) {
   if (!ix || !offsets || !out_offsets || (cap && !out)) return CBH_E_INVAL;
   const size_t nq = n_needles ? (size_t)offsets[n_needles] : 0;
-  std::vector<uint32_t> row, cnt;
-  std::vector<uint16_t> dist;
-  int rc = knn_core(ix, needle_rows, nq, k, thresh, &row, &dist, &cnt);
+  const size_t places = nq * (size_t)std::max(k, 0);
+  std::vector<uint32_t> row(places), cnt(nq);
+  std::vector<uint16_t> dist(places);
+  int rc = knn256(ix, needle_rows, nq, k, thresh, row.data(), dist.data(), cnt.data());
   if (rc) return rc;
-  uint64_t pos = 0;
-  for (size_t i = 0; i < n_needles; ++i) {
-    out_offsets[i] = pos;
-    std::vector<cbh_match> res;
-    score256(ix, row.data(), dist.data(), cnt.data(), (size_t)offsets[i], (size_t)offsets[i + 1], k, &res);
-    for (auto& m : res) {
-      if (pos < cap) out[pos] = m;
-      ++pos;
-    }
-  }
-  out_offsets[n_needles] = pos;
-  return pos > cap ? CBH_E_OVERFLOW : CBH_OK;
+  auto score = [&](size_t i, std::vector<cbh_match>* res) {
+    score256(ix, row.data(), dist.data(), cnt.data(), (size_t)offsets[i], (size_t)offsets[i + 1], k, res);
+  };
+  return pack_matches(n_needles, score, out, cap, out_offsets);
 }
 
 /* cv::BFMatcher(NORM_HAMMING).radiusMatch(queryDescriptors, matches, maxDistance) against the rows of the index as
@@ -812,7 +808,7 @@ int cbh_idx256_radius_match(cbh_idx256* ix, const uint8_t* queries, size_t nq, i
   if (max_dist < 0) max_dist = -1;
   if (max_dist > 256) max_dist = 256;
   std::vector<unsigned long long> rec;
-  int rc = knn_core(ix, queries, nq, 1, max_dist + 1, nullptr, nullptr, nullptr, &rec);
+  int rc = radius256(ix, queries, nq, max_dist + 1, &rec);
   if (rc) return rc;
   size_t p = 0;
   for (size_t q = 0; q < nq; ++q) {

@@ -1,9 +1,9 @@
 """Where a (row, needle) pair lands in the 256-bit scan kernels (cbird_amd/csrc/hamm256_mfma.hip, k_hamm256_scan in
-idx256.hip), an exact-integer model of the three-field accumulator, a plain reference of the scan, and seeded fixtures
+hamm256_scan.hip), an exact-integer model of the three-field accumulator, a plain reference of the scan, and seeded fixtures
 that put matches at chosen places of that layout.
 
-Plain numpy, no GPU and nothing from cbird_amd.  The model restates the launch arithmetic of launch_scan256_mfma /
-launch_scan256 and the accumulator's bookkeeping; it never decides what the right answer is -- that is
+Plain numpy, no GPU and nothing from cbird_amd.  The model restates route256 (hamm256_scan.hip), the launch arithmetic of
+each kernel's launcher and the accumulator's bookkeeping; it never decides what the right answer is -- that is
 reference_records(): every pair compared on all 256 bits.  It does not predict what the hardware rounds; it proves that a
 fixture reaches the state it names.
 
@@ -97,7 +97,7 @@ def row_reg(rit):
 
 
 def route(n: int, nq: int, thresh: int, path: str, forced: bool = True) -> int:
-    """the kernel launch_scan256 picks: path as conftest's scan256_path ("mfma" = "scan256_mfma" 2 + "scan256_small" 1,
+    """the kernel route256 (hamm256_scan.hip) picks: path as conftest's scan256_path ("mfma" = "scan256_mfma" 2 + "scan256_small" 1,
     "mfma_rows" = 2 + 0, "valu" = 0); forced=False is "scan256_mfma" 1, the shipped default"""
     if path == "valu" or thresh < 1 or thresh > 257:
         return K_SCAN

@@ -166,6 +166,69 @@ def _cases(gpu):
     cases["idx256_knn_small"] = idx256(300)
     cases["idx256_knn_batch"] = idx256(2000)
 
+    def idx256_radius():  # the record-download path
+        from cbird_amd import _lib
+
+        idx = CvFeaturesIndex()
+        for i in range(40):
+            _lib.check(_lib.lib().cbh_idx256_add(idx.handle, i + 1, rows[i * 300:(i + 1) * 300].ctypes.data, 300), "add")
+        q = rows[5:305].copy()
+        q[::2, 3] ^= 0x21
+        return tuple(np.asarray(x) for x in idx.radius_match(q, 29))
+
+    cases["idx256_radius"] = idx256_radius
+    rows3 = rng.integers(0, 256, (120 * 300, 32), dtype=np.uint8)
+
+    def idx256_sharded():  # rows over three runs of 16384: every shard scans, translates its rows and takes part in the exchange
+        from cbird_amd import _lib
+
+        idx = CvFeaturesIndex(shards=(1, 3))
+        for i in range(120):
+            _lib.check(_lib.lib().cbh_idx256_add(idx.handle, i + 1, rows3[i * 300:(i + 1) * 300].ctypes.data, 300), "add")
+        assert min(idx.shard_rows()) > 0
+        q = rows3[::37][:500].copy()
+        q[::2, 3] ^= 0x21
+        return tuple(np.asarray(x) for x in idx.knn(q, 6, 30)) + tuple(np.asarray(x) for x in idx.radius_match(q, 29))
+
+    cases["idx256_sharded"] = idx256_sharded
+
+    # the grow-and-run-again route of the 256-bit index: all 3072 rows of the dense fixture sit on one of three shards.  The
+    # first call's records (the first nq1 needles) outgrow that shard's block of 2^22 / 3; the second call's (all needles)
+    # outgrow the handle's own 2^22 as well -- every allocation of the second round and of both regrows fails once too
+    import scan256_layout as S256
+
+    dense = S256.build("dense", 40)
+    per_needle = np.bincount((S256.reference(dense.rows, dense.needles, dense.thresh) >> np.uint64(41)).astype(np.int64),
+                             minlength=len(dense.needles))
+    upto = np.cumsum(per_needle)
+    nq1 = int(np.searchsorted(upto, (1 << 22) // 3, side="right")) + 1
+    assert (1 << 22) // 3 < upto[nq1 - 1] <= (1 << 22) < upto[-1]
+    dense_out = np.zeros((int(upto[-1]), 3), np.int32)
+
+    def idx256_sharded_regrow():
+        from cbird_amd import _lib
+
+        def rescans():
+            st = _lib.cbh_shard_stats()
+            _lib.check(_lib.lib().cbh_idx256_shard_stats(idx.handle, C.byref(st)), "stats")
+            return st.rescans
+
+        idx = CvFeaturesIndex(shards=(1, 3))
+        for i in range(0, len(dense.rows), 256):
+            _lib.check(_lib.lib().cbh_idx256_add(idx.handle, i // 256 + 1, dense.rows[i:i + 256].ctypes.data, 256), "add")
+        assert sorted(idx.shard_rows()) == [0, 0, len(dense.rows)]
+        r0 = rescans()
+        a = tuple(np.asarray(x) for x in idx.knn(dense.needles[:nq1], 6, dense.thresh))
+        r1 = rescans()
+        assert r1 > r0 and int(a[2].sum()) == int(upto[nq1 - 1])
+        first = np.zeros(len(dense.needles) + 1, np.uint64)
+        _lib.check(_lib.lib().cbh_idx256_radius_match(idx.handle, dense.needles.ctypes.data, len(dense.needles), dense.thresh - 1,
+                                                      dense_out.ctypes.data, len(dense_out), first.ctypes.data), "radius_match")
+        assert rescans() > r1 and int(first[-1]) == len(dense_out) > (1 << 22)
+        return a + (first, dense_out.copy())
+
+    cases["idx256_sharded_regrow"] = idx256_sharded_regrow
+
     cd, cids = synth_descriptors(3000, 8)
 
     def color():
@@ -216,7 +279,7 @@ def _cases(gpu):
 
 _CASE_NAMES = ["dcthash_256", "dcthash_general", "process_images", "idx64_mfma_full", "idx64_mfma_pre", "idx64_valu",
                "idx64_sharded", "idx64_sharded_regrow", "search_index_batch", "fdct_find_batch", "video_find_batch", "idx256_knn_small",
-               "idx256_knn_batch", "color_find_batch", "orb", "color_descriptor_create", "keypoint_hashes",
+               "idx256_knn_batch", "idx256_radius", "idx256_sharded", "idx256_sharded_regrow", "color_find_batch", "orb", "color_descriptor_create", "keypoint_hashes",
                "video_indexer"]
 
 

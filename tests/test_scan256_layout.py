@@ -334,6 +334,40 @@ def test_sharded_dense_grows_one_shards_block(gpu, scan256_path, thresh):
     _assert_knn(idx, fx.needles[:64], fx.thresh, S.restrict(want, 0, 64), (10,), "sharded knn")
 
 
+def _scan_stats(idx):
+    from cbird_amd import _lib
+
+    st = _lib.cbh_stats()
+    _lib.check(_lib.lib().cbh_idx256_get_stats(idx.handle, C.byref(st)), "get_stats")
+    return st
+
+
+@pytest.mark.gpu
+def test_statistics_of_a_scan_that_regrows(gpu):
+    """what cbh_idx256_get_stats and cbh_idx256_shard_stats count of ONE radius search whose 4.7 M records outgrow the first
+    block of 2^22 once.  A plain handle counts every attempt: 2 launches, 2 n nq pairs.  A sharded handle counts the call:
+    1 launch, n nq pairs -- while its one shard with rows scanned twice (scans + 2, rescans + 1)."""
+    from cbird_amd import _lib
+
+    fx = S.build("dense", 40)
+    n, nq = len(fx.rows), len(fx.needles)
+    total = len(_reference("dense", 40))
+    assert total > (1 << 22)
+    out = np.zeros((total, 3), np.int32)
+    first = np.zeros(nq + 1, np.uint64)
+    for shards, launches, scans, rescans in ((None, 2, 0, 0), ((1, 3), 1, 2, 1)):
+        idx = _index(fx.rows, per_media=256, shards=shards)
+        a, s0 = _scan_stats(idx), _shard_stats(idx)
+        _lib.check(_lib.lib().cbh_idx256_radius_match(idx.handle, fx.needles.ctypes.data, nq, fx.thresh - 1, out.ctypes.data,
+                                                      total, first.ctypes.data), "radius_match")
+        b, s1 = _scan_stats(idx), _shard_stats(idx)
+        assert int(first[-1]) == total, shards
+        assert b.scan_launches - a.scan_launches == launches, shards
+        assert b.scan_pairs - a.scan_pairs == launches * n * nq, shards
+        assert b.scan_ms > a.scan_ms, shards
+        assert (s1.scans - s0.scans, s1.rescans - s0.rescans) == (scans, rescans), shards
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("thresh,nq", [(25, 512), (40, 200), (41, 512)])
 def test_sharded_segments_translate_rows(gpu, scan256_path, thresh, nq):
