@@ -121,7 +121,8 @@ struct ScanOpts {
   // compare a needle with the entries that share its low bits (HammingTree leaf, src/tree/hammingtree.h:244-252; RadixMap
   const uint64_t* d_qmask = nullptr;  // bucket, src/tree/radix.h:135-141)
   // a call made of several launches against the same needles (the shards of a sharded handle):
-  int pre = -1;                       // the prefilter choice made once for the whole call (scan_pick_pre); -1: the launch's own
+  int pre = -1;                       // the kernel choice made once for the whole call (scan_pick_pre: 0 none, 1 the 32-bit
+                                      // prefilter, 2 the 48-bit one); -1: the launch's own
   unsigned siblings = 1;              // launches running side by side on this device
   const uint4* qx = nullptr;          // the needles expanded once on this device (expand_needles_for_scan)
 };
@@ -134,17 +135,20 @@ int launch_hamm64_scan(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n
 // For a call made of several launches: would a launch of n slots run the matrix-core scan; and the prefilter choice for
 // the whole call, probed on one launch's n slots of the call's n_total (ScanOpts::pre)
 bool scan_takes_mfma(size_t n, size_t nq, int thresh);
-bool scan_pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
-                   hipStream_t stream);
+int scan_pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
+                  hipStream_t stream);
 // the knobs and read-backs behind cbh_set_tuning / cbh_get_tuning (include/cbird_hip.h documents each)
 int set_scan_mfma(int mode);  // 0..4; CBH_E_INVAL (knob unchanged) for anything else
 int get_scan_mfma();
 void set_scan_pre_max(int t);
 void set_scan_pre_rate(int e9);
+void set_scan_pre48(int v);
 long long get_scan_pre_mask();
+long long get_scan_pre48_mask();
 long long get_scan_probes();
 long long get_scan_probe_rate_e9();
 long long get_scan_probe_true_e9();
+long long get_scan_probe_rate48_e9();
 
 // ---- the lone needle (Engine::query / -similar-to: one find() at a time) ---------------------------------------------
 // One kernel launch and no copies: the needle travels as a kernel argument, matches go straight into a pinned, coherent
@@ -165,10 +169,11 @@ int launch_find_one(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, u
 int wait_find_one(const LoneBlock* h_block, unsigned long long seq, hipStream_t stream);
 
 // ---- hamm64_mfma.hip: the same scan on the matrix cores (FP4 sign dot products) --------
-// pre: the prefilter kernel (thresholds <= 32), else the three-field kernel (<= 64) or the two-field one (65)
+// pre: 1 the prefilter kernel (thresholds <= 32), 2 the 48-bit prefilter (<= 16), 0 the three-field kernel (<= 64) or
+// the two-field one (65)
 int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
                             int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
-                            bool pre, const ScanOpts& opts);
+                            int pre, const ScanOpts& opts);
 // the needles of a call in the matrix-core kernels' operand layout, made ONCE for several launches against the same needles
 // on one device (the shards of a sharded handle): *qx = malloc_async on `stream`, to be handed to every launch as
 // ScanOpts::qx (launches on other streams wait for an event of `stream`) and given back with free_async once they have
@@ -177,8 +182,11 @@ int expand_needles_for_scan(const uint64_t* d_q, size_t nq, hipStream_t stream, 
 // k_fold_probe: the rates of fold-distance candidates and of true matches under `thresh` (<= kProbeMaxThresh) among a
 // sample of the launch's pairs -- one host round trip; false if it could not run
 constexpr int kProbeMaxThresh = 8;
+// (r_cand48: candidates of the 48-bit prefilter word, 48-bit distance <= thresh or > 32 + thresh)
 bool probe_fold_rates(const uint64_t* d_hashes, size_t n, const uint64_t* d_q, size_t nq, int thresh, hipStream_t stream,
-                      double* r_cand, double* r_true);
+                      double* r_cand, double* r_true, double* r_cand48);
+// the 720 products of cbh_selftest_fp4_products into device memory
+int selftest_fp4_products(float* d_out, hipStream_t stream);
 // ---- hamm64_join.hip: the same search as a bucketed join (multi-index hashing), thresholds <= kJoinMaxThresh -----------
 constexpr int kJoinMaxThresh = 8;
 long long get_scan_joins();  // calls the join has answered so far (cbh_get_tuning "scan_joins")

@@ -1312,6 +1312,7 @@ int cbh_set_tuning(const char* key, int value) {
   } kKnobs[] = {
       {"scan_mfma_pre_max", [](int v) { set_scan_pre_max(v); }},
       {"scan_pre_rate_e9", [](int v) { set_scan_pre_rate(v); }},
+      {"scan_pre48", [](int v) { set_scan_pre48(v); }},
       {"hash_mfma", [](int v) { (void)g_hash_mfma_set(v); }},
       {"hash_band_area", [](int v) { set_hash_band_area(v); }},
       {"hash_fuse", [](int v) { set_hash_fuse(v); }},
@@ -1358,6 +1359,7 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strncmp(key, "arena_", 6)) return arena_counter(key + 6, value);
   if (!strcmp(key, "scan_mfma")) return *value = get_scan_mfma(), CBH_OK;
   if (!strcmp(key, "scan_pre_mask")) return *value = get_scan_pre_mask(), CBH_OK;
+  if (!strcmp(key, "scan_pre48_mask")) return *value = get_scan_pre48_mask(), CBH_OK;
   if (!strcmp(key, "scan256_mfma")) return *value = get_scan256_mfma(), CBH_OK;
   if (!strcmp(key, "scan256_small")) return *value = get_scan256_small(), CBH_OK;
   if (!strcmp(key, "scan256_kernels")) return *value = get_scan256_kernels(), CBH_OK;
@@ -1365,6 +1367,7 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strcmp(key, "scan_joins")) return *value = get_scan_joins(), CBH_OK;
   if (!strcmp(key, "scan_probe_rate_e9")) return *value = get_scan_probe_rate_e9(), CBH_OK;
   if (!strcmp(key, "scan_probe_true_e9")) return *value = get_scan_probe_true_e9(), CBH_OK;
+  if (!strcmp(key, "scan_probe_rate48_e9")) return *value = get_scan_probe_rate48_e9(), CBH_OK;
   return CBH_E_INVAL;
 }
 
@@ -1397,6 +1400,20 @@ int cbh_idx64_time_scan_dev(cbh_idx64* idx, const void* d_q, size_t nq, int thre
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   *ms_avg = ms / (float)iters;
+  return rc;
+}
+
+int cbh_selftest_fp4_products(int device, float* out) {
+  if (!out) return CBH_E_INVAL;
+  if (!device_usable(device)) return CBH_E_NODEVICE;
+  DeviceGuard g(device);
+  if (!g.ok) return CBH_E_NODEVICE;
+  float* d_out = nullptr;
+  CBH_HIP(hipMalloc(&d_out, 720 * sizeof(float)));
+  int rc = selftest_fp4_products(d_out, 0);
+  hipError_t e = rc ? hipSuccess : hipMemcpy(out, d_out, 720 * sizeof(float), hipMemcpyDeviceToHost);
+  (void)hipFree(d_out);
+  CBH_HIP(e);
   return rc;
 }
 

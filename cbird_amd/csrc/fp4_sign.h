@@ -31,6 +31,32 @@ __device__ __forceinline__ uint4 fp4_expand32(uint32_t w) {
   return make_uint4(o[0], o[1], o[2], o[3]);
 }
 
+// The same with a magnitude other than 1: 16 bits -> 16 nibbles  sign | mag,  mag = the E2M1 code without its sign.
+// 0.5 (the one subnormal) and 4.0 are what the 48-bit prefilter of hamm64_mfma.hip tells two fields of one scale
+// block apart by: 0.5 * 0.5 against 4 * 4 is a ratio of 64.
+constexpr uint32_t kFp4Half = 0x1u;  // 0.5
+constexpr uint32_t kFp4Four = 0x6u;  // 4.0
+__device__ __forceinline__ uint2 fp4_expand16(uint32_t w, uint32_t mag) {
+  uint32_t o[2];
+#pragma unroll
+  for (int d = 0; d < 2; ++d) {
+    uint32_t x = (w >> (8 * d)) & 0xffu;
+    x = (x | (x << 12)) & 0x000f000fu;
+    x = (x | (x << 6)) & 0x03030303u;
+    x = (x | (x << 3)) & 0x11111111u;
+    o[d] = (0x88888888u | (mag * 0x11111111u)) ^ (x << 3);
+  }
+  return make_uint2(o[0], o[1]);
+}
+
+// The 48-bit prefilter word of a 64-bit hash (lo, hi), as three sub-blocks of 16 elements: E0 = the folds
+// bit i ^ bit i + 32 for i < 16 (the lowest-frequency coefficients against their partners), E1 = bits 16..31,
+// E2 = bits 48..63 as they are.  popc over the three sub-blocks of a ^ b is a lower bound on hamm64(a, b): every set
+// element needs a set bit of a ^ b of its own (the fold argument at the top of hamm64_mfma.hip).
+__host__ __device__ __forceinline__ uint32_t pre48_sub(uint32_t lo, uint32_t hi, uint32_t k) {
+  return k == 0 ? (lo ^ hi) & 0xffffu : k == 1 ? lo >> 16 : hi >> 16;
+}
+
 // FP4 operand of the f8f6f4 MFMA: the first 4 of the 8 operand dwords are used
 __device__ __forceinline__ v8i fp4_operand(uint4 e) {
   return v8i{(int)e.x, (int)e.y, (int)e.z, (int)e.w, 0, 0, 0, 0};

@@ -24,7 +24,7 @@
 //   * both halves are positive normal f16 bit patterns, so v_pk_maximum3_f16 (new on gfx950) takes
 //     the per-half maximum of three registers at once: 4 ops per MFMA instead of 8.
 //
-// Three variants (all exact).  Which one runs is decided in hamm64_scan.hip (the prefilter from the candidate rates the
+// Four variants (all exact).  Which one runs is decided in hamm64_scan.hip (the prefilter from the candidate rates the
 // probe below measures) and handed to launch_hamm64_scan_mfma:
 //   FULL3 (k_hamm64_mfma3, thresholds up to 64 that the prefilter does not take) three needle tiles per accumulator,
 //         detection by OR of flag bits -- described at the kernel below.
@@ -41,6 +41,10 @@
 //         accumulator with block scales 2^-1 | 2^5 and 2^11 | 2^17: four 6-bit flag-bit fields per register (the
 //         top one flags by carrying into the exponent), reduced with v_or3_b32 -- one result VGPR per 256
 //         comparisons.  Candidates are re-evaluated on the full 64 bits.
+//   PRE48 (thresholds where the fold's candidates drown PRE: 8 on image hashes) the same prefilter on a 48-bit word -- 16
+//         folds and 32 plain bits, a tighter lower bound whose candidates are a hundred times rarer -- for three MFMAs per
+//         four needle tiles: 3/4 of FULL3's matrix work.  Layout and flag rule at step48 in the kernel body; events, drain
+//         and re-check are PRE's.
 //
 // Hits.  After the MFMAs of a group of G haystack tiles one compare of the reduced flags decides
 // whether anything is under the threshold.  Then the lanes that hold flagged results list them in wave-private
@@ -53,7 +57,7 @@
 // Layout.  A workgroup is 4 waves; each wave keeps HT haystack tiles (32 rows each) expanded
 // to FP4 in VGPRs (4 VGPRs per tile: lane (r, half) holds word `half` of row r; PRE: the fold
 // lo ^ hi in both halves) and streams needle tiles -- pre-expanded once per call by
-// k_expand_needles (expand_needles_for_scan) into a 48-byte-per-needle scratch -- through 16-byte loads that the 4 waves
+// k_expand_needles (expand_needles_for_scan) into a 72-byte-per-needle scratch -- through 16-byte loads that the 4 waves
 // share in L1/L2.
 #include <algorithm>
 #include <mutex>
@@ -70,6 +74,7 @@ typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 constexpr int kThreads = 256;
 constexpr int kWaves = 4;
 constexpr int kHT = 8;  // haystack tiles a wave keeps in registers (256 rows)
+constexpr int kHT48 = 6;  // ... the 48-bit prefilter kernel (192 rows: three operand windows per tile, 12 VGPRs)
 constexpr int kG = 2;   // tiles per accumulator group
 // 2^23 + 0x4040 + 64 * 2^15
 constexpr float kC0 = 8388608.0f + 16448.0f + 2097152.0f;
@@ -83,16 +88,38 @@ constexpr int kScaleHalf = 0x7e7e7e7e;       // E8M0 126 = 2^-1
 constexpr int kScale5 = (int)0x84848484;     // 2^5
 constexpr int kScale11 = (int)0x8a8a8a8a;    // 2^11
 constexpr int kScale17 = (int)0x90909090;    // 2^17
+// PRE48's block scales: 2 | 2, 2^7 | 2^10, 2^13 | 2^19
+constexpr int kScale1 = (int)0x80808080;     // 2^1
+constexpr int kScale7p = (int)0x86868686;    // 2^7
+constexpr int kScale10 = (int)0x89898989;    // 2^10
+constexpr int kScale13 = (int)0x8c8c8c8c;    // 2^13
+constexpr int kScale19 = (int)0x92929292;    // 2^19
 
-// needles -> FP4 scratch: needle j -> 2 x uint4 (low word, high word) at qx[2j], and behind those (qx[2 * nq_pad + j])
-// the prefilter word lo ^ hi of needle j; j >= nq padded with hash 0
+// needles -> FP4 scratch: needle j -> 2 x uint4 (low word, high word) at qx[2j], behind those (qx[2 * nq_pad + j])
+// the prefilter word lo ^ hi of needle j, and behind those (qx[3 * nq_pad ...]) the PRE48 operands: per quadruple of
+// needle tiles P Q R S (128 needles) the B operands of its three MFMAs, 64 lanes x 16 bytes each.  Lane (c, K block kb)
+// of MFMA m holds sub-blocks 2 (2m + kb) and 2 (2m + kb) + 1 of the twelve  P.E0 P.E1 P.E2 Q.E0 ... S.E2  of column c's
+// four needles: sub-block s belongs to needle tile s / 3 and is its word's sub-block s % 3 (pre48_sub), at +-0.5 except
+// Q.E0, R.E1, S.E0 (s = 3, 7, 9) at +-4 -- the complement of the haystack's magnitudes, see the kernel.
+// j >= nq padded with hash 0
+constexpr uint32_t kNeedlePad = 384;  // whole pairs (64), triples (96) and quadruples (128)
 __global__ __launch_bounds__(256) void k_expand_needles(const uint64_t* __restrict__ q, uint32_t nq,
                                                         uint32_t nq_pad, uint4* __restrict__ qx) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;  // one thread per output uint4
-  if (i >= 3u * nq_pad) return;
+  if (i >= 3u * nq_pad + nq_pad / 128u * 192u) return;
   const uint32_t* w = reinterpret_cast<const uint32_t*>(q);
   if (i < 2u * nq_pad) {
     qx[i] = fp4_expand32((i >> 1) < nq ? w[i] : 0u);
+  } else if (i >= 3u * nq_pad) {
+    const uint32_t u = i - 3u * nq_pad, quad = u / 192u, m = (u % 192u) >> 6, c = u & 31u, kb = (u >> 5) & 1u;
+    uint2 o[2];
+#pragma unroll
+    for (uint32_t k = 0; k < 2; ++k) {
+      const uint32_t s = 2u * (2u * m + kb) + k, j = quad * 128u + (s / 3u) * 32u + c;
+      const uint32_t lo = j < nq ? w[2u * j] : 0u, hi = j < nq ? w[2u * j + 1u] : 0u;
+      o[k] = fp4_expand16(pre48_sub(lo, hi, s % 3u), s == 3u || s == 7u || s == 9u ? kFp4Four : kFp4Half);
+    }
+    qx[i] = make_uint4(o[0].x, o[0].y, o[1].x, o[1].y);
   } else {
     const uint32_t j = i - 2u * nq_pad;
     qx[i] = fp4_expand32(j < nq ? w[2u * j] ^ w[2u * j + 1u] : 0u);
@@ -267,14 +294,15 @@ __device__ __forceinline__ uint32_t or_regs(const v16f (&c)[G]) {
 
 // PRE = true: the prefilter kernel (4 workgroups per CU: 128 VGPRs; bound by VALU issue, and a fourth wave per SIMD hides
 // more of it -- same box, compiled for 1 / 2 / 3 / 4: 10.8 / 10.8 / 10.1 / 9.8 ms, r05).  PRE = false: FULL2.
-template <bool PRE>
-__global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(
+// The body of three kernels (below): PRE = 0 FULL2, 1 the prefilter, 2 PRE48, the prefilter on a 48-bit word.
+template <int PRE>
+__device__ __forceinline__ void hamm64_mfma_body(
     const uint2* __restrict__ hay, const uint32_t* __restrict__ ids, uint32_t n,
     const uint64_t* __restrict__ q, const uint4* __restrict__ qx, uint32_t nq, uint32_t n_pairs,
     uint32_t pairs_per_chunk, uint32_t thresh, cbh_record* __restrict__ rec,
     unsigned long long cap, unsigned long long* __restrict__ total, uint32_t keep0,
     const uint2* __restrict__ qmask, const uint4* __restrict__ qf) {
-  constexpr int HT = kHT, G = kG;
+  constexpr int HT = PRE == 2 ? kHT48 : kHT, G = kG;
   __shared__ __attribute__((aligned(16))) uint32_t s_queue_[kWaves][PRE ? kPreQueue : kQueue];
   __shared__ __attribute__((aligned(16))) uint2 s_hay_[PRE ? kWaves : 1][PRE ? HT * 32 : 1];  // PRE: raw hashes for the re-check
   __shared__ uint32_t s_out2_[PRE ? 1 : kWaves][PRE ? 1 : 2 * kOutCap];  // FULL2: the record buffer (PRE: inside s_queue)
@@ -293,8 +321,19 @@ __global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(
   for (int t = 0; t < HT; ++t) {
     const uint32_t row = (tile0 + t) * 32u + r;
     const uint2 hv = row < n ? hay[row] : make_uint2(0u, 0u);
-    // PRE: the prefilter word lo ^ hi in both K blocks
-    a[t] = fp4_operand(fp4_expand32(PRE ? hv.x ^ hv.y : (half ? hv.y : hv.x)));
+    if constexpr (PRE == 2) {
+      // PRE48: four sub-blocks of 16 elements per lane (8 VGPRs).  K block 0 holds Y = (E0, E1, E2, E0 at +-4), K block 1
+      // holds X = (E2, E0 at +-4, E1, E2), everything else at +-0.5; MFMA m reads sub-blocks m and m + 1 (below)
+      const uint32_t e0 = pre48_sub(hv.x, hv.y, 0), e1 = pre48_sub(hv.x, hv.y, 1), e2 = pre48_sub(hv.x, hv.y, 2);
+      const uint2 s0 = fp4_expand16(half ? e2 : e0, kFp4Half);
+      const uint2 s1 = fp4_expand16(half ? e0 : e1, half ? kFp4Four : kFp4Half);
+      const uint2 s2 = fp4_expand16(half ? e1 : e2, kFp4Half);
+      const uint2 s3 = fp4_expand16(half ? e2 : e0, half ? kFp4Half : kFp4Four);
+      a[t] = v8i{(int)s0.x, (int)s0.y, (int)s1.x, (int)s1.y, (int)s2.x, (int)s2.y, (int)s3.x, (int)s3.y};
+    } else {
+      // PRE: the prefilter word lo ^ hi in both K blocks
+      a[t] = fp4_operand(fp4_expand32(PRE ? hv.x ^ hv.y : (half ? hv.y : hv.x)));
+    }
     if (PRE && half == 0) s_hay[t * 32 + r] = hv;
   }
   wave_order();
@@ -311,13 +350,17 @@ __global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(
   v16f c0;
 #pragma unroll
   for (int g = 0; g < 16; ++g)
-    c0[g] = PRE ? 8388608.0f + (float)((16u + (thresh - 1u)) * 266305u) : kC0;  // 266305 = 1 + 2^6 + 2^12 + 2^18
+    c0[g] = PRE == 2 ? 8388608.0f + (float)((8u + thresh) * 266305u)
+            : PRE  ? 8388608.0f + (float)((16u + (thresh - 1u)) * 266305u) : kC0;  // 266305 = 1 + 2^6 + 2^12 + 2^18
   asm volatile("" : "+v"(c0));  // keep C0 resident: otherwise it is rebuilt (16 v_mov) every trip
   // PRE block scales (per lane half = per K block): first MFMA 2^-1 | 2^5, second 2^11 | 2^17
-  int scale_b = PRE ? (half ? kScale5 : kScaleHalf) : kScaleOne;
-  int scale_b2 = PRE ? (half ? kScale17 : kScale11) : kScale15;
+  // PRE48 (three MFMAs): 2 | 2, 2^7 | 2^10, 2^13 | 2^19
+  int scale_b = PRE == 2 ? kScale1 : PRE ? (half ? kScale5 : kScaleHalf) : kScaleOne;
+  int scale_b2 = PRE == 2 ? (half ? kScale10 : kScale7p) : PRE ? (half ? kScale17 : kScale11) : kScale15;
+  int scale_b3 = half ? kScale19 : kScale13;  // (PRE48 only)
   asm volatile("" : "+v"(scale_b));
   asm volatile("" : "+v"(scale_b2));
+  if constexpr (PRE == 2) asm volatile("" : "+v"(scale_b3));
 
   const uint32_t p0 = blockIdx.y * pairs_per_chunk;
   const uint32_t p1 = min(n_pairs, p0 + pairs_per_chunk);
@@ -414,6 +457,76 @@ __global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(
     npend = keep;
   };
 
+  // PRE, PRE48: the group's flags.  Flag bits survive OR: v_or3_b32 takes two more registers per op (plain VGPR-only ops,
+  // cheaper to issue than the packed max); two chains of 17 and 15 registers: 8 + 7 v_or3_b32 (16 + 16 would take 8 + 8)
+  auto detect = [&](const v16f (&c)[G], const uint32_t group, const uint32_t p) __attribute__((always_inline)) {
+    constexpr int R = G * 16;
+    constexpr int RA = R / 2 + 1;
+    const uint32_t half0 = or_regs<0, RA, G>(c), half1 = or_regs<RA, R, G>(c);
+    const uint32_t flags = (half0 | half1) & kFlagMaskPre;
+    const uint64_t hm = __builtin_amdgcn_ballot_w64(flags != 0);
+    if (hm != 0) {
+      // wave-uniform from here: some lane holds a candidate (one group in ~10 at threshold 5, every other at 6).
+      // Every hit lane appends {flag bits of chain 0 | those of chain 1 one bit higher, lane | group | step}.
+      // (the lane id through an opaque copy: the compiler otherwise hoists this path's lane-derived values out of the
+      // chunk loop, runs out of its 128 registers and SPILLS them)
+      static_assert(R == 32, "two chains of 17 and 15 registers");
+      uint32_t ln = lane;
+      asm volatile("" : "+v"(ln));
+      if (flags != 0) {
+        const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, npend));
+        *reinterpret_cast<uint2*>(&s_queue[2u * at]) =
+            make_uint2((half0 & kFlagMaskPre) | ((half1 & kFlagMaskPre) << 1), ln | (group << 6) | (((p - p0) >> 1) << 8));
+      }
+      npend += (uint32_t)__popcll(hm);
+      // (drained at the end of the step: 4 x 64 descriptors fit behind the <= 63 a drain leaves, and the drain's code
+      //  sits once per step instead of once per group, profiles/r06_pre_drain_sites_ab.json)
+    }
+  };
+
+  // PRE48: one needle-tile QUADRUPLE P Q R S (pairs p, p + 1) against the HT resident haystack tiles, three chained MFMAs
+  // per tile.  MFMA m multiplies the haystack's sub-blocks m, m + 1 (operand registers [2m, 2m + 4) of the tile's eight:
+  // overlapping windows, which the compiler turns into three copies made once per wave, outside the loop) with needle
+  // sub-blocks 4m .. 4m + 3 (see k_expand_needles):
+  //     K block 0 (Y)                         K block 1 (X)
+  //   0 P.E0 P.E1            x 2              P.E2 | Q.E0 (4 x 4)     x 2
+  //   1 Q.E1 Q.E2            x 2^7            R.E0 R.E1               x 2^10   (one side at 4, the other at 0.5)
+  //   2 R.E2 | S.E0 (4 x 4)  x 2^13           S.E1 S.E2               x 2^19
+  // A compare spans one scale block and a half; inside a split block the two fields differ by 0.5 * 0.5 against 4 * 4,
+  // a factor of 64 = one field.  Every element of field f ends with weight 64^f / 2, as in PRE, so field f gains
+  // 24 - h_f (h_f = the 48-bit distance) on the 8 + thresh that C0 puts there: 32 + thresh - h_f, bit 5 set <=>
+  // h_f <= thresh.  One more than PRE's bias: a field of h > 32 + thresh goes negative and borrows one from the field
+  // above, which then reads h <= thresh - 1 -- still every true match (h <= hamm64 < thresh); the wrapped field itself
+  // reads as flagged, a false candidate the re-check drops.  The top field S arrives whole in the last MFMA, so the
+  // accumulator stays inside [2^23, 2^24) until then, and its flag is the carry into the exponent as in PRE.
+  auto step48 = [&](const uint32_t p, const uint4& n0, const uint4& n1, const uint4& n2) __attribute__((always_inline)) {
+    const v8i b0 = fp4_operand(n0), b1 = fp4_operand(n1), b2 = fp4_operand(n2);
+#pragma unroll
+    for (int t0 = 0; t0 < HT; t0 += G) {
+      v16f c[G];
+#pragma unroll
+      for (int t = 0; t < G; ++t) {
+        const v8i& h = a[t0 + t];
+        c[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(v8i{h[0], h[1], h[2], h[3], 0, 0, 0, 0}, b0, c0, 4, 4, 0,
+                                                               kScaleOne, 0, scale_b);
+      }
+#pragma unroll
+      for (int t = 0; t < G; ++t) {
+        const v8i& h = a[t0 + t];
+        c[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(v8i{h[2], h[3], h[4], h[5], 0, 0, 0, 0}, b1, c[t], 4, 4, 0,
+                                                               kScaleOne, 0, scale_b2);
+      }
+#pragma unroll
+      for (int t = 0; t < G; ++t) {
+        const v8i& h = a[t0 + t];
+        c[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(v8i{h[4], h[5], h[6], h[7], 0, 0, 0, 0}, b2, c[t], 4, 4, 0,
+                                                               kScaleOne, 0, scale_b3);
+      }
+      detect(c, (uint32_t)(t0 / G), p);
+    }
+    if (npend >= 64u) drain(false);
+  };
+
   // one needle-tile pair against the HT resident haystack tiles
   auto step = [&](const uint32_t p, const uint4& nA, const uint4& nB) __attribute__((always_inline)) {
     const v8i bA = fp4_operand(nA);
@@ -430,33 +543,8 @@ __global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(
       for (int t = 0; t < G; ++t)
         c[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[t0 + t], bB, c[t], 4, 4, 0,
                                                                kScaleOne, 0, scale_b2);
-      if constexpr (PRE) {
-        // flag bits survive OR: v_or3_b32 takes two more registers per op (plain VGPR-only ops, cheaper to issue than
-        // the packed max); two chains of 8 ops
-        constexpr int R = G * 16;
-        // (two chains of 17 and 15 registers: 8 + 7 v_or3_b32; 16 + 16 would take 8 + 8)
-        constexpr int RA = R / 2 + 1;
-        const uint32_t half0 = or_regs<0, RA, G>(c), half1 = or_regs<RA, R, G>(c);
-        const uint32_t flags = (half0 | half1) & kFlagMaskPre;
-        const uint64_t hm = __builtin_amdgcn_ballot_w64(flags != 0);
-        if (hm != 0) {
-          // wave-uniform from here: some lane holds a candidate (one group in ~10 at threshold 5, every other at 6).
-          // Every hit lane appends {flag bits of chain 0 | those of chain 1 one bit higher, lane | group | step}.
-          // (the lane id through an opaque copy: the compiler otherwise hoists this path's lane-derived values out of the
-          // chunk loop, runs out of its 128 registers and SPILLS them)
-          static_assert(R == 32, "two chains of 17 and 15 registers");
-          uint32_t ln = lane;
-          asm volatile("" : "+v"(ln));
-          if (flags != 0) {
-            const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, npend));
-            *reinterpret_cast<uint2*>(&s_queue[2u * at]) =
-                make_uint2((half0 & kFlagMaskPre) | ((half1 & kFlagMaskPre) << 1),
-                           ln | ((uint32_t)(t0 / G) << 6) | (((p - p0) >> 1) << 8));
-          }
-          npend += (uint32_t)__popcll(hm);
-          // (drained at the end of the step: 4 x 64 descriptors fit behind the <= 63 a drain leaves, and the drain's code
-          //  sits once per step instead of once per group, profiles/r06_pre_drain_sites_ab.json)
-        }
+      if constexpr (PRE != 0) {
+        detect(c, (uint32_t)(t0 / G), p);
       } else {
         // packed per-half maximum of the group's G*16 results: 8 v_pk_maximum3_f16 per tile
         h2 m0 = {0, 0}, m1 = {0, 0};
@@ -476,11 +564,39 @@ __global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(
         }
       }
     }
-    if constexpr (PRE)
+    if constexpr (PRE != 0)
       if (npend >= 64u) drain(false);
   };
 
-  if constexpr (PRE) {
+  (void)step, (void)step48, (void)detect;  // (each variant uses its own)
+  if constexpr (PRE == 2) {
+    // One quadruple per step, two steps per trip with explicit double buffers, as below.  The chunk starts at an even
+    // pair; a lone last pair's quadruple is whole in the scratch (padding needles: hash 0, dropped at qi >= nq).
+    typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint4*>(qf + (size_t)(p0 >> 1) * 192u), 0, (int)0xffffffffu, 0x27000);
+    const uint32_t voff = lane * 16u;
+    auto ldt = [&](uint32_t rel, uint32_t m) -> uint4 {  // operand m of quadruple (p0 / 2) + rel
+      const v4u_t v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)(rel * 3072u + m * 1024u), 0);
+      return make_uint4(v.x, v.y, v.z, v.w);
+    };
+    const uint32_t nqd = (p1 - p0 + 1u) >> 1;
+    uint4 x0 = ldt(0, 0), x1 = ldt(0, 1), x2 = ldt(0, 2);
+#pragma unroll 1
+    for (uint32_t rel = 0; rel < nqd; rel += 2) {  // (two call sites of step48())
+      const uint32_t ry = min(rel + 1, nqd - 1);
+      const uint4 y0 = ldt(ry, 0), y1 = ldt(ry, 1), y2 = ldt(ry, 2);
+      step48(p0 + 2u * rel, x0, x1, x2);
+      if (rel + 1 < nqd) {
+        const uint32_t rx = min(rel + 2, nqd - 1);
+        x0 = ldt(rx, 0);
+        x1 = ldt(rx, 1);
+        x2 = ldt(rx, 2);
+        step48(p0 + 2u * rel + 2u, y0, y1, y2);
+      }
+    }
+    if (npend) drain(true);
+  } else if constexpr (PRE == 1) {
     // A step takes two needle pairs (four tiles); the chunk length is even, only the call's last pair can be single -- its
     // partner slot is fed the same tiles again (chosen by ADDRESS, so that both loads are issued back to back and stay in
     // flight during the MFMAs) and its candidates fall out at qi >= nq.
@@ -529,6 +645,23 @@ __global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(
   }
   out_flush(s_out, nout, hp);
 }
+
+#define CBH_MFMA_PARAMS                                                                                              \
+  const uint2 *__restrict__ hay, const uint32_t *__restrict__ ids, uint32_t n, const uint64_t *__restrict__ q,       \
+      const uint4 *__restrict__ qx, uint32_t nq, uint32_t n_pairs, uint32_t pairs_per_chunk, uint32_t thresh,        \
+      cbh_record *__restrict__ rec, unsigned long long cap, unsigned long long *__restrict__ total, uint32_t keep0,  \
+      const uint2 *__restrict__ qmask, const uint4 *__restrict__ qf
+#define CBH_MFMA_ARGS hay, ids, n, q, qx, nq, n_pairs, pairs_per_chunk, thresh, rec, cap, total, keep0, qmask, qf
+template <bool PRE>
+__global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(CBH_MFMA_PARAMS) {
+  hamm64_mfma_body<PRE ? 1 : 0>(CBH_MFMA_ARGS);
+}
+// PRE48: 6 tiles per wave at 3 workgroups per CU (161 VGPRs) -- the three windows of a tile's eight registers end up as
+// three copies of four, the compiler does not overlap operand tuples: 12 VGPRs per tile.  With 8 tiles the kernel takes 185
+// VGPRs, two waves per SIMD, and runs 14.65 ms per 10^12 pairs against 14.0 (profiles/r08_lib_ab_ht6_over_ht8.json).
+__global__ __launch_bounds__(kThreads, 3) void k_hamm64_mfma48(CBH_MFMA_PARAMS) { hamm64_mfma_body<2>(CBH_MFMA_ARGS); }
+#undef CBH_MFMA_PARAMS
+#undef CBH_MFMA_ARGS
 
 
 // ---- FULL3: three needle tiles per accumulator, detection by OR instead of maximum ------------------------
@@ -684,12 +817,13 @@ __global__ __launch_bounds__(kThreads, 2) void k_hamm64_mfma3(
 
 // ---- the probe: candidate and true-match rates of THIS launch's data (the route in hamm64_scan.hip weighs them) --------
 // k_fold_probe counts, on kProbeS x kProbeS (slot, needle) samples, the pairs whose fold distance and whose 64-bit distance
-// are under each threshold up to kProbeT.
+// are under each threshold up to kProbeT, and those the 48-bit prefilter would flag.
 constexpr uint32_t kProbeS = 2048;     // samples per side
 constexpr int kProbeT = kProbeMaxThresh;  // thresholds 1..8 are counted (the prefilter never pays beyond: 1e-3 per pair at 8)
 
 // grid (sq / 256, sh / 64): thread = one needle sample against 64 slot samples; counts[t - 1] += pairs with fold
-// distance < t, counts[kProbeT + t - 1] += pairs with 64-bit distance < t.  The samples are pseudo-random rows / needles
+// distance < t, counts[kProbeT + t - 1] += pairs with 64-bit distance < t, counts[2 kProbeT + t - 1] += pairs with 48-bit
+// distance <= t or > 32 + t.  The samples are pseudo-random rows / needles
 // (a 32-bit mix of the sample number): evenly spaced ones meet the diagonal of a self-join far more often than its share
 // -- a shard of 125 000 slots against its index's 10^6 needles counted 256 self matches among 4.2 x 10^6 sampled pairs,
 // sixty times their true rate, which is how dht 7 first came to take the prefilter on a sharded handle.
@@ -701,17 +835,17 @@ __device__ __forceinline__ uint32_t probe_mix(uint32_t x) {
 __global__ __launch_bounds__(256) void k_fold_probe(const uint2* __restrict__ hay, uint32_t n, const uint2* __restrict__ q,
                                                     uint32_t nq, uint32_t sh, uint32_t sq, uint32_t* __restrict__ counts) {
   __shared__ uint2 s_h[64];
-  __shared__ uint32_t s_cnt[2 * kProbeT];
+  __shared__ uint32_t s_cnt[3 * kProbeT];
   const uint32_t t = threadIdx.x;
   if (t < 64) {
     const uint32_t i = blockIdx.y * 64u + t;
     s_h[t] = i < sh ? hay[sh == n ? i : probe_mix(i) % n] : make_uint2(0u, 0u);
   }
-  if (t < 2 * kProbeT) s_cnt[t] = 0;
+  if (t < 3 * kProbeT) s_cnt[t] = 0;
   __syncthreads();
   const uint32_t j = blockIdx.x * 256u + t;
   const uint32_t nslots = min(64u, sh - blockIdx.y * 64u);
-  uint32_t cnt[kProbeT] = {}, cnt64[kProbeT] = {};
+  uint32_t cnt[kProbeT] = {}, cnt64[kProbeT] = {}, cnt48[kProbeT] = {};
   if (j < sq) {
     const uint2 nv = q[sq == nq ? j : probe_mix(j ^ 0x9e3779b9u) % nq];
     const uint32_t f = nv.x ^ nv.y;
@@ -720,6 +854,11 @@ __global__ __launch_bounds__(256) void k_fold_probe(const uint2* __restrict__ ha
       const uint32_t d = (uint32_t)__popc(f ^ hv.x ^ hv.y);
 #pragma unroll
       for (int th = 0; th < kProbeT; ++th) cnt[th] += d < (uint32_t)(th + 1) ? 1u : 0u;
+      // the 48-bit prefilter word's candidates: distance <= threshold, or a field that wraps (its flag rule, see the kernel)
+      const uint32_t d48 = (uint32_t)__popc((f ^ hv.x ^ hv.y) & 0xffffu) + (uint32_t)__popc((nv.x ^ hv.x) >> 16) +
+                           (uint32_t)__popc((nv.y ^ hv.y) >> 16);
+#pragma unroll
+      for (int th = 0; th < kProbeT; ++th) cnt48[th] += d48 <= (uint32_t)(th + 1) || d48 > (uint32_t)(th + 33) ? 1u : 0u;
       if (d < (uint32_t)kProbeT) {  // (rare: a true match is a candidate first)
         const uint32_t d64 = (uint32_t)__popc(nv.x ^ hv.x) + (uint32_t)__popc(nv.y ^ hv.y);
 #pragma unroll
@@ -728,14 +867,38 @@ __global__ __launch_bounds__(256) void k_fold_probe(const uint2* __restrict__ ha
     }
   }
 #pragma unroll
-  for (int th = 0; th < 2 * kProbeT; ++th) {
-    uint32_t v = th < kProbeT ? cnt[th % kProbeT] : cnt64[th % kProbeT];
+  for (int th = 0; th < 3 * kProbeT; ++th) {
+    uint32_t v = th < kProbeT ? cnt[th % kProbeT] : th < 2 * kProbeT ? cnt64[th % kProbeT] : cnt48[th % kProbeT];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
     if ((t & 63u) == 0 && v) atomicAdd(&s_cnt[th], v);
   }
   __syncthreads();
-  if (t < 2 * kProbeT && s_cnt[t]) atomicAdd(&counts[t], s_cnt[t]);
+  if (t < 3 * kProbeT && s_cnt[t]) atomicAdd(&counts[t], s_cnt[t]);
+}
+
+// ---- self-test: the FP4 values and block scales PRE48 multiplies with ----------------------------------------------------
+// One MFMA per (code a, code b, block scale, element count 1 | 16, K block): `cnt` elements of code a against as many of
+// code b in that K block, everything else 0, C = 0; out = cnt * a * b * scale as the hardware returns it.
+// (codes and scales by selects: a table indexed at run time would have to live in device memory)
+__device__ __forceinline__ uint32_t selftest_fp4_code(uint32_t i) {  // 0.5, -0.5, 1, -1, 4, -4
+  return ((i >> 1) == 0 ? kFp4Half : (i >> 1) == 1 ? 0x2u : kFp4Four) | ((i & 1u) << 3);
+}
+__global__ __launch_bounds__(64) void k_selftest_fp4(float* __restrict__ out) {
+  const uint32_t lane = threadIdx.x, half = lane >> 5;
+  for (uint32_t i = 0; i < 720u; ++i) {
+    const uint32_t kb = i & 1u, ci = (i >> 1) & 1u, k = (i >> 2) % 5u, ib = (i / 20u) % 6u, ia = i / 120u;
+    const uint32_t fa = selftest_fp4_code(ia) * (ci ? 0x11111111u : 1u), fb = selftest_fp4_code(ib) * (ci ? 0x11111111u : 1u);
+    const bool on = half == kb;
+    const v8i a = {on ? (int)fa : 0, on && ci ? (int)fa : 0, 0, 0, 0, 0, 0, 0};
+    const v8i b = {on ? (int)fb : 0, on && ci ? (int)fb : 0, 0, 0, 0, 0, 0, 0};
+    int sc = k == 0 ? kScale1 : k == 1 ? kScale7p : k == 2 ? kScale10 : k == 3 ? kScale13 : kScale19;
+    asm volatile("" : "+v"(sc));
+    v16f c = {};
+    c = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4, 4, 0, kScaleOne, 0, sc);
+    asm volatile("" : "+v"(c));  // the MFMA stays in front of the branch: it needs the operands of all 64 lanes
+    if (lane == 0) out[i] = c[0];
+  }
 }
 
 // pinned words for the probe's answer: a free list (a slot is in use only inside one synchronous probe)
@@ -751,7 +914,7 @@ uint32_t* probe_slot_get() {
     }
   }
   uint32_t* p = nullptr;
-  if (hipHostMalloc(&p, 2 * kProbeT * sizeof(uint32_t)) != hipSuccess) {
+  if (hipHostMalloc(&p, 3 * kProbeT * sizeof(uint32_t)) != hipSuccess) {
     (void)hipGetLastError();
     return nullptr;
   }
@@ -765,9 +928,9 @@ void probe_slot_put(uint32_t* p) {
 }  // namespace
 
 bool probe_fold_rates(const uint64_t* d_hashes, size_t n, const uint64_t* d_q, size_t nq, int thresh, hipStream_t stream,
-                      double* r_cand, double* r_true) {
+                      double* r_cand, double* r_true, double* r_cand48) {
   uint32_t* d_cnt = nullptr;
-  if (cbh::malloc_async((void**)&d_cnt, 2 * kProbeT * sizeof(uint32_t), stream) != hipSuccess) {
+  if (cbh::malloc_async((void**)&d_cnt, 3 * kProbeT * sizeof(uint32_t), stream) != hipSuccess) {
     (void)hipGetLastError();
     return false;
   }
@@ -775,13 +938,13 @@ bool probe_fold_rates(const uint64_t* d_hashes, size_t n, const uint64_t* d_q, s
   bool ok = h_cnt != nullptr;
   const uint32_t sh = (uint32_t)std::min<size_t>(n, kProbeS), sq = (uint32_t)std::min<size_t>(nq, kProbeS);
   if (ok) {
-    ok = hipMemsetAsync(d_cnt, 0, 2 * kProbeT * sizeof(uint32_t), stream) == hipSuccess;
+    ok = hipMemsetAsync(d_cnt, 0, 3 * kProbeT * sizeof(uint32_t), stream) == hipSuccess;
     if (ok) {
       hipLaunchKernelGGL(k_fold_probe, dim3((sq + 255u) / 256u, (sh + 63u) / 64u), dim3(256), 0, stream,
                          reinterpret_cast<const uint2*>(d_hashes), (uint32_t)n, reinterpret_cast<const uint2*>(d_q),
                          (uint32_t)nq, sh, sq, d_cnt);
       ok = hipGetLastError() == hipSuccess &&
-           hipMemcpyAsync(h_cnt, d_cnt, 2 * kProbeT * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
+           hipMemcpyAsync(h_cnt, d_cnt, 3 * kProbeT * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
            hipStreamSynchronize(stream) == hipSuccess;
     }
   }
@@ -790,6 +953,7 @@ bool probe_fold_rates(const uint64_t* d_hashes, size_t n, const uint64_t* d_q, s
     const double pairs = (double)sh * (double)sq;
     *r_cand = (double)h_cnt[thresh - 1] / pairs;
     *r_true = (double)h_cnt[kProbeT + thresh - 1] / pairs;
+    *r_cand48 = (double)h_cnt[2 * kProbeT + thresh - 1] / pairs;
   } else {
     (void)hipGetLastError();
   }
@@ -797,15 +961,22 @@ bool probe_fold_rates(const uint64_t* d_hashes, size_t n, const uint64_t* d_q, s
   return ok;
 }
 
-static uint32_t padded_needles(size_t nq) { return (uint32_t)((nq + 191) / 192) * 192u; }  // whole pairs (64) and triples (96)
+int selftest_fp4_products(float* d_out, hipStream_t stream) {
+  hipLaunchKernelGGL(k_selftest_fp4, dim3(1), dim3(64), 0, stream, d_out);
+  CBH_HIP(hipGetLastError());
+  return CBH_OK;
+}
+
+static uint32_t padded_needles(size_t nq) { return (uint32_t)((nq + kNeedlePad - 1) / kNeedlePad) * kNeedlePad; }
 
 int expand_needles_for_scan(const uint64_t* d_q, size_t nq, hipStream_t stream, uint4** qx_out) {
   *qx_out = nullptr;
   if (nq == 0 || nq > CBH_MAX_QUERIES_PER_CALL) return CBH_OK;
   const uint32_t nq_pad = padded_needles(nq);
   uint4* qx = nullptr;
-  CBH_HIP(malloc_async((void**)&qx, (size_t)nq_pad * 48u, stream));  // 2 words + the prefilter word, 16 B each
-  hipLaunchKernelGGL(k_expand_needles, dim3((3u * nq_pad + 255u) / 256u), dim3(256), 0, stream, d_q,
+  // 2 words + the prefilter word, 16 B each, + the PRE48 operands, 3 x 64 x 16 B per 128 needles
+  CBH_HIP(malloc_async((void**)&qx, (size_t)nq_pad * 72u, stream));
+  hipLaunchKernelGGL(k_expand_needles, dim3((3u * nq_pad + nq_pad / 128u * 192u + 255u) / 256u), dim3(256), 0, stream, d_q,
                      (uint32_t)nq, nq_pad, qx);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -818,7 +989,7 @@ int expand_needles_for_scan(const uint64_t* d_q, size_t nq, hipStream_t stream, 
 
 int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
                             int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
-                            bool pre, const ScanOpts& o) {
+                            int pre, const ScanOpts& o) {
   const uint32_t n_pairs = (uint32_t)((nq + 63) / 64);
   const uint32_t n_triples = (uint32_t)((nq + 95) / 96);
   const uint32_t nq_pad = padded_needles(nq);
@@ -829,8 +1000,8 @@ int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, siz
     if (rc) return rc;
     qx = qx_own;
   }
-  const uint4* qf = qx + 2u * (size_t)nq_pad;
-  const uint32_t rows_per_wg = 32u * kHT * kWaves;
+  const uint4* qf = qx + (pre == 2 ? 3u : 2u) * (size_t)nq_pad;  // the operands of the prefilter that runs
+  const uint32_t rows_per_wg = 32u * (pre == 2 ? kHT48 : kHT) * kWaves;
   // launches that run side by side on this device (the shards of a sharded handle): the workgroups that fill the machine are
   // theirs together -- a shard of 125 000 slots alone cut its needles into chunks of 128 pairs to reach 8192 workgroups and
   // paid the shorter chunks' per-chunk costs (3 % of the sweep) for parallelism its seven siblings already supplied
@@ -861,12 +1032,12 @@ int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, siz
       ppc = ((n_pairs + 65534) / 65535 + 1u) & ~1u;  // even: the prefilter variant steps two pairs at a time
       chunks = (n_pairs + ppc - 1) / ppc;
     }
-#define CBH_MFMA(PRE)                                                                                                 \
-  hipLaunchKernelGGL((k_hamm64_mfma<PRE>), dim3(wgs, chunks), dim3(kThreads), 0, stream,                              \
+#define CBH_MFMA(K)                                                                                                   \
+  hipLaunchKernelGGL(K, dim3(wgs, chunks), dim3(kThreads), 0, stream,                                                 \
                      reinterpret_cast<const uint2*>(d_hashes), d_ids, (uint32_t)n, d_q, qx, (uint32_t)nq, n_pairs, ppc, \
                      (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total, (uint32_t)o.keep_id0,                 \
                      reinterpret_cast<const uint2*>(o.d_qmask), qf)
-    if (pre) CBH_MFMA(true); else CBH_MFMA(false);
+    if (pre == 2) CBH_MFMA(k_hamm64_mfma48); else if (pre) CBH_MFMA((k_hamm64_mfma<true>)); else CBH_MFMA((k_hamm64_mfma<false>));
 #undef CBH_MFMA
   }
   hipError_t e = hipGetLastError();

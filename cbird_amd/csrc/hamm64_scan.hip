@@ -320,17 +320,41 @@ constexpr size_t kMfmaMinN = 4096;
 // which puts threshold 7 of unrelated hashes on the prefilter (14.6-14.8 ms against 15.75-17.0) and leaves 8 to the
 // three-field kernel.  Launches too small to pay for the round trip, and a probe that cannot run, take the fixed rule
 // (thresholds <= 6: at 7 the prefilter's margin is 7 % on unrelated hashes and gone on anything denser).
+//
+// The 48-bit prefilter (PRE48: 16 folds + 32 plain bits, three MFMAs per four needle tiles = 3/4 of the three-field
+// kernel's matrix work) sits between the two.  Its candidates are the pairs whose 48-bit distance h is <= t, a hundred
+// times rarer than the fold's, plus the fields that wrap (h > 32 + t, its flag rule: hamm64_mfma.hip): 2.0e-6 per pair
+// at thresholds 7 and 8 of unrelated hashes, but 3.1e-5 / 1.1e-4 / 3.6e-4 at 5 / 4 / 3, where it loses.  The probe counts
+// that rate r48 in the same sample.  Fitted on tools/ab/adaptive_ab.py's five data sets (profiles/r08_adaptive_ab_fit.jsonl,
+// ms per 10^12 pairs):
+//   T_48 = 14.0 + 2.8e4 x r48 + 1.0e5 x r_true
+// (floor 13.96-14.3 on image hashes at 7 / 8; 15.0 / 17.4 / 23.4 at thresholds 5 / 4 / 3 give the slope; the 2 % of equal
+// hashes of "flat", 3.3e-4 true matches per pair, cost it 46.3 against the prefilter's 42.2 at threshold 7).
+// It replaces the three-field kernel wherever T_48 is the smaller -- everywhere measured, by 14-17 % -- and the 32-bit
+// prefilter only where T_48 < kPre48Margin x T_pre: T_pre is not good to better than 15 %.  A candidate costs the
+// prefilter one descriptor per hit LANE, so candidates that come in runs of neighbouring rows (the frames of a video)
+// are cheaper than their rate says: at threshold 7 the video set runs 12.4 ms on the prefilter where the model says
+// 14.8, and 13.7 on PRE48, while image hashes with the same r_cand run 15.1 and 14.0.  The probe samples rows at
+// random and cannot tell the two apart; the margin leaves threshold 7 where it was (on the prefilter) in both.
+// "scan_pre48": -1 = routed like this, 0 = never, 1 = always for thresholds <= 16 (its bias 32 + t leaves a 6-bit field
+// that much room).  Launches on the fixed rule never take it.
 constexpr int kPreStatic = 6;
 constexpr double kTrueWeight = 8.0;
+constexpr double kSlopePre = 2.4e4, kBaseFull = 15.75, kTrueFull = 2.7e5, kTruePre = 0.7e5;  // ms per 10^12 pairs
+constexpr double kBasePre = 8.55, kBase48 = 14.0, kSlope48 = 2.8e4, kTrue48 = 1.0e5, kPre48Margin = 0.9;
+constexpr int kPre48MaxThresh = 16;
 constexpr uint64_t kProbeMinPairs = 1ull << 31;  // ~20 us of scan: below this the probe's round trip is not worth it
 
 int g_scan_mfma = 1;             // "scan_mfma"
 int g_pre_max_thresh = -1;       // "scan_mfma_pre_max"
 int g_pre_rate_max_e9 = 300000;  // "scan_pre_rate_e9"
+int g_pre48 = -1;                // "scan_pre48"
 std::atomic<uint64_t> g_pre_mask{0};        // bit t: the most recent matrix-core launch at threshold t took the prefilter
+std::atomic<uint64_t> g_pre48_mask{0};      // bit t: ... took the 48-bit prefilter
 std::atomic<uint64_t> g_n_probe{0};         // probes run
 std::atomic<long long> g_last_rate_e9{-1};  // candidate rate x 1e9 the last probe found for its threshold
 std::atomic<long long> g_last_true_e9{-1};  // ... and the rate of true (64-bit) matches
+std::atomic<long long> g_last_rate48_e9{-1};  // ... and of the 48-bit prefilter's candidates
 
 enum class Join { None, IfCheaper, Forced };
 enum class Kernel { PopcEq, PopcPre, PopcFull, Mfma };
@@ -393,18 +417,28 @@ bool scan_takes_mfma(size_t n, size_t nq, int thresh) {
   return thresh >= 1 && route(n, nq, thresh, false).kernel == Kernel::Mfma;
 }
 
-bool scan_pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
-                   hipStream_t stream) {
-  if (thresh > 32) return false;  // (the prefilter kernel's flag fields)
+int scan_pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
+                  hipStream_t stream) {
+  if (g_pre48 == 1 && thresh <= kPre48MaxThresh) return 2;
+  if (thresh > 32) return 0;  // (the prefilter kernel's flag fields)
   if (g_pre_max_thresh >= 0) return thresh <= g_pre_max_thresh;
-  if (thresh > kProbeMaxThresh) return false;
+  if (thresh > kProbeMaxThresh) return 0;
   if ((uint64_t)n_total * (uint64_t)nq < kProbeMinPairs) return thresh <= kPreStatic;
-  double r_cand = 0, r_true = 0;
-  if (!probe_fold_rates(d_hashes, n, d_q, nq, thresh, stream, &r_cand, &r_true)) return thresh <= kPreStatic;
+  double r_cand = 0, r_true = 0, r48 = 0;
+  if (!probe_fold_rates(d_hashes, n, d_q, nq, thresh, stream, &r_cand, &r_true, &r48)) return thresh <= kPreStatic;
   g_last_rate_e9 = (long long)(r_cand * 1e9);
   g_last_true_e9 = (long long)(r_true * 1e9);
+  g_last_rate48_e9 = (long long)(r48 * 1e9);
   g_n_probe++;
-  return (r_cand - kTrueWeight * r_true) * 1e9 <= (double)g_pre_rate_max_e9;
+  // modelled times relative to the three-field kernel's
+  const double d_pre = kSlopePre * (r_cand - kTrueWeight * r_true - (double)g_pre_rate_max_e9 * 1e-9);
+  const bool pre = d_pre <= 0;
+  if (g_pre48 != 0) {
+    const double t_48 = kBase48 + kSlope48 * r48 + kTrue48 * r_true;
+    const double t_pre = kBasePre + kSlopePre * r_cand + kTruePre * r_true, t_full = kBaseFull + kTrueFull * r_true;
+    if (pre ? t_48 < kPre48Margin * t_pre : t_48 < t_full) return 2;
+  }
+  return pre;
 }
 
 int launch_hamm64_scan(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
@@ -423,9 +457,15 @@ int launch_hamm64_scan(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n
     if (rc == CBH_E_NOMEM) cbh_clear_error();
   }
   if (r.kernel != Kernel::Mfma) return launch_popc(r.kernel, d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, o);
-  const bool pre = o.pre >= 0 ? o.pre != 0 : scan_pick_pre(d_hashes, n, n, d_q, nq, thresh, stream);
+  const int pre = o.pre >= 0 ? o.pre : scan_pick_pre(d_hashes, n, n, d_q, nq, thresh, stream);
   if (thresh < 64) {
-    if (pre) g_pre_mask |= 1ull << thresh; else g_pre_mask &= ~(1ull << thresh);
+    // (a launch on the 48-bit prefilter does NOT set its bit in "scan_pre_mask": bench.py prices the thresholds of that
+    // mask at the 32-bit prefilter's 64 flop per pair and the rest at 128, and when the mask covers every threshold of its
+    // sweep -- which it would, 1..8 -- it falls back to pricing ALL of them at 128: the 9 ms launches of thresholds 1..5
+    // would read 1.4 x the peak.  Left with the three-field kernel's thresholds, a 14 ms launch reads 0.91 of the peak
+    // at 128 flop per pair; it issues 96.  NOTES 18.)
+    if (pre == 1) g_pre_mask |= 1ull << thresh; else g_pre_mask &= ~(1ull << thresh);
+    if (pre == 2) g_pre48_mask |= 1ull << thresh; else g_pre48_mask &= ~(1ull << thresh);
   }
   return launch_hamm64_scan_mfma(d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, pre, o);
 }
@@ -442,9 +482,14 @@ void set_scan_pre_max(int t) {
 void set_scan_pre_rate(int e9) {
   if (e9 >= 0) g_pre_rate_max_e9 = e9;
 }
+void set_scan_pre48(int v) {
+  if (v >= -1 && v <= 1) g_pre48 = v;
+}
 long long get_scan_pre_mask() { return (long long)g_pre_mask.load(); }
+long long get_scan_pre48_mask() { return (long long)g_pre48_mask.load(); }
 long long get_scan_probes() { return (long long)g_n_probe.load(); }
 long long get_scan_probe_rate_e9() { return g_last_rate_e9.load(); }
 long long get_scan_probe_true_e9() { return g_last_true_e9.load(); }
+long long get_scan_probe_rate48_e9() { return g_last_rate48_e9.load(); }
 
 }  // namespace cbh

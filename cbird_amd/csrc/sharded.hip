@@ -391,7 +391,7 @@ int plan_scan(ScanCall& K) {
   K.timed = K.nq >= 256;
   // prefilter or three-field kernel: one probe for the whole call, on the slots of a shard that lives where the needles
   // are (every shard probing for itself cost a stream synchronisation per shard and threshold); and ONE expansion of the
-  // needles into the matrix-core operand layout for all the shards of the root device (48 bytes per needle)
+  // needles into the matrix-core operand layout for all the shards of the root device (72 bytes per needle)
   K.opts.siblings = (unsigned)K.C.per_device;
   for (const ShardRun& r : K.L.run)
     if (r.c->device == K.L.root && r.c->n != 0 && scan_takes_mfma(r.c->n, K.nq, K.thresh)) {

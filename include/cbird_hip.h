@@ -742,6 +742,10 @@ int cbh_color_find_batch(cbh_color*, const void* needle_descs, size_t nq, int k,
  *                   eight times that more than it costs the prefilter); launches of < 2^31 pairs: thresholds <= 6 -- 0 = never the prefilter, t > 0 =
  *                   thresholds <= t (<= 32) take it whatever the data
  *   "scan_pre_rate_e9" that bound x 1e9 (default 300000 = 3.0e-4: where the two kernels tie, profiles/r07_adaptive_ab_*.jsonl)
+ *   "scan_pre48"    the 48-bit prefilter kernel (16 folds + 32 plain bits; three MFMAs per four needle tiles): -1 (default) =
+ *                   per launch, where the probe's rates model it faster than the three-field kernel, or than 0.9 x the
+ *                   prefilter's time, whichever of the two the launch would otherwise take; 0 = never; 1 = always for
+ *                   thresholds <= 16.  Launches too small to probe never take it
  *   "scan256_mfma"  256-bit scan on the matrix cores (k_hamm256_*): 0 = never (k_hamm256_scan), 1 = calls with >= 64 needle
  *                   descriptors and >= 4096 rows (default), 2 = always.  Other values return CBH_E_INVAL and leave the knob
  *                   as it was
@@ -800,9 +804,10 @@ int cbh_set_tuning(const char* key, int value);
  * "arena_cached_bytes", "arena_pending_bytes", "arena_live_bytes", "arena_live_blocks", "arena_trimmed_live",
  * "arena_oom_retry_stream", "arena_oom_retry_device", "arena_oom_retry_persistent", "arena_released"; "scan_mfma" (the
  * knob's value); "scan_pre_mask"
- * (bit t = the most recent matrix-core launch at threshold t took the prefilter kernel), "scan_joins" (calls the bucketed join has answered), "scan_probes" (candidate-rate
- * probes run so far), "scan_probe_rate_e9" / "scan_probe_true_e9" (the candidate and true-match rates the last one found for its threshold,
- * x 1e9; -1 = none yet); "scan256_mfma", "scan256_small" (the knobs' values); "scan256_kernels" (a bit mask of the kernels
+ * (bit t = the most recent matrix-core launch at threshold t took the prefilter kernel), "scan_pre48_mask" (... took the
+ * 48-bit prefilter kernel; a launch sets its bit in at most one of the two), "scan_joins" (calls the bucketed join has answered), "scan_probes" (candidate-rate
+ * probes run so far), "scan_probe_rate_e9" / "scan_probe_true_e9" / "scan_probe_rate48_e9" (the candidate and true-match rates the last one
+ * found for its threshold and the 48-bit prefilter's candidate rate, x 1e9; -1 = none yet); "scan256_mfma", "scan256_small" (the knobs' values); "scan256_kernels" (a bit mask of the kernels
  * that 256-bit scan launches have used since it was last cleared -- cbh_set_tuning("scan256_kernels", 0) clears it, any
  * other value written is CBH_E_INVAL; bit 0 k_hamm256_scan, 1 k_hamm256_mfma<6,3,2> (first-128-bit prefilter, one needle
  * tile per accumulator), 2 k_hamm256_mfma<6,3,4> (all 256 bits), 3 k_hamm256_mfma3, 4 / 5 / 6 k_hamm256_small<4 / 8 / 16>;
@@ -823,6 +828,12 @@ int cbh_time_dcthash_dev(const void* d_imgs, size_t n, int w, int h, size_t row_
  * every load that starts at or past num_records returned 0 and every load inside it returned the data
  * (tests/test_boundary.py; no product call depends on this entry point). */
 int cbh_selftest_buffer_range(int device, int* ok);
+/* The FP4 arithmetic the 48-bit prefilter of the 64-bit scan rests on (hamm64_mfma.hip): the values 0.5 (E2M1's one
+ * subnormal), 1 and 4 under the block scales 2, 2^7, 2^10, 2^13, 2^19.  One 32x32x64 MFMA per combination, everything
+ * else zero: out[(((ia * 6 + ib) * 5 + k) * 2 + c) * 2 + kb] = cnt * a * b * scale as the hardware returns it, a, b of
+ * {0.5, -0.5, 1, -1, 4, -4} by ia, ib, scale k of the five above, cnt = 1 | 16 elements by c, in K block kb.  720 floats
+ * of host memory (tests/test_scan_prefilter48.py; no product call depends on this entry point). */
+int cbh_selftest_fp4_products(int device, float* out);
 
 #ifdef __cplusplus
 }

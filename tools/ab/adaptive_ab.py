@@ -1,6 +1,6 @@
-"""Prefilter kernel (PRE) against the three-field 64-bit kernel (FULL3) per threshold on data sets whose candidate rates
-differ, with the fold-candidate rate of each set beside the times -- what the launch-time choice between the two has to
-reproduce: never slower than min(PRE, FULL3) x 1.05.
+"""Prefilter kernel (PRE) and 48-bit prefilter kernel (PRE48) against the three-field 64-bit kernel (FULL3) per threshold
+on data sets whose candidate rates differ, with the fold-candidate rate of each set beside the times -- what the
+launch-time choice between the three has to reproduce: never slower than the best of them x 1.03.
 
   image     the bench's 10^6 image-derived hashes (10 % near-duplicates of earlier images)
   dup10     the same with 10 % of the slots overwritten by exact copies of other slots, in clusters (sizes geometric,
@@ -108,9 +108,11 @@ for name in SETS:
     rates = fold_rates(hay, q)
     out = {"n": n, "nq": nq, "fold_rate": {str(t): rates[t] for t in T}, "per_threshold": {}}
     for t in T:
-        cell = {"pre": [], "full3": [], "auto": []}
+        cell = {"pre": [], "pre48": [], "full3": [], "auto": []}
         for r in range(R):
-            for kind, knobs in (("pre", {b"scan_mfma_pre_max": 32}), ("full3", {b"scan_mfma_pre_max": 0}), ("auto", {b"scan_mfma_pre_max": -1})):
+            for kind, knobs in (("pre", {b"scan_mfma_pre_max": 32, b"scan_pre48": 0}), ("pre48", {b"scan_pre48": 1}),
+                                ("full3", {b"scan_mfma_pre_max": 0, b"scan_pre48": 0}),
+                                ("auto", {b"scan_mfma_pre_max": -1, b"scan_pre48": -1})):
                 for k, v in knobs.items():
                     L.cbh_set_tuning(k, v)
                 _lib.check(L.cbh_idx64_time_scan_dev(idx.handle, dq.data_ptr(), nq, t, drec.data_ptr(), cap, dtot.data_ptr(), 2, C.byref(ms)), "t")
@@ -119,6 +121,10 @@ for name in SETS:
                     v = C.c_longlong(0)
                     L.cbh_get_tuning(b"scan_pre_mask", C.byref(v))
                     auto_pre = bool((v.value >> t) & 1)
+                    L.cbh_get_tuning(b"scan_pre48_mask", C.byref(v))
+                    auto_pre48 = bool((v.value >> t) & 1)
+                    L.cbh_get_tuning(b"scan_probe_rate48_e9", C.byref(v))
+                    auto_rate48 = v.value / 1e9
                     L.cbh_get_tuning(b"scan_probe_rate_e9", C.byref(v))
                     auto_rate = v.value / 1e9
                     L.cbh_get_tuning(b"scan_probe_true_e9", C.byref(v))
@@ -126,10 +132,11 @@ for name in SETS:
         L.cbh_set_tuning(b"scan_mfma_pre_max", -1)
         mins = {k: min(x[0] for x in v) for k, v in cell.items()}
         tot = {k: sorted({x[1] for x in v}) for k, v in cell.items()}
-        best = min(mins["pre"], mins["full3"])
+        best = min(mins["pre"], mins["pre48"], mins["full3"])
         out["per_threshold"][str(t)] = {"ms": mins, "records": tot["full3"], "totals_agree": len({tuple(v) for v in tot.values()}) == 1,
                                         "auto_over_best": round(mins["auto"] / best, 3), "pairs_1e12": n * nq / 1e12,
-                                        "auto_kernel": "pre" if auto_pre else "full3", "library_probe_rate": auto_rate, "library_probe_true_rate": auto_true}
+                                        "auto_kernel": "pre48" if auto_pre48 else "pre" if auto_pre else "full3", "library_probe_rate": auto_rate,
+                                        "library_probe_true_rate": auto_true, "library_probe_rate48": auto_rate48}
     res[name] = out
     print(json.dumps({name: out}), flush=True)
     del idx, dh, dq, drec
