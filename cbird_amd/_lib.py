@@ -118,6 +118,9 @@ _SIGS = {
     "cbh_idx64_memory_usage": (_sz, [_vp]),
     "cbh_idx64_media_ids": (C.c_int, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "cbh_idx64_slice": (_vp, [_vp, _vp, _sz]),
+    "cbh_idx256_slice": (_vp, [_vp, _vp, _sz]),
+    "cbh_color_slice": (_vp, [_vp, _vp, _sz]),
+    "cbh_vidx_slice": (_vp, [_vp, _vp, _sz]),
     "cbh_idx64_download": (C.c_int, [_vp, _vp, _vp, _sz]),
     "cbh_idx64_find": (C.c_int, [_vp, C.c_uint64, C.c_int, _vp, _sz, C.POINTER(_sz)]),
     "cbh_idx64_find_batch": (C.c_int, [_vp, _vp, _sz, C.c_int, C.c_int, _vp, _vp]),

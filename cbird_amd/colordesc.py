@@ -57,11 +57,11 @@ def create_descriptors(images, device: int = 0):
 
 
 class ColorDescIndex:
-    def __init__(self, device: int = 0) -> None:
+    def __init__(self, device: int = 0, _handle=None) -> None:
         self._L = _lib.lib()
         self._device = device
         self._id = SearchParams.AlgoColor
-        self._h = self._L.cbh_color_create(device)
+        self._h = _handle if _handle is not None else self._L.cbh_color_create(device)  # (slice(): cbh_color_slice's)
         if not self._h:
             raise CbhError(_lib.CBH_E_NODEVICE, "cbh_color_create")
 
@@ -97,18 +97,13 @@ class ColorDescIndex:
         check(self._L.cbh_color_remove(self._h, i.ctypes.data, len(i)), "remove")
 
     def slice(self, mediaIds) -> "ColorDescIndex":
-        """ColorDescIndex::slice (colordescindex.cpp:231-248): entries whose mediaId is in the set, index order"""
-        n = self.count()
-        ids = np.zeros(max(n, 1), np.uint32)
-        descs = np.zeros(max(n, 1), COLOR_DTYPE)
-        if n:
-            check(self._L.cbh_color_download(self._h, ids.ctypes.data, descs.ctypes.data, n), "download")
-        keep = np.isin(ids[:n], np.array(sorted(set(int(x) for x in mediaIds)), np.uint32))
-        chunk = ColorDescIndex(self._device)
-        if keep.any():
-            ki, kd = np.ascontiguousarray(ids[:n][keep]), np.ascontiguousarray(descs[:n][keep])
-            check(self._L.cbh_color_add(chunk._h, ki.ctypes.data, kd.ctypes.data, len(ki)), "add")
-        return chunk
+        """ColorDescIndex::slice (colordescindex.cpp:231-248): entries whose mediaId is in the set, index order; the
+        device planes are gathered from this index's on the device (cbh_color_slice)"""
+        i = np.ascontiguousarray(sorted(set(int(x) for x in mediaIds)), np.uint32)
+        h = self._L.cbh_color_slice(self._h, i.ctypes.data, len(i))
+        if not h:
+            raise CbhError(self._L.cbh_last_error_code() or _lib.CBH_E_HIP, "slice")
+        return ColorDescIndex(self._device, _handle=h)
 
     def findIndexData(self, m) -> bool:
         d = np.zeros((), COLOR_DTYPE)
@@ -117,6 +112,10 @@ class ColorDescIndex:
             m.colorDescriptor = buf.view(COLOR_DTYPE)[0]
             return True
         return False
+
+    @property
+    def handle(self):
+        return self._h
 
     def find(self, m, p: SearchParams | None = None):
         target = getattr(m, "colorDescriptor", None)

@@ -218,26 +218,27 @@ class GpuCvFeaturesIndex : public CvFeaturesIndex {
   }
 
   // slice(): the descriptors of the given media in ascending id order, like load() builds them
-  // (cvfeaturesindex.cpp:285-312)
+  // (cvfeaturesindex.cpp:285-312) -- the rows move inside the device(s), cbh_idx256_slice
   Index* slice(const QSet<uint32_t>& mediaIds) const override {
-    GpuCvFeaturesIndex* chunk = _devs.single() ? new GpuCvFeaturesIndex(_device) : new GpuCvFeaturesIndex(_devs);
     std::vector<uint32_t> ids(mediaIds.begin(), mediaIds.end());
     std::sort(ids.begin(), ids.end());
-    std::vector<uint8_t> rows;
-    for (uint32_t id : ids) {
-      size_t first = 0, cnt = 0;
-      if (!CBH_QUERY(cbh_idx256_rows_of(_idx, id, &first, &cnt)) || !cnt) continue;
-      rows.resize(cnt * 32);
-      if (!CBH_QUERY(cbh_idx256_download_rows(_idx, first, cnt, rows.data()))) continue;
-      (void)CBH_QUERY(cbh_idx256_add(chunk->_idx, id, rows.data(), cnt));  // (a slice that lacks a media finds less)
+    cbh_idx256* sub = cbh_idx256_slice(_idx, ids.data(), ids.size());
+    if (!sub && cbh_last_error_code() == CBH_E_NOMEM) {  // transient: give cached scratch back, once more
+      gpuidx::releaseScratch(scratchMask());
+      sub = cbh_idx256_slice(_idx, ids.data(), ids.size());
     }
-    return chunk;
+    if (!sub) {  // a slice that cannot be made is an empty one (its searches find nothing), not the end of the process
+      qCritical("GpuCvFeaturesIndex::slice: %s", cbh_last_error());
+      return _devs.single() ? new GpuCvFeaturesIndex(_device) : new GpuCvFeaturesIndex(_devs);
+    }
+    return new GpuCvFeaturesIndex(sub, _device, _devs);
   }
 
   cbh_idx256* handle() const { return _idx; }  // for statistics (cbh_combine_stats)
   uint32_t scratchMask() const { return _devs.single() ? 1u << _device : _devs.mask; }  // the devices this index lives on
 
  private:
+  GpuCvFeaturesIndex(cbh_idx256* adopted, int device, const GpuDeviceSet& devs) : _device(device), _devs(devs), _idx(adopted) {}
   int _device = 0;
   GpuDeviceSet _devs;  // (declared before _idx: the sharded constructor initialises it first)
   cbh_idx256* _idx;
@@ -329,26 +330,27 @@ class GpuColorDescIndex : public ColorDescIndex {
     return results;
   }
 
-  // slice(): the descriptors whose media id is in the set, in index order (colordescindex.cpp:231-248)
+  // slice(): the descriptors whose media id is in the set, in index order (colordescindex.cpp:231-248) -- the planes are
+  // gathered on the device, cbh_color_slice
   Index* slice(const QSet<uint32_t>& mediaIds) const override {
-    GpuColorDescIndex* chunk = new GpuColorDescIndex(_device);
-    const size_t n = size_t(count());
-    std::vector<uint32_t> ids(n), keepIds;
-    std::vector<ColorDescriptor> descs(n), keep;
-    if (n && !CBH_QUERY(cbh_color_download(_idx, ids.data(), descs.data(), n))) return chunk;
-    for (size_t i = 0; i < n; ++i)
-      if (mediaIds.contains(ids[i])) {
-        keepIds.push_back(ids[i]);
-        keep.push_back(descs[i]);
-      }
-    if (!keepIds.empty()) chunk->addRows(keepIds.data(), keep.data(), keepIds.size());
-    return chunk;
+    std::vector<uint32_t> ids(mediaIds.begin(), mediaIds.end());
+    cbh_color* sub = cbh_color_slice(_idx, ids.data(), ids.size());
+    if (!sub && cbh_last_error_code() == CBH_E_NOMEM) {  // transient: give cached scratch back, once more
+      gpuidx::releaseScratch(scratchMask());
+      sub = cbh_color_slice(_idx, ids.data(), ids.size());
+    }
+    if (!sub) {  // a slice that cannot be made is an empty one (its searches find nothing), not the end of the process
+      qCritical("GpuColorDescIndex::slice: %s", cbh_last_error());
+      return new GpuColorDescIndex(_device);
+    }
+    return new GpuColorDescIndex(sub, _device);
   }
 
   cbh_color* handle() const { return _idx; }  // for statistics (cbh_combine_stats)
   uint32_t scratchMask() const { return 1u << _device; }
 
  private:
+  GpuColorDescIndex(cbh_color* adopted, int device) : _device(device), _idx(adopted) {}
   int _device = 0;
   cbh_color* _idx;
 };
@@ -441,12 +443,29 @@ class GpuDctVideoIndex : public DctVideoIndex {
     return results;
   }
 
-  // slice(): "replicate what load() does, but use the subset" (dctvideoindex.cpp:389-397)
+  // slice(): "replicate what load() does, but use the subset" (dctvideoindex.cpp:389-397) -- from the frames the handle
+  // already holds (cbh_vidx_slice); only an id it does not hold is read from its .vdx file, as load() does.  The held
+  // videos come first, in the set's iteration order, the others after them: with every id held (load() adds an empty
+  // video even for a missing file) that is the one order the former loop gave; otherwise the video indexes of the slice,
+  // and so the order of equal-scored matches, can differ from it.
   Index* slice(const QSet<uint32_t>& mediaIds) const override {
-    GpuDctVideoIndex* copy = _devs.single() ? new GpuDctVideoIndex(_device, _radixCompat)
-                                            : new GpuDctVideoIndex(_devs, _radixCompat);
+    std::vector<uint32_t> held, missing;
+    for (uint32_t id : mediaIds) (_ids.count(id) ? held : missing).push_back(id);
+    cbh_vidx* sub = cbh_vidx_slice(_idx, held.data(), held.size());
+    if (!sub && cbh_last_error_code() == CBH_E_NOMEM) {  // transient: give cached scratch back, once more
+      gpuidx::releaseScratch(scratchMask());
+      sub = cbh_vidx_slice(_idx, held.data(), held.size());
+    }
+    GpuDctVideoIndex* copy;
+    if (sub) {
+      copy = new GpuDctVideoIndex(sub, _device, _devs, _radixCompat);
+      copy->_ids.insert(held.begin(), held.end());
+    } else {  // a slice that cannot be made is an empty one (its searches find nothing), not the end of the process
+      qCritical("GpuDctVideoIndex::slice: %s", cbh_last_error());
+      copy = _devs.single() ? new GpuDctVideoIndex(_device, _radixCompat) : new GpuDctVideoIndex(_devs, _radixCompat);
+    }
     copy->_dataPath = _dataPath;
-    for (uint32_t id : mediaIds) copy->addOne(id);
+    for (uint32_t id : missing) copy->addOne(id);
     copy->_loaded = true;
     return copy;
   }
@@ -454,6 +473,8 @@ class GpuDctVideoIndex : public DctVideoIndex {
   cbh_vidx* handle() const { return _idx; }  // for statistics (cbh_combine_stats)
 
  private:
+  GpuDctVideoIndex(cbh_vidx* adopted, int device, const GpuDeviceSet& devs, bool radixCompat)
+      : _device(device), _devs(devs), _idx(adopted), _radixCompat(radixCompat) {}
   void addOne(uint32_t id) {
     VideoIndex vi;
     const QString path = QString("%1/%2.vdx").arg(_dataPath).arg(id);

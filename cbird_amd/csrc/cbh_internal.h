@@ -268,6 +268,19 @@ int launch_records_topk(const unsigned long long* d_blocks, unsigned nb, size_t 
                         cbh_match* d_out, uint32_t* d_counts, unsigned* d_status, void* d_scratch,
                         hipStream_t stream);
 
+// ---- slice.hip: Index::slice() on the device (row-range copy, planar gather) -------------------------------------
+// 32-byte rows by ranges: d_table = 3 x (n_ranges + 1) words: packed firsts (from 0; the last = total_rows), dst firsts,
+// src firsts
+int launch_slice_rows256(const uint8_t* d_src, uint8_t* d_dst, const uint32_t* d_table, size_t n_ranges,
+                         size_t total_rows, hipStream_t stream);
+// entries d_pos[0..m) of the colour planes [32][src_cap] into entries 0..m of planes [32][dst_cap]; dst_cap is a
+// multiple of 4 and entries m..dst_cap are written as padding (1e18 in L, no colours, id 0)
+int launch_slice_color(const float* sL, const float* sU, const float* sV, const unsigned char* s_num,
+                       const uint32_t* s_ids, size_t src_cap, const uint32_t* d_pos, size_t m, float* dL, float* dU,
+                       float* dV, unsigned char* d_num, uint32_t* d_ids, size_t dst_cap, hipStream_t stream);
+void note_slice_on_device();         // one more slice call succeeded on this route (with or without a launch) ...
+long long get_slices_on_device();    // ... cbh_get_tuning "slices_on_device"
+
 // ---- reduce.hip: K5 (fdct votes) and K8 (video closest-frame + adjacency) on the device ---------
 struct cbh_nmatch {   // one DctFeaturesIndex result of needle image `needle`
   uint32_t needle, id;

@@ -1365,6 +1365,7 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strcmp(key, "scan256_kernels")) return *value = get_scan256_kernels(), CBH_OK;
   if (!strcmp(key, "scan_probes")) return *value = get_scan_probes(), CBH_OK;
   if (!strcmp(key, "scan_joins")) return *value = get_scan_joins(), CBH_OK;
+  if (!strcmp(key, "slices_on_device")) return *value = get_slices_on_device(), CBH_OK;
   if (!strcmp(key, "scan_probe_rate_e9")) return *value = get_scan_probe_rate_e9(), CBH_OK;
   if (!strcmp(key, "scan_probe_true_e9")) return *value = get_scan_probe_true_e9(), CBH_OK;
   if (!strcmp(key, "scan_probe_rate48_e9")) return *value = get_scan_probe_rate48_e9(), CBH_OK;

@@ -559,6 +559,66 @@ int cbh_color_remove(cbh_color* c, const uint32_t* ids, size_t n) {
   return CBH_OK;
 }
 
+/* slice() (colordescindex.cpp:231-248): the entries whose id is listed, in index order.  The host copies are filtered on
+ * the host; the device planes are gathered from the parent's by position (slice.hip: k_slice_color) -- no descriptor is
+ * decompressed or uploaded again. */
+static int color_slice(cbh_color* c, const std::vector<uint32_t>& want, cbh_color* out) {
+  cbh::DeviceGuard g(c->device);
+  if (!g.ok) return CBH_E_NODEVICE;
+  std::lock_guard<std::mutex> lk(c->mu);
+  std::vector<uint32_t> pos;
+  for (size_t i = 0; i < c->n; ++i)
+    if (std::binary_search(want.begin(), want.end(), c->host_ids[i])) pos.push_back((uint32_t)i);
+  const size_t m = pos.size();
+  if (m) {
+    out->host_ids.resize(m);
+    out->host_desc.resize(m * kDescBytes);
+    for (size_t j = 0; j < m; ++j) {
+      out->host_ids[j] = c->host_ids[pos[j]];
+      memcpy(out->host_desc.data() + j * kDescBytes, c->host_desc.data() + (size_t)pos[j] * kDescBytes, kDescBytes);
+    }
+    // a multiple of 4: even, as the pair loads need it, and every plane 16-byte aligned for the gather's stores.  The
+    // planes fit exactly; a later add() lands in the slack or grows them (grow_index copies by the old pitch)
+    const size_t cap = (m + 3) & ~(size_t)3;
+    CBH_HIP(hipMalloc(&out->dL, cap * kNC * 4));
+    CBH_HIP(hipMalloc(&out->dU, cap * kNC * 4));
+    CBH_HIP(hipMalloc(&out->dV, cap * kNC * 4));
+    CBH_HIP(hipMalloc(&out->d_num, cap));
+    CBH_HIP(hipMalloc(&out->d_ids, cap * 4));
+    out->cap = cap;
+    if (!c->stream) CBH_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    cbh::Scratch scratch(c->stream);
+    uint32_t* d_pos = nullptr;
+    int rc = CBH_OK;
+    hipError_t e = scratch.get(&d_pos, m * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_pos, pos.data(), m * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+      rc = cbh::launch_slice_color(c->dL, c->dU, c->dV, c->d_num, c->d_ids, c->cap, d_pos, m, out->dL, out->dU, out->dV,
+                                   out->d_num, out->d_ids, cap, c->stream);
+    const hipError_t drained = hipStreamSynchronize(c->stream);  // on every path: pos is read by the copy
+    if (rc) return rc;
+    CBH_HIP(e);
+    CBH_HIP(drained);
+    out->n = m;
+  }
+  cbh::note_slice_on_device();
+  return CBH_OK;
+}
+
+cbh_color* cbh_color_slice(const cbh_color* c, const uint32_t* ids, size_t n) {
+  cbh::clear_last_error();
+  if (!c || (n && !ids)) return (cbh_color*)cbh::fail_handle(CBH_E_INVAL, "cbh_color_slice: no index, or a count without ids");
+  std::vector<uint32_t> want(ids, ids + (ids ? n : 0));
+  std::sort(want.begin(), want.end());
+  cbh_color* out = cbh_color_create(c->device);
+  if (!out) return nullptr;  // (the create call has set the code)
+  if (const int rc = color_slice(const_cast<cbh_color*>(c), want, out)) {
+    cbh_color_destroy(out);
+    return (cbh_color*)cbh::fail_handle(rc, nullptr);
+  }
+  return out;
+}
+
 size_t cbh_color_count(const cbh_color* c) { return c ? c->n : 0; }
 int cbh_color_is_loaded(const cbh_color* c) { return c && c->n > 0; }  // `_count > 0` (:114)
 size_t cbh_color_memory_usage(const cbh_color* c) { return c ? (kDescBytes + 4) * c->n : 0; }  // (:118-121)

@@ -731,6 +731,180 @@ int cbh_idx256_download_rows(const cbh_idx256* ix, size_t first, size_t count, u
   return CBH_OK;
 }
 
+/* slice() (cvfeaturesindex.cpp:285-309): the rows of the listed media in ascending id order, as add() media by media
+ * would build them -- the same maps, the same rows in the same global order and, on a sharded parent, the same shards.
+ * A media takes the rows cbh_idx256_rows_of reports (a removed media too: _idMap keeps it); ids without rows are skipped.
+ * The host plans one row range per kept media from the maps; the rows move on the device (slice.hip: k_slice_rows),
+ * and rows that change ordinal travel as one staged contiguous block per (source shard, destination shard). */
+extern "C++" {
+namespace {
+
+struct Move256 {  // the kept media that go from one source Rows256 to one destination Rows256, in id order
+  const Rows256* src = nullptr;
+  Rows256 *dst = nullptr, *via = nullptr;  // via: the new handle's Rows256 on the source's device (its stream does the source side)
+  std::vector<uint32_t> dstf, srcf, len;
+  std::vector<uint32_t> table, table2;  // as launch_slice_rows256 takes them (kept until the copies have run)
+  size_t rows = 0;
+};
+
+// arena blocks and the streams they were used on: the blocks go back, then the streams are drained -- on every return
+struct Held256 {
+  std::vector<std::pair<void*, Rows256*>> blocks;
+  std::vector<Rows256*> used;
+  template <class T>
+  int take(T** p, size_t bytes, Rows256* on) {  // (on->device is current)
+    void* q = nullptr;
+    *p = nullptr;
+    CBH_HIP(cbh::malloc_async(&q, std::max<size_t>(bytes, 16), on->stream));
+    blocks.emplace_back(q, on);
+    *p = static_cast<T*>(q);
+    return CBH_OK;
+  }
+  int use(Rows256* r) {  // (r->device is current)
+    if (std::find(used.begin(), used.end(), r) != used.end()) return CBH_OK;
+    const int rc = r->ensure_scan(0, 0);
+    if (!rc) used.push_back(r);
+    return rc;
+  }
+  ~Held256() {
+    for (auto& b : blocks) {
+      cbh::DeviceGuard g(b.second->device);  // (a cache over its budget records an event on the block's stream)
+      (void)cbh::free_async(b.first, b.second->stream);
+    }
+    for (Rows256* r : used) {
+      cbh::DeviceGuard g(r->device);
+      (void)hipStreamSynchronize(r->stream);
+    }
+  }
+};
+
+// pk | dst firsts | src firsts, n + 1 words each (the last pk = the row count); `packed` replaces one side by pk
+void make_table(const Move256& m, int packed_side, std::vector<uint32_t>* t) {
+  const size_t k = m.len.size();
+  t->assign(3 * (k + 1), 0);
+  uint32_t at = 0;
+  for (size_t i = 0; i < k; ++i) {
+    (*t)[i] = at;
+    (*t)[(k + 1) + i] = packed_side == 1 ? at : m.dstf[i];
+    (*t)[2 * (k + 1) + i] = packed_side == 2 ? at : m.srcf[i];
+    at += m.len[i];
+  }
+  (*t)[k] = at;
+}
+
+int slice256(cbh_idx256* ix, const std::vector<uint32_t>& ids, cbh_idx256* out) {
+  std::lock_guard<std::mutex> lk(ix->mu);
+  Shards256 *S = ix->shards, *T = out->shards;
+  const size_t R = S ? S->shard.size() : 1;
+  std::vector<Move256> moves(R * R);  // [source shard * R + destination shard]
+  // plan: the maps of the new handle and where every kept media's rows come from and go to
+  for (uint32_t id : ids) {
+    size_t first = 0, cnt = 0;
+    cbh_idx256_rows_of(ix, id, &first, &cnt);
+    if (!cnt) continue;
+    size_t s = 0, src_local = first, d = 0;
+    if (S) {
+      auto g = std::upper_bound(S->segs.begin(), S->segs.end(), first,
+                                [](size_t row, const Shards256::Seg& sg) { return row < sg.global; });
+      --g;  // (the run that holds the media's first row holds all of them: a media is appended in one piece)
+      s = g->shard, src_local = g->local + (first - g->global);
+      d = T->next_shard();
+    }
+    Rows256& dst = T ? T->shard[d] : out->own;
+    Move256& m = moves[s * R + d];
+    m.src = S ? &S->shard[s] : &ix->own;
+    m.dst = &dst;
+    m.via = T ? &T->shard[s] : &out->own;
+    m.dstf.push_back((uint32_t)dst.n), m.srcf.push_back((uint32_t)src_local), m.len.push_back((uint32_t)cnt);
+    m.rows += cnt;
+    if (T) T->note_rows(dst.n, out->n, cnt);
+    dst.n += cnt;
+    out->first_row.back() = (uint32_t)out->n;
+    out->media_id.back() = id;
+    out->id_to_first[id] = (uint32_t)out->n;
+    out->n += cnt;
+    out->first_row.push_back((uint32_t)out->n);
+    out->media_id.push_back(0);
+    out->loaded = true;
+  }
+  // room for the rows, exactly
+  for (size_t d = 0; d < R; ++d) {
+    Rows256& dst = T ? T->shard[d] : out->own;
+    if (!dst.n) continue;
+    cbh::DeviceGuard g(dst.device);
+    if (!g.ok) return CBH_E_NODEVICE;
+    CBH_HIP(hipMalloc(&dst.d_rows, dst.n * 32));
+    dst.cap = dst.n;
+  }
+  Held256 H;
+  int rc;
+  for (Move256& m : moves) {
+    if (!m.rows) continue;
+    const size_t k = m.len.size();
+    uint32_t* d_table = nullptr;
+    cbh::DeviceGuard g(m.src->device);
+    if (!g.ok) return CBH_E_NODEVICE;
+    if ((rc = H.use(m.via))) return rc;
+    hipStream_t st = m.via->stream;
+    const bool across = m.dst->device != m.src->device;
+    make_table(m, across ? 1 : 0, &m.table);
+    if ((rc = H.take(&d_table, m.table.size() * 4, m.via))) return rc;
+    CBH_HIP(hipMemcpyAsync(d_table, m.table.data(), m.table.size() * 4, hipMemcpyHostToDevice, st));
+    if (!across) {  // (the moves of a call fill disjoint rows of a destination: no order between their streams)
+      if ((rc = cbh::launch_slice_rows256(m.src->d_rows, m.dst->d_rows, d_table, k, m.rows, st))) return rc;
+      continue;
+    }
+    // gather into a contiguous block here, carry it across, scatter it there
+    uint8_t *stage = nullptr, *landed = nullptr;
+    uint32_t* d_table2 = nullptr;
+    if ((rc = H.take(&stage, m.rows * 32, m.via))) return rc;
+    if ((rc = cbh::launch_slice_rows256(m.src->d_rows, stage, d_table, k, m.rows, st))) return rc;
+    {
+      cbh::DeviceGuard gd(m.dst->device);
+      if (!gd.ok) return CBH_E_NODEVICE;
+      if ((rc = H.use(m.dst))) return rc;
+      if ((rc = H.take(&landed, m.rows * 32, m.dst)) || (rc = H.take(&d_table2, m.table.size() * 4, m.dst))) return rc;
+      CBH_HIP(hipEventRecord(m.dst->ev0, m.dst->stream));  // (what the landing block was used for before has finished)
+    }
+    CBH_HIP(hipStreamWaitEvent(st, m.dst->ev0, 0));
+    CBH_HIP(hipMemcpyPeerAsync(landed, m.dst->device, stage, m.src->device, m.rows * 32, st));
+    CBH_HIP(hipEventRecord(m.via->ev1, st));
+    if (T) T->comm.n_peer_copies++;
+    cbh::DeviceGuard gd(m.dst->device);
+    if (!gd.ok) return CBH_E_NODEVICE;
+    make_table(m, 2, &m.table2);
+    CBH_HIP(hipMemcpyAsync(d_table2, m.table2.data(), m.table2.size() * 4, hipMemcpyHostToDevice, m.dst->stream));
+    CBH_HIP(hipStreamWaitEvent(m.dst->stream, m.via->ev1, 0));
+    if ((rc = cbh::launch_slice_rows256(landed, m.dst->d_rows, d_table2, k, m.rows, m.dst->stream))) return rc;
+  }
+  for (Rows256* r : H.used) {
+    cbh::DeviceGuard g(r->device);
+    if (!g.ok) return CBH_E_NODEVICE;
+    CBH_HIP(hipStreamSynchronize(r->stream));
+  }
+  cbh::note_slice_on_device();
+  return CBH_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+cbh_idx256* cbh_idx256_slice(const cbh_idx256* ix, const uint32_t* ids, size_t n) {
+  cbh::clear_last_error();
+  if (!ix || (n && !ids)) return (cbh_idx256*)cbh::fail_handle(CBH_E_INVAL, "cbh_idx256_slice: no index, or a count without ids");
+  std::vector<uint32_t> want(ids, ids + (ids ? n : 0));
+  std::sort(want.begin(), want.end());
+  want.erase(std::unique(want.begin(), want.end()), want.end());
+  cbh_idx256* out = ix->shards ? cbh_idx256_create_sharded(ix->shards->comm.mask, ix->shards->comm.per_device)
+                               : cbh_idx256_create(ix->own.device);
+  if (!out) return nullptr;  // (the create call has set the code)
+  if (const int rc = slice256(const_cast<cbh_idx256*>(ix), want, out)) {
+    cbh_idx256_destroy(out);
+    return (cbh_idx256*)cbh::fail_handle(rc, nullptr);
+  }
+  return out;
+}
+
 /* exact knnSearch(needles, k) restricted to distance < thresh: out_row/out_dist [nq*k] in (distance, row)
  * order, counts[nq] = number of rows under thresh (may exceed k) */
 int cbh_idx256_knn(cbh_idx256* ix, const uint8_t* needles, size_t nq, int k, int thresh, uint32_t* out_row,

@@ -348,6 +348,31 @@ int cbh_vidx_remove(cbh_vidx* v, const uint32_t* media_ids, size_t n) {
   return CBH_OK;
 }
 
+/* slice(): "replicate what load() does, but use the subset" (dctvideoindex.cpp:389-397) -- from the frames and hashes the
+ * handle already holds, not from the .vdx files again: the videos whose media id is listed, in the order of ids[] (an id
+ * listed twice is taken once, an id the handle lacks is skipped), in a handle of the same device or sharded shape and
+ * radix.  Host code; like the parent, the result builds its search structure on the first search. */
+cbh_vidx* cbh_vidx_slice(const cbh_vidx* v, const uint32_t* ids, size_t n) {
+  clear_last_error();
+  if (!v || (n && !ids)) return (cbh_vidx*)fail_handle(CBH_E_INVAL, "cbh_vidx_slice: no index, or a count without ids");
+  cbh_vidx* out = new (std::nothrow) cbh_vidx;
+  if (!out) return (cbh_vidx*)fail_handle(CBH_E_NOMEM, "cbh_vidx_slice: host allocation failed");
+  out->device = v->device;
+  out->device_mask = v->device_mask;
+  out->shards_per_device = v->shards_per_device;
+  out->radix = v->radix;
+  std::lock_guard<std::mutex> lk(const_cast<cbh_vidx*>(v)->build_mu);
+  std::unordered_map<uint32_t, size_t> at;  // media id -> its first video
+  for (size_t i = 0; i < v->videos.size(); ++i) at.emplace(v->videos[i].media_id, i);
+  for (size_t i = 0; i < n; ++i) {
+    auto it = at.find(ids[i]);
+    if (it == at.end()) continue;
+    out->videos.push_back(v->videos[it->second]);
+    at.erase(it);
+  }
+  return out;
+}
+
 size_t cbh_vidx_count(const cbh_vidx* v) { return v ? v->videos.size() : 0; }  // _mediaId.size() (:55-59)
 
 // memoryUsage() (:57-59): nothing before buildTree; then 8 + 6 bytes per entry (hash_t + packed VideoTreeIndex)

@@ -16,12 +16,15 @@ from .index import Match, SearchParams
 class CvFeaturesIndex:
     KNN = 10  # `_index->knnSearch(descriptors, ..., 10)` (cvfeaturesindex.cpp:497)
 
-    def __init__(self, device: int = 0, shards=None) -> None:
+    def __init__(self, device: int = 0, shards=None, _handle=None) -> None:
         """shards = (device_mask, shards_per_device): one index sharded by image over several GPUs / logical shards in
         this process (cbh_idx256_create_sharded); None = one device (or the process default, _lib.default_sharding)"""
         self._L = _lib.lib()
         self._device = device
         self._id = SearchParams.AlgoCVFeatures
+        if _handle is not None:  # (slice(): the handle comes from cbh_idx256_slice)
+            self._h = _handle
+            return
         shards = shards if shards is not None else _lib.default_sharding()
         self._h = self._L.cbh_idx256_create_sharded(shards[0], shards[1]) if shards else self._L.cbh_idx256_create(device)
         if not self._h:
@@ -79,13 +82,13 @@ class CvFeaturesIndex:
         return out
 
     def slice(self, mediaIds) -> "CvFeaturesIndex":
-        """CvFeaturesIndex::slice (cvfeaturesindex.cpp:285-312): the descriptors of the given media, ascending id"""
-        chunk = CvFeaturesIndex(self._device)
-        for mid in sorted(set(int(x) for x in mediaIds)):
-            d = self.descriptorsForMediaId(mid)
-            if len(d):
-                check(self._L.cbh_idx256_add(chunk._h, mid, np.ascontiguousarray(d).ctypes.data, len(d)), "add")
-        return chunk
+        """CvFeaturesIndex::slice (cvfeaturesindex.cpp:285-312): the descriptors of the given media, ascending id; the
+        rows move inside the device(s) (cbh_idx256_slice) and a sharded index gives a slice of the same shape"""
+        i = np.ascontiguousarray(sorted(set(int(x) for x in mediaIds)), np.uint32)
+        h = self._L.cbh_idx256_slice(self._h, i.ctypes.data, len(i))
+        if not h:
+            raise CbhError(self._L.cbh_last_error_code() or _lib.CBH_E_HIP, "slice")
+        return CvFeaturesIndex(self._device, _handle=h)
 
     def knn(self, needles, k: int, thresh: int):
         d = self._rows(needles)

@@ -172,7 +172,8 @@ class VideoSearchParams(SearchParams):
 class DctVideoIndex:
     """Detect similar videos with full-frame dct hashes (src/dctvideoindex.h:66-70)."""
 
-    def __init__(self, device: int = 0, data_path: str | None = None, radix_compat: bool = False, shards=None) -> None:
+    def __init__(self, device: int = 0, data_path: str | None = None, radix_compat: bool = False, shards=None,
+                 _handle=None) -> None:
         # False: exact search (the reference's vradix = 0).  True: a needle frame only sees the entries of its
         # RadixMap bucket, (hash >> 1) & (2^videoRadix - 1) (src/tree/radix.h:135-141): the reference's
         # approximate candidate sets for `-p.vradix N`.
@@ -181,11 +182,15 @@ class DctVideoIndex:
         self._L = _lib.lib()
         self._id = SearchParams.AlgoVideo
         self._data_path = data_path
+        self._ids: set = set()  # the media ids the handle holds (what DctVideoIndex::_mediaId holds in the reference)
+        self._loaded = False
+        if _handle is not None:  # (slice(): the handle comes from cbh_vidx_slice)
+            self._h = _handle
+            return
         shards = shards if shards is not None else _lib.default_sharding()  # (device_mask, shards_per_device)
         self._h = self._L.cbh_vidx_create_sharded(shards[0], shards[1]) if shards else self._L.cbh_vidx_create(device)
         if not self._h:
             raise CbhError(_lib.CBH_E_NODEVICE, "cbh_vidx_create")
-        self._loaded = False
 
     def __del__(self) -> None:
         h, self._h = getattr(self, "_h", None), None
@@ -209,10 +214,15 @@ class DctVideoIndex:
         then 8 + 6 bytes per entry"""
         return int(self._L.cbh_vidx_memory_usage(self._h))
 
+    @property
+    def handle(self):
+        return self._h
+
     def _add_one(self, media_id: int, vi: VideoIndex) -> None:
         f = np.ascontiguousarray(vi.frames, np.int32)
         h = np.ascontiguousarray(vi.hashes, np.uint64)
         check(self._L.cbh_vidx_add_video(self._h, media_id, f.ctypes.data, h.ctypes.data, len(f)), "add_video")
+        self._ids.add(int(media_id))
 
     def load(self, media_ids, data_path: str | None = None) -> None:
         """load(): `select id from media where type=video order by id` (:172-211); each id's frames come
@@ -237,14 +247,29 @@ class DctVideoIndex:
     def remove(self, ids) -> None:
         i = np.ascontiguousarray(list(ids), np.uint32)
         check(self._L.cbh_vidx_remove(self._h, i.ctypes.data, len(i)), "remove")
+        self._ids.difference_update(int(x) for x in i)
 
     def slice(self, mediaIds) -> "DctVideoIndex":
         """DctVideoIndex::slice (dctvideoindex.cpp:389-397): "replicate what load() does, but use the subset" -- the
-        frames come from <dataPath>/<id>.vdx again, so the index must have been loaded from a data path"""
+        videos the handle holds are copied from it (cbh_vidx_slice), only an id it does not hold is read from
+        <dataPath>/<id>.vdx as load() does.
+
+        Order: the videos the handle holds come first, in the order of mediaIds, and the ones it lacks follow, in the
+        order of mediaIds too.  When every id is held (the usual case: load() adds an empty video even for a missing
+        file) that is the order of mediaIds, as before; when some are not, the video indexes of the slice, and with
+        them the order of equal-scored matches, can differ from a slice that read every file in the order of mediaIds.
+
+        A data path is required even when every id is held, as it was when every id was read from its file."""
         if self._data_path is None:
-            raise ValueError("slice() re-reads the .vdx files: the index needs a data path")
-        copy = DctVideoIndex(self._device, self._data_path, self.radix_compat)
-        copy.load(list(mediaIds))
+            raise ValueError("slice() reads the .vdx files of media the index does not hold: the index needs a data path")
+        ids = [int(x) for x in mediaIds]
+        held = np.ascontiguousarray([i for i in ids if i in self._ids], np.uint32)
+        h = self._L.cbh_vidx_slice(self._h, held.ctypes.data, len(held))
+        if not h:
+            raise CbhError(self._L.cbh_last_error_code() or _lib.CBH_E_HIP, "slice")
+        copy = DctVideoIndex(self._device, self._data_path, self.radix_compat, _handle=h)
+        copy._ids = set(int(x) for x in held)
+        copy.load([i for i in ids if i not in self._ids])
         return copy
 
     @staticmethod

@@ -336,7 +336,9 @@ size_t cbh_idx64_memory_usage(const cbh_idx64*);                 /* memoryUsage(
  * *n_out = full number. */
 int cbh_idx64_media_ids(const cbh_idx64*, uint32_t* out, size_t cap, size_t* n_out);
 /* slice(): new index holding the slots whose id is in ids[], original order (:222-250);
- * caller destroys it (src/database.cpp:1435,1491). */
+ * caller destroys it (src/database.cpp:1435,1491).  A wanted 0 keeps removed slots; ids == NULL or n == 0 gives a
+ * loaded, empty index.  This one still goes through the host (download, filter, load); a slice of a sharded index is
+ * sharded the same way.  NULL + cbh_last_error_code() on failure; the parent stays usable. */
 cbh_idx64* cbh_idx64_slice(const cbh_idx64*, const uint32_t* ids, size_t n);
 /* copy the resident SoA back (tests, save()) */
 int cbh_idx64_download(const cbh_idx64*, uint64_t* hashes, uint32_t* ids, size_t cap);
@@ -562,6 +564,11 @@ int cbh_vidx_set_radix(cbh_vidx*, int radix);
  * decoded lists over (cbh_vdx_decode below reads the files).  Order of calls = _mediaId order. */
 int cbh_vidx_add_video(cbh_vidx*, uint32_t media_id, const int32_t* frames, const uint64_t* hashes, size_t n);
 int cbh_vidx_remove(cbh_vidx*, const uint32_t* media_ids, size_t n);           /* remove() :256-275 */
+/* slice() (:389-397): a new index of the same device or sharded shape and radix with the videos whose media id is
+ * listed, in the order of ids[] (first occurrence of an id only; ids the handle lacks are skipped) -- copied from the
+ * frames and hashes the handle holds, no .vdx file is read.  Host code; the result builds its search structure on the
+ * first search.  Caller destroys it; NULL + cbh_last_error_code() on failure. */
+cbh_vidx* cbh_vidx_slice(const cbh_vidx*, const uint32_t* ids, size_t n);
 size_t cbh_vidx_count(const cbh_vidx*);                                         /* count() = #videos */
 /* memoryUsage() (src/dctvideoindex.cpp:57-59: `_tree ? _tree->stats().memory : 0`): 0 until the search structure is
  * built; then the payload bytes the reference's RadixMap holds for the same entries -- 8 (hash_t) + 6 (the packed 24+24-bit
@@ -670,6 +677,12 @@ size_t cbh_idx256_memory_usage(const cbh_idx256*); /* memoryUsage() = 2 * rows *
 /* descriptorsForMediaId (:421-436): row range of a media; download of a row range */
 int cbh_idx256_rows_of(const cbh_idx256*, uint32_t media_id, size_t* first, size_t* count);
 int cbh_idx256_download_rows(const cbh_idx256*, size_t first, size_t count, uint8_t* out);
+/* slice() (:285-309): a new index of the same device or sharded shape with the rows of the listed media, built as add()
+ * in ascending id order builds it -- ids may come in any order and repeat; an id without rows is skipped; a media that
+ * was remove()d keeps its rows and comes back under its id, as cbh_idx256_rows_of still reports it (_idMap, :152-165).
+ * The rows move on the device.  Takes the index's search lock.  Caller destroys the result; NULL +
+ * cbh_last_error_code() on failure, the parent stays usable. */
+cbh_idx256* cbh_idx256_slice(const cbh_idx256*, const uint32_t* ids, size_t n);
 /* exact `knnSearch(needles, k)` below thresh: out_row/out_dist[nq*k] ordered (distance, row), counts[nq] =
  * rows under thresh.  nq < 2^23. */
 int cbh_idx256_knn(cbh_idx256*, const uint8_t* needles, size_t nq, int k, int thresh, uint32_t* out_row,
@@ -711,6 +724,12 @@ int cbh_color_is_loaded(const cbh_color*);                                      
 size_t cbh_color_memory_usage(const cbh_color*);                                 /* (258 + 4) * count (:118-121) */
 int cbh_color_find_index_data(const cbh_color*, uint32_t id, void* out_desc);    /* :231-239; returns 1/0 */
 int cbh_color_download(const cbh_color*, uint32_t* ids, void* descs, size_t cap);
+/* slice() (:231-248): a new index on the same device with the entries whose id is listed, in index order (a listed 0
+ * keeps removed entries).  The device planes are gathered from the parent's on the device.  Takes the index's search
+ * lock, and under it creates the parent's stream if no search has yet: const here means that the parent's entries do
+ * not change, not that the handle is untouched.  Caller destroys the result; NULL + cbh_last_error_code() on failure,
+ * the parent stays usable. */
+cbh_color* cbh_color_slice(const cbh_color*, const uint32_t* ids, size_t n);
 /* find() (:250-278) with ColorDescriptor::distance (src/cvutil.cpp:682-749): every entry whose distance is
  * finite (both sides have colours, counts differ by <= 2) and whose id != 0, in index order,
  * score = int(1 + sum of nearest-colour distances).  Bit-exact to the reference's float arithmetic. */
@@ -811,7 +830,10 @@ int cbh_set_tuning(const char* key, int value);
  * that 256-bit scan launches have used since it was last cleared -- cbh_set_tuning("scan256_kernels", 0) clears it, any
  * other value written is CBH_E_INVAL; bit 0 k_hamm256_scan, 1 k_hamm256_mfma<6,3,2> (first-128-bit prefilter, one needle
  * tile per accumulator), 2 k_hamm256_mfma<6,3,4> (all 256 bits), 3 k_hamm256_mfma3, 4 / 5 / 6 k_hamm256_small<4 / 8 / 16>;
- * a sharded handle notes one launch per shard, a buffer that had to grow one per attempt). */
+ * a sharded handle notes one launch per shard, a buffer that had to grow one per attempt); "slices_on_device" (the
+ * cbh_idx256_slice and cbh_color_slice calls so far that succeeded on the device route, the one that
+ * runs the kernels of slice.hip; a call that had nothing to move -- an empty list, an empty index, nothing kept --
+ * counts too, although it launches none of them). */
 int cbh_get_tuning(const char* key, long long* value);
 
 /* ---- measurement support ---------------------------------------------------------------- */
