@@ -120,6 +120,11 @@ struct ScanOpts {
   // one u64 per needle: also require ((q[j] ^ hashes[i]) & qmask[j]) == 0 -- the reference's approximate structures only
   // compare a needle with the entries that share its low bits (HammingTree leaf, src/tree/hammingtree.h:244-252; RadixMap
   const uint64_t* d_qmask = nullptr;  // bucket, src/tree/radix.h:135-141)
+  // a needle hash of 0 is a needle like any other: findVideo and DctFeaturesIndex::find hand every hash to the tree
+  // (src/dctvideoindex.cpp:437, src/dctfeaturesindex.cpp:293); only DctHashIndex::find returns nothing for it.  The scan
+  // kernels skip such needles, so the callers that hold one set this and launch_hamm64_scan adds their records in a
+  // pass of its own (k_zero_needle_scan)
+  bool zero_needles = false;
   // a call made of several launches against the same needles (the shards of a sharded handle):
   int pre = -1;                       // the kernel choice made once for the whole call (scan_pick_pre: 0 none, 1 the 32-bit
                                       // prefilter, 2 the 48-bit one); -1: the launch's own
@@ -127,7 +132,8 @@ struct ScanOpts {
   const uint4* qx = nullptr;          // the needles expanded once on this device (expand_needles_for_scan)
 };
 // Appends one record per (query j, slot i) with popc(q[j]^hashes[i]) < thresh, ids[i] != 0,
-// q[j] != 0.  *d_total += number of such pairs; records with slot index >= cap are dropped.
+// q[j] != 0 (ScanOpts::zero_needles: q[j] == 0 as well).  *d_total += number of such pairs; records with slot index >= cap
+// are dropped.
 // Runs the bucketed join, the popcount kernel or the matrix-core scan: the route at the end of hamm64_scan.hip.
 int launch_hamm64_scan(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n,
                        const uint64_t* d_q, size_t nq, int thresh, cbh_record* d_rec, size_t cap,
@@ -295,7 +301,7 @@ int sort_pairs_u64_u32(unsigned long long* d_keys, uint32_t* d_vals, size_t n, i
 int launch_fdct_vote(const cbh_match* d_top, const uint32_t* d_counts, const uint32_t* d_qneedle, size_t nq, int k,
                      const uint32_t* d_needle_id, size_t n_needles, std::vector<cbh_nmatch>* h_out, hipStream_t s);
 int launch_video_reduce(const unsigned* d_off, const unsigned long long* d_seg, size_t total, size_t nq,
-                        const uint32_t* d_evidx, const int32_t* d_eframe, const uint32_t* d_vmedia,
+                        const uint32_t* d_egroup, const int32_t* d_eframe, const uint32_t* d_vmedia,
                         const uint32_t* d_qneedle, const int32_t* d_qframe, const uint32_t* d_needle_id, int filter_self,
                         int min_matched, int min_near, std::vector<cbh_nvmatch>* h_out, hipStream_t s);
 

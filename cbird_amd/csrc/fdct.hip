@@ -132,7 +132,9 @@ int fdct_core(cbh_idx64* idx, const uint64_t* hashes, const std::vector<Needle>&
     CBH_HIP(hipMemcpyAsync(ws->d_qmask, masks.data(), nq * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
   }
   unsigned long long total = 0;
-  rc = scan_all(idx, ws, ws->d_q, nq, thresh, ws->stream, &total, ScanOpts{true, tree_compat ? ws->d_qmask : nullptr});
+  // (a keypoint hash of 0 is searched like any other, src/dctfeaturesindex.cpp:293)
+  rc = scan_all(idx, ws, ws->d_q, nq, thresh, ws->stream, &total,
+                ScanOpts{true, tree_compat ? ws->d_qmask : nullptr, std::find(hashes, hashes + nq, 0ull) != hashes + nq});
   if (rc) return rc;
   hipStream_t s = ws->stream;
   // per needle hash: the first 10 candidates by (distance, id) -- K4 counting select on the workspace block

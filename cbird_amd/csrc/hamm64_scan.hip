@@ -223,6 +223,36 @@ __global__ __launch_bounds__(kThreads) void k_hamm64_scan(
   if (qb < q1) exact_block<H>(h, base_idx, n, ids, q, qb, q1, thresh, rec, cap, total, keep0, qmask);
 }
 
+// ScanOpts::zero_needles: the records of the needles whose hash is 0, which every scan kernel skips.  Such needles are rare
+// (a black frame of a needle video, a flat keypoint patch) and the slots within `thresh` of 0 rarer still, so this is two
+// small launches behind the scan: the zero needles into list[1..], their number into list[0] (zeroed by the caller); then
+// one lane per slot, which leaves at once unless popcount(slot) < thresh.
+__global__ __launch_bounds__(256) void k_zero_needle_list(const uint64_t* __restrict__ q, uint32_t nq,
+                                                          uint32_t* __restrict__ list /* nq + 1 */) {
+  const uint32_t qi = blockIdx.x * 256u + threadIdx.x;
+  if (qi < nq && q[qi] == 0) list[1u + atomicAdd(&list[0], 1u)] = qi;
+}
+
+__global__ __launch_bounds__(256) void k_zero_needle_scan(const uint2* __restrict__ hay, const uint32_t* __restrict__ ids,
+                                                          uint32_t n, const uint32_t* __restrict__ list, uint32_t thresh,
+                                                          cbh_record* __restrict__ rec, unsigned long long cap,
+                                                          unsigned long long* __restrict__ total, uint32_t keep0,
+                                                          const uint2* __restrict__ qmask) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t nz = list[0];
+  if (i >= n || nz == 0) return;
+  const uint2 h = hay[i];
+  const uint32_t d = (uint32_t)__popc(h.x) + (uint32_t)__popc(h.y);
+  if (d >= thresh) return;
+  const uint32_t id = ids[i];
+  if (id == 0 && !keep0) return;
+  for (uint32_t k = 0; k < nz; ++k) {
+    const uint32_t qi = list[1u + k];
+    const uint2 mk = qmask ? qmask[qi] : make_uint2(0u, 0u);
+    if (((h.x & mk.x) | (h.y & mk.y)) == 0) emit(rec, cap, total, qi, d, id);
+  }
+}
+
 // the lone needle: see cbh_internal.h.  A thread takes 8 slots 256 apart (coalesced 8-byte loads).
 constexpr unsigned kLoneSlots = 8;
 __global__ __launch_bounds__(256) void k_find_one(const uint2* __restrict__ hay, const uint32_t* __restrict__ ids,
@@ -441,11 +471,45 @@ int scan_pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint
   return pre;
 }
 
+namespace {
+
+// the second pass of a call with ScanOpts::zero_needles, behind whichever path took the call
+int launch_zero_needles(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
+                        int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
+                        const ScanOpts& o) {
+  Scratch scratch(stream);
+  uint32_t* list = nullptr;
+  CBH_HIP(scratch.get(&list, (nq + 1) * sizeof(uint32_t)));
+  CBH_HIP(hipMemsetAsync(list, 0, sizeof(uint32_t), stream));
+  hipLaunchKernelGGL(k_zero_needle_list, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, d_q, (uint32_t)nq, list);
+  hipLaunchKernelGGL(k_zero_needle_scan, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                     reinterpret_cast<const uint2*>(d_hashes), d_ids, (uint32_t)n, list, (uint32_t)thresh, d_rec,
+                     (unsigned long long)cap, d_total, (uint32_t)o.keep_id0, reinterpret_cast<const uint2*>(o.d_qmask));
+  CBH_HIP(hipGetLastError());
+  return CBH_OK;
+}
+
+int scan_nonzero_needles(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
+                         int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
+                         const ScanOpts& o);
+
+}  // namespace
+
 int launch_hamm64_scan(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
                        int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
                        const ScanOpts& o) {
   if (n == 0 || nq == 0 || thresh <= 0) return CBH_OK;
   if (n > 0xfffffff0ull || nq > CBH_MAX_QUERIES_PER_CALL) return CBH_E_INVAL;
+  const int rc = scan_nonzero_needles(d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, o);
+  if (rc || !o.zero_needles) return rc;
+  return launch_zero_needles(d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, o);
+}
+
+namespace {
+
+int scan_nonzero_needles(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
+                         int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
+                         const ScanOpts& o) {
   const Route r = route(n, nq, thresh, o.d_qmask != nullptr);
   if (r.join != Join::None) {
     const bool force = r.join == Join::Forced;
@@ -469,6 +533,8 @@ int launch_hamm64_scan(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n
   }
   return launch_hamm64_scan_mfma(d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, pre, o);
 }
+
+}  // namespace
 
 int set_scan_mfma(int mode) {
   if (mode < 0 || mode > 4) return CBH_E_INVAL;

@@ -13,9 +13,11 @@
 // K8  k_video_winners / k_video_score                 src/dctvideoindex.cpp:475-509, 595-654
 //     input: unordered scan records (needle frame, distance, entry position) grouped per needle frame by the
 //     count/scan/scatter of topk.hip.  A record WINS when no other record of its needle frame points into the same
-//     video with a smaller (distance, position): the closest frame per video (:499-502; position order = the
-//     reference's scan order among equals), minus the needle's own video when filterSelf (:494).  Winners become
-//     (key = video (24) | needle frame (25), value = entry position); sorted, a run of equal (video, needle) is the
+//     group with a smaller (distance, position): the closest frame per media id (:492-502; position order = the
+//     reference's scan order among equals), minus the needle's own media when filterSelf (:494).  A group is the
+//     first video that carries a media id (video.hip build(): add() takes an id twice, :256-260, and closestMatch
+//     and cand are keyed by id); without a doubled id it is the video.  Winners become
+//     (key = group (24) | needle frame (25), value = entry position); sorted, a run of equal (group, needle) is the
 //     candidate list of that pair in source-frame order, and one lane walks it: numAdjacent with frameMargin 15
 //     (:593-613), the vfm / vfn gates (:619-641), score 100 - percentNear, range = first pair .. max(src, dst) extent
 //     (:645-651).
@@ -99,7 +101,7 @@ __global__ __launch_bounds__(256) void k_fdct_score(const FdctRun* __restrict__ 
 // ---- K8 ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_video_winners(const unsigned long long* __restrict__ seg,
                                                        const unsigned* __restrict__ off, unsigned nq,
-                                                       const uint32_t* __restrict__ evidx,
+                                                       const uint32_t* __restrict__ egroup,
                                                        const uint32_t* __restrict__ vmedia,
                                                        const uint32_t* __restrict__ qneedle,
                                                        const uint32_t* __restrict__ needle_id, int filter_self,
@@ -116,13 +118,13 @@ __global__ __launch_bounds__(256) void k_video_winners(const unsigned long long*
   const unsigned qi = lo;
   const unsigned long long mine = seg[g];
   const uint32_t pos = (uint32_t)(mine & 0xffffffffull);
-  const uint32_t vi = evidx[pos - 1];
+  const uint32_t vi = egroup[pos - 1];
   bool win = !(filter_self && vmedia[vi] == needle_id[qneedle[qi]]);
   if (win) {
     const unsigned a = off[qi], b = off[qi + 1];
     for (unsigned e = a; e < b; ++e) {
       const unsigned long long o = seg[e];
-      if (o < mine && evidx[(uint32_t)(o & 0xffffffffull) - 1] == vi) {
+      if (o < mine && egroup[(uint32_t)(o & 0xffffffffull) - 1] == vi) {
         win = false;
         break;
       }
@@ -222,9 +224,10 @@ int launch_fdct_vote(const cbh_match* d_top, const uint32_t* d_counts, const uin
   return CBH_OK;
 }
 
-// K8.  d_off/d_seg: records grouped per needle frame (launch_records_group), `total` of them.
+// K8.  d_off/d_seg: records grouped per needle frame (launch_records_group), `total` of them; d_egroup: entry -> the
+// first video of its media id.
 int launch_video_reduce(const unsigned* d_off, const unsigned long long* d_seg, size_t total, size_t nq,
-                        const uint32_t* d_evidx, const int32_t* d_eframe, const uint32_t* d_vmedia,
+                        const uint32_t* d_egroup, const int32_t* d_eframe, const uint32_t* d_vmedia,
                         const uint32_t* d_qneedle, const int32_t* d_qframe, const uint32_t* d_needle_id, int filter_self,
                         int min_matched, int min_near, std::vector<cbh_nvmatch>* h_out, hipStream_t s) {
   h_out->clear();
@@ -242,7 +245,7 @@ int launch_video_reduce(const unsigned* d_off, const unsigned long long* d_seg, 
   unsigned n = 0;
   if (e == hipSuccess) {
     const unsigned g = (unsigned)((total + 255) / 256);
-    hipLaunchKernelGGL(k_video_winners, dim3(g), dim3(256), 0, s, d_seg, d_off, (unsigned)nq, d_evidx, d_vmedia, d_qneedle,
+    hipLaunchKernelGGL(k_video_winners, dim3(g), dim3(256), 0, s, d_seg, d_off, (unsigned)nq, d_egroup, d_vmedia, d_qneedle,
                        d_needle_id, filter_self, keys, vals, total);
     rc = sort_pairs_u64_u32(keys, vals, total, 64, s);
     if (!rc) {

@@ -8,6 +8,7 @@
 // vradix=0 behaviour, used by its own test unit/testdctvideoindex.cpp:24); vradix>0 only ever returns
 // a subset of this.  findVideo's reductions (closest frame per video, adjacency scoring) run on the device
 // (reduce.hip); the host versions below remain as a second implementation (knob "video_host_reduce").
+#include <algorithm>
 #include <map>
 #include <unordered_map>
 
@@ -29,8 +30,11 @@ struct cbh_vidx {
   cbh_idx64* idx = nullptr;
   std::vector<uint32_t> evidx;   // entry -> video index
   std::vector<int32_t> eframe;   // entry -> frame number
-  // device copies for the on-device reduction (reduce.hip): entry -> video index / frame, video index -> mediaId
-  uint32_t* d_evidx = nullptr;
+  // device copies for the on-device reduction (reduce.hip): entry -> group / frame, video index -> mediaId.  The group
+  // of an entry is the index of the FIRST video that carries its media id: findVideo keeps its closest match and its
+  // candidates per media id (closestMatch[id], cand[id], :492-508) and add() does not refuse an id it already holds
+  // (:256-260), so two videos of one id are one group.  Without a doubled id, group == video index.
+  uint32_t* d_egroup = nullptr;
   int32_t* d_eframe = nullptr;
   uint32_t* d_vmedia = nullptr;
   std::mutex build_mu;           // QMutex _mutex (dctvideoindex.cpp:118)
@@ -75,17 +79,22 @@ int build(cbh_vidx* v, int skip) {
   {
     DeviceGuard g(v->device);
     if (!g.ok) return CBH_E_NODEVICE;
-    for (void* p : {(void*)v->d_evidx, (void*)v->d_eframe, (void*)v->d_vmedia})
+    for (void* p : {(void*)v->d_egroup, (void*)v->d_eframe, (void*)v->d_vmedia})
       if (p) (void)hipFree(p);
-    v->d_evidx = nullptr, v->d_eframe = nullptr, v->d_vmedia = nullptr;
+    v->d_egroup = nullptr, v->d_eframe = nullptr, v->d_vmedia = nullptr;
     const size_t ne = std::max<size_t>(1, v->evidx.size()), nv = std::max<size_t>(1, v->videos.size());
-    std::vector<uint32_t> vmedia(v->videos.size());
-    for (size_t i = 0; i < v->videos.size(); ++i) vmedia[i] = v->videos[i].media_id;
-    CBH_HIP(hipMalloc(&v->d_evidx, ne * 4));
+    std::vector<uint32_t> vmedia(v->videos.size()), vgroup(v->videos.size()), egroup(v->evidx.size());
+    std::unordered_map<uint32_t, uint32_t> first;  // media id -> its first video
+    for (size_t i = 0; i < v->videos.size(); ++i) {
+      vmedia[i] = v->videos[i].media_id;
+      vgroup[i] = first.emplace(vmedia[i], (uint32_t)i).first->second;
+    }
+    for (size_t e = 0; e < v->evidx.size(); ++e) egroup[e] = vgroup[v->evidx[e]];
+    CBH_HIP(hipMalloc(&v->d_egroup, ne * 4));
     CBH_HIP(hipMalloc(&v->d_eframe, ne * 4));
     CBH_HIP(hipMalloc(&v->d_vmedia, nv * 4));
     if (!v->evidx.empty()) {
-      CBH_HIP(hipMemcpy(v->d_evidx, v->evidx.data(), v->evidx.size() * 4, hipMemcpyHostToDevice));
+      CBH_HIP(hipMemcpy(v->d_egroup, egroup.data(), egroup.size() * 4, hipMemcpyHostToDevice));
       CBH_HIP(hipMemcpy(v->d_eframe, v->eframe.data(), v->eframe.size() * 4, hipMemcpyHostToDevice));
     }
     if (!vmedia.empty()) CBH_HIP(hipMemcpy(v->d_vmedia, vmedia.data(), vmedia.size() * 4, hipMemcpyHostToDevice));
@@ -121,7 +130,9 @@ int scan_to_host(cbh_vidx* v, const uint64_t* q, size_t nq, int thresh, std::vec
     CBH_HIP(hipMemcpyAsync(ws->d_qmask, masks.data(), nq * sizeof(uint64_t), hipMemcpyHostToDevice, ws->stream));
   }
   unsigned long long total = 0;
-  rc = scan_all(idx, ws, ws->d_q, nq, thresh, ws->stream, &total, ScanOpts{false, v->radix ? ws->d_qmask : nullptr});
+  // (a needle frame whose hash is 0 is searched like any other, :437)
+  rc = scan_all(idx, ws, ws->d_q, nq, thresh, ws->stream, &total,
+                ScanOpts{false, v->radix ? ws->d_qmask : nullptr, std::find(q, q + nq, 0ull) != q + nq});
   if (rc) return rc;
   if ((rc = ws->ensure_sort())) return rc;
   rc = launch_sort_records(ws->d_rec, ws->d_alt, (size_t)total, nq, ws->d_tmp, ws->tmp_bytes, ws->stream);
@@ -169,7 +180,7 @@ struct VNeedle {
   uint32_t id;
 };
 
-// scan -> group per needle frame (topk.hip) -> K8 on the device (reduce.hip): closest frame per video, adjacency
+// scan -> group per needle frame (topk.hip) -> K8 on the device (reduce.hip): closest frame per media id, adjacency
 // scoring, gates.  Only the final matches come back.
 int reduce_on_device(cbh_vidx* v, const std::vector<uint64_t>& q, const std::vector<int32_t>& qframe,
                      const std::vector<uint32_t>& qneedle, const std::vector<VNeedle>& needles, int thresh,
@@ -194,7 +205,8 @@ int reduce_on_device(cbh_vidx* v, const std::vector<uint64_t>& q, const std::vec
     CBH_HIP(hipMemcpyAsync(ws->d_qmask, masks.data(), nq * sizeof(uint64_t), hipMemcpyHostToDevice, s));
   }
   unsigned long long total = 0;
-  rc = scan_all(idx, ws, ws->d_q, nq, thresh, s, &total, ScanOpts{false, v->radix ? ws->d_qmask : nullptr});
+  rc = scan_all(idx, ws, ws->d_q, nq, thresh, s, &total,
+                ScanOpts{false, v->radix ? ws->d_qmask : nullptr, std::find(q.begin(), q.end(), 0ull) != q.end()});
   if (rc) return rc;
   if (total == 0) return CBH_OK;
   if (total >= (1ull << 32)) return CBH_E_OVERFLOW;
@@ -219,7 +231,7 @@ int reduce_on_device(cbh_vidx* v, const std::vector<uint64_t>& q, const std::vec
     rc = topk_scratch_init(scratch, nq, s);
     if (!rc) rc = launch_records_group(ws->d_total, 1, 0, (size_t)total, nq, d_status, scratch, &d_off, &d_seg, s);
     if (!rc)
-      rc = launch_video_reduce(d_off, d_seg, (size_t)total, nq, v->d_evidx, v->d_eframe, v->d_vmedia, d_qneedle, d_qframe,
+      rc = launch_video_reduce(d_off, d_seg, (size_t)total, nq, v->d_egroup, v->d_eframe, v->d_vmedia, d_qneedle, d_qframe,
                                d_nid, filter_self, min_matched, min_near, &flat, s);
   }
   for (void* p : {scratch, (void*)d_qneedle, (void*)d_qframe, (void*)d_nid})
@@ -319,7 +331,7 @@ void cbh_vidx_destroy(cbh_vidx* v) {
   if (!v) return;
   cbh::combiner_drop(v);  // combine.hip: the queue of cbh_*_find_coalesced callers
   if (v->idx) cbh_idx64_destroy(v->idx);
-  for (void* p : {(void*)v->d_evidx, (void*)v->d_eframe, (void*)v->d_vmedia})
+  for (void* p : {(void*)v->d_egroup, (void*)v->d_eframe, (void*)v->d_vmedia})
     if (p) (void)hipFree(p);
   delete v;
 }

@@ -1190,7 +1190,9 @@ static int cmp_range(const void* a, const void* b) {
 
 /* findVideo (:399-657).  Needle frames outside [skip, lastFrame - skip] are dropped unconditionally
  * (:431); per needle frame and matched media the closest entry (first in scan order among equals, :499-502)
- * contributes MatchRange(needle frame, entry frame); per media: ranges sorted by needle frame, numAdjacent
+ * contributes MatchRange(needle frame, entry frame) -- per media ID (closestMatch[id], cand[id], :492-508): add() takes
+ * an id the index already holds (:256-260), and the videos of one id are then one candidate list, kept here under the
+ * first video of that id; per media: ranges sorted by needle frame, numAdjacent
  * counts |dstIn - previous dstIn| < 15 starting from 0 (:606-613), percentNear = numAdjacent*100/num,
  * rejected when num < minFramesMatched or percentNear < minFramesNear, score = 100 - percentNear, range =
  * first pair, len = max(src span, dst span).  Results ascending mediaId (QMap). */
@@ -1205,6 +1207,15 @@ long long orc_video_find_video(const uint32_t* evidx, const int32_t* eframe, con
   size_t* rn = (size_t*)calloc(nvid ? nvid : 1, sizeof(size_t));
   int32_t* best = (int32_t*)malloc(sizeof(int32_t) * (nvid ? nvid : 1));
   int32_t* bestf = (int32_t*)malloc(sizeof(int32_t) * (nvid ? nvid : 1));
+  uint32_t* group = (uint32_t*)malloc(sizeof(uint32_t) * (nvid ? nvid : 1)); /* first video with the same media id */
+  for (size_t v = 0; v < nvid; ++v) {
+    group[v] = (uint32_t)v;
+    for (size_t u = 0; u < v; ++u)
+      if (mediaIds[u] == mediaIds[v]) {
+        group[v] = (uint32_t)u;
+        break;
+      }
+  }
   int lastFrame = nframes[nn - 1];
   for (size_t q = 0; q < nn; ++q) {
     int srcFrame = nframes[q];
@@ -1215,7 +1226,7 @@ long long orc_video_find_video(const uint32_t* evidx, const int32_t* eframe, con
       if (radix && radix_index_of(ehash[i], radix) != bucket) continue;
       int d = __builtin_popcountll(nhashes[q] ^ ehash[i]);
       if (d < thresh) {
-        uint32_t v = evidx[i];
+        uint32_t v = group[evidx[i]];
         if (filter_self && mediaIds[v] == needle_id) continue;
         if (best[v] < 0 || d < best[v]) {
           best[v] = d;
@@ -1231,7 +1242,7 @@ long long orc_video_find_video(const uint32_t* evidx, const int32_t* eframe, con
         rn[v]++;
       }
   }
-  /* results keyed by media id ascending: order video indices by media id (ids are unique per video) */
+  /* results keyed by media id ascending: order video indices by media id (only the first video of an id has ranges) */
   size_t* order = (size_t*)malloc(sizeof(size_t) * (nvid ? nvid : 1));
   for (size_t v = 0; v < nvid; ++v) order[v] = v;
   for (size_t a = 1; a < nvid; ++a) { /* insertion sort: _mediaId is ascending in practice (:186) */
@@ -1275,6 +1286,7 @@ long long orc_video_find_video(const uint32_t* evidx, const int32_t* eframe, con
   free(rn);
   free(best);
   free(bestf);
+  free(group);
   return r;
 }
 
