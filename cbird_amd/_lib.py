@@ -40,6 +40,11 @@ class cbh_stats(C.Structure):
     _fields_ = [("scan_launches", C.c_uint64), ("scan_pairs", C.c_uint64), ("scan_ms", C.c_double)]
 
 
+class cbh_join_stats(C.Structure):
+    _fields_ = [("builds", C.c_uint64), ("hits", C.c_uint64), ("drops", C.c_uint64), ("failed_builds", C.c_uint64),
+                ("bytes", C.c_uint64), ("plans", C.c_uint32)]
+
+
 class cbh_shard_stats(C.Structure):
     _fields_ = [("shards", C.c_uint32), ("devices", C.c_uint32), ("device_mask", C.c_uint32),
                 ("segments", C.c_uint64), ("scans", C.c_uint64), ("rescans", C.c_uint64), ("collectives", C.c_uint64),
@@ -229,6 +234,9 @@ _SIGS = {
     "cbh_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "cbh_get_tuning": (C.c_int, [C.c_char_p, C.POINTER(C.c_longlong)]),
     "cbh_idx64_get_stats": (C.c_int, [_vp, C.POINTER(cbh_stats)]),
+    "cbh_idx64_join_prepare": (C.c_int, [_vp, C.c_int]),
+    "cbh_idx64_join_release": (C.c_int, [_vp]),
+    "cbh_idx64_join_stats": (C.c_int, [_vp, C.POINTER(cbh_join_stats)]),
     "cbh_idx64_reset_stats": (C.c_int, [_vp]),
     "cbh_idx64_time_scan_dev": (C.c_int, [_vp, _vp, _sz, C.c_int, _vp, _sz, _vp, C.c_int,
                                           C.POINTER(C.c_float)]),

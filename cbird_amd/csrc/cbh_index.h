@@ -213,6 +213,12 @@ struct cbh_idx64 {
   // cbh_idx64_create_sharded: this handle owns no slots itself (d_hashes == nullptr, n = total over the shards); its
   // children hold contiguous shares on their devices and every search goes through scan_all below (sharded.hip)
   ShardSet* shards = nullptr;
+  // the bucketed join's resident slot tables (cbh_internal.h JoinCache): every path that bumps `generation` drops them
+  JoinCache join;
+  void contents_changed() {
+    generation++;
+    join.drop_all();
+  }
 
   Workspace* acquire(int* rc) {
     {
@@ -318,11 +324,15 @@ inline int scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t n
   if (idx->shards) return sharded_scan_all(idx, ws, d_q, nq, thresh, stream, total, opts, max_records);
   int rc = ws->ensure_records(first_record_block(idx, max_records));
   if (rc) return rc;
+  // the join's resident tables of this handle; `hold` keeps what a launch read until this function has seen the stream drained
+  std::shared_ptr<const JoinTables> hold;
+  ScanOpts o = opts;
+  o.join = &idx->join, o.join_hold = &hold;
   for (int attempt = 0; attempt < 3; ++attempt) {
     CBH_HIP(hipMemsetAsync(ws->d_total, 0, sizeof(unsigned long long), stream));
     CBH_HIP(hipEventRecord(ws->ev0, stream));
     rc = launch_hamm64_scan(idx->d_hashes, idx->d_ids, idx->n, d_q, nq, thresh, ws->d_rec,
-                            ws->rec_cap, ws->d_total, stream, opts);
+                            ws->rec_cap, ws->d_total, stream, o);
     if (rc) return rc;
     CBH_HIP(hipEventRecord(ws->ev1, stream));
     CBH_HIP(hipMemcpyAsync(ws->h_total, ws->d_total, sizeof(unsigned long long),

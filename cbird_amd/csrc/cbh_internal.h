@@ -7,7 +7,9 @@
 #include <stdint.h>
 
 #include <cstring>
+#include <atomic>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -114,6 +116,9 @@ static inline hipError_t gated_host_malloc(T** p, size_t bytes, unsigned flags =
   } while (0)
 
 // ---- the 64-bit threshold search: hamm64_scan.hip decides, hamm64_join.hip / hamm64_mfma.hip launch what they are told --
+struct JoinCache;    // the resident slot tables of one index, below (hamm64_join.hip)
+struct JoinTables;
+struct JoinNeedles;
 // What a caller says about a search besides its shape.
 struct ScanOpts {
   bool keep_id0 = false;              // also emit slots whose id is 0 (DctFeaturesIndex top-10 cut)
@@ -130,6 +135,12 @@ struct ScanOpts {
                                       // prefilter, 2 the 48-bit one); -1: the launch's own
   unsigned siblings = 1;              // launches running side by side on this device
   const uint4* qx = nullptr;          // the needles expanded once on this device (expand_needles_for_scan)
+  // the bucketed join (hamm64_join.hip): the resident slot tables of the handle whose slots these are, and the slot in
+  // which the launch leaves its reference to the tables it read -- the caller drops it once the stream has finished the
+  // launch's kernels.  Both or neither; without them the join prepares the slots' side per call from the scratch arena
+  JoinCache* join = nullptr;
+  std::shared_ptr<const JoinTables>* join_hold = nullptr;
+  const JoinNeedles* join_needles = nullptr;  // the needles' side prepared once on this device (join_prepare_needles)
 };
 // Appends one record per (query j, slot i) with popc(q[j]^hashes[i]) < thresh, ids[i] != 0,
 // q[j] != 0 (ScanOpts::zero_needles: q[j] == 0 as well).  *d_total += number of such pairs; records with slot index >= cap
@@ -196,11 +207,61 @@ int selftest_fp4_products(float* d_out, hipStream_t stream);
 // ---- hamm64_join.hip: the same search as a bucketed join (multi-index hashing), thresholds <= kJoinMaxThresh -----------
 constexpr int kJoinMaxThresh = 8;
 long long get_scan_joins();  // calls the join has answered so far (cbh_get_tuning "scan_joins")
+long long get_join_needle_preps();  // needle sides prepared so far (cbh_get_tuning "join_needle_preps")
+int set_join_resident(int v);     // "join_resident": 0 only handles opted in by cbh_idx64_join_prepare keep tables, 1 all
+int set_join_resident_mb(int v);  // "join_resident_mb": what the tables of one index may hold, all plans together
+int get_join_resident();
+int get_join_resident_mb();
+// The slots' side of one join plan (m = max(4, thresh) chunks), which depends on the index contents alone: the chunk
+// values' histogram, its exclusive scans and the m chunk-ordered copies of the slots.  Immutable once published and
+// reference counted: the index holds one reference, every launch that reads them another until its kernels are done, so a
+// mutation only ever drops the index's (the rule of coalesce.hip's retired snapshots).
+struct JoinTables {
+  int m = 0, device = 0;
+  size_t n = 0, bytes = 0;
+  uint32_t *hist_h = nullptr, *start_h = nullptr, *hid = nullptr;
+  uint64_t* hx = nullptr;
+  JoinTables() = default;
+  JoinTables(const JoinTables&) = delete;
+  JoinTables& operator=(const JoinTables&) = delete;
+  ~JoinTables();
+};
+// What an index owns of them (cbh_idx64::join; every shard of a sharded handle has its own).  plan[m] is current by
+// construction: every path that changes the contents calls drop_all().
+struct JoinCache {
+  std::mutex mu;  // building and dropping; two first calls build once
+  std::shared_ptr<const JoinTables> plan[kJoinMaxThresh + 1];
+  std::atomic<bool> opted{false};  // cbh_idx64_join_prepare / _release
+  std::atomic<uint64_t> builds{0}, hits{0}, drops{0}, failed_builds{0}, bytes{0};
+  bool enabled() const { return opted.load() || get_join_resident() != 0; }
+  std::shared_ptr<const JoinTables> current(int m);
+  // the tables of plan m, built now if they are not there: nullptr (failure counted, *rc = CBH_E_NOMEM, error text set) when
+  // memory or the budget does not allow them -- everything is allocated before anything is published.  Synchronises `stream`.
+  std::shared_ptr<const JoinTables> get_or_build(int m, const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, int device,
+                                                 hipStream_t stream, int* rc);
+  void drop_all();  // load, load_dev, add, remove, remove_ids_only, a shard's redistribution, release, destroy
+  uint32_t plans();
+};
+// The needles' side of plans 5..8 (histogram -> start_q, the m chunk-ordered copies qx / qidx): independent of the slots,
+// so a sharded call prepares it once per device (ScanOpts::join_needles).  The blocks are malloc_async on `stream`;
+// launches on other streams wait for an event of it, and free() gives them back once they have all finished.
+struct JoinNeedles {
+  int m = 0;
+  size_t nq = 0;
+  uint32_t *start_q = nullptr, *qidx = nullptr;
+  uint64_t* qx = nullptr;
+  hipStream_t stream = nullptr;
+  void free();
+};
+int join_prepare_needles(const uint64_t* d_q, size_t nq, int thresh, hipStream_t stream, JoinNeedles* out);
+// would a launch of this shape go to the join at all (the route's answer)
+bool scan_routes_to_join(size_t n, size_t nq, int thresh, bool masked);
 // CBH_OK = done; CBH_E_UNSUPPORTED = the scan is cheaper for this call (decided from the exact candidate count against
 // scan_ms_estimate unless `force`), or its jobs do not fit a grid: nothing written, the caller may scan.  No needle masks.
+// Of `o`: keep_id0, join / join_hold, join_needles.
 int launch_hamm64_join(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
                        int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
-                       bool keep_id0, bool force, double scan_ms_estimate);
+                       const ScanOpts& o, bool force, double scan_ms_estimate);
 
 // ---- the 256-bit threshold scan: hamm256_scan.hip decides, hamm256_mfma.hip launches what it is told -------------------
 // "scan256_kernels": which kernels 256-bit launches have used since the mask was last cleared (cbh_set_tuning(.., 0)).

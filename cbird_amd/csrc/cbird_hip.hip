@@ -850,6 +850,7 @@ void cbh_idx64_destroy(cbh_idx64* idx) {
     w->release();
     delete w;
   }
+  idx->join.drop_all();
   if (idx->d_hashes) (void)hipFree(idx->d_hashes);
   if (idx->d_ids) (void)hipFree(idx->d_ids);
   if (idx->coalescer.load()) coalescer_free(idx->coalescer.load());
@@ -868,7 +869,7 @@ static int idx_append(cbh_idx64* idx, const void* hashes, const void* ids, size_
   CBH_HIP(hipMemcpyAsync(idx->d_ids + idx->n, ids, n * sizeof(uint32_t), kind, s));
   CBH_HIP(hipStreamSynchronize(s));
   idx->n += n;
-  idx->generation++;
+  idx->contents_changed();
   {
     std::lock_guard<std::mutex> lk(idx->tree_mu);
     idx->tree_valid = false;  // the HammingTree shape depends on the contents
@@ -881,7 +882,7 @@ int cbh_idx64_load(cbh_idx64* idx, const uint64_t* hashes, const uint32_t* ids, 
   DeviceGuard g(idx->device);
   if (!g.ok) return CBH_E_NODEVICE;
   idx->n = 0;  // load() on a loaded index is a no-op in the reference (:75); here it reloads
-  idx->generation++;
+  idx->contents_changed();
   idx->loaded = true;
   if (idx->shards) {
     std::lock_guard<std::mutex> lk(idx->tree_mu);
@@ -897,7 +898,7 @@ int cbh_idx64_load_dev(cbh_idx64* idx, const void* d_hashes, const void* d_ids, 
   DeviceGuard g(idx->device);
   if (!g.ok) return CBH_E_NODEVICE;
   idx->n = 0;
-  idx->generation++;
+  idx->contents_changed();
   idx->loaded = true;
   if (idx->shards) {
     std::lock_guard<std::mutex> lk(idx->tree_mu);
@@ -917,7 +918,7 @@ int cbh_idx64_add(cbh_idx64* idx, const uint64_t* hashes, const uint32_t* ids, s
   if (idx->shards) {
     int rc = sharded_add(idx, hashes, ids, n);
     if (!rc && n) {
-      idx->generation++;
+      idx->contents_changed();
       std::lock_guard<std::mutex> lk(idx->tree_mu);
       idx->tree_valid = false;
     }
@@ -947,7 +948,7 @@ static int idx_remove(cbh_idx64* idx, const uint32_t* ids, size_t n, int zero_ha
   if (!ids) return CBH_E_INVAL;
   DeviceGuard g(idx->device);
   if (!g.ok) return CBH_E_NODEVICE;
-  idx->generation++;
+  idx->contents_changed();  // (remove and remove_ids_only alike: the join's copies carry the ids)
   if (idx->shards) return sharded_remove(idx, ids, n, zero_hash);
   std::vector<uint32_t> rm(ids, ids + n);
   std::sort(rm.begin(), rm.end());
@@ -967,6 +968,62 @@ static int idx_remove(cbh_idx64* idx, const uint32_t* ids, size_t n, int zero_ha
   }
   (void)hipFree(d_rm);
   return rc;
+}
+
+/* ---- the bucketed join's resident slot tables (hamm64_join.hip) ------------------------------------------------------
+ * The reference builds its tree once (buildTree, src/dcthashindex.cpp:61-68, at load :110) and searches it many times
+ * (:208); these three let a handle keep the join's view of the slots in the same way. */
+
+int cbh_idx64_join_prepare(cbh_idx64* idx, int thresh) {
+  if (!idx || thresh < 1 || thresh > kJoinMaxThresh) return CBH_E_INVAL;
+  const int m = std::max(4, thresh);
+  auto one = [m](cbh_idx64* c) -> int {
+    c->join.opted = true;
+    if (c->n == 0) return CBH_OK;  // nothing to order: an empty handle (or shard) is current at every plan
+    DeviceGuard g(c->device);
+    if (!g.ok) return CBH_E_NODEVICE;
+    int rc;
+    WsLease L(c, &rc);
+    if (!L.ws) return rc;
+    (void)c->join.get_or_build(m, c->d_hashes, c->d_ids, c->n, c->device, L.ws->stream, &rc);
+    return rc;
+  };
+  if (!idx->shards) return one(idx);
+  idx->join.opted = true;
+  for (int i = 0; i < cbh_idx64_shard_count(idx); ++i)
+    if (int rc = one(cbh_idx64_shard(idx, i))) return rc;
+  return CBH_OK;
+}
+
+int cbh_idx64_join_release(cbh_idx64* idx) {
+  if (!idx) return CBH_E_INVAL;
+  idx->join.opted = false;
+  idx->join.drop_all();
+  if (idx->shards)
+    for (int i = 0; i < cbh_idx64_shard_count(idx); ++i) {
+      cbh_idx64* c = cbh_idx64_shard(idx, i);
+      c->join.opted = false;
+      c->join.drop_all();
+    }
+  return CBH_OK;
+}
+
+int cbh_idx64_join_stats(const cbh_idx64* idx, cbh_join_stats* out) {
+  if (!idx || !out) return CBH_E_INVAL;
+  memset(out, 0, sizeof *out);
+  cbh_idx64* m = const_cast<cbh_idx64*>(idx);
+  uint32_t plans = 0x1f0u;
+  bool any = false;
+  auto one = [&](cbh_idx64* c) {
+    out->builds += c->join.builds.load(), out->hits += c->join.hits.load(), out->drops += c->join.drops.load();
+    out->failed_builds += c->join.failed_builds.load(), out->bytes += c->join.bytes.load();
+    if (c->n != 0) plans &= c->join.plans(), any = true;
+  };
+  if (!m->shards) one(m);
+  else
+    for (int i = 0; i < cbh_idx64_shard_count(m); ++i) one(cbh_idx64_shard(m, i));
+  out->plans = any ? plans : 0u;
+  return CBH_OK;
 }
 
 size_t cbh_idx64_count(const cbh_idx64* idx) { return idx ? idx->n : 0; }
@@ -1338,6 +1395,8 @@ int cbh_set_tuning(const char* key, int value) {
   if (!strcmp(key, "scan_mfma")) return set_scan_mfma(value);
   if (!strcmp(key, "scan256_mfma")) return set_scan256_mfma(value);
   if (!strcmp(key, "scan256_small")) return set_scan256_small(value);
+  if (!strcmp(key, "join_resident")) return set_join_resident(value);
+  if (!strcmp(key, "join_resident_mb")) return set_join_resident_mb(value);
   if (!strcmp(key, "scan256_kernels")) {  // a read-back, not a knob: writing 0 clears it, nothing else can be written
     if (value != 0) return CBH_E_INVAL;
     clear_scan256_kernels();
@@ -1365,6 +1424,9 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strcmp(key, "scan256_kernels")) return *value = get_scan256_kernels(), CBH_OK;
   if (!strcmp(key, "scan_probes")) return *value = get_scan_probes(), CBH_OK;
   if (!strcmp(key, "scan_joins")) return *value = get_scan_joins(), CBH_OK;
+  if (!strcmp(key, "join_needle_preps")) return *value = get_join_needle_preps(), CBH_OK;
+  if (!strcmp(key, "join_resident")) return *value = get_join_resident(), CBH_OK;
+  if (!strcmp(key, "join_resident_mb")) return *value = get_join_resident_mb(), CBH_OK;
   if (!strcmp(key, "slices_on_device")) return *value = get_slices_on_device(), CBH_OK;
   if (!strcmp(key, "scan_probe_rate_e9")) return *value = get_scan_probe_rate_e9(), CBH_OK;
   if (!strcmp(key, "scan_probe_true_e9")) return *value = get_scan_probe_true_e9(), CBH_OK;
@@ -1389,9 +1451,12 @@ int cbh_idx64_time_scan_dev(cbh_idx64* idx, const void* d_q, size_t nq, int thre
   CBH_HIP(hipEventCreate(&e1));
   CBH_HIP(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), s));
   CBH_HIP(hipEventRecord(e0, s));
+  std::shared_ptr<const JoinTables> hold;  // (let go behind the event wait below)
+  ScanOpts o;
+  o.join = &idx->join, o.join_hold = &hold;
   for (int i = 0; i < iters; ++i) {
     rc = launch_hamm64_scan(idx->d_hashes, idx->d_ids, idx->n, (const uint64_t*)d_q, nq, thresh,
-                            (cbh_record*)d_records, cap, (unsigned long long*)d_total, s);
+                            (cbh_record*)d_records, cap, (unsigned long long*)d_total, s, o);
     if (rc) break;
   }
   CBH_HIP(hipEventRecord(e1, s));

@@ -9,10 +9,13 @@
 // MORE work than the scan -- the launcher counts the candidate pairs exactly (sum over chunk values of slots x needles, from
 // the two histograms) before it commits, and hands the call back (CBH_E_UNSUPPORTED) when the matrix-core scan is cheaper.
 //
-//   k_join_hist        a histogram of every chunk's values, slots and needles alike (one atomic per item and chunk; every
-//                      n / 16384-th item only for the sampled pre-check, whose pairs k_join_pairs_only adds up)
-//   k_join_scan        per chunk: exclusive scans -> where each value's slots / needles start; the jobs of the wide join (one
-//                      per 512 slots x 2048 needles of a value) and their prefix; the chunk's candidate pairs
+//   k_join_hist        a histogram of every chunk's values, one global atomic per item and chunk: the 16-bit chunks of
+//                      thresholds <= 4, and every n / 16384-th item for the sampled pre-check (k_join_pairs_only adds up
+//                      its pairs)
+//   k_join_hist_lds    the same for chunks of <= 13 bits (thresholds 5..8), privatised in LDS
+//   k_join_scan1       per chunk, one side: the exclusive scan -> where each value's slots / needles start
+//   k_join_jobs        per chunk, from the two sides' starts: the jobs of the wide join (one per 512 slots x 2048 needles of
+//                      a value) and their prefix; the chunk's candidate pairs, exactly
 //   k_join_scatter     slots (hash, id) and needles (hash, needle index) in chunk-value order, one copy per chunk
 //   k_join_pairs       chunks of <= 11 bits: a workgroup per job, two slots per lane, the value's needles through the scalar
 //                      cache eight at a time, one min-test per block and the exact look only behind it
@@ -20,8 +23,15 @@
 //   k_join_by_needle   four 16-bit chunks (thresholds <= 4): only the slots' side is prepared; a lane per NEEDLE walks the
 //                      ~15 slots of each of its four values
 // A pair that also agrees on an EARLIER chunk is that chunk's to report; records are parked per wave in LDS and appended with
-// one atomic per flush.  Scratch from the stream-ordered arena; nothing is cached on the index (a call at 10^6 x 10^6 costs
-// 0.8 ms of bookkeeping at thresholds <= 4, 1.7 ms above, besides the join proper).
+// one atomic per flush.
+//
+// The slots' side (histogram, scans, the m chunk-ordered copies) depends on the index contents alone.  A handle that asks
+// for it (cbh_idx64_join_prepare, or "join_resident" 1) keeps it: JoinCache / JoinTables in cbh_internal.h -- built once per
+// plan under the cache's mutex, reference counted, dropped by every mutation, bounded by "join_resident_mb".  Such a handle
+// stands for the reference's tree, built once at load / the first find and queried many times (buildTree, src/dcthashindex.cpp:61-68,
+// called at :110, searched at :208).  A launch without a handle behind it (cbh_idx64_scan_dev on the caller's stream, which nobody waits for) or
+// whose tables could not be had prepares the slots per call from the stream-ordered arena, as every launch used to.
+// The needles' side of thresholds 5..8 is prepared per call -- once per device for the shards of a sharded handle.
 #include "cbh_internal.h"
 
 #include <atomic>
@@ -45,7 +55,9 @@ __device__ __forceinline__ uint32_t chunk_of(uint64_t h, int lo, int hi) {
   return (uint32_t)((h >> lo) & ((1ull << (hi - lo)) - 1ull));
 }
 
-// hist[voff[j] + j + value] += 1 for every item and chunk (the arrays carry one extra entry per chunk for the scans' ends)
+// hist[voff[j] + j + value] += 1 for every item and chunk (the arrays carry one extra entry per chunk for the scans' ends).
+// One global atomic per item and chunk: the 16-bit chunks of plan 4 (slots only, and with resident tables only when they
+// are built) and the sampled pre-check (stride > 1).
 __global__ __launch_bounds__(256) void k_join_hist(const uint64_t* __restrict__ x, uint32_t n, uint32_t stride, JoinPlan P,
                                                    uint32_t* __restrict__ hist) {
   const uint32_t i = (blockIdx.x * 256u + threadIdx.x) * stride;  // (stride > 1: the sampled pre-check)
@@ -55,53 +67,99 @@ __global__ __launch_bounds__(256) void k_join_hist(const uint64_t* __restrict__ 
   for (int j = 0; j < P.m; ++j) atomicAdd(&hist[P.voff[j] + (uint32_t)j + chunk_of(h, P.lo[j], P.lo[j + 1])], 1u);
 }
 
-// One workgroup per chunk.  In: the two histograms.  Out: start_h / start_q (exclusive scans, nv + 1 entries per chunk),
-// jobstart (exclusive scan of ceil(nh / 256) * ceil(nq / kJQ) per value, nv + 1 entries), stats[j] = {jobs, 0, pairs lo, hi}.
-__global__ __launch_bounds__(1024) void k_join_scan(JoinPlan P, const uint32_t* __restrict__ hist_h,
-                                                    const uint32_t* __restrict__ hist_q, uint32_t* __restrict__ start_h,
-                                                    uint32_t* __restrict__ start_q, uint32_t* __restrict__ jobstart,
+// The same histogram for chunks of <= 13 bits (every chunk of plans 5..8), privatised in LDS: a workgroup per (span of
+// items, chunk) counts into 2^bits bins of its own (32 KB at 13 bits: five workgroups fit a CU's 160 KB) and adds every
+// non-empty bin to the global array once.  A span is at least eight items per bin, so the global adds are at most an
+// eighth of the items (k_join_hist: one per item), and a million equal hashes meet in LDS, not on one global word.
+constexpr int kHistLdsBits = 13;
+constexpr uint32_t kHistSpan = 16384;  // items per workgroup at <= 11 bits; 8 << bits above
+__global__ __launch_bounds__(256) void k_join_hist_lds(const uint64_t* __restrict__ x, uint32_t n, JoinPlan P,
+                                                       uint32_t* __restrict__ hist) {
+  __shared__ uint32_t bins[1u << kHistLdsBits];
+  const int j = blockIdx.y;
+  const int bits = P.lo[j + 1] - P.lo[j];
+  const uint32_t nv = 1u << bits, span = max(kHistSpan, 8u << bits);
+  const uint64_t i0 = (uint64_t)blockIdx.x * span;  // (the grid is sized for the shortest span: the rest leave, as one)
+  if (i0 >= n) return;
+  const uint32_t i1 = (uint32_t)min((uint64_t)n, i0 + span);
+  for (uint32_t v = threadIdx.x; v < nv; v += 256u) bins[v] = 0u;
+  __syncthreads();
+  for (uint32_t i = (uint32_t)i0 + threadIdx.x; i < i1; i += 256u) atomicAdd(&bins[chunk_of(x[i], P.lo[j], P.lo[j + 1])], 1u);
+  __syncthreads();
+  const uint32_t off = P.voff[j] + (uint32_t)j;
+  for (uint32_t v = threadIdx.x; v < nv; v += 256u) {
+    const uint32_t c = bins[v];
+    if (c) atomicAdd(&hist[off + v], c);
+  }
+}
+
+// One workgroup per chunk, one side: start = the exclusive scan of hist (nv + 1 entries per chunk).  `zero`: hist is left
+// zeroed -- it becomes the scatter's cursors.  (At build time for the slots, per call for the needles.)
+__global__ __launch_bounds__(1024) void k_join_scan1(JoinPlan P, uint32_t* hist, uint32_t* __restrict__ start, uint32_t zero) {
+  const int j = blockIdx.x;
+  const uint32_t nv = 1u << (P.lo[j + 1] - P.lo[j]);
+  const uint32_t off = P.voff[j] + (uint32_t)j;
+  __shared__ uint32_t sa[1024];
+  const uint32_t per = (nv + 1023u) / 1024u, v0 = min(nv, threadIdx.x * per), v1 = min(nv, v0 + per);
+  uint32_t a = 0;
+  for (uint32_t v = v0; v < v1; ++v) a += hist[off + v];
+  sa[threadIdx.x] = a;
+  __syncthreads();
+  for (uint32_t d = 1; d < 1024u; d <<= 1) {  // inclusive scan of the per-thread sums
+    const uint32_t ta = threadIdx.x >= d ? sa[threadIdx.x - d] : 0u;
+    __syncthreads();
+    sa[threadIdx.x] += ta;
+    __syncthreads();
+  }
+  uint32_t ea = sa[threadIdx.x] - a;
+  for (uint32_t v = v0; v < v1; ++v) {
+    const uint32_t c = hist[off + v];
+    start[off + v] = ea;
+    ea += c;
+    if (zero) hist[off + v] = 0u;
+  }
+  if (threadIdx.x == 1023) start[off + nv] = sa[1023];
+}
+
+// One workgroup per chunk, per call.  In: the slots' starts (resident, or this call's) and the call's needle starts.  Out:
+// jobstart (exclusive scan of ceil(nh / kJH) * ceil(nq / kJQ) per value, nv + 1 entries), stats[2 j] = the chunk's jobs,
+// stats[2 j + 1] = its candidate pairs, exactly (sum over the values of slots x needles).
+__global__ __launch_bounds__(1024) void k_join_jobs(JoinPlan P, const uint32_t* __restrict__ start_h,
+                                                    const uint32_t* __restrict__ start_q, uint32_t* __restrict__ jobstart,
                                                     unsigned long long* __restrict__ stats) {
   const int j = blockIdx.x;
   const uint32_t nv = 1u << (P.lo[j + 1] - P.lo[j]);
   const uint32_t off = P.voff[j] + (uint32_t)j;
-  __shared__ uint32_t sa[1024], sb[1024], sc[1024];
-  __shared__ unsigned long long sp[1024];
-  const uint32_t per = (nv + 1023u) / 1024u, v0 = threadIdx.x * per, v1 = min(nv, v0 + per);
-  uint32_t a = 0, b = 0, c = 0;
-  unsigned long long p = 0;
+  __shared__ unsigned long long sc[1024], sp[1024];  // (64-bit job sums: the launcher refuses more than 2^31 - 1)
+  const uint32_t per = (nv + 1023u) / 1024u, v0 = min(nv, threadIdx.x * per), v1 = min(nv, v0 + per);
+  unsigned long long c = 0, p = 0;
   for (uint32_t v = v0; v < v1; ++v) {
-    const uint32_t nh = hist_h[off + v], nq = hist_q[off + v];
-    a += nh;
-    b += nq;
-    c += (nh && nq) ? ((nh + kJH - 1u) / kJH) * ((nq + kJQ - 1u) / kJQ) : 0u;
+    const uint32_t nh = start_h[off + v + 1] - start_h[off + v], nq = start_q[off + v + 1] - start_q[off + v];
+    c += (nh && nq) ? (unsigned long long)((nh + kJH - 1u) / kJH) * ((nq + kJQ - 1u) / kJQ) : 0ull;
     p += (unsigned long long)nh * nq;
   }
-  sa[threadIdx.x] = a, sb[threadIdx.x] = b, sc[threadIdx.x] = c, sp[threadIdx.x] = p;
+  sc[threadIdx.x] = c, sp[threadIdx.x] = p;
   __syncthreads();
-  for (uint32_t d = 1; d < 1024u; d <<= 1) {  // inclusive scans of the per-thread sums
-    const uint32_t ta = threadIdx.x >= d ? sa[threadIdx.x - d] : 0u, tb = threadIdx.x >= d ? sb[threadIdx.x - d] : 0u,
-                   tc = threadIdx.x >= d ? sc[threadIdx.x - d] : 0u;
-    const unsigned long long tp_ = threadIdx.x >= d ? sp[threadIdx.x - d] : 0ull;
+  for (uint32_t d = 1; d < 1024u; d <<= 1) {
+    const unsigned long long tc = threadIdx.x >= d ? sc[threadIdx.x - d] : 0ull, tp_ = threadIdx.x >= d ? sp[threadIdx.x - d] : 0ull;
     __syncthreads();
-    sa[threadIdx.x] += ta, sb[threadIdx.x] += tb, sc[threadIdx.x] += tc, sp[threadIdx.x] += tp_;
+    sc[threadIdx.x] += tc, sp[threadIdx.x] += tp_;
     __syncthreads();
   }
-  uint32_t ea = sa[threadIdx.x] - a, eb = sb[threadIdx.x] - b, ec = sc[threadIdx.x] - c;
+  unsigned long long ec = sc[threadIdx.x] - c;
   for (uint32_t v = v0; v < v1; ++v) {
-    const uint32_t nh = hist_h[off + v], nq = hist_q[off + v];
-    start_h[off + v] = ea, start_q[off + v] = eb, jobstart[off + v] = ec;
-    ea += nh;
-    eb += nq;
-    ec += (nh && nq) ? ((nh + kJH - 1u) / kJH) * ((nq + kJQ - 1u) / kJQ) : 0u;
+    const uint32_t nh = start_h[off + v + 1] - start_h[off + v], nq = start_q[off + v + 1] - start_q[off + v];
+    jobstart[off + v] = (uint32_t)ec;  // (only read when the chunk's jobs fit a grid)
+    ec += (nh && nq) ? (unsigned long long)((nh + kJH - 1u) / kJH) * ((nq + kJQ - 1u) / kJQ) : 0ull;
   }
   if (threadIdx.x == 1023) {
-    start_h[off + nv] = sa[1023], start_q[off + nv] = sb[1023], jobstart[off + nv] = sc[1023];
+    jobstart[off + nv] = (uint32_t)sc[1023];
     stats[2 * j] = sc[1023];
     stats[2 * j + 1] = sp[1023];
   }
 }
 
-// the sampled pre-check needs the candidate pairs only: stats[2 j + 1] = sum over chunk j's values of slots x needles
+// the pre-check needs the candidate pairs only: stats[2 j + 1] = sum over chunk j's values of slots x needles
 __global__ __launch_bounds__(1024) void k_join_pairs_only(JoinPlan P, const uint32_t* __restrict__ hist_h,
                                                           const uint32_t* __restrict__ hist_q,
                                                           unsigned long long* __restrict__ stats) {
@@ -341,17 +399,10 @@ __global__ __launch_bounds__(kJT) void k_join_by_needle(JoinPlan P, uint32_t n, 
 constexpr int g_join_model_ps_e3 = 250;  // the launcher's cost model: 0.25 ns of ONE SIMD lane... i.e. 2.5e-13 s of the
                                          // machine per candidate pair (measured 2.8e-13 at threshold 8)
 
-std::atomic<long long> g_n_join{0};
+std::atomic<long long> g_n_join{0}, g_n_needle_preps{0};
+std::atomic<int> g_join_resident{0}, g_join_resident_mb{2048};
 
-}  // namespace
-
-long long get_scan_joins() { return g_n_join.load(); }
-
-// CBH_OK: done (records appended, *d_total advanced like the scans do); CBH_E_UNSUPPORTED: the caller's scan is cheaper
-// (or `force` is false and the call is too small to be worth the bookkeeping) -- nothing has been written.
-int launch_hamm64_join(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
-                       int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
-                       bool keep_id0, bool force, double scan_ms_estimate) {
+JoinPlan make_plan(int thresh) {
   JoinPlan P;
   memset(&P, 0, sizeof P);
   P.m = std::max(4, thresh);
@@ -362,45 +413,223 @@ int launch_hamm64_join(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n
     nvals += 1u << (P.lo[j + 1] - P.lo[j]);
   }
   P.voff[P.m] = nvals;
-  const size_t nslots = (size_t)nvals + (size_t)P.m;  // one extra entry per chunk
+  return P;
+}
+size_t plan_entries(const JoinPlan& P) { return (size_t)P.voff[P.m] + (size_t)P.m; }  // one extra entry per chunk
+
+// the full histogram of n items into the zeroed `hist`: privatised in LDS where every chunk fits (plans 5..8)
+void launch_hist(const uint64_t* x, size_t n, const JoinPlan& P, uint32_t* hist, hipStream_t stream) {
+  if (P.m >= 5)
+    hipLaunchKernelGGL(k_join_hist_lds, dim3((unsigned)((n + kHistSpan - 1) / kHistSpan), (unsigned)P.m), dim3(256), 0, stream,
+                       x, (uint32_t)n, P, hist);
+  else
+    hipLaunchKernelGGL(k_join_hist, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, (uint32_t)n, 1u, P, hist);
+}
+
+// the needles' side in two steps, so that a launch can count its candidate pairs before it orders anything
+int needles_alloc(const JoinPlan& P, size_t nq, hipStream_t stream, JoinNeedles* N) {
+  N->m = P.m, N->nq = nq, N->stream = stream;
+  CBH_HIP(malloc_async((void**)&N->start_q, plan_entries(P) * 4, stream));
+  CBH_HIP(malloc_async((void**)&N->qx, (size_t)P.m * nq * 8, stream));
+  CBH_HIP(malloc_async((void**)&N->qidx, (size_t)P.m * nq * 4, stream));
+  return CBH_OK;
+}
+int needles_count(const uint64_t* d_q, size_t nq, const JoinPlan& P, uint32_t* cursor, hipStream_t stream, JoinNeedles* N) {
+  CBH_HIP(hipMemsetAsync(cursor, 0, plan_entries(P) * 4, stream));
+  launch_hist(d_q, nq, P, cursor, stream);
+  hipLaunchKernelGGL(k_join_scan1, dim3((unsigned)P.m), dim3(1024), 0, stream, P, cursor, N->start_q, 1u);
+  CBH_HIP(hipGetLastError());
+  g_n_needle_preps++;
+  return CBH_OK;
+}
+void needles_scatter(const uint64_t* d_q, size_t nq, const JoinPlan& P, uint32_t* cursor, hipStream_t stream, JoinNeedles* N) {
+  hipLaunchKernelGGL(k_join_scatter, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, d_q, (const uint32_t*)nullptr,
+                     (uint32_t)nq, P, N->start_q, cursor, N->qx, N->qidx);
+}
+
+}  // namespace
+
+long long get_scan_joins() { return g_n_join.load(); }
+long long get_join_needle_preps() { return g_n_needle_preps.load(); }
+int set_join_resident(int v) {
+  if (v != 0 && v != 1) return CBH_E_INVAL;
+  g_join_resident = v;
+  return CBH_OK;
+}
+int set_join_resident_mb(int v) {
+  if (v < 0) return CBH_E_INVAL;
+  g_join_resident_mb = v;
+  return CBH_OK;
+}
+int get_join_resident() { return g_join_resident.load(); }
+int get_join_resident_mb() { return g_join_resident_mb.load(); }
+
+// ---- the resident slot tables --------------------------------------------------------------------------------------------
+
+JoinTables::~JoinTables() {
+  int prev = -1;
+  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+  if (prev != device) (void)hipSetDevice(device);
+  if (hist_h) (void)hipFree(hist_h);
+  if (start_h) (void)hipFree(start_h);
+  if (hx) (void)hipFree(hx);
+  if (hid) (void)hipFree(hid);
+  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
+}
+
+std::shared_ptr<const JoinTables> JoinCache::current(int m) {
+  std::lock_guard<std::mutex> lk(mu);
+  return plan[m];
+}
+
+uint32_t JoinCache::plans() {
+  std::lock_guard<std::mutex> lk(mu);
+  uint32_t b = 0;
+  for (int m = 4; m <= kJoinMaxThresh; ++m)
+    if (plan[m]) b |= 1u << m;
+  return b;
+}
+
+void JoinCache::drop_all() {
+  std::lock_guard<std::mutex> lk(mu);
+  for (int m = 4; m <= kJoinMaxThresh; ++m)
+    if (plan[m]) {
+      bytes -= plan[m]->bytes;
+      plan[m].reset();  // (the memory goes when the last launch that reads it has let go)
+      drops++;
+    }
+}
+
+std::shared_ptr<const JoinTables> JoinCache::get_or_build(int m, const uint64_t* d_hashes, const uint32_t* d_ids, size_t n,
+                                                          int device, hipStream_t stream, int* rc) {
+  std::lock_guard<std::mutex> lk(mu);
+  *rc = CBH_OK;
+  if (plan[m] && plan[m]->n == n) return plan[m];  // a concurrent first call has built it
+  if (plan[m]) {  // (of another size: no mutation path leaves one behind, and a table never outlives its contents)
+    bytes -= plan[m]->bytes;
+    plan[m].reset();
+    drops++;
+  }
+  const JoinPlan P = make_plan(m);
+  const size_t entries = plan_entries(P), cost = (size_t)12 * P.m * n + 2 * entries * 4;
+  auto give_up = [&](int code) -> std::shared_ptr<const JoinTables> {
+    failed_builds++;
+    *rc = code;
+    return nullptr;
+  };
+  if (bytes.load() + cost > ((uint64_t)(unsigned)g_join_resident_mb.load() << 20)) {
+    set_last_error_text("join tables: over the \"join_resident_mb\" budget");
+    return give_up(CBH_E_NOMEM);
+  }
+  std::shared_ptr<JoinTables> T(new (std::nothrow) JoinTables);
+  if (!T) return give_up(CBH_E_NOMEM);
+  T->m = P.m, T->n = n, T->bytes = cost, T->device = device;
+  // everything is allocated before anything is written, let alone published (a failure frees what T holds)
   Scratch scratch(stream);
-  uint32_t *hist_h = nullptr, *hist_q = nullptr, *start_h = nullptr, *start_q = nullptr, *jobstart = nullptr;
+  uint32_t* cursor = nullptr;
+  hipError_t e;
+  if ((e = hipMalloc(&T->hist_h, entries * 4)) != hipSuccess || (e = hipMalloc(&T->start_h, entries * 4)) != hipSuccess ||
+      (e = hipMalloc(&T->hx, (size_t)P.m * n * 8)) != hipSuccess || (e = hipMalloc(&T->hid, (size_t)P.m * n * 4)) != hipSuccess ||
+      (e = scratch.get(&cursor, entries * 4)) != hipSuccess) {
+    set_last_error("join tables", e);
+    return give_up(e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP);
+  }
+  if ((e = hipMemsetAsync(T->hist_h, 0, entries * 4, stream)) == hipSuccess && (e = hipMemsetAsync(cursor, 0, entries * 4, stream)) == hipSuccess) {
+    launch_hist(d_hashes, n, P, T->hist_h, stream);
+    hipLaunchKernelGGL(k_join_scan1, dim3((unsigned)P.m), dim3(1024), 0, stream, P, T->hist_h, T->start_h, 0u);
+    hipLaunchKernelGGL(k_join_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_hashes, d_ids, (uint32_t)n, P,
+                       T->start_h, cursor, T->hx, T->hid);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);  // complete before any other stream may read them
+  if (e != hipSuccess) {
+    set_last_error("join tables build", e);
+    return give_up(CBH_E_HIP);
+  }
+  plan[m] = T;
+  bytes += cost;
+  builds++;
+  return T;
+}
+
+void JoinNeedles::free() {
+  if (start_q) (void)free_async(start_q, stream);
+  if (qx) (void)free_async(qx, stream);
+  if (qidx) (void)free_async(qidx, stream);
+  start_q = nullptr, qidx = nullptr, qx = nullptr;
+}
+
+int join_prepare_needles(const uint64_t* d_q, size_t nq, int thresh, hipStream_t stream, JoinNeedles* out) {
+  const JoinPlan P = make_plan(thresh);
+  if (P.m < 5 || P.m > kMaxChunks || nq == 0) return CBH_E_INVAL;
+  Scratch scratch(stream);
+  uint32_t* cursor = nullptr;
+  int rc = needles_alloc(P, nq, stream, out);
+  if (!rc) {
+    hipError_t e = scratch.get(&cursor, plan_entries(P) * 4);
+    if (e != hipSuccess) {
+      set_last_error("join needles", e);
+      rc = e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
+    }
+  }
+  if (!rc) rc = needles_count(d_q, nq, P, cursor, stream, out);
+  if (!rc) {
+    needles_scatter(d_q, nq, P, cursor, stream, out);
+    if (hipGetLastError() != hipSuccess) rc = CBH_E_HIP;
+  }
+  if (rc) out->free();
+  return rc;
+}
+
+// CBH_OK: done (records appended, *d_total advanced like the scans do); CBH_E_UNSUPPORTED: the caller's scan is cheaper
+// (or `force` is false and the call is too small to be worth the bookkeeping) -- nothing has been written.
+int launch_hamm64_join(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
+                       int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
+                       const ScanOpts& o, bool force, double scan_ms_estimate) {
+  const JoinPlan P = make_plan(thresh);
+  const size_t entries = plan_entries(P);
+  const bool keep_id0 = o.keep_id0;
+  // (16-bit chunks only: ~15 slots a value.  At five chunks of 12-13 bits a needle walks 5 x 122 slots by per-lane loads: 5.8 ms
+  // against the 2.9 of sorting both sides)
+  const bool by_needle = P.m == 4;
+  JoinCache* jc = o.join && o.join_hold && o.join->enabled() ? o.join : nullptr;
+  std::shared_ptr<const JoinTables> T;
+  if (jc) T = jc->current(P.m);
+  if (T && T->n != n) T.reset();
+  const bool reused = (bool)T;
+  Scratch scratch(stream);
   unsigned long long* stats = nullptr;
-  CBH_HIP(scratch.get(&hist_h, nslots * 4));
-  CBH_HIP(scratch.get(&hist_q, nslots * 4));
-  CBH_HIP(scratch.get(&start_h, nslots * 4));
-  CBH_HIP(scratch.get(&start_q, nslots * 4));
-  CBH_HIP(scratch.get(&jobstart, nslots * 4));
   CBH_HIP(scratch.get(&stats, 2 * kMaxChunks * 8));
   unsigned long long h_stats[2 * kMaxChunks];
-  auto count = [&](uint32_t sh, uint32_t sq, bool pairs_only) -> int {  // histograms of every sh-th slot / sq-th needle,
-                                                                        // scans (or just the pair count), read-back
-    CBH_HIP(hipMemsetAsync(hist_h, 0, nslots * 4, stream));
-    CBH_HIP(hipMemsetAsync(hist_q, 0, nslots * 4, stream));
-    const size_t nh_ = (n + sh - 1) / sh, nq_ = (nq + sq - 1) / sq;
-    hipLaunchKernelGGL(k_join_hist, dim3((unsigned)((nh_ + 255) / 256)), dim3(256), 0, stream, d_hashes, (uint32_t)n, sh, P,
-                       hist_h);
-    hipLaunchKernelGGL(k_join_hist, dim3((unsigned)((nq_ + 255) / 256)), dim3(256), 0, stream, d_q, (uint32_t)nq, sq, P, hist_q);
-    if (pairs_only)
-      hipLaunchKernelGGL(k_join_pairs_only, dim3((unsigned)P.m), dim3(1024), 0, stream, P, hist_h, hist_q, stats);
-    else
-      hipLaunchKernelGGL(k_join_scan, dim3((unsigned)P.m), dim3(1024), 0, stream, P, hist_h, hist_q, start_h, start_q,
-                         jobstart, stats);
+  uint32_t *hist_h = nullptr, *hist_q = nullptr;  // this call's histograms, then its scatters' cursors
+  auto read_stats = [&]() -> int {
     CBH_HIP(hipGetLastError());
     CBH_HIP(hipMemcpyAsync(h_stats, stats, (size_t)2 * P.m * 8, hipMemcpyDeviceToHost, stream));
     CBH_HIP(hipStreamSynchronize(stream));
     return CBH_OK;
   };
   int rc;
-  // (16-bit chunks only: ~15 slots a value.  At five chunks of 12-13 bits a needle walks 5 x 122 slots by per-lane loads: 5.8 ms
-  // against the 2.9 of sorting both sides)
-  const bool by_needle = P.m == 4;
   if (!force) {
     // a library of near-identical hashes makes the full histogram itself expensive (10^6 atomics on one counter): look at
-    // 16 384 of each side first and leave if THEIR candidate pairs, scaled up, already say the scan is cheaper
-    const uint32_t sh = (uint32_t)std::max<size_t>(1, n / 16384), sq = (uint32_t)std::max<size_t>(1, nq / 16384);
-    if (sh > 1 || sq > 1 || by_needle) {
-      if ((rc = count(sh, sq, true))) return rc;
+    // 16 384 of each side first and leave if THEIR candidate pairs, scaled up, already say the scan is cheaper.  Resident
+    // tables have the slots' FULL histogram: only the needles are sampled, and plans 5..8 skip the look altogether (their
+    // exact count below costs a needle histogram in LDS and one kernel).
+    const uint32_t sh = T ? 1u : (uint32_t)std::max<size_t>(1, n / 16384), sq = (uint32_t)std::max<size_t>(1, nq / 16384);
+    if (T ? by_needle : (sh > 1 || sq > 1 || by_needle)) {
+      CBH_HIP(scratch.get(&hist_q, entries * 4));
+      CBH_HIP(hipMemsetAsync(hist_q, 0, entries * 4, stream));
+      const uint32_t* hh = T ? T->hist_h : nullptr;
+      if (!T) {
+        CBH_HIP(scratch.get(&hist_h, entries * 4));
+        CBH_HIP(hipMemsetAsync(hist_h, 0, entries * 4, stream));
+        hipLaunchKernelGGL(k_join_hist, dim3((unsigned)(((n + sh - 1) / sh + 255) / 256)), dim3(256), 0, stream, d_hashes,
+                           (uint32_t)n, sh, P, hist_h);
+        hh = hist_h;
+      }
+      hipLaunchKernelGGL(k_join_hist, dim3((unsigned)(((nq + sq - 1) / sq + 255) / 256)), dim3(256), 0, stream, d_q, (uint32_t)nq,
+                         sq, P, hist_q);
+      hipLaunchKernelGGL(k_join_pairs_only, dim3((unsigned)P.m), dim3(1024), 0, stream, P, hh, hist_q, stats);
+      if ((rc = read_stats())) return rc;
       double sp = 0;
       for (int j = 0; j < P.m; ++j) sp += (double)h_stats[2 * j + 1];
       // (sampling thins the occupied values' pairs by sh x sq on average; a generous factor keeps borderline calls in --
@@ -409,20 +638,54 @@ int launch_hamm64_join(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n
       if (est_ms > (by_needle ? 0.6 : 4.0) * scan_ms_estimate) return CBH_E_UNSUPPORTED;
     }
   }
-  if (by_needle) {
-    uint64_t* hx = nullptr;
-    uint32_t* hid = nullptr;
-    CBH_HIP(scratch.get(&hx, (size_t)P.m * n * 8));
-    CBH_HIP(scratch.get(&hid, (size_t)P.m * n * 4));
-    CBH_HIP(hipMemsetAsync(hist_h, 0, nslots * 4, stream));
-    CBH_HIP(hipMemsetAsync(hist_q, 0, nslots * 4, stream));  // (no needles' side: the scans see empty needle buckets)
-    hipLaunchKernelGGL(k_join_hist, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_hashes, (uint32_t)n, 1u, P,
-                       hist_h);
-    hipLaunchKernelGGL(k_join_scan, dim3((unsigned)P.m), dim3(1024), 0, stream, P, hist_h, hist_q, start_h, start_q, jobstart,
-                       stats);
-    CBH_HIP(hipMemsetAsync(hist_h, 0, nslots * 4, stream));
+  // the slots' side: resident (built now if this is the handle's first call at this plan), or made for this call alone
+  if (!T && jc) {
+    int device = 0, brc = CBH_OK;
+    CBH_HIP(hipGetDevice(&device));
+    T = jc->get_or_build(P.m, d_hashes, d_ids, n, device, stream, &brc);
+    if (!T) cbh_clear_error();  // (no memory, over budget: not an error of the search, which goes on as it always has)
+  }
+  uint32_t *own_start_h = nullptr, *own_hid = nullptr, *jobstart = nullptr;
+  uint64_t* own_hx = nullptr;
+  if (T) {
+    *o.join_hold = T;  // (the caller lets go once the stream has finished what is queued below)
+    if (reused) jc->hits++;
+  } else {
+    if (!hist_h) CBH_HIP(scratch.get(&hist_h, entries * 4));
+    CBH_HIP(scratch.get(&own_start_h, entries * 4));
+    CBH_HIP(scratch.get(&own_hx, (size_t)P.m * n * 8));
+    CBH_HIP(scratch.get(&own_hid, (size_t)P.m * n * 4));
+  }
+  const uint32_t* start_h = T ? T->start_h : own_start_h;
+  const uint64_t* hx = T ? T->hx : own_hx;
+  const uint32_t* hid = T ? T->hid : own_hid;
+  // the needles' side (plans 5..8): the caller's, prepared once for several launches, or this call's own
+  struct OwnNeedles : JoinNeedles {
+    ~OwnNeedles() { free(); }
+  } own_needles;
+  const JoinNeedles* N = nullptr;
+  if (!by_needle) {
+    CBH_HIP(scratch.get(&jobstart, entries * 4));
+    if (o.join_needles && o.join_needles->m == P.m && o.join_needles->nq == nq) {
+      N = o.join_needles;
+    } else {
+      if (!hist_q) CBH_HIP(scratch.get(&hist_q, entries * 4));
+      if ((rc = needles_alloc(P, nq, stream, &own_needles))) return rc;
+      N = &own_needles;
+    }
+  }
+  // ---- every block is taken: from here on nothing fails for lack of memory, and no record has been written yet
+  auto scatter_slots = [&] {
     hipLaunchKernelGGL(k_join_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_hashes, d_ids, (uint32_t)n, P,
-                       start_h, hist_h, hx, hid);
+                       own_start_h, hist_h, own_hx, own_hid);
+  };
+  if (!T) {
+    CBH_HIP(hipMemsetAsync(hist_h, 0, entries * 4, stream));
+    launch_hist(d_hashes, n, P, hist_h, stream);
+    hipLaunchKernelGGL(k_join_scan1, dim3((unsigned)P.m), dim3(1024), 0, stream, P, hist_h, own_start_h, 1u);
+  }
+  if (by_needle) {  // (with resident tables: this kernel and nothing else)
+    if (!T) scatter_slots();
     hipLaunchKernelGGL(k_join_by_needle, dim3((unsigned)((nq + kJT - 1) / kJT)), dim3(kJT), 0, stream, P, (uint32_t)n,
                        (uint32_t)nq, hx, hid, d_q, start_h, (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total,
                        (uint32_t)keep_id0);
@@ -430,7 +693,9 @@ int launch_hamm64_join(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n
     g_n_join++;
     return CBH_OK;
   }
-  if ((rc = count(1, 1, false))) return rc;
+  if (N == &own_needles && (rc = needles_count(d_q, nq, P, hist_q, stream, &own_needles))) return rc;
+  hipLaunchKernelGGL(k_join_jobs, dim3((unsigned)P.m), dim3(1024), 0, stream, P, start_h, N->start_q, jobstart, stats);
+  if ((rc = read_stats())) return rc;
   double pairs = 0;
   unsigned long long jobs_max = 0;
   for (int j = 0; j < P.m; ++j) {
@@ -442,29 +707,18 @@ int launch_hamm64_join(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n
     const double join_ms = pairs * (double)g_join_model_ps_e3 * 1e-12 + 0.1 * P.m + 0.2;
     if (join_ms > 0.9 * scan_ms_estimate) return CBH_E_UNSUPPORTED;
   }
-  uint64_t *hx = nullptr, *qx = nullptr;
-  uint32_t *hid = nullptr, *qidx = nullptr;
-  CBH_HIP(scratch.get(&hx, (size_t)P.m * n * 8));
-  CBH_HIP(scratch.get(&hid, (size_t)P.m * n * 4));
-  CBH_HIP(scratch.get(&qx, (size_t)P.m * nq * 8));
-  CBH_HIP(scratch.get(&qidx, (size_t)P.m * nq * 4));
-  // (the histograms have served the scans: they become the scatters' cursors)
-  CBH_HIP(hipMemsetAsync(hist_h, 0, nslots * 4, stream));
-  CBH_HIP(hipMemsetAsync(hist_q, 0, nslots * 4, stream));
-  hipLaunchKernelGGL(k_join_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_hashes, d_ids, (uint32_t)n, P,
-                     start_h, hist_h, hx, hid);
-  hipLaunchKernelGGL(k_join_scatter, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, d_q,
-                     (const uint32_t*)nullptr, (uint32_t)nq, P, start_q, hist_q, qx, qidx);
+  if (!T) scatter_slots();
+  if (N == &own_needles) needles_scatter(d_q, nq, P, hist_q, stream, &own_needles);
   for (int j = 0; j < P.m; ++j) {
     if (h_stats[2 * j] == 0) continue;
     if (P.lo[j + 1] - P.lo[j] >= 12)
       hipLaunchKernelGGL(k_join_narrow, dim3((unsigned)((n + kJT - 1) / kJT)), dim3(kJT), 0, stream, j, P, (uint32_t)n,
-                         (uint32_t)nq, hx, hid, qx, qidx, start_q, (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total,
-                         (uint32_t)keep_id0);
+                         (uint32_t)nq, hx, hid, N->qx, N->qidx, N->start_q, (uint32_t)thresh, d_rec, (unsigned long long)cap,
+                         d_total, (uint32_t)keep_id0);
     else
       hipLaunchKernelGGL(k_join_pairs, dim3((unsigned)h_stats[2 * j]), dim3(kJT), 0, stream, j, P, (uint32_t)n, (uint32_t)nq,
-                         hx, hid, qx, qidx, start_h, start_q, jobstart, (uint32_t)thresh, d_rec, (unsigned long long)cap,
-                         d_total, (uint32_t)keep_id0);
+                         hx, hid, N->qx, N->qidx, start_h, N->start_q, jobstart, (uint32_t)thresh, d_rec,
+                         (unsigned long long)cap, d_total, (uint32_t)keep_id0);
   }
   CBH_HIP(hipGetLastError());
   g_n_join++;

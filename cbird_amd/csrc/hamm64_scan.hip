@@ -447,6 +447,10 @@ bool scan_takes_mfma(size_t n, size_t nq, int thresh) {
   return thresh >= 1 && route(n, nq, thresh, false).kernel == Kernel::Mfma;
 }
 
+bool scan_routes_to_join(size_t n, size_t nq, int thresh, bool masked) {
+  return thresh >= 1 && n >= 1 && nq >= 1 && route(n, nq, thresh, masked).join != Join::None;
+}
+
 int scan_pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
                   hipStream_t stream) {
   if (g_pre48 == 1 && thresh <= kPre48MaxThresh) return 2;
@@ -513,8 +517,7 @@ int scan_nonzero_needles(const uint64_t* d_hashes, const uint32_t* d_ids, size_t
   const Route r = route(n, nq, thresh, o.d_qmask != nullptr);
   if (r.join != Join::None) {
     const bool force = r.join == Join::Forced;
-    const int rc = launch_hamm64_join(d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, o.keep_id0, force,
-                                      r.scan_ms);
+    const int rc = launch_hamm64_join(d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, o, force, r.scan_ms);
     if (rc == CBH_OK || force || (rc != CBH_E_UNSUPPORTED && rc != CBH_E_NOMEM)) return rc;
     // (its scratch is all taken before the first record is written: a join that could not get it, like one whose count
     // said no, leaves the call to the scan)

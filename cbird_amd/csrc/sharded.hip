@@ -308,6 +308,7 @@ struct ShardRun {
   unsigned long long count = 0;  // records in its own block (the direct shards' are ScanCall::direct_count)
   const uint64_t *q = nullptr, *qmask = nullptr;  // needles and masks on its own device
   bool drained = true;           // (a workspace is idle when it is leased)
+  std::shared_ptr<const JoinTables> join_hold;  // the join tables its launch read: let go with the lease, behind the stream
   hipStream_t work() { return drained = false, ws->stream; }
   void saw_drained() { drained = true; }
 };
@@ -316,6 +317,7 @@ struct ShardRun {
 struct ShardLeases {
   std::vector<ShardRun> run;
   uint4* qx_root = nullptr;  // the shards read it on their own streams; allocated on the root stream
+  JoinNeedles jn_root;       // likewise the join's needle side (join_prepare_needles); m == 0: none
   hipStream_t root_stream;
   int root;
   ShardLeases(cbh_idx64* idx, hipStream_t st) : run(idx->shards->child.size()), root_stream(st), root(idx->device) {
@@ -346,9 +348,10 @@ struct ShardLeases {
           if (x.bytes > kKeepXBufBytes) x.release();
         r.c->give_back(r.ws);
       }
-    if (qx_root) {
+    if (qx_root || jn_root.m) {
       DeviceGuard g(root);
-      (void)free_async(qx_root, root_stream);
+      if (qx_root) (void)free_async(qx_root, root_stream);
+      jn_root.free();
     }
   }
 };
@@ -393,6 +396,23 @@ int plan_scan(ScanCall& K) {
   // are (every shard probing for itself cost a stream synchronisation per shard and threshold); and ONE expansion of the
   // needles into the matrix-core operand layout for all the shards of the root device (72 bytes per needle)
   K.opts.siblings = (unsigned)K.C.per_device;
+  // the bucketed join at thresholds 5..8 on shards that keep their slot tables: ONE needle side (histogram, starts, the
+  // chunk-ordered copies) for all the shards of the root device, which then run their jobs kernel and their joins only.
+  // No memory for it: every shard prepares its own, as a handle that keeps no tables does.
+  for (const ShardRun& r : K.L.run)
+    if (r.c->device == K.L.root && r.c->n != 0 && K.thresh >= 5 && r.c->join.enabled() &&
+        scan_routes_to_join(r.c->n, K.nq, K.thresh, K.opts.d_qmask != nullptr)) {
+      DeviceGuard g(K.L.root);
+      const int rc = join_prepare_needles(K.d_q, K.nq, K.thresh, K.stream, &K.L.jn_root);
+      if (rc == CBH_E_NOMEM) {
+        K.L.jn_root.m = 0;
+        cbh_clear_error();
+      } else if (rc) {
+        K.L.jn_root.m = 0;
+        return rc;
+      }
+      break;
+    }
   for (const ShardRun& r : K.L.run)
     if (r.c->device == K.L.root && r.c->n != 0 && scan_takes_mfma(r.c->n, K.nq, K.thresh)) {
       DeviceGuard g(K.L.root);
@@ -438,6 +458,8 @@ int launch_round(ScanCall& K, int attempt) {
     ScanOpts o = K.opts;
     o.d_qmask = r.qmask;
     o.qx = c->device == K.L.root ? K.L.qx_root : nullptr;
+    o.join = &c->join, o.join_hold = &r.join_hold;
+    o.join_needles = c->device == K.L.root && K.L.jn_root.m ? &K.L.jn_root : nullptr;
     rc = launch_hamm64_scan(c->d_hashes, c->d_ids, c->n, r.q, K.nq, K.thresh, into->d_rec, into->rec_cap, into->d_total, cs, o);
     if (rc) return rc;
     if (K.timed || r.direct) CBH_HIP(hipEventRecord(cw->ev1, cs));
@@ -630,7 +652,7 @@ int sharded_load(cbh_idx64* idx, const void* hashes, const void* ids, size_t n, 
       DeviceGuard g(c->device);
       if (!g.ok) return CBH_E_NODEVICE;
       c->n = 0;
-      c->generation++;
+      c->contents_changed();
       c->loaded = true;
       rc = c->reserve(b - a);
       if (!rc && b > a) {

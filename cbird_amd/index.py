@@ -244,6 +244,19 @@ class DctHashIndex:
     def set_record_capacity(self, records: int) -> None:
         check(self._L.cbh_idx64_set_record_capacity(self._h, records), "set_record_capacity")
 
+    def join_prepare(self, thresh: int) -> None:
+        """keep the bucketed join's slot tables of plan max(4, thresh) on this handle, built now (the reference's tree,
+        built once at load: src/dcthashindex.cpp:61-68, :110); "scan_mfma" still decides which calls take the join"""
+        check(self._L.cbh_idx64_join_prepare(self._h, int(thresh)), "join_prepare")
+
+    def join_release(self) -> None:
+        check(self._L.cbh_idx64_join_release(self._h), "join_release")
+
+    def join_stats(self) -> "_lib.cbh_join_stats":
+        st = _lib.cbh_join_stats()
+        check(self._L.cbh_idx64_join_stats(self._h, C.byref(st)), "join_stats")
+        return st
+
     def shard_count(self) -> int:
         return int(self._L.cbh_idx64_shard_count(self._h))
 
@@ -350,6 +363,19 @@ class DctFeaturesIndex:
             return
         i = _as_u32(ids)
         check(self._L.cbh_idx64_remove_ids_only(self._h, i.ctypes.data, len(i)), "remove")
+
+    def join_prepare(self, thresh: int) -> None:
+        """keep the bucketed join's slot tables of plan max(4, thresh) on this handle, built now (the reference's tree,
+        built once at load: src/dcthashindex.cpp:61-68, :110); "scan_mfma" still decides which calls take the join"""
+        check(self._L.cbh_idx64_join_prepare(self._h, int(thresh)), "join_prepare")
+
+    def join_release(self) -> None:
+        check(self._L.cbh_idx64_join_release(self._h), "join_release")
+
+    def join_stats(self) -> "_lib.cbh_join_stats":
+        st = _lib.cbh_join_stats()
+        check(self._L.cbh_idx64_join_stats(self._h, C.byref(st)), "join_stats")
+        return st
 
     def hashesForId(self, media_id: int):
         n = C.c_size_t(0)

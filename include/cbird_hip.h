@@ -424,6 +424,30 @@ int cbh_idx64_get_stats(const cbh_idx64*, cbh_stats* out);
 int cbh_idx64_reset_stats(cbh_idx64*);
 int cbh_idx256_get_stats(const cbh_idx256*, cbh_stats* out);
 
+/* ---- the bucketed join's resident slot tables (cbird_amd/csrc/hamm64_join.hip) -----------------------------------
+ * The reference builds its tree once -- buildTree (src/dcthashindex.cpp:61-68), called when load() has read the rows
+ * (:110) -- and every find() searches that tree (:208).  A handle that opts in keeps the join's view of its slots the same
+ * way: per join plan m = max(4, thresh) the chunk values' histogram, its scans and the m chunk-ordered copies of the slots
+ * (12 m n bytes plus the per-value arrays), built by the first joined call at that plan or by join_prepare, reused by
+ * every later joined call, dropped by load / load_dev / add / remove / remove_ids_only / destroy.  A slice starts without
+ * tables and is not opted in.  Which calls take the join is "scan_mfma"'s business as before; results never change.
+ * cbh_idx64_memory_usage keeps the reference's formula (:56-59): the tables are reported here, in `bytes`. */
+typedef struct {
+  uint64_t builds;         /* table sets built (per plan, summed over shards) */
+  uint64_t hits;           /* joined launches that reused resident tables */
+  uint64_t drops;          /* table sets dropped by a mutation or release */
+  uint64_t failed_builds;  /* builds given up for lack of memory or budget */
+  uint64_t bytes;          /* resident now, all plans, all shards */
+  uint32_t plans;          /* bit m: plan m resident and current on every non-empty shard */
+} cbh_join_stats;
+/* thresh 1..8, else CBH_E_INVAL; opts the handle in and builds plan max(4, thresh) now (the tree built at load, :110);
+ * CBH_E_NOMEM if it cannot (no memory, or over "join_resident_mb"): the handle stays opted in and searches as before */
+int cbh_idx64_join_prepare(cbh_idx64*, int thresh);
+/* frees the tables and opts the handle out (unload()'s `delete _tree`, src/dcthashindex.cpp:52) */
+int cbh_idx64_join_release(cbh_idx64*);
+/* (the reference has no counters: what `_tree != nullptr` says, :202, and what the tables cost) */
+int cbh_idx64_join_stats(const cbh_idx64*, cbh_join_stats*);
+
 /* ---- Database::searchIndex / Database::similar for a whole needle batch (cbird_amd/csrc/search.hip) ------------
  * searchIndex (src/database.cpp:1691-1757) over DctHashIndex for nq needles: find at `thresh`; when max_thresh > 0 the
  * needles whose match count is <= min_matches are searched again at thresh + 1, + 2, ... <= max_thresh (:1703-1725);
@@ -745,7 +769,7 @@ int cbh_color_distances(cbh_color*, const void* needle_descs, size_t nq, float* 
 int cbh_color_find_batch(cbh_color*, const void* needle_descs, size_t nq, int k, cbh_match* out,
                          uint32_t* counts);
 
-/* Knobs (25).  Results never change with any of them except "color_fma".  Unknown keys return CBH_E_INVAL.
+/* Knobs (27).  Results never change with any of them except "color_fma".  Unknown keys return CBH_E_INVAL.
  * Which kernel serves a call:
  *   "scan_mfma"     64-bit scan on the matrix cores (k_hamm64_mfma*): 0 = never (the popcount kernel k_hamm64_scan), 1 = calls
  *                   with >= 256 needles and >= 4096 slots (default), 2 = always; 3 = as 1, and calls with thresholds <= 8 and
@@ -754,6 +778,12 @@ int cbh_color_find_batch(cbh_color*, const void* needle_descs, size_t nq, int k,
  *                   its exact candidate count says it is cheaper; 4 = the join for every call it can represent (tests).
  *                   The join avoids comparisons rather than making them faster: it is opt-in, the default compares every pair.
  *                   Other values return CBH_E_INVAL and leave the knob as it was
+ *   "join_resident" which handles keep the join's slot tables between calls (cbh_idx64_join_prepare above): 0 (default) =
+ *                   those opted in by cbh_idx64_join_prepare, 1 = every handle, built by its first joined call at a plan.
+ *                   Other values return CBH_E_INVAL and leave the knob as it was
+ *   "join_resident_mb" what those tables may hold per index (per shard of a sharded handle), all plans together, in MB
+ *                   (default 2048: every plan of 5 * 10^6 slots; a plan costs 12 m n bytes).  A plan that would not fit is
+ *                   not kept: the call prepares the slots itself, as without tables.  Negative values: CBH_E_INVAL
  *   "scan_mfma_pre_max" prefilter kernel or three-field 64-bit kernel: -1 (default) = per launch, by the candidate rate of the
  *                   launch's own data -- r_cand = P[popc(fold(a) ^ fold(b)) < thresh] and r_true = P[hamm64(a, b) < thresh], counted
  *                   on 2048 x 2048 sampled (slot, needle) pairs by k_fold_probe; the prefilter while r_cand - 8 r_true <=
@@ -824,7 +854,9 @@ int cbh_set_tuning(const char* key, int value);
  * "arena_oom_retry_stream", "arena_oom_retry_device", "arena_oom_retry_persistent", "arena_released"; "scan_mfma" (the
  * knob's value); "scan_pre_mask"
  * (bit t = the most recent matrix-core launch at threshold t took the prefilter kernel), "scan_pre48_mask" (... took the
- * 48-bit prefilter kernel; a launch sets its bit in at most one of the two), "scan_joins" (calls the bucketed join has answered), "scan_probes" (candidate-rate
+ * 48-bit prefilter kernel; a launch sets its bit in at most one of the two), "scan_joins" (calls the bucketed join has answered), "join_needle_preps" (needle sides -- histogram, starts,
+ * chunk-ordered copies -- the join has prepared at thresholds 5..8: one per launch, one per device and call on a sharded handle that keeps
+ * tables), "join_resident" / "join_resident_mb" (the knobs' values), "scan_probes" (candidate-rate
  * probes run so far), "scan_probe_rate_e9" / "scan_probe_true_e9" / "scan_probe_rate48_e9" (the candidate and true-match rates the last one
  * found for its threshold and the 48-bit prefilter's candidate rate, x 1e9; -1 = none yet); "scan256_mfma", "scan256_small" (the knobs' values); "scan256_kernels" (a bit mask of the kernels
  * that 256-bit scan launches have used since it was last cleared -- cbh_set_tuning("scan256_kernels", 0) clears it, any
