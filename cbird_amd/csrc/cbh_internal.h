@@ -309,6 +309,9 @@ void set_kp_lds_side(int v);       // kphash.hip "kp_lds_side": largest keypoint
 extern int g_fdct_host_vote, g_video_host_reduce;  // fdct.hip: 0 = device for batches / host for one needle, 1 = host, 2 = device
 void set_orb_retain_order(int v);  // orb.hip: 1 (default) retainBest in libstdc++'s order, 0 canonical (ties kept, raster order)
 void set_cd_chunk_mb(int v);       // colordesc_create.hip "color_create_chunk_mb": MB of scratch one launch may take
+int set_cd_group(int v);           // colordesc_create.hip "color_create_group": images per wave of k_cdw_round, 0 (by size) / 1 / 2 / 4 / 8 / 16 / 21; else CBH_E_INVAL, knob unchanged
+int get_cd_group();
+int get_cd_group_last();           // "color_create_group_last": images per wave of the most recent chunk launch (0 = none yet)
 void set_color_fma(int on);        // color.hip "color_fma": fused squares in k_color_dist3 (default off: not bit-identical)
 
 // ---- records.hip ----------------------------------------------------------------------

@@ -1397,6 +1397,7 @@ int cbh_set_tuning(const char* key, int value) {
   if (!strcmp(key, "scan256_small")) return set_scan256_small(value);
   if (!strcmp(key, "join_resident")) return set_join_resident(value);
   if (!strcmp(key, "join_resident_mb")) return set_join_resident_mb(value);
+  if (!strcmp(key, "color_create_group")) return set_cd_group(value);
   if (!strcmp(key, "scan256_kernels")) {  // a read-back, not a knob: writing 0 clears it, nothing else can be written
     if (value != 0) return CBH_E_INVAL;
     clear_scan256_kernels();
@@ -1422,6 +1423,8 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strcmp(key, "scan256_mfma")) return *value = get_scan256_mfma(), CBH_OK;
   if (!strcmp(key, "scan256_small")) return *value = get_scan256_small(), CBH_OK;
   if (!strcmp(key, "scan256_kernels")) return *value = get_scan256_kernels(), CBH_OK;
+  if (!strcmp(key, "color_create_group")) return *value = get_cd_group(), CBH_OK;
+  if (!strcmp(key, "color_create_group_last")) return *value = get_cd_group_last(), CBH_OK;
   if (!strcmp(key, "scan_probes")) return *value = get_scan_probes(), CBH_OK;
   if (!strcmp(key, "scan_joins")) return *value = get_scan_joins(), CBH_OK;
   if (!strcmp(key, "join_needle_preps")) return *value = get_join_needle_preps(), CBH_OK;

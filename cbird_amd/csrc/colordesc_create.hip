@@ -909,6 +909,12 @@ __global__ __launch_bounds__(64) void k_cdw_finish(const CdW* __restrict__ W, un
 // (4-6 s per call against 0.9 s in chunks, tools/ab/color_create_pool.py).
 int g_cd_chunk_mb = 32768;
 
+// "color_create_group": images per wave of k_cdw_round -- 0 (default) = by the chunk's size (launch_color_descriptors_chunk),
+// 1 / 2 / 4 / 8 / 16 / 21 = that many for every chunk (tests: every instantiation on a few dozen images; results do not
+// depend on it).  "color_create_group_last": what the most recent chunk launched with, 0 before any.
+int g_cd_group = 0;
+std::atomic<int> g_cd_group_last{0};
+
 }  // namespace
 
 static int launch_color_descriptors_chunk(const uint8_t* d_imgs, size_t n, const uint64_t* img_off,
@@ -976,7 +982,9 @@ static int launch_color_descriptors_chunk(const uint8_t* d_imgs, size_t n, const
     // per wave = 76 / 60 / 68 / 88 / 131 ms -- the chain phases of one wave hide behind the produce phase of the
     // other), at most 21 (63 chain lanes); a large batch is bound by the HBM traffic of the distance arrays instead
     const unsigned want = (ni + 2047) / 2048;
-    const int G = want <= 1 ? 1 : want <= 2 ? 2 : want <= 4 ? 4 : want <= 8 ? 8 : want <= 16 ? 16 : 21;
+    const int G = g_cd_group ? g_cd_group  // "color_create_group": forced (tests)
+                  : want <= 1 ? 1 : want <= 2 ? 2 : want <= 4 ? 4 : want <= 8 ? 8 : want <= 16 ? 16 : 21;
+    g_cd_group_last.store(G);  // "color_create_group_last"
     for (int round = 0; round < kK; ++round) {  // generateCentersPP: centre 0, then 31 rounds of three trials
 #define CBH_ROUND(GG)                                                                                                 \
   hipLaunchKernelGGL(k_cdw_round<GG>, dim3((ni + GG - 1) / GG), dim3(64), 0, s, d_w, ni, d_samples, d_dists, cap, \
@@ -1053,6 +1061,13 @@ void set_cd_chunk_mb(int v) {
   if (v > 0) g_cd_chunk_mb = v;
 }
 
+int set_cd_group(int v) {
+  if (v != 0 && v != 1 && v != 2 && v != 4 && v != 8 && v != 16 && v != 21) return CBH_E_INVAL;
+  g_cd_group = v;
+  return CBH_OK;
+}
+int get_cd_group() { return g_cd_group; }
+int get_cd_group_last() { return g_cd_group_last.load(); }
 
 void color_ellipse_mask(int cols, int rows, uint8_t* mask) { ellipse_mask(cols, rows, mask); }
 

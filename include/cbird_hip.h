@@ -769,7 +769,7 @@ int cbh_color_distances(cbh_color*, const void* needle_descs, size_t nq, float* 
 int cbh_color_find_batch(cbh_color*, const void* needle_descs, size_t nq, int k, cbh_match* out,
                          uint32_t* counts);
 
-/* Knobs (27).  Results never change with any of them except "color_fma".  Unknown keys return CBH_E_INVAL.
+/* Knobs (28).  Results never change with any of them except "color_fma".  Unknown keys return CBH_E_INVAL.
  * Which kernel serves a call:
  *   "scan_mfma"     64-bit scan on the matrix cores (k_hamm64_mfma*): 0 = never (the popcount kernel k_hamm64_scan), 1 = calls
  *                   with >= 256 needles and >= 4096 slots (default), 2 = always; 3 = as 1, and calls with thresholds <= 8 and
@@ -816,6 +816,10 @@ int cbh_color_find_batch(cbh_color*, const void* needle_descs, size_t nq, int k,
  *   "kp_blur_side"  largest keypoint square whose blurred copy also stays in LDS (default 112)
  *   "fdct_host_vote", "video_host_reduce"  the per-needle reductions of DctFeaturesIndex / DctVideoIndex finds: 0 (default) =
  *                   on the device for batches, on the host for a single needle; 1 = host, 2 = device
+ *   "color_create_group" images per wave of ColorDescriptor::create's seeding kernel k_cdw_round<G>: 0 (default) = by the
+ *                   chunk's size (G = 1 up to 2048 images, 2 up to 4096, 4 up to 8192, 8 up to 16384, 16 up to 32768, 21 above),
+ *                   1 / 2 / 4 / 8 / 16 / 21 = that G for every chunk (tests: every instantiation on a few dozen images).  Other
+ *                   values return CBH_E_INVAL and leave the knob as it was
  *   "orb_retain_order" KeyPointsFilter::retainBest: 1 (default) = the survivors in the order libstdc++'s nth_element +
  *                   partition leave them (cbird's Linux builds), 0 = canonical (every tie kept, raster order)
  * The one knob that CHANGES results (within north_star's float tolerance; not the default: the shipped kernel is
@@ -858,7 +862,8 @@ int cbh_set_tuning(const char* key, int value);
  * chunk-ordered copies -- the join has prepared at thresholds 5..8: one per launch, one per device and call on a sharded handle that keeps
  * tables), "join_resident" / "join_resident_mb" (the knobs' values), "scan_probes" (candidate-rate
  * probes run so far), "scan_probe_rate_e9" / "scan_probe_true_e9" / "scan_probe_rate48_e9" (the candidate and true-match rates the last one
- * found for its threshold and the 48-bit prefilter's candidate rate, x 1e9; -1 = none yet); "scan256_mfma", "scan256_small" (the knobs' values); "scan256_kernels" (a bit mask of the kernels
+ * found for its threshold and the 48-bit prefilter's candidate rate, x 1e9; -1 = none yet); "scan256_mfma", "scan256_small", "color_create_group" (the knobs' values);
+ * "color_create_group_last" (the G of the most recent k_cdw_round<G> chunk launch, 0 before any; read-only); "scan256_kernels" (a bit mask of the kernels
  * that 256-bit scan launches have used since it was last cleared -- cbh_set_tuning("scan256_kernels", 0) clears it, any
  * other value written is CBH_E_INVAL; bit 0 k_hamm256_scan, 1 k_hamm256_mfma<6,3,2> (first-128-bit prefilter, one needle
  * tile per accumulator), 2 k_hamm256_mfma<6,3,4> (all 256 bits), 3 k_hamm256_mfma3, 4 / 5 / 6 k_hamm256_small<4 / 8 / 16>;
