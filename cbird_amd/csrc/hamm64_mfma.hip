@@ -263,19 +263,22 @@ __device__ __forceinline__ void handle_tile2(const v16f& c, uint32_t row0, uint3
 //     The lane does NOT find out which of its 32 accumulator registers held the flag (that took parking them in LDS and
 //     reading them back -- most of what a candidate used to cost, NOTES 11);
 //   * when 64 descriptors are pending at the end of a step (and at the end of the wave's needle chunk) the wave drains
-//     the list, one descriptor per lane: the needles of the flagged fields from global memory (64 lanes' loads in flight
-//     together), then ALL 17 or 15 haystack rows of a flagged chain from LDS against them, popcount on 64 bits; real
-//     matches go to the wave's record buffer.  Every (row, needle) pair belongs to one (lane, group, step) and one
-//     chain, so a match is emitted once.
+//     the list: the descriptors become work items, one per flagged chain and candidate field, and the items are worked
+//     off 64 at a time, one per lane -- its needle from global memory (64 lanes' loads in flight together), then ALL 17
+//     or 15 haystack rows of its chain from LDS against it, popcount on 64 bits; real matches go to the wave's record
+//     buffer.  Every (row, needle) pair belongs to one (lane, group, step), one chain and one field, so a match is
+//     emitted once.
 // (An immediate scalar re-check -- s_load + s_bcnt1 per candidate -- was built first: no VALU at all, but every event
 //  stalled the wave for a scalar-cache miss, 15.9 ms at threshold 6; NOTES 11.  The per-tile queue path of rounds 1-4
 //  -- ~750 cycles per candidate group -- and the parking path of rounds 5-6 are in the history.)
-// The wave's words: pending list (2 words per descriptor) | record buffer.
+// The wave's words: pending list (2 words per descriptor) | record buffer | item list (1 word per item).
 // Pending descriptors.  A group adds at most one per lane, a step has kHT / kG groups, a drain keeps npend & 63: a step
 // that starts with <= 63 ends with <= 63 + 4 x 64 = 319, so the list is drained between steps only.
 constexpr uint32_t kPendCap = 320;                          // descriptors the pending list holds
 constexpr uint32_t kOutOff = 2u * kPendCap;                 // word offset of the record buffer
-constexpr uint32_t kPreQueue = kOutOff + 2u * kOutCap;      // the prefilter kernel's words per wave
+constexpr uint32_t kItemOff = kOutOff + 2u * kOutCap;       // word offset of the drain's item list
+constexpr uint32_t kItemCap = 63u + 64u * 8u;               // items: the kept remainder + two chains x four fields of 64 descriptors
+constexpr uint32_t kPreQueue = kItemOff + kItemCap + 1u;    // the prefilter kernel's words per wave
 static_assert(kPendCap >= 63u + (kHT / kG) * 64u, "pending list: every lane of every group of a step");
 static_assert(kPreQueue <= kQueue, "the prefilter kernel's LDS must not grow");
 static_assert(kG == 2, "a descriptor names the two reduction chains of a group of 32 registers");
@@ -376,84 +379,106 @@ __device__ __forceinline__ void hamm64_mfma_body(
   const HitParams hp = {lo_key, hi_key, lo_zero, hi_zero, thresh, n, nq, keep0, q, ids, rec, cap, total, hay, qmask};
 
   uint32_t npend = 0;  // PRE: descriptors waiting in s_queue (wave-uniform)
-  // one descriptor per lane: every row of its flagged chains against the needles of its flagged fields, on all 64 bits
-  // (whole passes of 64 only -- the newest descriptors; the < 64 oldest wait for company, and for the chunk's end: a pass
-  // costs its global-memory round trip whether one lane works in it or all of them)
+  uint32_t nitem = 0;  // PRE: work items waiting in s_item (wave-uniform)
+  uint32_t* s_item = s_queue + kItemOff;
+  // One ITEM per lane: a descriptor's flagged chain x candidate field = 17 or 15 haystack rows against ONE needle, on all
+  // 64 bits.  (One DESCRIPTOR per lane made every pass run at the pace of its unluckiest lane: a top-field carry makes all
+  // four fields of its chain candidates, a quarter of all candidates sit in the top field, so some lane of 64 nearly always
+  // held four or more and the wave walked the rows four times for a mean of 1.75 candidates per lane.)
+  // Whole batches of 64 only -- the newest items; the < 64 oldest wait for company, and for the chunk's end, as the
+  // descriptors do: a batch costs its global-memory round trip and its row walk whether one lane works in it or all.
+  auto work = [&](uint32_t idx, bool live) {
+    const uint32_t it = s_item[idx];
+    const uint32_t f = it & 3u, ch = (it >> 2) & 1u, L = (it >> 3) & 63u, pp = p0 + 2u * (it >> 11);
+    // register 16 t + g of the group is wave row  64 group + 32 t + (g & 3) + 8 (g >> 2) + 4 (L >> 5)  (C/D layout, see
+    // handle_tile2)  =  base + 8 (register >> 2) + (register & 3): a quad of registers is four rows in a row
+    const uint32_t base = ((it >> 9) & 3u) * 64u + 4u * (L >> 5);
+    const uint32_t qi = pp * 64u + (L & 31u) + 32u * f;  // the needle of field f
+    // all lanes' loads in flight together; a null needle (and one past nq: the padding, the partner of a lone last pair)
+    // matches nothing
+    const uint64_t nv = live && qi < hp.nq ? hp.q[qi] : 0;
+    const uint32_t qlo = (uint32_t)nv, qhi = (uint32_t)(nv >> 32);
+    // chain 0 = registers 0..16 (quads 0..3 and the first of quad 4), chain 1 = 17..31 (the rest of quad 4, quads 5..7)
+    const uint32_t rows = nv == 0 ? 0u : ch ? 0xfffe0000u : 0x0001ffffu;
+    const uint2* hq = s_hay + base + 32u * ch;
+    uint32_t hit = 0;
+#pragma unroll 1
+    for (uint32_t i = 0; i < 5u; ++i) {
+      const uint32_t qd = 4u * ch + i;  // chain 1 at i = 4: quad 8, masked below; clamped to stay inside s_hay
+      const uint4* h4 = reinterpret_cast<const uint4*>(hq + 8u * min(i, 4u - ch));
+      const uint4 x = h4[0], y = h4[1];
+      const uint32_t d0 = __popc(x.x ^ qlo) + __popc(x.y ^ qhi), d1 = __popc(x.z ^ qlo) + __popc(x.w ^ qhi);
+      const uint32_t d2 = __popc(y.x ^ qlo) + __popc(y.y ^ qhi), d3 = __popc(y.z ^ qlo) + __popc(y.w ^ qhi);
+      const uint32_t m4 = (d0 < hp.thresh ? 1u : 0u) | (d1 < hp.thresh ? 2u : 0u) | (d2 < hp.thresh ? 4u : 0u) |
+                          (d3 < hp.thresh ? 8u : 0u);
+      hit |= qd < 8u ? m4 << (4u * qd) : 0u;
+    }
+    hit &= rows;
+    // a needle can match several rows of a chain (duplicates): one record per lane and round; the loop is uniform -- the
+    // record buffer ballots
+    while (__builtin_amdgcn_ballot_w64(hit != 0) != 0) {
+      const uint32_t rr = (uint32_t)__builtin_ctz(hit | 0x80000000u);
+      const uint32_t wr = base + 8u * (rr >> 2) + (rr & 3u), row = tile0 * 32u + wr;
+      const uint2 hv = s_hay[wr];
+      const uint32_t d = __popc(hv.x ^ qlo) + __popc(hv.y ^ qhi);
+      bool has = false;
+      uint32_t id = 0;
+      if (hit != 0 && row < hp.n && mask_ok(hp, row, qi, nv)) {
+        id = hp.ids[row];
+        has = id != 0 || hp.keep0;
+      }
+      out_push(s_out, nout, has, qi, d, id, hp);
+      hit &= hit - 1u;
+    }
+  };
+  // the pending descriptors -> items, 64 descriptors at a time (at most 8 items each behind the <= 63 kept: kItemCap),
+  // and the full batches worked off; all: the kept descriptors and items too (the end of the wave's needle chunk)
   auto drain = [&](bool all) {
     wave_order();
     const uint32_t keep = all ? 0u : (npend & 63u);
-    for (uint32_t k0 = keep; k0 < npend; k0 += 64u) {
-      const uint32_t k = min(k0 + lane, npend - 1u);
-      const uint2 e = *reinterpret_cast<const uint2*>(&s_queue[2u * k]);
-      const uint32_t L = e.y & 63u, pp = p0 + 2u * (e.y >> 8);
-      // register 16 t + g of the group is wave row  64 group + 32 t + (g & 3) + 8 (g >> 2) + 4 (L >> 5)  (C/D layout, see
-      // handle_tile2)  =  base + 8 (register >> 2) + (register & 3): a quad of registers is four rows in a row
-      const uint32_t base = ((e.y >> 6) & 3u) * 64u + 4u * (L >> 5);
-      const uint32_t col = pp * 64u + (L & 31u);  // needle of field f: col + 32 f
-      // candidates: bit 4 c + f = field f in the rows of chain c (flag bits of chain c at 5 + c, 11 + c, 17 + c, 23 + c).
-      // A carry into the exponent (top field flagged) leaves the lower fields of that register unreadable, and the OR
-      // cannot say which register it was: all four fields are candidates in that chain's rows.
-      uint32_t cm = 0;
+    uint32_t k0 = keep;
+    for (;;) {  // (one site of work(): its code is large)
+      if (nitem < 64u && k0 < npend) {
+        const uint2 e = *reinterpret_cast<const uint2*>(&s_queue[2u * min(k0 + lane, npend - 1u)]);
+        // candidates: bit 4 c + f = field f in the rows of chain c (flag bits of chain c at 5 + c, 11 + c, 17 + c,
+        // 23 + c).  A carry into the exponent (top field flagged) leaves the lower fields of that register unreadable,
+        // and the OR cannot say which register it was: all four fields are candidates in that chain's rows.
+        uint32_t cm = 0;
 #pragma unroll
-      for (uint32_t c = 0; c < 2; ++c) {
-        const uint32_t w = e.x >> c;
-        cm |= (((w >> 23) & 1u) ? 0xfu : (((w >> 5) & 1u) | (((w >> 11) & 1u) << 1) | (((w >> 17) & 1u) << 2))) << (4u * c);
-      }
-      if (k0 + lane >= npend) cm = 0;
-      // the needles of the candidate fields, all loads in flight together; a null needle (and one past nq: the padding,
-      // the partner of a lone last pair) matches nothing
-      uint32_t nlo[4], nhi[4];
-#pragma unroll
-      for (uint32_t f = 0; f < 4; ++f) {
-        const uint64_t nv = (((cm | (cm >> 4)) >> f) & 1u) != 0 && col + 32u * f < hp.nq ? hp.q[col + 32u * f] : 0;
-        nlo[f] = (uint32_t)nv;
-        nhi[f] = (uint32_t)(nv >> 32);
-      }
-#pragma unroll
-      for (uint32_t f = 0; f < 4; ++f)
-        if ((nlo[f] | nhi[f]) == 0) cm &= ~(0x11u << f);
-      // every lane takes its lowest candidate per round (one round while candidates are rare and the top field is not
-      // among them); the loops are uniform -- the record buffer ballots
-      while (__builtin_amdgcn_ballot_w64(cm != 0) != 0) {
-        const uint32_t b = (uint32_t)__builtin_ctz(cm | 0x100u), f = b & 3u, ch = (b >> 2) & 1u;
-        const uint32_t qlo = f == 0 ? nlo[0] : f == 1 ? nlo[1] : f == 2 ? nlo[2] : nlo[3];
-        const uint32_t qhi = f == 0 ? nhi[0] : f == 1 ? nhi[1] : f == 2 ? nhi[2] : nhi[3];
-        // chain 0 = registers 0..16 (quads 0..3 and the first of quad 4), chain 1 = 17..31 (the rest of quad 4, quads 5..7)
-        const uint32_t rows = cm == 0 ? 0u : ch ? 0xfffe0000u : 0x0001ffffu;
-        const uint2* hq = s_hay + base + 32u * ch;
-        uint32_t hit = 0;
-#pragma unroll 1
-        for (uint32_t i = 0; i < 5u; ++i) {
-          const uint32_t qd = 4u * ch + i;  // chain 1 at i = 4: quad 8, masked below; clamped to stay inside s_hay
-          const uint4* h4 = reinterpret_cast<const uint4*>(hq + 8u * min(i, 4u - ch));
-          const uint4 x = h4[0], y = h4[1];
-          const uint32_t d0 = __popc(x.x ^ qlo) + __popc(x.y ^ qhi), d1 = __popc(x.z ^ qlo) + __popc(x.w ^ qhi);
-          const uint32_t d2 = __popc(y.x ^ qlo) + __popc(y.y ^ qhi), d3 = __popc(y.z ^ qlo) + __popc(y.w ^ qhi);
-          const uint32_t m4 = (d0 < hp.thresh ? 1u : 0u) | (d1 < hp.thresh ? 2u : 0u) | (d2 < hp.thresh ? 4u : 0u) |
-                              (d3 < hp.thresh ? 8u : 0u);
-          hit |= qd < 8u ? m4 << (4u * qd) : 0u;
+        for (uint32_t c = 0; c < 2; ++c) {
+          const uint32_t w = e.x >> c;
+          cm |= (((w >> 23) & 1u) ? 0xfu : (((w >> 5) & 1u) | (((w >> 11) & 1u) << 1) | (((w >> 17) & 1u) << 2))) << (4u * c);
         }
-        hit &= rows;
-        // a needle can match several rows of a chain (duplicates): one record per lane and round
-        const uint32_t qi = col + 32u * f;
-        while (__builtin_amdgcn_ballot_w64(hit != 0) != 0) {
-          const uint32_t rr = (uint32_t)__builtin_ctz(hit | 0x80000000u);
-          const uint32_t wr = base + 8u * (rr >> 2) + (rr & 3u), row = tile0 * 32u + wr;
-          const uint2 hv = s_hay[wr];
-          const uint32_t d = __popc(hv.x ^ qlo) + __popc(hv.y ^ qhi);
-          bool has = false;
-          uint32_t id = 0;
-          if (hit != 0 && row < hp.n && mask_ok(hp, row, qi, ((uint64_t)qhi << 32) | qlo)) {
-            id = hp.ids[row];
-            has = id != 0 || hp.keep0;
-          }
-          out_push(s_out, nout, has, qi, d, id, hp);
-          hit &= hit - 1u;
+        if (k0 + lane >= npend) cm = 0;
+        // item = {lane | group | step} << 3 | chain << 2 | field, listed bit by bit of cm: a ballot and an mbcnt each
+#pragma unroll
+        for (uint32_t b = 0; b < 8; ++b) {
+          const bool on = ((cm >> b) & 1u) != 0;
+          const uint64_t m = __builtin_amdgcn_ballot_w64(on);
+          if (on)
+            s_item[nitem + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] =
+                (e.y << 3) | b;
+          nitem += (uint32_t)__popcll(m);
         }
-        cm &= cm - 1u;
+        k0 += 64u;
+        wave_order();
+        continue;
       }
+      uint32_t idx;
+      bool live = true;
+      if (nitem >= 64u) {
+        nitem -= 64u;
+        idx = nitem + lane;
+      } else if (all && nitem != 0) {
+        idx = min(lane, nitem - 1u);
+        live = lane < nitem;
+        nitem = 0;
+      } else {
+        break;
+      }
+      work(idx, live);
+      wave_order();
     }
-    wave_order();
     npend = keep;
   };
 
@@ -595,7 +620,7 @@ __device__ __forceinline__ void hamm64_mfma_body(
         step48(p0 + 2u * rel + 2u, y0, y1, y2);
       }
     }
-    if (npend) drain(true);
+    if (npend | nitem) drain(true);
   } else if constexpr (PRE == 1) {
     // A step takes two needle pairs (four tiles); the chunk length is even, only the call's last pair can be single -- its
     // partner slot is fed the same tiles again (chosen by ADDRESS, so that both loads are issued back to back and stay in
@@ -625,7 +650,7 @@ __device__ __forceinline__ void hamm64_mfma_body(
         step(p0 + rel + 2, b0, b1);
       }
     }
-    if (npend) drain(true);
+    if (npend | nitem) drain(true);
   } else {
     // two pairs per trip with explicit double buffers: the loads of the next pair are in flight
     // while the 2*HT MFMAs of the current one run

@@ -334,21 +334,23 @@ constexpr int kPreMax = 7;            // largest threshold served by the popcoun
 constexpr size_t kMfmaMinNq = 256;    // below this the needle expansion + tile padding is not worth it
 constexpr size_t kMfmaMinN = 4096;
 // The prefilter kernel is twice as fast as the three-field kernel while its candidates are rare and loses to it when
-// they are not: every candidate costs a descriptor and a share of a re-check of its chain's rows (~40 SIMD cycles).
+// they are not: every candidate costs a descriptor and one lane's walk of its chain's rows (~22 SIMD cycles).
 // How many there are is a property of the data -- r_cand(t) = P[popc(fold(a) ^ fold(b)) < t] over the launch's
 // needle x slot pairs: 5.8e-5 at t = 6, 2.7e-4 at t = 7 and 1.04e-3 at t = 8 for unrelated hashes, but anything for a
 // library of scans of one form, blank frames or a video against itself.  The three-field kernel in turn pays for every
 // TRUE match (a flagged group goes through three passes of sixteen ballots, 2.7e5 ms per unit of r_true against the
 // prefilter's 0.7e5): where the candidates are mostly true matches -- a dense cluster of near-identical hashes -- the
 // prefilter wins again, at any rate.  Measured per 10^12 pairs (tools/ab/adaptive_ab.py, profiles/r07_adaptive_ab_*.jsonl):
-//   T_pre = 8.55 ms + 2.4e4 ms x r_cand  (8.6 / 8.7 / 10.0 / 14.7 / 33.9 ms at thresholds 4..8 of image hashes),
+//   T_pre = 8.55 ms + 1.3e4 ms x r_cand  (8.8 / 9.0 / 9.7 / 12.1 ms at thresholds 4..7 of image hashes; the slope was 2.4e4
+//   while the drain took one descriptor per lane instead of one candidate field, NOTES 23 -- re-fitted at threshold 7 of
+//   profiles/r09_lib_ab_A.json; the true-match weights below are round 7's),
 //   T_full = 15.75 ms + 2.7e5 ms x r_true.
 // The probe counts both rates on a sample of the launch's pairs -- a few microseconds and one host round trip, against
 // launches of milliseconds -- and the prefilter is taken while
-//   r_cand - kTrueWeight x r_true <= "scan_pre_rate_e9" x 1e-9      (the rate at which the two kernels tie: 3.0e-4;
-//   kTrueWeight = (2.7e5 - 0.7e5) / 2.4e4),
-// which puts threshold 7 of unrelated hashes on the prefilter (14.6-14.8 ms against 15.75-17.0) and leaves 8 to the
-// three-field kernel.  Launches too small to pay for the round trip, and a probe that cannot run, take the fixed rule
+//   r_cand - kTrueWeight x r_true <= "scan_pre_rate_e9" x 1e-9      (3.0e-4: where the prefilter tied with the three-field
+//   kernel at the old slope, kTrueWeight = (2.7e5 - 0.7e5) / 2.4e4; at the new one it reaches 12.5 ms there, which is
+//   where it ties with the 48-bit prefilter below -- the kernel that now takes the launches beyond it),
+// which puts threshold 7 of unrelated hashes on the prefilter (12.1 ms against 13.9-17.0) and leaves 8 to the others.  Launches too small to pay for the round trip, and a probe that cannot run, take the fixed rule
 // (thresholds <= 6: at 7 the prefilter's margin is 7 % on unrelated hashes and gone on anything denser).
 //
 // The 48-bit prefilter (PRE48: 16 folds + 32 plain bits, three MFMAs per four needle tiles = 3/4 of the three-field
@@ -370,7 +372,7 @@ constexpr size_t kMfmaMinN = 4096;
 // that much room).  Launches on the fixed rule never take it.
 constexpr int kPreStatic = 6;
 constexpr double kTrueWeight = 8.0;
-constexpr double kSlopePre = 2.4e4, kBaseFull = 15.75, kTrueFull = 2.7e5, kTruePre = 0.7e5;  // ms per 10^12 pairs
+constexpr double kSlopePre = 1.3e4, kBaseFull = 15.75, kTrueFull = 2.7e5, kTruePre = 0.7e5;  // ms per 10^12 pairs
 constexpr double kBasePre = 8.55, kBase48 = 14.0, kSlope48 = 2.8e4, kTrue48 = 1.0e5, kPre48Margin = 0.9;
 constexpr int kPre48MaxThresh = 16;
 constexpr uint64_t kProbeMinPairs = 1ull << 31;  // ~20 us of scan: below this the probe's round trip is not worth it
@@ -398,7 +400,7 @@ struct Route {
 Route route(size_t n, size_t nq, int thresh, bool masked) {
   Route r;
   // (the prefilter at thresholds <= 5, at 6 and at 7 on unrelated hashes; the three-field kernel)
-  r.scan_ms = (double)n * (double)nq * (thresh <= 5 ? 8.7e-12 : thresh == 6 ? 10.0e-12 : thresh == 7 ? 14.7e-12 : 15.8e-12);
+  r.scan_ms = (double)n * (double)nq * (thresh <= 5 ? 8.7e-12 : thresh == 6 ? 9.7e-12 : thresh == 7 ? 12.1e-12 : 15.8e-12);
   // thresholds <= 8, "scan_mfma" 3: the join when its candidate count says it is cheaper than looking at every pair (only
   // asked where a scan would take >= 1 ms); 4: whenever it can represent the call (the parity suite).  As shipped (1)
   // every pair is compared: the join avoids comparisons, it does not make them faster.
