@@ -132,7 +132,7 @@ struct ScanOpts {
   bool zero_needles = false;
   // a call made of several launches against the same needles (the shards of a sharded handle):
   int pre = -1;                       // the kernel choice made once for the whole call (scan_pick_pre: 0 none, 1 the 32-bit
-                                      // prefilter, 2 the 48-bit one); -1: the launch's own
+                                      // prefilter, 2 the 48-bit one, 3 the 16-bit one); -1: the launch's own
   unsigned siblings = 1;              // launches running side by side on this device
   const uint4* qx = nullptr;          // the needles expanded once on this device (expand_needles_for_scan)
   // the bucketed join (hamm64_join.hip): the resident slot tables of the handle whose slots these are, and the slot in
@@ -160,12 +160,15 @@ int get_scan_mfma();
 void set_scan_pre_max(int t);
 void set_scan_pre_rate(int e9);
 void set_scan_pre48(int v);
+int set_scan_pre16(int v);  // -1, 0, 1; CBH_E_INVAL (knob unchanged) for anything else
 long long get_scan_pre_mask();
 long long get_scan_pre48_mask();
+long long get_scan_pre16_mask();
 long long get_scan_probes();
 long long get_scan_probe_rate_e9();
 long long get_scan_probe_true_e9();
 long long get_scan_probe_rate48_e9();
+long long get_scan_probe_rate16_e9();
 
 // ---- the lone needle (Engine::query / -similar-to: one find() at a time) ---------------------------------------------
 // One kernel launch and no copies: the needle travels as a kernel argument, matches go straight into a pinned, coherent
@@ -186,8 +189,9 @@ int launch_find_one(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, u
 int wait_find_one(const LoneBlock* h_block, unsigned long long seq, hipStream_t stream);
 
 // ---- hamm64_mfma.hip: the same scan on the matrix cores (FP4 sign dot products) --------
-// pre: 1 the prefilter kernel (thresholds <= 32), 2 the 48-bit prefilter (<= 16), 0 the three-field kernel (<= 64) or
-// the two-field one (65)
+// pre: 1 the prefilter kernel (thresholds <= 32), 2 the 48-bit prefilter (<= 16), 3 the 16-bit prefilter
+// (<= kPre16MaxThresh, CBH_E_INVAL beyond), 0 the three-field kernel (<= 64) or the two-field one (65)
+constexpr int kPre16MaxThresh = 8;
 int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
                             int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
                             int pre, const ScanOpts& opts);
@@ -199,9 +203,10 @@ int expand_needles_for_scan(const uint64_t* d_q, size_t nq, hipStream_t stream, 
 // k_fold_probe: the rates of fold-distance candidates and of true matches under `thresh` (<= kProbeMaxThresh) among a
 // sample of the launch's pairs -- one host round trip; false if it could not run
 constexpr int kProbeMaxThresh = 8;
-// (r_cand48: candidates of the 48-bit prefilter word, 48-bit distance <= thresh or > 32 + thresh)
+// (r_cand48: candidates of the 48-bit prefilter word, 48-bit distance <= thresh or > 32 + thresh; r_cand16: of the 16-bit
+// one, fold16 distance < thresh)
 bool probe_fold_rates(const uint64_t* d_hashes, size_t n, const uint64_t* d_q, size_t nq, int thresh, hipStream_t stream,
-                      double* r_cand, double* r_true, double* r_cand48);
+                      double* r_cand, double* r_true, double* r_cand48, double* r_cand16);
 // the 720 products of cbh_selftest_fp4_products into device memory
 int selftest_fp4_products(float* d_out, hipStream_t stream);
 // ---- hamm64_join.hip: the same search as a bucketed join (multi-index hashing), thresholds <= kJoinMaxThresh -----------

@@ -1393,6 +1393,7 @@ int cbh_set_tuning(const char* key, int value) {
   };
   if (!strcmp(key, "orb_retain_order") && value != 0 && value != 1) return CBH_E_INVAL;
   if (!strcmp(key, "scan_mfma")) return set_scan_mfma(value);
+  if (!strcmp(key, "scan_pre16")) return set_scan_pre16(value);
   if (!strcmp(key, "scan256_mfma")) return set_scan256_mfma(value);
   if (!strcmp(key, "scan256_small")) return set_scan256_small(value);
   if (!strcmp(key, "join_resident")) return set_join_resident(value);
@@ -1420,6 +1421,7 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strcmp(key, "scan_mfma")) return *value = get_scan_mfma(), CBH_OK;
   if (!strcmp(key, "scan_pre_mask")) return *value = get_scan_pre_mask(), CBH_OK;
   if (!strcmp(key, "scan_pre48_mask")) return *value = get_scan_pre48_mask(), CBH_OK;
+  if (!strcmp(key, "scan_pre16_mask")) return *value = get_scan_pre16_mask(), CBH_OK;
   if (!strcmp(key, "scan256_mfma")) return *value = get_scan256_mfma(), CBH_OK;
   if (!strcmp(key, "scan256_small")) return *value = get_scan256_small(), CBH_OK;
   if (!strcmp(key, "scan256_kernels")) return *value = get_scan256_kernels(), CBH_OK;
@@ -1434,6 +1436,7 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strcmp(key, "scan_probe_rate_e9")) return *value = get_scan_probe_rate_e9(), CBH_OK;
   if (!strcmp(key, "scan_probe_true_e9")) return *value = get_scan_probe_true_e9(), CBH_OK;
   if (!strcmp(key, "scan_probe_rate48_e9")) return *value = get_scan_probe_rate48_e9(), CBH_OK;
+  if (!strcmp(key, "scan_probe_rate16_e9")) return *value = get_scan_probe_rate16_e9(), CBH_OK;
   return CBH_E_INVAL;
 }
 

@@ -57,6 +57,15 @@ __host__ __device__ __forceinline__ uint32_t pre48_sub(uint32_t lo, uint32_t hi,
   return k == 0 ? (lo ^ hi) & 0xffffu : k == 1 ? lo >> 16 : hi >> 16;
 }
 
+// The 16-bit prefilter word: the 32-bit fold lo ^ hi folded once more, bit i = the XOR of bits i, i + 16, i + 32, i + 48.
+// A set bit of fold16(a) ^ fold16(b) needs an odd number of set bits among those four of a ^ b, so its popcount is a lower
+// bound on hamm64(a, b) by the same argument.  One scale block split by magnitude (0.5 x 0.5 against 4 x 4) holds two such
+// words: the threshold-1 prefilter of hamm64_mfma.hip compares four needle tiles in ONE MFMA.
+__host__ __device__ __forceinline__ uint32_t fold16(uint32_t lo, uint32_t hi) {
+  const uint32_t f = lo ^ hi;
+  return (f ^ (f >> 16)) & 0xffffu;
+}
+
 // FP4 operand of the f8f6f4 MFMA: the first 4 of the 8 operand dwords are used
 __device__ __forceinline__ v8i fp4_operand(uint4 e) {
   return v8i{(int)e.x, (int)e.y, (int)e.z, (int)e.w, 0, 0, 0, 0};

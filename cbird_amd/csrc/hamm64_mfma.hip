@@ -24,7 +24,7 @@
 //   * both halves are positive normal f16 bit patterns, so v_pk_maximum3_f16 (new on gfx950) takes
 //     the per-half maximum of three registers at once: 4 ops per MFMA instead of 8.
 //
-// Four variants (all exact).  Which one runs is decided in hamm64_scan.hip (the prefilter from the candidate rates the
+// Five variants (all exact).  Which one runs is decided in hamm64_scan.hip (the prefilter from the candidate rates the
 // probe below measures) and handed to launch_hamm64_scan_mfma:
 //   FULL3 (k_hamm64_mfma3, thresholds up to 64 that the prefilter does not take) three needle tiles per accumulator,
 //         detection by OR of flag bits -- described at the kernel below.
@@ -45,6 +45,9 @@
 //         folds and 32 plain bits, a tighter lower bound whose candidates are a hundred times rarer -- for three MFMAs per
 //         four needle tiles: 3/4 of FULL3's matrix work.  Layout and flag rule at step48 in the kernel body; events, drain
 //         and re-check are PRE's.
+//   PRE16 (threshold 1 of unrelated hashes; wherever its candidates are rare enough, thresholds <= 8) the prefilter on the
+//         16-bit word fold16 (fp4_sign.h): ONE MFMA per four needle tiles, half of PRE's matrix work, for candidates at
+//         the rate of 16-bit words (1.5e-5 per pair at threshold 1, 2.6e-4 at 2).  Layout at step16 in the kernel body.
 //
 // Hits.  After the MFMAs of a group of G haystack tiles one compare of the reduced flags decides
 // whether anything is under the threshold.  Then the lanes that hold flagged results list them in wave-private
@@ -57,7 +60,7 @@
 // Layout.  A workgroup is 4 waves; each wave keeps HT haystack tiles (32 rows each) expanded
 // to FP4 in VGPRs (4 VGPRs per tile: lane (r, half) holds word `half` of row r; PRE: the fold
 // lo ^ hi in both halves) and streams needle tiles -- pre-expanded once per call by
-// k_expand_needles (expand_needles_for_scan) into a 72-byte-per-needle scratch -- through 16-byte loads that the 4 waves
+// k_expand_needles (expand_needles_for_scan) into an 80-byte-per-needle scratch -- through 16-byte loads that the 4 waves
 // share in L1/L2.
 #include <algorithm>
 #include <mutex>
@@ -101,14 +104,23 @@ constexpr int kScale19 = (int)0x92929292;    // 2^19
 // of MFMA m holds sub-blocks 2 (2m + kb) and 2 (2m + kb) + 1 of the twelve  P.E0 P.E1 P.E2 Q.E0 ... S.E2  of column c's
 // four needles: sub-block s belongs to needle tile s / 3 and is its word's sub-block s % 3 (pre48_sub), at +-0.5 except
 // Q.E0, R.E1, S.E0 (s = 3, 7, 9) at +-4 -- the complement of the haystack's magnitudes, see the kernel.
+// Behind those (qx[4.5 * nq_pad ...]) the PRE16 operands: per quadruple ONE B operand of 64 lanes x 16 bytes, lane
+// (c, K block kb) = fold16 of needle c of tile 2 kb at +-0.5 | fold16 of needle c of tile 2 kb + 1 at +-4.
 // j >= nq padded with hash 0
 constexpr uint32_t kNeedlePad = 384;  // whole pairs (64), triples (96) and quadruples (128)
 __global__ __launch_bounds__(256) void k_expand_needles(const uint64_t* __restrict__ q, uint32_t nq,
                                                         uint32_t nq_pad, uint4* __restrict__ qx) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;  // one thread per output uint4
-  if (i >= 3u * nq_pad + nq_pad / 128u * 192u) return;
+  const uint32_t o16 = 3u * nq_pad + nq_pad / 128u * 192u;
+  if (i >= o16 + nq_pad / 128u * 64u) return;
   const uint32_t* w = reinterpret_cast<const uint32_t*>(q);
-  if (i < 2u * nq_pad) {
+  if (i >= o16) {
+    const uint32_t u = i - o16, c = u & 31u, kb = (u >> 5) & 1u;
+    const uint32_t j0 = (u >> 6) * 128u + kb * 64u + c, j1 = j0 + 32u;
+    const uint2 lo = fp4_expand16(j0 < nq ? fold16(w[2u * j0], w[2u * j0 + 1u]) : 0u, kFp4Half);
+    const uint2 hi = fp4_expand16(j1 < nq ? fold16(w[2u * j1], w[2u * j1 + 1u]) : 0u, kFp4Four);
+    qx[i] = make_uint4(lo.x, lo.y, hi.x, hi.y);
+  } else if (i < 2u * nq_pad) {
     qx[i] = fp4_expand32((i >> 1) < nq ? w[i] : 0u);
   } else if (i >= 3u * nq_pad) {
     const uint32_t u = i - 3u * nq_pad, quad = u / 192u, m = (u % 192u) >> 6, c = u & 31u, kb = (u >> 5) & 1u;
@@ -297,7 +309,8 @@ __device__ __forceinline__ uint32_t or_regs(const v16f (&c)[G]) {
 
 // PRE = true: the prefilter kernel (4 workgroups per CU: 128 VGPRs; bound by VALU issue, and a fourth wave per SIMD hides
 // more of it -- same box, compiled for 1 / 2 / 3 / 4: 10.8 / 10.8 / 10.1 / 9.8 ms, r05).  PRE = false: FULL2.
-// The body of three kernels (below): PRE = 0 FULL2, 1 the prefilter, 2 PRE48, the prefilter on a 48-bit word.
+// The body of four kernels (below): PRE = 0 FULL2, 1 the prefilter, 2 PRE48, the prefilter on a 48-bit word, 3 PRE16, the
+// prefilter on the 16-bit fold.
 template <int PRE>
 __device__ __forceinline__ void hamm64_mfma_body(
     const uint2* __restrict__ hay, const uint32_t* __restrict__ ids, uint32_t n,
@@ -333,6 +346,11 @@ __device__ __forceinline__ void hamm64_mfma_body(
       const uint2 s2 = fp4_expand16(half ? e1 : e2, kFp4Half);
       const uint2 s3 = fp4_expand16(half ? e2 : e0, half ? kFp4Half : kFp4Four);
       a[t] = v8i{(int)s0.x, (int)s0.y, (int)s1.x, (int)s1.y, (int)s2.x, (int)s2.y, (int)s3.x, (int)s3.y};
+    } else if constexpr (PRE == 3) {
+      // PRE16: fold16 at +-0.5 | the same at +-4, in both K blocks
+      const uint32_t f = fold16(hv.x, hv.y);
+      const uint2 s0 = fp4_expand16(f, kFp4Half), s1 = fp4_expand16(f, kFp4Four);
+      a[t] = v8i{(int)s0.x, (int)s0.y, (int)s1.x, (int)s1.y, 0, 0, 0, 0};
     } else {
       // PRE: the prefilter word lo ^ hi in both K blocks
       a[t] = fp4_operand(fp4_expand32(PRE ? hv.x ^ hv.y : (half ? hv.y : hv.x)));
@@ -353,16 +371,17 @@ __device__ __forceinline__ void hamm64_mfma_body(
   v16f c0;
 #pragma unroll
   for (int g = 0; g < 16; ++g)
-    c0[g] = PRE == 2 ? 8388608.0f + (float)((8u + thresh) * 266305u)
+    c0[g] = PRE == 3 ? 8388608.0f + (float)((24u + (thresh - 1u)) * 266305u)  // (step16)
+            : PRE == 2 ? 8388608.0f + (float)((8u + thresh) * 266305u)
             : PRE  ? 8388608.0f + (float)((16u + (thresh - 1u)) * 266305u) : kC0;  // 266305 = 1 + 2^6 + 2^12 + 2^18
   asm volatile("" : "+v"(c0));  // keep C0 resident: otherwise it is rebuilt (16 v_mov) every trip
   // PRE block scales (per lane half = per K block): first MFMA 2^-1 | 2^5, second 2^11 | 2^17
-  // PRE48 (three MFMAs): 2 | 2, 2^7 | 2^10, 2^13 | 2^19
-  int scale_b = PRE == 2 ? kScale1 : PRE ? (half ? kScale5 : kScaleHalf) : kScaleOne;
+  // PRE48 (three MFMAs): 2 | 2, 2^7 | 2^10, 2^13 | 2^19;  PRE16 (one): 2 | 2^13
+  int scale_b = PRE == 3 ? (half ? kScale13 : kScale1) : PRE == 2 ? kScale1 : PRE ? (half ? kScale5 : kScaleHalf) : kScaleOne;
   int scale_b2 = PRE == 2 ? (half ? kScale10 : kScale7p) : PRE ? (half ? kScale17 : kScale11) : kScale15;
   int scale_b3 = half ? kScale19 : kScale13;  // (PRE48 only)
   asm volatile("" : "+v"(scale_b));
-  asm volatile("" : "+v"(scale_b2));
+  if constexpr (PRE != 3) asm volatile("" : "+v"(scale_b2));
   if constexpr (PRE == 2) asm volatile("" : "+v"(scale_b3));
 
   const uint32_t p0 = blockIdx.y * pairs_per_chunk;
@@ -552,6 +571,26 @@ __device__ __forceinline__ void hamm64_mfma_body(
     if (npend >= 64u) drain(false);
   };
 
+  // PRE16: one needle-tile quadruple P Q R S (pairs p, p + 1) against the HT resident haystack tiles, ONE MFMA per tile.
+  // Both operands split each scale block of 32 elements by magnitude: sub-block 0 at +-0.5, sub-block 1 at +-4, so a
+  // block's sum is  0.25 dot(tile 2 kb) + 16 dot(tile 2 kb + 1)  with dot = 16 - 2 d16, and the B block scales 2 | 2^13 put
+  // the four tiles at 0.5, 32, 2^11, 2^17 = 64^f / 2: field f gains 8 - d16_f on the 24 + b that C0 puts there,
+  // 32 + b - d16_f in [16 + b, 32 + b] -- no field goes negative, bit 5 set <=> d16_f <= b, the top field flags by the
+  // carry into the exponent.  PRE's flag layout: detect, the descriptors, the items and the drain are PRE's unchanged.
+  // C0 < 2^24 needs 24 + b < 32: thresholds 1..8 (launch_hamm64_scan_mfma refuses the rest).
+  auto step16 = [&](const uint32_t p, const uint4& nn) __attribute__((always_inline)) {
+    const v8i bq = fp4_operand(nn);
+#pragma unroll
+    for (int t0 = 0; t0 < HT; t0 += G) {
+      v16f c[G];
+#pragma unroll
+      for (int t = 0; t < G; ++t)
+        c[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[t0 + t], bq, c0, 4, 4, 0, kScaleOne, 0, scale_b);
+      detect(c, (uint32_t)(t0 / G), p);
+    }
+    if (npend >= 64u) drain(false);
+  };
+
   // one needle-tile pair against the HT resident haystack tiles
   auto step = [&](const uint32_t p, const uint4& nA, const uint4& nB) __attribute__((always_inline)) {
     const v8i bA = fp4_operand(nA);
@@ -593,8 +632,32 @@ __device__ __forceinline__ void hamm64_mfma_body(
       if (npend >= 64u) drain(false);
   };
 
-  (void)step, (void)step48, (void)detect;  // (each variant uses its own)
-  if constexpr (PRE == 2) {
+  (void)step, (void)step48, (void)step16, (void)detect, (void)scale_b2, (void)scale_b3;  // (each variant uses its own)
+  if constexpr (PRE == 3) {
+    // One quadruple = one 16-byte load per lane per step, two steps per trip with explicit double buffers, as below.  The
+    // chunk starts at an even pair; a lone last pair's quadruple is whole in the scratch (padding needles: hash 0, dropped
+    // at qi >= nq).
+    typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint4*>(qf + (size_t)(p0 >> 1) * 64u), 0, (int)0xffffffffu, 0x27000);
+    const uint32_t voff = lane * 16u;
+    auto ldt = [&](uint32_t rel) -> uint4 {  // the operand of quadruple (p0 / 2) + rel
+      const v4u_t v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)(rel * 1024u), 0);
+      return make_uint4(v.x, v.y, v.z, v.w);
+    };
+    const uint32_t nqd = (p1 - p0 + 1u) >> 1;
+    uint4 x0 = ldt(0);
+#pragma unroll 1
+    for (uint32_t rel = 0; rel < nqd; rel += 2) {  // (two call sites of step16())
+      const uint4 y0 = ldt(min(rel + 1, nqd - 1));
+      step16(p0 + 2u * rel, x0);
+      if (rel + 1 < nqd) {
+        x0 = ldt(min(rel + 2, nqd - 1));
+        step16(p0 + 2u * rel + 2u, y0);
+      }
+    }
+    if (npend | nitem) drain(true);
+  } else if constexpr (PRE == 2) {
     // One quadruple per step, two steps per trip with explicit double buffers, as below.  The chunk starts at an even
     // pair; a lone last pair's quadruple is whole in the scratch (padding needles: hash 0, dropped at qi >= nq).
     typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
@@ -685,6 +748,8 @@ __global__ __launch_bounds__(kThreads, PRE ? 4 : 1) void k_hamm64_mfma(CBH_MFMA_
 // three copies of four, the compiler does not overlap operand tuples: 12 VGPRs per tile.  With 8 tiles the kernel takes 185
 // VGPRs, two waves per SIMD, and runs 14.65 ms per 10^12 pairs against 14.0 (profiles/r08_lib_ab_ht6_over_ht8.json).
 __global__ __launch_bounds__(kThreads, 3) void k_hamm64_mfma48(CBH_MFMA_PARAMS) { hamm64_mfma_body<2>(CBH_MFMA_ARGS); }
+// PRE16: PRE's tiles, LDS and occupancy; one needle operand in flight per buffer instead of two
+__global__ __launch_bounds__(kThreads, 4) void k_hamm64_mfma16(CBH_MFMA_PARAMS) { hamm64_mfma_body<3>(CBH_MFMA_ARGS); }
 #undef CBH_MFMA_PARAMS
 #undef CBH_MFMA_ARGS
 
@@ -848,7 +913,7 @@ constexpr int kProbeT = kProbeMaxThresh;  // thresholds 1..8 are counted (the pr
 
 // grid (sq / 256, sh / 64): thread = one needle sample against 64 slot samples; counts[t - 1] += pairs with fold
 // distance < t, counts[kProbeT + t - 1] += pairs with 64-bit distance < t, counts[2 kProbeT + t - 1] += pairs with 48-bit
-// distance <= t or > 32 + t.  The samples are pseudo-random rows / needles
+// distance <= t or > 32 + t, counts[3 kProbeT + t - 1] += pairs with fold16 distance < t.  The samples are pseudo-random rows / needles
 // (a 32-bit mix of the sample number): evenly spaced ones meet the diagonal of a self-join far more often than its share
 // -- a shard of 125 000 slots against its index's 10^6 needles counted 256 self matches among 4.2 x 10^6 sampled pairs,
 // sixty times their true rate, which is how dht 7 first came to take the prefilter on a sharded handle.
@@ -860,17 +925,17 @@ __device__ __forceinline__ uint32_t probe_mix(uint32_t x) {
 __global__ __launch_bounds__(256) void k_fold_probe(const uint2* __restrict__ hay, uint32_t n, const uint2* __restrict__ q,
                                                     uint32_t nq, uint32_t sh, uint32_t sq, uint32_t* __restrict__ counts) {
   __shared__ uint2 s_h[64];
-  __shared__ uint32_t s_cnt[3 * kProbeT];
+  __shared__ uint32_t s_cnt[4 * kProbeT];
   const uint32_t t = threadIdx.x;
   if (t < 64) {
     const uint32_t i = blockIdx.y * 64u + t;
     s_h[t] = i < sh ? hay[sh == n ? i : probe_mix(i) % n] : make_uint2(0u, 0u);
   }
-  if (t < 3 * kProbeT) s_cnt[t] = 0;
+  if (t < 4 * kProbeT) s_cnt[t] = 0;
   __syncthreads();
   const uint32_t j = blockIdx.x * 256u + t;
   const uint32_t nslots = min(64u, sh - blockIdx.y * 64u);
-  uint32_t cnt[kProbeT] = {}, cnt64[kProbeT] = {}, cnt48[kProbeT] = {};
+  uint32_t cnt[kProbeT] = {}, cnt64[kProbeT] = {}, cnt48[kProbeT] = {}, cnt16[kProbeT] = {};
   if (j < sq) {
     const uint2 nv = q[sq == nq ? j : probe_mix(j ^ 0x9e3779b9u) % nq];
     const uint32_t f = nv.x ^ nv.y;
@@ -884,6 +949,9 @@ __global__ __launch_bounds__(256) void k_fold_probe(const uint2* __restrict__ ha
                            (uint32_t)__popc((nv.y ^ hv.y) >> 16);
 #pragma unroll
       for (int th = 0; th < kProbeT; ++th) cnt48[th] += d48 <= (uint32_t)(th + 1) || d48 > (uint32_t)(th + 33) ? 1u : 0u;
+      const uint32_t x32 = f ^ hv.x ^ hv.y, d16 = (uint32_t)__popc((x32 ^ (x32 >> 16)) & 0xffffu);  // (fold16, fp4_sign.h)
+#pragma unroll
+      for (int th = 0; th < kProbeT; ++th) cnt16[th] += d16 < (uint32_t)(th + 1) ? 1u : 0u;
       if (d < (uint32_t)kProbeT) {  // (rare: a true match is a candidate first)
         const uint32_t d64 = (uint32_t)__popc(nv.x ^ hv.x) + (uint32_t)__popc(nv.y ^ hv.y);
 #pragma unroll
@@ -892,14 +960,15 @@ __global__ __launch_bounds__(256) void k_fold_probe(const uint2* __restrict__ ha
     }
   }
 #pragma unroll
-  for (int th = 0; th < 3 * kProbeT; ++th) {
-    uint32_t v = th < kProbeT ? cnt[th % kProbeT] : th < 2 * kProbeT ? cnt64[th % kProbeT] : cnt48[th % kProbeT];
+  for (int th = 0; th < 4 * kProbeT; ++th) {
+    uint32_t v = th < kProbeT ? cnt[th % kProbeT] : th < 2 * kProbeT ? cnt64[th % kProbeT]
+                 : th < 3 * kProbeT ? cnt48[th % kProbeT] : cnt16[th % kProbeT];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
     if ((t & 63u) == 0 && v) atomicAdd(&s_cnt[th], v);
   }
   __syncthreads();
-  if (t < 3 * kProbeT && s_cnt[t]) atomicAdd(&counts[t], s_cnt[t]);
+  if (t < 4 * kProbeT && s_cnt[t]) atomicAdd(&counts[t], s_cnt[t]);
 }
 
 // ---- self-test: the FP4 values and block scales PRE48 multiplies with ----------------------------------------------------
@@ -939,7 +1008,7 @@ uint32_t* probe_slot_get() {
     }
   }
   uint32_t* p = nullptr;
-  if (hipHostMalloc(&p, 3 * kProbeT * sizeof(uint32_t)) != hipSuccess) {
+  if (hipHostMalloc(&p, 4 * kProbeT * sizeof(uint32_t)) != hipSuccess) {
     (void)hipGetLastError();
     return nullptr;
   }
@@ -953,9 +1022,9 @@ void probe_slot_put(uint32_t* p) {
 }  // namespace
 
 bool probe_fold_rates(const uint64_t* d_hashes, size_t n, const uint64_t* d_q, size_t nq, int thresh, hipStream_t stream,
-                      double* r_cand, double* r_true, double* r_cand48) {
+                      double* r_cand, double* r_true, double* r_cand48, double* r_cand16) {
   uint32_t* d_cnt = nullptr;
-  if (cbh::malloc_async((void**)&d_cnt, 3 * kProbeT * sizeof(uint32_t), stream) != hipSuccess) {
+  if (cbh::malloc_async((void**)&d_cnt, 4 * kProbeT * sizeof(uint32_t), stream) != hipSuccess) {
     (void)hipGetLastError();
     return false;
   }
@@ -963,13 +1032,13 @@ bool probe_fold_rates(const uint64_t* d_hashes, size_t n, const uint64_t* d_q, s
   bool ok = h_cnt != nullptr;
   const uint32_t sh = (uint32_t)std::min<size_t>(n, kProbeS), sq = (uint32_t)std::min<size_t>(nq, kProbeS);
   if (ok) {
-    ok = hipMemsetAsync(d_cnt, 0, 3 * kProbeT * sizeof(uint32_t), stream) == hipSuccess;
+    ok = hipMemsetAsync(d_cnt, 0, 4 * kProbeT * sizeof(uint32_t), stream) == hipSuccess;
     if (ok) {
       hipLaunchKernelGGL(k_fold_probe, dim3((sq + 255u) / 256u, (sh + 63u) / 64u), dim3(256), 0, stream,
                          reinterpret_cast<const uint2*>(d_hashes), (uint32_t)n, reinterpret_cast<const uint2*>(d_q),
                          (uint32_t)nq, sh, sq, d_cnt);
       ok = hipGetLastError() == hipSuccess &&
-           hipMemcpyAsync(h_cnt, d_cnt, 3 * kProbeT * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
+           hipMemcpyAsync(h_cnt, d_cnt, 4 * kProbeT * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
            hipStreamSynchronize(stream) == hipSuccess;
     }
   }
@@ -979,6 +1048,7 @@ bool probe_fold_rates(const uint64_t* d_hashes, size_t n, const uint64_t* d_q, s
     *r_cand = (double)h_cnt[thresh - 1] / pairs;
     *r_true = (double)h_cnt[kProbeT + thresh - 1] / pairs;
     *r_cand48 = (double)h_cnt[2 * kProbeT + thresh - 1] / pairs;
+    *r_cand16 = (double)h_cnt[3 * kProbeT + thresh - 1] / pairs;
   } else {
     (void)hipGetLastError();
   }
@@ -999,9 +1069,9 @@ int expand_needles_for_scan(const uint64_t* d_q, size_t nq, hipStream_t stream, 
   if (nq == 0 || nq > CBH_MAX_QUERIES_PER_CALL) return CBH_OK;
   const uint32_t nq_pad = padded_needles(nq);
   uint4* qx = nullptr;
-  // 2 words + the prefilter word, 16 B each, + the PRE48 operands, 3 x 64 x 16 B per 128 needles
-  CBH_HIP(malloc_async((void**)&qx, (size_t)nq_pad * 72u, stream));
-  hipLaunchKernelGGL(k_expand_needles, dim3((3u * nq_pad + nq_pad / 128u * 192u + 255u) / 256u), dim3(256), 0, stream, d_q,
+  // 2 words + the prefilter word, 16 B each, + the PRE48 operands, 3 x 64 x 16 B per 128 needles, + PRE16's, 64 x 16 B
+  CBH_HIP(malloc_async((void**)&qx, (size_t)nq_pad * 80u, stream));
+  hipLaunchKernelGGL(k_expand_needles, dim3((5u * nq_pad + 255u) / 256u), dim3(256), 0, stream, d_q,
                      (uint32_t)nq, nq_pad, qx);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -1015,6 +1085,7 @@ int expand_needles_for_scan(const uint64_t* d_q, size_t nq, hipStream_t stream, 
 int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
                             int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
                             int pre, const ScanOpts& o) {
+  if (pre == 3 && thresh > kPre16MaxThresh) return CBH_E_INVAL;  // (its C0 leaves 2^24 behind)
   const uint32_t n_pairs = (uint32_t)((nq + 63) / 64);
   const uint32_t n_triples = (uint32_t)((nq + 95) / 96);
   const uint32_t nq_pad = padded_needles(nq);
@@ -1025,7 +1096,8 @@ int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, siz
     if (rc) return rc;
     qx = qx_own;
   }
-  const uint4* qf = qx + (pre == 2 ? 3u : 2u) * (size_t)nq_pad;  // the operands of the prefilter that runs
+  // the operands of the prefilter that runs
+  const uint4* qf = qx + (pre == 3 ? 3u * (size_t)nq_pad + nq_pad / 128u * 192u : (pre == 2 ? 3u : 2u) * (size_t)nq_pad);
   const uint32_t rows_per_wg = 32u * (pre == 2 ? kHT48 : kHT) * kWaves;
   // launches that run side by side on this device (the shards of a sharded handle): the workgroups that fill the machine are
   // theirs together -- a shard of 125 000 slots alone cut its needles into chunks of 128 pairs to reach 8192 workgroups and
@@ -1062,7 +1134,7 @@ int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, siz
                      reinterpret_cast<const uint2*>(d_hashes), d_ids, (uint32_t)n, d_q, qx, (uint32_t)nq, n_pairs, ppc, \
                      (uint32_t)thresh, d_rec, (unsigned long long)cap, d_total, (uint32_t)o.keep_id0,                 \
                      reinterpret_cast<const uint2*>(o.d_qmask), qf)
-    if (pre == 2) CBH_MFMA(k_hamm64_mfma48); else if (pre) CBH_MFMA((k_hamm64_mfma<true>)); else CBH_MFMA((k_hamm64_mfma<false>));
+    if (pre == 3) CBH_MFMA(k_hamm64_mfma16); else if (pre == 2) CBH_MFMA(k_hamm64_mfma48); else if (pre) CBH_MFMA((k_hamm64_mfma<true>)); else CBH_MFMA((k_hamm64_mfma<false>));
 #undef CBH_MFMA
   }
   hipError_t e = hipGetLastError();

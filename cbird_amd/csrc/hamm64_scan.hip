@@ -370,10 +370,22 @@ constexpr size_t kMfmaMinN = 4096;
 // random and cannot tell the two apart; the margin leaves threshold 7 where it was (on the prefilter) in both.
 // "scan_pre48": -1 = routed like this, 0 = never, 1 = always for thresholds <= 16 (its bias 32 + t leaves a 6-bit field
 // that much room).  Launches on the fixed rule never take it.
+//
+// The 16-bit prefilter (PRE16: fold16, ONE MFMA per four needle tiles = half of the 32-bit prefilter's matrix work) sits
+// under it.  Its candidates are the pairs whose fold16 distance is < t, at the rate of uniform 16-bit words on unrelated
+// hashes: 1.5e-5 per pair at t = 1, 2.6e-4 at 2, 2.1e-3 at 3 -- the probe counts that rate r16 in the same sample -- and a
+// candidate costs it what it costs the 32-bit prefilter (the events, the drain and the re-check are the same code):
+//   T_16 = 5.85 + 1.3e4 x r16 + 0.7e5 x r_true
+// (6.09 ms per 10^12 pairs at threshold 1 of image hashes, r16 = 1.8e-5, against the 32-bit prefilter's 8.78 on the same
+// box, profiles/r10_lib_ab.json; the issue model 24 M + 4 V gave 6.2 + 0.24).
+// It is taken where T_16 < kPre16Margin x T_pre, at thresholds <= 8 (its bias 24 + t): threshold 1 of unrelated hashes;
+// at 2 the candidates cost 3.4 ms, more than the kernel saves.  "scan_pre16": -1 = routed like this, 0 = never, 1 = always
+// for thresholds <= 8 (larger thresholds are routed as if it were -1).  Launches on the fixed rule never take it.
 constexpr int kPreStatic = 6;
 constexpr double kTrueWeight = 8.0;
 constexpr double kSlopePre = 1.3e4, kBaseFull = 15.75, kTrueFull = 2.7e5, kTruePre = 0.7e5;  // ms per 10^12 pairs
 constexpr double kBasePre = 8.55, kBase48 = 14.0, kSlope48 = 2.8e4, kTrue48 = 1.0e5, kPre48Margin = 0.9;
+constexpr double kBase16 = 5.85, kPre16Margin = 0.9;
 constexpr int kPre48MaxThresh = 16;
 constexpr uint64_t kProbeMinPairs = 1ull << 31;  // ~20 us of scan: below this the probe's round trip is not worth it
 
@@ -381,12 +393,15 @@ int g_scan_mfma = 1;             // "scan_mfma"
 int g_pre_max_thresh = -1;       // "scan_mfma_pre_max"
 int g_pre_rate_max_e9 = 300000;  // "scan_pre_rate_e9"
 int g_pre48 = -1;                // "scan_pre48"
+int g_pre16 = -1;                // "scan_pre16"
 std::atomic<uint64_t> g_pre_mask{0};        // bit t: the most recent matrix-core launch at threshold t took the prefilter
 std::atomic<uint64_t> g_pre48_mask{0};      // bit t: ... took the 48-bit prefilter
+std::atomic<uint64_t> g_pre16_mask{0};      // bit t: ... took the 16-bit prefilter (its bit in g_pre_mask is set too)
 std::atomic<uint64_t> g_n_probe{0};         // probes run
 std::atomic<long long> g_last_rate_e9{-1};  // candidate rate x 1e9 the last probe found for its threshold
 std::atomic<long long> g_last_true_e9{-1};  // ... and the rate of true (64-bit) matches
 std::atomic<long long> g_last_rate48_e9{-1};  // ... and of the 48-bit prefilter's candidates
+std::atomic<long long> g_last_rate16_e9{-1};  // ... and of the 16-bit prefilter's
 
 enum class Join { None, IfCheaper, Forced };
 enum class Kernel { PopcEq, PopcPre, PopcFull, Mfma };
@@ -399,14 +414,19 @@ struct Route {
 // the route of one launch of n slots x nq needles (n, nq >= 1, n <= 0xfffffff0, thresh >= 1)
 Route route(size_t n, size_t nq, int thresh, bool masked) {
   Route r;
-  // (the prefilter at thresholds <= 5, at 6 and at 7 on unrelated hashes; the three-field kernel)
-  r.scan_ms = (double)n * (double)nq * (thresh <= 5 ? 8.7e-12 : thresh == 6 ? 9.7e-12 : thresh == 7 ? 12.1e-12 : 15.8e-12);
+  // (the 16-bit prefilter at threshold 1; the 32-bit one at thresholds <= 5, at 6 and at 7 on unrelated hashes; the
+  // three-field kernel)
+  const double pairs = (double)n * (double)nq;
+  const double pre_ms = pairs * (thresh <= 5 ? 8.7e-12 : thresh == 6 ? 9.7e-12 : thresh == 7 ? 12.1e-12 : 15.8e-12);
+  r.scan_ms = thresh == 1 ? pairs * 6.1e-12 : pre_ms;
   // thresholds <= 8, "scan_mfma" 3: the join when its candidate count says it is cheaper than looking at every pair (only
-  // asked where a scan would take >= 1 ms); 4: whenever it can represent the call (the parity suite).  As shipped (1)
-  // every pair is compared: the join avoids comparisons, it does not make them faster.
+  // asked where a scan on the 32-bit prefilter or the three-field kernel would take >= 1 ms: the bound weighs the call's
+  // size against the fixed cost of the join's count, which a faster scan at threshold 1 did not change -- it keeps its
+  // reach in pairs; what the join then has to beat is scan_ms); 4: whenever it can represent the call (the parity suite).
+  // As shipped (1) every pair is compared: the join avoids comparisons, it does not make them faster.
   const bool joinable = thresh <= kJoinMaxThresh && !masked && n < 0xfffffff0ull;
   r.join = !joinable ? Join::None : g_scan_mfma == 4 ? Join::Forced
-           : g_scan_mfma == 3 && r.scan_ms >= 1.0 ? Join::IfCheaper : Join::None;
+           : g_scan_mfma == 3 && pre_ms >= 1.0 ? Join::IfCheaper : Join::None;
   // "scan_mfma" 2 and 4 force the matrix cores for any size (tests); 3 sizes like 1
   const bool mfma = thresh <= 65 && (g_scan_mfma == 2 || g_scan_mfma == 4 ||
                                      (g_scan_mfma != 0 && nq >= kMfmaMinNq && n >= kMfmaMinN));
@@ -455,23 +475,29 @@ bool scan_routes_to_join(size_t n, size_t nq, int thresh, bool masked) {
 
 int scan_pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
                   hipStream_t stream) {
+  if (g_pre16 == 1 && thresh <= kPre16MaxThresh) return 3;
   if (g_pre48 == 1 && thresh <= kPre48MaxThresh) return 2;
   if (thresh > 32) return 0;  // (the prefilter kernel's flag fields)
   if (g_pre_max_thresh >= 0) return thresh <= g_pre_max_thresh;
   if (thresh > kProbeMaxThresh) return 0;
   if ((uint64_t)n_total * (uint64_t)nq < kProbeMinPairs) return thresh <= kPreStatic;
-  double r_cand = 0, r_true = 0, r48 = 0;
-  if (!probe_fold_rates(d_hashes, n, d_q, nq, thresh, stream, &r_cand, &r_true, &r48)) return thresh <= kPreStatic;
+  double r_cand = 0, r_true = 0, r48 = 0, r16 = 0;
+  if (!probe_fold_rates(d_hashes, n, d_q, nq, thresh, stream, &r_cand, &r_true, &r48, &r16)) return thresh <= kPreStatic;
   g_last_rate_e9 = (long long)(r_cand * 1e9);
   g_last_true_e9 = (long long)(r_true * 1e9);
   g_last_rate48_e9 = (long long)(r48 * 1e9);
+  g_last_rate16_e9 = (long long)(r16 * 1e9);
   g_n_probe++;
   // modelled times relative to the three-field kernel's
   const double d_pre = kSlopePre * (r_cand - kTrueWeight * r_true - (double)g_pre_rate_max_e9 * 1e-9);
   const bool pre = d_pre <= 0;
+  const double t_pre = kBasePre + kSlopePre * r_cand + kTruePre * r_true, t_full = kBaseFull + kTrueFull * r_true;
+  // (the 16-bit prefilter only against the 32-bit one: where that has lost already, fold16's candidates are denser still)
+  if (g_pre16 != 0 && pre && thresh <= kPre16MaxThresh &&
+      kBase16 + kSlopePre * r16 + kTruePre * r_true < kPre16Margin * t_pre)
+    return 3;
   if (g_pre48 != 0) {
     const double t_48 = kBase48 + kSlope48 * r48 + kTrue48 * r_true;
-    const double t_pre = kBasePre + kSlopePre * r_cand + kTruePre * r_true, t_full = kBaseFull + kTrueFull * r_true;
     if (pre ? t_48 < kPre48Margin * t_pre : t_48 < t_full) return 2;
   }
   return pre;
@@ -533,8 +559,11 @@ int scan_nonzero_needles(const uint64_t* d_hashes, const uint32_t* d_ids, size_t
     // sweep -- which it would, 1..8 -- it falls back to pricing ALL of them at 128: the 9 ms launches of thresholds 1..5
     // would read 1.4 x the peak.  Left with the three-field kernel's thresholds, a 14 ms launch reads 0.91 of the peak
     // at 128 flop per pair; it issues 96.  NOTES 18.)
-    if (pre == 1) g_pre_mask |= 1ull << thresh; else g_pre_mask &= ~(1ull << thresh);
+    // (a launch on the 16-bit prefilter DOES set it: outside the mask bench.py would price its 6 ms at 128 flop per pair,
+    // twice the FP4 peak; inside, roofline_pre averages it in at 64 flop per pair where it issues 32.  NOTES 24.)
+    if (pre == 1 || pre == 3) g_pre_mask |= 1ull << thresh; else g_pre_mask &= ~(1ull << thresh);
     if (pre == 2) g_pre48_mask |= 1ull << thresh; else g_pre48_mask &= ~(1ull << thresh);
+    if (pre == 3) g_pre16_mask |= 1ull << thresh; else g_pre16_mask &= ~(1ull << thresh);
   }
   return launch_hamm64_scan_mfma(d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, pre, o);
 }
@@ -557,10 +586,17 @@ void set_scan_pre48(int v) {
   if (v >= -1 && v <= 1) g_pre48 = v;
 }
 long long get_scan_pre_mask() { return (long long)g_pre_mask.load(); }
+int set_scan_pre16(int v) {
+  if (v < -1 || v > 1) return CBH_E_INVAL;
+  g_pre16 = v;
+  return CBH_OK;
+}
 long long get_scan_pre48_mask() { return (long long)g_pre48_mask.load(); }
+long long get_scan_pre16_mask() { return (long long)g_pre16_mask.load(); }
 long long get_scan_probes() { return (long long)g_n_probe.load(); }
 long long get_scan_probe_rate_e9() { return g_last_rate_e9.load(); }
 long long get_scan_probe_true_e9() { return g_last_true_e9.load(); }
 long long get_scan_probe_rate48_e9() { return g_last_rate48_e9.load(); }
+long long get_scan_probe_rate16_e9() { return g_last_rate16_e9.load(); }
 
 }  // namespace cbh

@@ -795,6 +795,11 @@ int cbh_color_find_batch(cbh_color*, const void* needle_descs, size_t nq, int k,
  *                   per launch, where the probe's rates model it faster than the three-field kernel, or than 0.9 x the
  *                   prefilter's time, whichever of the two the launch would otherwise take; 0 = never; 1 = always for
  *                   thresholds <= 16.  Launches too small to probe never take it
+ *   "scan_pre16"    the 16-bit prefilter kernel (the fold lo ^ hi folded once more; ONE MFMA per four needle tiles, half the
+ *                   32-bit prefilter's matrix work, for candidates at the rate of 16-bit words): -1 (default) = per launch,
+ *                   where the probe's rates model it below 0.9 x the 32-bit prefilter's time -- threshold 1 of unrelated
+ *                   hashes; 0 = never; 1 = always for thresholds <= 8 (larger thresholds are routed as with -1).  Other
+ *                   values return CBH_E_INVAL and leave the knob as it was.  Launches too small to probe never take it
  *   "scan256_mfma"  256-bit scan on the matrix cores (k_hamm256_*): 0 = never (k_hamm256_scan), 1 = calls with >= 64 needle
  *                   descriptors and >= 4096 rows (default), 2 = always.  Other values return CBH_E_INVAL and leave the knob
  *                   as it was
@@ -858,11 +863,12 @@ int cbh_set_tuning(const char* key, int value);
  * "arena_oom_retry_stream", "arena_oom_retry_device", "arena_oom_retry_persistent", "arena_released"; "scan_mfma" (the
  * knob's value); "scan_pre_mask"
  * (bit t = the most recent matrix-core launch at threshold t took the prefilter kernel), "scan_pre48_mask" (... took the
- * 48-bit prefilter kernel; a launch sets its bit in at most one of the two), "scan_joins" (calls the bucketed join has answered), "join_needle_preps" (needle sides -- histogram, starts,
+ * 48-bit prefilter kernel; a launch sets its bit in at most one of the two), "scan_pre16_mask" (... took the 16-bit prefilter
+ * kernel; such a launch sets its bit in "scan_pre_mask" as well: it is a fold prefilter), "scan_joins" (calls the bucketed join has answered), "join_needle_preps" (needle sides -- histogram, starts,
  * chunk-ordered copies -- the join has prepared at thresholds 5..8: one per launch, one per device and call on a sharded handle that keeps
  * tables), "join_resident" / "join_resident_mb" (the knobs' values), "scan_probes" (candidate-rate
- * probes run so far), "scan_probe_rate_e9" / "scan_probe_true_e9" / "scan_probe_rate48_e9" (the candidate and true-match rates the last one
- * found for its threshold and the 48-bit prefilter's candidate rate, x 1e9; -1 = none yet); "scan256_mfma", "scan256_small", "color_create_group" (the knobs' values);
+ * probes run so far), "scan_probe_rate_e9" / "scan_probe_true_e9" / "scan_probe_rate48_e9" / "scan_probe_rate16_e9" (the candidate and true-match rates the last one
+ * found for its threshold and the 48-bit and 16-bit prefilters' candidate rates, x 1e9; -1 = none yet); "scan256_mfma", "scan256_small", "color_create_group" (the knobs' values);
  * "color_create_group_last" (the G of the most recent k_cdw_round<G> chunk launch, 0 before any; read-only); "scan256_kernels" (a bit mask of the kernels
  * that 256-bit scan launches have used since it was last cleared -- cbh_set_tuning("scan256_kernels", 0) clears it, any
  * other value written is CBH_E_INVAL; bit 0 k_hamm256_scan, 1 k_hamm256_mfma<6,3,2> (first-128-bit prefilter, one needle

@@ -1,6 +1,7 @@
-"""Prefilter kernel (PRE) and 48-bit prefilter kernel (PRE48) against the three-field 64-bit kernel (FULL3) per threshold
+"""Prefilter kernel (PRE), 48-bit prefilter kernel (PRE48) and 16-bit prefilter kernel (PRE16, thresholds <= 8) against the
+three-field 64-bit kernel (FULL3) per threshold
 on data sets whose candidate rates differ, with the fold-candidate rate of each set beside the times -- what the
-launch-time choice between the three has to reproduce: never slower than the best of them x 1.03.
+launch-time choice between the four has to reproduce: never slower than the best of them x 1.03.
 
   image     the bench's 10^6 image-derived hashes (10 % near-duplicates of earlier images)
   dup10     the same with 10 % of the slots overwritten by exact copies of other slots, in clusters (sizes geometric,
@@ -27,6 +28,7 @@ T = [int(x) for x in (sys.argv[2] if len(sys.argv) > 2 else "3,4,5,6,7,8").split
 SETS = (sys.argv[3] if len(sys.argv) > 3 else "image,dup10,dup50,flat,video").split(",")
 dev = torch.device("cuda", 0)
 N = 1_000_000
+PRE16_MAX_T = 3  # fold16's candidates are 1 % of unrelated pairs at threshold 4 and 40 % at 8: seconds per launch
 
 
 def image_hashes():
@@ -108,11 +110,15 @@ for name in SETS:
     rates = fold_rates(hay, q)
     out = {"n": n, "nq": nq, "fold_rate": {str(t): rates[t] for t in T}, "per_threshold": {}}
     for t in T:
-        cell = {"pre": [], "pre48": [], "full3": [], "auto": []}
+        cell = {"pre": [], "pre48": [], "pre16": [], "full3": [], "auto": []}
         for r in range(R):
-            for kind, knobs in (("pre", {b"scan_mfma_pre_max": 32, b"scan_pre48": 0}), ("pre48", {b"scan_pre48": 1}),
-                                ("full3", {b"scan_mfma_pre_max": 0, b"scan_pre48": 0}),
-                                ("auto", {b"scan_mfma_pre_max": -1, b"scan_pre48": -1})):
+            for kind, knobs in (("pre", {b"scan_mfma_pre_max": 32, b"scan_pre48": 0, b"scan_pre16": 0}),
+                                ("pre48", {b"scan_pre48": 1, b"scan_pre16": 0}),
+                                ("pre16", {b"scan_pre16": 1}),  # (timed at thresholds <= PRE16_MAX_T only)
+                                ("full3", {b"scan_mfma_pre_max": 0, b"scan_pre48": 0, b"scan_pre16": 0}),
+                                ("auto", {b"scan_mfma_pre_max": -1, b"scan_pre48": -1, b"scan_pre16": -1})):
+                if kind == "pre16" and t > PRE16_MAX_T:
+                    continue
                 for k, v in knobs.items():
                     L.cbh_set_tuning(k, v)
                 _lib.check(L.cbh_idx64_time_scan_dev(idx.handle, dq.data_ptr(), nq, t, drec.data_ptr(), cap, dtot.data_ptr(), 2, C.byref(ms)), "t")
@@ -123,6 +129,10 @@ for name in SETS:
                     auto_pre = bool((v.value >> t) & 1)
                     L.cbh_get_tuning(b"scan_pre48_mask", C.byref(v))
                     auto_pre48 = bool((v.value >> t) & 1)
+                    L.cbh_get_tuning(b"scan_pre16_mask", C.byref(v))
+                    auto_pre16 = bool((v.value >> t) & 1)
+                    L.cbh_get_tuning(b"scan_probe_rate16_e9", C.byref(v))
+                    auto_rate16 = v.value / 1e9
                     L.cbh_get_tuning(b"scan_probe_rate48_e9", C.byref(v))
                     auto_rate48 = v.value / 1e9
                     L.cbh_get_tuning(b"scan_probe_rate_e9", C.byref(v))
@@ -130,12 +140,13 @@ for name in SETS:
                     L.cbh_get_tuning(b"scan_probe_true_e9", C.byref(v))
                     auto_true = v.value / 1e9
         L.cbh_set_tuning(b"scan_mfma_pre_max", -1)
-        mins = {k: min(x[0] for x in v) for k, v in cell.items()}
-        tot = {k: sorted({x[1] for x in v}) for k, v in cell.items()}
-        best = min(mins["pre"], mins["pre48"], mins["full3"])
+        mins = {k: min(x[0] for x in v) for k, v in cell.items() if v}
+        tot = {k: sorted({x[1] for x in v}) for k, v in cell.items() if v}
+        best = min(v for k, v in mins.items() if k != "auto")
         out["per_threshold"][str(t)] = {"ms": mins, "records": tot["full3"], "totals_agree": len({tuple(v) for v in tot.values()}) == 1,
                                         "auto_over_best": round(mins["auto"] / best, 3), "pairs_1e12": n * nq / 1e12,
-                                        "auto_kernel": "pre48" if auto_pre48 else "pre" if auto_pre else "full3", "library_probe_rate": auto_rate,
+                                        "auto_kernel": "pre16" if auto_pre16 else "pre48" if auto_pre48 else "pre" if auto_pre else "full3",
+                                        "library_probe_rate": auto_rate, "library_probe_rate16": auto_rate16,
                                         "library_probe_true_rate": auto_true, "library_probe_rate48": auto_rate48}
     res[name] = out
     print(json.dumps({name: out}), flush=True)
