@@ -62,6 +62,12 @@ class cbh_vmatch(C.Structure):
                 ("len", C.c_int32)]
 
 
+class cbh_quality_detail(C.Structure):
+    _fields_ = [("h_sum", C.c_uint64), ("v_sum", C.c_uint64), ("h_mean", C.c_float), ("v_mean", C.c_float),
+                ("h_long", C.c_int32), ("v_long", C.c_int32), ("num_edges", C.c_int32), ("qw", C.c_int32),
+                ("qh", C.c_int32), ("score", C.c_int32)]
+
+
 class cbh_match(C.Structure):
     _fields_ = [("id", C.c_uint32), ("score", C.c_int32)]
 
@@ -87,6 +93,9 @@ _SIGS = {
     "cbh_color_ellipse_mask": (C.c_int, [C.c_int, C.c_int, _vp]),
     "cbh_color_descriptors": (C.c_int, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int]),
     "cbh_color_descriptors_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]),
+    "cbh_quality_dims": (None, [C.c_int, C.c_int, _vp, _vp]),
+    "cbh_quality_scores": (C.c_int, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int]),
+    "cbh_quality_scores_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "cbh_index_images": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, C.c_int]),
     "cbh_index_images_views": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,

@@ -9,6 +9,7 @@
 //   void Media::makeVideoIndex(VideoContext&, int threshold, VideoIndex&, const std::function<void(int)>&) const
 //                                                                                                  src/media.cpp:925-1037
 //   the scoring block of TemplateMatcher::match (mask, two dctHash64, hamm64)                     src/templatematcher.cpp:331-371
+//   int qualityScore(const Media&, QVector<QImage>* visuals = nullptr)   (decoded images, one or a group)   src/cimgops.cpp:313-596
 //
 // Same arguments and effects as the originals for 8-bit single-channel images (what Scanner::processImage passes
 // after grayscale(), src/scanner.cpp:859,876-889): the hash is returned, and with inPlace = true the blurred pixels
@@ -283,6 +284,52 @@ inline int gpuTemplateScore(const cv::Mat& img, const cv::Mat& tmplImg, uint64_t
   if (rc != CBH_OK) qFatal("gpuTemplateScore: cbh_template_scores failed");
   if (candHash) *candHash = ch;
   if (tmplHash) *tmplHash = th;
+  return score;
+}
+
+// qualityScore(const Media&) (src/cimgops.cpp:313-596) for images that are already decoded: 8-bit cv::Mat of 1, 3 (BGR)
+// or 4 (BGRA) channels, the layout loadImage / qImageToCvImg give.  Only the red channel takes part, as in the
+// reference (its crop keeps channel 0 of qImageToCImg's planes).  INT32_MIN = no score (no edges at all, or a side of 1,
+// where the reference's behaviour is undefined).  The visuals of the original are cbh_quality_scores_dev's planes.
+// One group per call: what qualityScoreAction (src/gui/mediagrouplistwidget.cpp:1433-1441) would call once per group
+// instead of once per member; images of different channel counts go in separate calls to the library.
+inline void gpuQualityScores(const std::vector<cv::Mat>& images, std::vector<int>& scores) {
+  scores.assign(images.size(), 0);
+  for (int cn : {1, 3, 4}) {
+    std::vector<size_t> which;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> w, h, step;
+    std::vector<uint8_t> buf;
+    for (size_t i = 0; i < images.size(); ++i) {
+      const cv::Mat& m = images[i];
+      if (m.rows <= 0 || m.cols <= 0 || (m.type() != CV_8UC1 && m.type() != CV_8UC3 && m.type() != CV_8UC4))
+        qFatal("gpuQualityScores: expected non-empty 8-bit images of 1, 3 or 4 channels");
+      if (m.channels() != cn) continue;
+      const size_t row = size_t(m.cols) * size_t(cn);
+      off.push_back((buf.size() + 15) / 16 * 16);
+      buf.resize(size_t(off.back()) + row * size_t(m.rows));
+      for (int y = 0; y < m.rows; ++y) memcpy(buf.data() + off.back() + size_t(y) * row, m.ptr<uint8_t>(y), row);
+      which.push_back(i), w.push_back(uint32_t(m.cols)), h.push_back(uint32_t(m.rows)), step.push_back(uint32_t(row));
+    }
+    if (which.empty()) continue;
+    std::vector<int32_t> out(which.size());
+    const int rc = cbh_quality_scores(buf.data(), buf.size(), which.size(), off.data(), w.data(), h.data(), step.data(), cn,
+                                      out.data(), nullptr, hashDevice());
+    if (rc) qFatal("gpuQualityScores: %s (%s)", cbh_strerror(rc), cbh_last_error());
+    for (size_t k = 0; k < which.size(); ++k) scores[which[k]] = out[k];
+  }
+}
+
+// one image, read where it lies (rows may be padded; a view's rows are read from its parent)
+inline int gpuQualityScore(const cv::Mat& img) {
+  if (img.rows <= 0 || img.cols <= 0 || (img.type() != CV_8UC1 && img.type() != CV_8UC3 && img.type() != CV_8UC4))
+    qFatal("gpuQualityScore: expected a non-empty 8-bit image of 1, 3 or 4 channels");
+  const uint64_t off = 0;
+  const uint32_t w = uint32_t(img.cols), h = uint32_t(img.rows), step = uint32_t(img.step);
+  int32_t score = 0;
+  const int rc = cbh_quality_scores(img.data, size_t(h - 1) * step + size_t(w) * size_t(img.channels()), 1, &off, &w, &h,
+                                    &step, img.channels(), &score, nullptr, hashDevice());
+  if (rc) qFatal("gpuQualityScore: %s (%s)", cbh_strerror(rc), cbh_last_error());
   return score;
 }
 

@@ -317,6 +317,9 @@ void set_cd_chunk_mb(int v);       // colordesc_create.hip "color_create_chunk_m
 int set_cd_group(int v);           // colordesc_create.hip "color_create_group": images per wave of k_cdw_round, 0 (by size) / 1 / 2 / 4 / 8 / 16 / 21; else CBH_E_INVAL, knob unchanged
 int get_cd_group();
 int get_cd_group_last();           // "color_create_group_last": images per wave of the most recent chunk launch (0 = none yet)
+void set_quality_chunk_mb(int v);  // quality.hip "quality_chunk_mb": MB one upload / one group's working planes may take
+int get_quality_chunk_mb();
+int get_quality_strip_rows();      // "quality_strip_rows": rows one thread of the quality kernels walks
 void set_color_fma(int on);        // color.hip "color_fma": fused squares in k_color_dist3 (default off: not bit-identical)
 
 // ---- records.hip ----------------------------------------------------------------------

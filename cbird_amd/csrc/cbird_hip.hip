@@ -1378,6 +1378,7 @@ int cbh_set_tuning(const char* key, int value) {
       {"kp_blur_side", [](int v) { set_kp_blur_side(v); }},
       {"color_fma", [](int v) { set_color_fma(v); }},
       {"color_create_chunk_mb", [](int v) { set_cd_chunk_mb(v); }},
+      {"quality_chunk_mb", [](int v) { set_quality_chunk_mb(v); }},
       {"fdct_host_vote", [](int v) { g_fdct_host_vote = v; }},
       {"video_host_reduce", [](int v) { g_video_host_reduce = v; }},
       {"orb_retain_order", [](int v) { set_orb_retain_order(v); }},
@@ -1427,6 +1428,8 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strcmp(key, "scan256_kernels")) return *value = get_scan256_kernels(), CBH_OK;
   if (!strcmp(key, "color_create_group")) return *value = get_cd_group(), CBH_OK;
   if (!strcmp(key, "color_create_group_last")) return *value = get_cd_group_last(), CBH_OK;
+  if (!strcmp(key, "quality_chunk_mb")) return *value = get_quality_chunk_mb(), CBH_OK;
+  if (!strcmp(key, "quality_strip_rows")) return *value = get_quality_strip_rows(), CBH_OK;
   if (!strcmp(key, "scan_probes")) return *value = get_scan_probes(), CBH_OK;
   if (!strcmp(key, "scan_joins")) return *value = get_scan_joins(), CBH_OK;
   if (!strcmp(key, "join_needle_preps")) return *value = get_join_needle_preps(), CBH_OK;

@@ -205,6 +205,39 @@ int cbh_color_descriptors_dev(const void* d_imgs, size_t n, const uint64_t* img_
                               const uint32_t* img_h, const uint32_t* img_row_stride, int channels, void* d_descs,
                               void* d_ok, int device, void* stream);
 
+/* ---- qualityScore(const Media&) (src/cimgops.cpp:313-596) for a ragged batch of 8-bit images -------------------
+ * The no-reference score the result browser shows per group member (src/gui/mediagrouplistwidget.cpp:1433-1441).
+ * Images in cv::Mat order, channels 1 (the byte itself), 3 (BGR) or 4 (BGRA, alpha ignored): only the RED channel
+ * takes part -- src.crop(.., 0, 0, .., 0, 0) keeps channel 0 of qImageToCImg's r, g, b planes (:335, :154-167) and
+ * get_norm(1) of one channel is its absolute value (:344).  The crop hCrop = int(w * 0.10), vCrop = int(h * 0.10) is
+ * inclusive: the working plane is (w - 2 hCrop + 1) x (h - 2 vCrop + 1), and with a crop of 0 its last column / row
+ * lies outside the image and is 0 (:332-335).  hd = |p(x-1) - p(x+1)| inside each row (makeDiff, :37-60),
+ * hMean = float(double(sum hd) / ((qw-1) * (qh-1))) (filterHorizontalMT, :252), hE = the local maxima along x of
+ * hd > uint8(hMean) ? hd : 0 (makeEdge, :88-121); vd, vMean, vE the same along y.  h_long = runs of hE along y,
+ * v_long = runs of vE along x, counted where a zero ends a run longer than 1 at positions 3 .. L-2 of the line
+ * (longEdgeCount on the transposed maps, :131-152, :264-270); num_edges = set pixels of hE | vE inside
+ * [1, qw-2] x [1, qh-2] (:456-464).  score = int(100 * er + 100 * elr) in float, er = float(num_edges) /
+ * ((qw-2) * (qh-2)), elr = float(v_long + h_long) / num_edges (:495, :500, :592).
+ * INT32_MIN = no score: num_edges == 0 (the reference converts NaN), or a working plane below 3 x 3 (a source side of
+ * 1: the reference overruns its buffers, :337); the detail record of the latter is all zero.  A mean above 255 (only
+ * working planes three rows or columns high can reach one) keeps the low byte of its integer part. */
+void cbh_quality_dims(int w, int h, int* qw, int* qh);   /* working size after the crop; 0 x 0 when below 3 x 3 */
+typedef struct cbh_quality_detail {
+  uint64_t h_sum, v_sum; float h_mean, v_mean;
+  int32_t h_long, v_long, num_edges, qw, qh, score;
+} cbh_quality_detail;
+/* images in host memory, uploaded in pieces of at most "quality_chunk_mb" (cbh_set_tuning) */
+int cbh_quality_scores(const uint8_t* imgs, size_t imgs_bytes, size_t n, const uint64_t* img_off, const uint32_t* img_w,
+                       const uint32_t* img_h, const uint32_t* img_row_stride, int channels, int32_t* scores,
+                       cbh_quality_detail* detail /* NULL or n */, int device);
+/* images and outputs in device memory (the size arrays stay on the host).  d_planes: NULL, or per image at plane_off[i]
+ * three packed qw x qh byte planes -- hE | vE (0 / 255), hd, vd: the images qualityScore hands to addVisual (:430-432),
+ * before its normalisation.  Returns when the scores are complete (it synchronises the stream). */
+int cbh_quality_scores_dev(const void* d_imgs, size_t n, const uint64_t* img_off, const uint32_t* img_w,
+                           const uint32_t* img_h, const uint32_t* img_row_stride, int channels, void* d_scores,
+                           void* d_detail /* NULL or n */, void* d_planes /* NULL or see above */,
+                           const uint64_t* plane_off /* n, with d_planes */, int device, void* stream);
+
 /* ---- the steps in front of dctHash64 in Scanner::processImage (src/scanner.cpp:852-862) -------------------
  * grayscale(): cv::cvtColor(BGR2GRAY/BGRA2GRAY) on 8-bit data (src/cvutil.cpp:1265-1283); d_gray is packed
  * n*w*h bytes. */
@@ -834,6 +867,8 @@ int cbh_color_find_batch(cbh_color*, const void* needle_descs, size_t nq, int k,
  * Memory:
  *   "color_create_chunk_mb" scratch one launch of ColorDescriptor::create may take, in MB (default 32768): larger batches
  *                   are worked off in chunks of that many images (1.6 MB per 256 x 192 image)
+ *   "quality_chunk_mb" what one upload of cbh_quality_scores, and the working planes of one group of launches of
+ *                   cbh_quality_scores_dev, may take, in MB (default 1024; at least one image each)
  *   "pool_keep_mb"  cached scratch that may outlive its stream, per device, in MB (default 16384; < 0: everything)
  *   "pool_live_keep_mb" what the cache of a LIVE stream may hold, in MB (0 = default: a quarter of the device's memory, at
  *                   least 16384; < 0: everything).  Beyond it the blocks freed longest ago go back to the driver once the
@@ -876,7 +911,8 @@ int cbh_set_tuning(const char* key, int value);
  * a sharded handle notes one launch per shard, a buffer that had to grow one per attempt); "slices_on_device" (the
  * cbh_idx256_slice and cbh_color_slice calls so far that succeeded on the device route, the one that
  * runs the kernels of slice.hip; a call that had nothing to move -- an empty list, an empty index, nothing kept --
- * counts too, although it launches none of them). */
+ * counts too, although it launches none of them); "quality_chunk_mb" (the knob's value); "quality_strip_rows" (rows of
+ * the working plane one thread of the quality kernels walks: their strips start at every multiple of it; read-only). */
 int cbh_get_tuning(const char* key, long long* value);
 
 /* ---- measurement support ---------------------------------------------------------------- */
