@@ -119,6 +119,14 @@ static inline hipError_t gated_host_malloc(T** p, size_t bytes, unsigned flags =
 struct JoinCache;    // the resident slot tables of one index, below (hamm64_join.hip)
 struct JoinTables;
 struct JoinNeedles;
+// Which matrix-core kernel takes a launch (hamm64_mfma.hip), and the largest threshold each can take: the prefilters keep a
+// biased distance in a 6-bit field (Pre32: bias 16 + t - 1 against 32 bits; Pre48: 8 + t, which leaves that much room;
+// Pre16: 24 + t - 1 has to stay under 32), Full is the three-field kernel up to 64 and the two-field one at 65.
+// The values are what "scan_pre16" / "scan_pre48" and recorded profiles mean by them.
+enum class ScanVariant : int { Auto = -1, Full = 0, Pre32 = 1, Pre48 = 2, Pre16 = 3 };
+constexpr int max_thresh(ScanVariant v) {
+  return v == ScanVariant::Pre32 ? 32 : v == ScanVariant::Pre48 ? 16 : v == ScanVariant::Pre16 ? 8 : 65;
+}
 // What a caller says about a search besides its shape.
 struct ScanOpts {
   bool keep_id0 = false;              // also emit slots whose id is 0 (DctFeaturesIndex top-10 cut)
@@ -131,8 +139,7 @@ struct ScanOpts {
   // pass of its own (k_zero_needle_scan)
   bool zero_needles = false;
   // a call made of several launches against the same needles (the shards of a sharded handle):
-  int pre = -1;                       // the kernel choice made once for the whole call (scan_pick_pre: 0 none, 1 the 32-bit
-                                      // prefilter, 2 the 48-bit one, 3 the 16-bit one); -1: the launch's own
+  ScanVariant pre = ScanVariant::Auto;  // the kernel choice made once for the whole call (scan_pick_pre); Auto: the launch's own
   unsigned siblings = 1;              // launches running side by side on this device
   const uint4* qx = nullptr;          // the needles expanded once on this device (expand_needles_for_scan)
   // the bucketed join (hamm64_join.hip): the resident slot tables of the handle whose slots these are, and the slot in
@@ -152,8 +159,17 @@ int launch_hamm64_scan(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n
 // For a call made of several launches: would a launch of n slots run the matrix-core scan; and the prefilter choice for
 // the whole call, probed on one launch's n slots of the call's n_total (ScanOpts::pre)
 bool scan_takes_mfma(size_t n, size_t nq, int thresh);
-int scan_pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
-                  hipStream_t stream);
+ScanVariant scan_pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
+                          hipStream_t stream);
+// Needles (pairs, triples) per blockIdx.y chunk of a scan launch that has `wgs` workgroups per chunk: halved (rounding up)
+// from the start value `c` while above `floor` and the launch has fewer than 8192 workgroups -- enough to fill 256 CUs several times
+// over, while each workgroup still amortises its tile load over `floor` items; then at most 65535 chunks, in whole
+// `multiple`s
+inline uint32_t scan_chunk(uint64_t wgs, size_t items, uint32_t c, uint32_t floor, uint32_t multiple) {
+  while (c > floor && wgs * ((items + c - 1) / c) < 8192) c = (c + 1) / 2;
+  if ((items + c - 1) / c > 65535) c = (uint32_t)(((items + 65534) / 65535 + multiple - 1) / multiple) * multiple;
+  return c;
+}
 // the knobs and read-backs behind cbh_set_tuning / cbh_get_tuning (include/cbird_hip.h documents each)
 int set_scan_mfma(int mode);  // 0..4; CBH_E_INVAL (knob unchanged) for anything else
 int get_scan_mfma();
@@ -189,12 +205,10 @@ int launch_find_one(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, u
 int wait_find_one(const LoneBlock* h_block, unsigned long long seq, hipStream_t stream);
 
 // ---- hamm64_mfma.hip: the same scan on the matrix cores (FP4 sign dot products) --------
-// pre: 1 the prefilter kernel (thresholds <= 32), 2 the 48-bit prefilter (<= 16), 3 the 16-bit prefilter
-// (<= kPre16MaxThresh, CBH_E_INVAL beyond), 0 the three-field kernel (<= 64) or the two-field one (65)
-constexpr int kPre16MaxThresh = 8;
+// variant: never Auto; CBH_E_INVAL for a threshold beyond max_thresh(variant)
 int launch_hamm64_scan_mfma(const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
                             int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
-                            int pre, const ScanOpts& opts);
+                            ScanVariant variant, const ScanOpts& opts);
 // the needles of a call in the matrix-core kernels' operand layout, made ONCE for several launches against the same needles
 // on one device (the shards of a sharded handle): *qx = malloc_async on `stream`, to be handed to every launch as
 // ScanOpts::qx (launches on other streams wait for an event of `stream`) and given back with free_async once they have

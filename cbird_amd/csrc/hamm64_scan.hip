@@ -386,7 +386,6 @@ constexpr double kTrueWeight = 8.0;
 constexpr double kSlopePre = 1.3e4, kBaseFull = 15.75, kTrueFull = 2.7e5, kTruePre = 0.7e5;  // ms per 10^12 pairs
 constexpr double kBasePre = 8.55, kBase48 = 14.0, kSlope48 = 2.8e4, kTrue48 = 1.0e5, kPre48Margin = 0.9;
 constexpr double kBase16 = 5.85, kPre16Margin = 0.9;
-constexpr int kPre48MaxThresh = 16;
 constexpr uint64_t kProbeMinPairs = 1ull << 31;  // ~20 us of scan: below this the probe's round trip is not worth it
 
 int g_scan_mfma = 1;             // "scan_mfma"
@@ -394,9 +393,7 @@ int g_pre_max_thresh = -1;       // "scan_mfma_pre_max"
 int g_pre_rate_max_e9 = 300000;  // "scan_pre_rate_e9"
 int g_pre48 = -1;                // "scan_pre48"
 int g_pre16 = -1;                // "scan_pre16"
-std::atomic<uint64_t> g_pre_mask{0};        // bit t: the most recent matrix-core launch at threshold t took the prefilter
-std::atomic<uint64_t> g_pre48_mask{0};      // bit t: ... took the 48-bit prefilter
-std::atomic<uint64_t> g_pre16_mask{0};      // bit t: ... took the 16-bit prefilter (its bit in g_pre_mask is set too)
+std::atomic<uint64_t> g_variant_mask[4];    // by ScanVariant; bit t: the most recent matrix-core launch at threshold t took it
 std::atomic<uint64_t> g_n_probe{0};         // probes run
 std::atomic<long long> g_last_rate_e9{-1};  // candidate rate x 1e9 the last probe found for its threshold
 std::atomic<long long> g_last_true_e9{-1};  // ... and the rate of true (64-bit) matches
@@ -434,6 +431,19 @@ Route route(size_t n, size_t nq, int thresh, bool masked) {
   return r;
 }
 
+// which variant the launch at `thresh` took, behind the read-backs "scan_pre_mask" / "scan_pre48_mask" / "scan_pre16_mask".
+// "scan_pre_mask" (get_scan_pre_mask) is the launches on the 32-bit prefilter OR those on the 16-bit one, and NOT those on
+// the 48-bit one: bench.py prices the thresholds of that mask at the 32-bit prefilter's 64 flop per pair and the rest at
+// 128.  With the 48-bit prefilter's launches in it the mask would cover every threshold of the sweep, 1..8, and bench.py
+// then falls back to pricing ALL of them at 128: the 9 ms launches of thresholds 1..5 would read 1.4 x the peak.  Left
+// with the three-field kernel's thresholds, a 14 ms launch reads 0.91 of the peak at 128 flop per pair; it issues 96
+// (NOTES 18).  Without the 16-bit prefilter's launches bench.py would price their 6 ms at 128 flop per pair, twice the
+// FP4 peak; inside, roofline_pre averages them in at 64 flop per pair where they issue 32 (NOTES 24).
+void note_variant(int thresh, ScanVariant v) {
+  for (int i = 1; i < 4; ++i)  // (Full keeps none)
+    if (i == (int)v) g_variant_mask[i] |= 1ull << thresh; else g_variant_mask[i] &= ~(1ull << thresh);
+}
+
 int launch_popc(Kernel kernel, const uint64_t* d_hashes, const uint32_t* d_ids, size_t n, const uint64_t* d_q, size_t nq,
                 int thresh, cbh_record* d_rec, size_t cap, unsigned long long* d_total, hipStream_t stream,
                 const ScanOpts& o) {
@@ -441,15 +451,8 @@ int launch_popc(Kernel kernel, const uint64_t* d_hashes, const uint32_t* d_ids, 
   const uint32_t tiles = (uint32_t)((n + tile - 1) / tile);
   // needle chunk: enough workgroups to fill 256 CUs x 8 waves/SIMD several times over, but each
   // workgroup amortises its 16 KB tile load over >= 1024 needles when there are that many.
-  uint32_t q_chunk = 16384;
-  while (q_chunk > 1024 && (uint64_t)tiles * ((nq + q_chunk - 1) / q_chunk) < 8192) q_chunk >>= 1;
-  uint32_t chunks = (uint32_t)((nq + q_chunk - 1) / q_chunk);
-  if (chunks > 65535) {
-    q_chunk = (uint32_t)((nq + 65534) / 65535);
-    q_chunk = (q_chunk + kQB - 1) / kQB * kQB;
-    chunks = (uint32_t)((nq + q_chunk - 1) / q_chunk);
-  }
-  dim3 grid(tiles, chunks), block(kThreads);
+  const uint32_t q_chunk = scan_chunk(tiles, nq, 16384, 1024, kQB);
+  dim3 grid(tiles, (uint32_t)((nq + q_chunk - 1) / q_chunk)), block(kThreads);
   const uint2* hay = reinterpret_cast<const uint2*>(d_hashes);
 #define CBH_SCAN(MODE)                                                                                                  \
   hipLaunchKernelGGL((k_hamm64_scan<kH, kQB, MODE>), grid, block, 0, stream, hay, d_ids, (uint32_t)n, d_q, (uint32_t)nq, \
@@ -473,16 +476,18 @@ bool scan_routes_to_join(size_t n, size_t nq, int thresh, bool masked) {
   return thresh >= 1 && n >= 1 && nq >= 1 && route(n, nq, thresh, masked).join != Join::None;
 }
 
-int scan_pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
-                  hipStream_t stream) {
-  if (g_pre16 == 1 && thresh <= kPre16MaxThresh) return 3;
-  if (g_pre48 == 1 && thresh <= kPre48MaxThresh) return 2;
-  if (thresh > 32) return 0;  // (the prefilter kernel's flag fields)
-  if (g_pre_max_thresh >= 0) return thresh <= g_pre_max_thresh;
-  if (thresh > kProbeMaxThresh) return 0;
-  if ((uint64_t)n_total * (uint64_t)nq < kProbeMinPairs) return thresh <= kPreStatic;
+ScanVariant scan_pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint64_t* d_q, size_t nq, int thresh,
+                          hipStream_t stream) {
+  using V = ScanVariant;
+  if (g_pre16 == 1 && thresh <= max_thresh(V::Pre16)) return V::Pre16;
+  if (g_pre48 == 1 && thresh <= max_thresh(V::Pre48)) return V::Pre48;
+  if (thresh > max_thresh(V::Pre32)) return V::Full;
+  if (g_pre_max_thresh >= 0) return thresh <= g_pre_max_thresh ? V::Pre32 : V::Full;
+  if (thresh > kProbeMaxThresh) return V::Full;
   double r_cand = 0, r_true = 0, r48 = 0, r16 = 0;
-  if (!probe_fold_rates(d_hashes, n, d_q, nq, thresh, stream, &r_cand, &r_true, &r48, &r16)) return thresh <= kPreStatic;
+  if ((uint64_t)n_total * (uint64_t)nq < kProbeMinPairs ||
+      !probe_fold_rates(d_hashes, n, d_q, nq, thresh, stream, &r_cand, &r_true, &r48, &r16))
+    return thresh <= kPreStatic ? V::Pre32 : V::Full;  // the fixed rule
   g_last_rate_e9 = (long long)(r_cand * 1e9);
   g_last_true_e9 = (long long)(r_true * 1e9);
   g_last_rate48_e9 = (long long)(r48 * 1e9);
@@ -493,14 +498,14 @@ int scan_pick_pre(const uint64_t* d_hashes, size_t n, size_t n_total, const uint
   const bool pre = d_pre <= 0;
   const double t_pre = kBasePre + kSlopePre * r_cand + kTruePre * r_true, t_full = kBaseFull + kTrueFull * r_true;
   // (the 16-bit prefilter only against the 32-bit one: where that has lost already, fold16's candidates are denser still)
-  if (g_pre16 != 0 && pre && thresh <= kPre16MaxThresh &&
+  if (g_pre16 != 0 && pre && thresh <= max_thresh(V::Pre16) &&
       kBase16 + kSlopePre * r16 + kTruePre * r_true < kPre16Margin * t_pre)
-    return 3;
+    return V::Pre16;
   if (g_pre48 != 0) {
     const double t_48 = kBase48 + kSlope48 * r48 + kTrue48 * r_true;
-    if (pre ? t_48 < kPre48Margin * t_pre : t_48 < t_full) return 2;
+    if (pre ? t_48 < kPre48Margin * t_pre : t_48 < t_full) return V::Pre48;
   }
-  return pre;
+  return pre ? V::Pre32 : V::Full;
 }
 
 namespace {
@@ -552,20 +557,9 @@ int scan_nonzero_needles(const uint64_t* d_hashes, const uint32_t* d_ids, size_t
     if (rc == CBH_E_NOMEM) cbh_clear_error();
   }
   if (r.kernel != Kernel::Mfma) return launch_popc(r.kernel, d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, o);
-  const int pre = o.pre >= 0 ? o.pre : scan_pick_pre(d_hashes, n, n, d_q, nq, thresh, stream);
-  if (thresh < 64) {
-    // (a launch on the 48-bit prefilter does NOT set its bit in "scan_pre_mask": bench.py prices the thresholds of that
-    // mask at the 32-bit prefilter's 64 flop per pair and the rest at 128, and when the mask covers every threshold of its
-    // sweep -- which it would, 1..8 -- it falls back to pricing ALL of them at 128: the 9 ms launches of thresholds 1..5
-    // would read 1.4 x the peak.  Left with the three-field kernel's thresholds, a 14 ms launch reads 0.91 of the peak
-    // at 128 flop per pair; it issues 96.  NOTES 18.)
-    // (a launch on the 16-bit prefilter DOES set it: outside the mask bench.py would price its 6 ms at 128 flop per pair,
-    // twice the FP4 peak; inside, roofline_pre averages it in at 64 flop per pair where it issues 32.  NOTES 24.)
-    if (pre == 1 || pre == 3) g_pre_mask |= 1ull << thresh; else g_pre_mask &= ~(1ull << thresh);
-    if (pre == 2) g_pre48_mask |= 1ull << thresh; else g_pre48_mask &= ~(1ull << thresh);
-    if (pre == 3) g_pre16_mask |= 1ull << thresh; else g_pre16_mask &= ~(1ull << thresh);
-  }
-  return launch_hamm64_scan_mfma(d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, pre, o);
+  const ScanVariant v = o.pre != ScanVariant::Auto ? o.pre : scan_pick_pre(d_hashes, n, n, d_q, nq, thresh, stream);
+  if (thresh < 64) note_variant(thresh, v);
+  return launch_hamm64_scan_mfma(d_hashes, d_ids, n, d_q, nq, thresh, d_rec, cap, d_total, stream, v, o);
 }
 
 }  // namespace
@@ -577,7 +571,7 @@ int set_scan_mfma(int mode) {
 }
 int get_scan_mfma() { return g_scan_mfma; }
 void set_scan_pre_max(int t) {
-  if (t >= -1 && t <= 32) g_pre_max_thresh = t;
+  if (t >= -1 && t <= max_thresh(ScanVariant::Pre32)) g_pre_max_thresh = t;
 }
 void set_scan_pre_rate(int e9) {
   if (e9 >= 0) g_pre_rate_max_e9 = e9;
@@ -585,14 +579,14 @@ void set_scan_pre_rate(int e9) {
 void set_scan_pre48(int v) {
   if (v >= -1 && v <= 1) g_pre48 = v;
 }
-long long get_scan_pre_mask() { return (long long)g_pre_mask.load(); }
+long long get_scan_pre_mask() { return (long long)(g_variant_mask[(int)ScanVariant::Pre32] | g_variant_mask[(int)ScanVariant::Pre16]); }
 int set_scan_pre16(int v) {
   if (v < -1 || v > 1) return CBH_E_INVAL;
   g_pre16 = v;
   return CBH_OK;
 }
-long long get_scan_pre48_mask() { return (long long)g_pre48_mask.load(); }
-long long get_scan_pre16_mask() { return (long long)g_pre16_mask.load(); }
+long long get_scan_pre48_mask() { return (long long)g_variant_mask[(int)ScanVariant::Pre48].load(); }
+long long get_scan_pre16_mask() { return (long long)g_variant_mask[(int)ScanVariant::Pre16].load(); }
 long long get_scan_probes() { return (long long)g_n_probe.load(); }
 long long get_scan_probe_rate_e9() { return g_last_rate_e9.load(); }
 long long get_scan_probe_true_e9() { return g_last_true_e9.load(); }

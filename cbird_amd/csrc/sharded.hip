@@ -394,7 +394,7 @@ int plan_scan(ScanCall& K) {
   K.timed = K.nq >= 256;
   // prefilter or three-field kernel: one probe for the whole call, on the slots of a shard that lives where the needles
   // are (every shard probing for itself cost a stream synchronisation per shard and threshold); and ONE expansion of the
-  // needles into the matrix-core operand layout for all the shards of the root device (72 bytes per needle)
+  // needles into the matrix-core operand layout for all the shards of the root device (80 bytes per padded needle)
   K.opts.siblings = (unsigned)K.C.per_device;
   // the bucketed join at thresholds 5..8 on shards that keep their slot tables: ONE needle side (histogram, starts, the
   // chunk-ordered copies) for all the shards of the root device, which then run their jobs kernel and their joins only.

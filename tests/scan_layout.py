@@ -5,20 +5,25 @@ Plain numpy, no GPU and nothing from cbird_amd: the model restates the kernels' 
 many descriptors, records and queue entries a launch needs where); it never decides what the right answer is -- that is
 reference_records(), every pair compared on all 64 bits.
 
-Layout (line numbers of hamm64_mfma.hip):
-  * wave W = 4 b + w of workgroup b owns slots [256 W, 256 W + 256): kHT = 8 tiles of 32 rows (:72, :283); group k of a
-    step is tiles 2k, 2k+1 (kG = 2, :73, :380); slots past n are hash 0 (:294), and a wave with no slot < n exits (:284);
+Layout (names of hamm64_mfma.hip):
+  * wave W = 4 b + w of workgroup b owns slots [256 W, 256 W + 256): kHT = 8 tiles of 32 rows (`tile0` of each kernel);
+    group k of a step is tiles 2k, 2k+1 (kG = 2); slots past n are hash 0, and a wave with no slot < n exits
+    (prefilter_body, load_hay_words);
   * MFMA C/D layout: lane L holds needle column c = L & 31, half = L >> 5, and register g (0..15) of a tile is slot row
-    (g & 3) + 8 (g >> 2) + 4 half of the tile (:174-175, :345); register r of a group = 16 t + g for its tile t (:426);
-  * PRE (k_hamm64_mfma<true>): a step is two needle pairs, 128 needles from 64 p; field f of a register is needle
-    64 p + 32 f + c (:300-304, :355), and a step whose second pair does not exist takes the first again (:506-508, :518);
-    needles past nq are hash 0 (:98).  A register is flagged when any field has popc(fold(slot) ^ fold(needle)) < thresh,
-    fold(x) = lo32 ^ hi32 (:32-34); a flagged top field makes all four fields candidates (:347-349);
-  * FULL3 (k_hamm64_mfma3): a triple is 96 needles, field f = needle 96 p + 32 f + c (:599), flagged per field on the full
-    64 bits; the per-tile queue takes one field at a time, <= 16 registers x 64 lanes (:577-592, :623);
-  * FULL2 (threshold 65): pair p = needles 64 p + 32 f + c, two entries per register, <= 2048 per tile (:190-206, :77).
-Prefilter bookkeeping (:246-253, :334-372, :432-502): a group whose flags sit in ONE lane lists that lane's flagged
-registers (<= 32 descriptors) and does not drain; several hit lanes are parked kParkLanes = 16 at a time, each listing
+    (g & 3) + 8 (g >> 2) + 4 half of the tile (cd_row); register r of a group = 16 t + g for its tile t;
+  * PRE (k_hamm64_mfma<true>, description Pre32): a step is two needle pairs, 128 needles from 64 p; field f of a
+    register is needle 64 p + 32 f + c (`work` in prefilter_body), and a step whose second pair does not exist takes the
+    first again (Pre32::last_op, the clamp of needle_loop); needles past nq are hash 0 (k_expand_needles).  A register
+    is flagged when any field has popc(fold(slot) ^ fold(needle)) < thresh, fold(x) = lo32 ^ hi32 (Pre32::hay,
+    NeedleScratch::fold); a flagged top field makes all four fields candidates (`drain` in prefilter_body);
+  * FULL3 (k_hamm64_mfma3): a triple is 96 needles, field f = needle 96 p + 32 f + c, flagged per field on the full
+    64 bits; the per-tile queue takes one field at a time, <= 16 registers x 64 lanes (handle_tile3, queue_drain);
+  * FULL2 (k_hamm64_mfma<false>, threshold 65): pair p = needles 64 p + 32 f + c, two entries per register, <= 2048 per
+    tile (handle_tile2, kQueue).
+Prefilter bookkeeping (as the kernel stood at the commit that added this module; today's rules are `detect` and `drain`
+in prefilter_body, which tests/test_scan_prefilter_events.py and test_scan_prefilter_items.py follow):
+a group whose flags sit in ONE lane lists that lane's flagged registers (<= 32 descriptors) and does not drain;
+several hit lanes are parked kParkLanes = 16 at a time, each listing
 its flagged registers; a drain keeps npend & 63 descriptors; the pending list holds kOutOff / 2 = 640.  Up to the commit
 that added this module a multi-lane group drained only AFTER each chunk (at >= 64 pending), so a chunk could land on
 63 + 3 x 32 pending descriptors: 671.  Draining only BEFORE a chunk that might not fit is not enough either: a chunk
@@ -39,7 +44,7 @@ TILES = 8  # kHT
 PARK_LANES = 16  # kParkLanes
 PEND_CAP = 640  # kOutOff / 2 = (kQueue - kParkLanes * 32 - 2 * kOutCap) / 2
 FULL3_QUEUE = 16 * 64  # s_queue_ of k_hamm64_mfma3, words per wave
-FULL2_QUEUE = 2048  # kQueue
+FULL2_QUEUE = 2048  # kQueue of k_hamm64_mfma<false>
 
 M32 = np.uint64(0xFFFFFFFF)
 
