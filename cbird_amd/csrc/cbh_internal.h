@@ -335,6 +335,10 @@ void set_quality_chunk_mb(int v);  // quality.hip "quality_chunk_mb": MB one upl
 int get_quality_chunk_mb();
 int get_quality_strip_rows();      // "quality_strip_rows": rows one thread of the quality kernels walks
 void set_color_fma(int on);        // color.hip "color_fma": fused squares in k_color_dist3 (default off: not bit-identical)
+int set_color_chunk_scores(int v);  // color.hip "color_chunk_scores": most score elements per chunk of the needle loops, 0 (default) = 2^28 / 2^27 / 2^27; < 0: CBH_E_INVAL, knob unchanged
+int get_color_chunk_scores();
+long long get_color_full_sorts();   // "color_full_sorts": needles cbh_color_find_batch has sent through color_full_sort_one
+long long get_color_window_cuts();  // "color_window_cuts": needles it has answered from the candidate list
 
 // ---- records.hip ----------------------------------------------------------------------
 // Ascending u64 sort of n records in place (uses d_alt as the ping-pong buffer and d_tmp as

@@ -1400,6 +1400,7 @@ int cbh_set_tuning(const char* key, int value) {
   if (!strcmp(key, "join_resident")) return set_join_resident(value);
   if (!strcmp(key, "join_resident_mb")) return set_join_resident_mb(value);
   if (!strcmp(key, "color_create_group")) return set_cd_group(value);
+  if (!strcmp(key, "color_chunk_scores")) return set_color_chunk_scores(value);
   if (!strcmp(key, "scan256_kernels")) {  // a read-back, not a knob: writing 0 clears it, nothing else can be written
     if (value != 0) return CBH_E_INVAL;
     clear_scan256_kernels();
@@ -1428,6 +1429,9 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strcmp(key, "scan256_kernels")) return *value = get_scan256_kernels(), CBH_OK;
   if (!strcmp(key, "color_create_group")) return *value = get_cd_group(), CBH_OK;
   if (!strcmp(key, "color_create_group_last")) return *value = get_cd_group_last(), CBH_OK;
+  if (!strcmp(key, "color_chunk_scores")) return *value = get_color_chunk_scores(), CBH_OK;
+  if (!strcmp(key, "color_full_sorts")) return *value = get_color_full_sorts(), CBH_OK;
+  if (!strcmp(key, "color_window_cuts")) return *value = get_color_window_cuts(), CBH_OK;
   if (!strcmp(key, "quality_chunk_mb")) return *value = get_quality_chunk_mb(), CBH_OK;
   if (!strcmp(key, "quality_strip_rows")) return *value = get_quality_strip_rows(), CBH_OK;
   if (!strcmp(key, "scan_probes")) return *value = get_scan_probes(), CBH_OK;

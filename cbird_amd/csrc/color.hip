@@ -16,6 +16,7 @@
 // colour (either side can be "a"); sqrtf is monotonic, so it is applied to the 32 minima instead of the 1024
 // pair distances (bit-identical result), then summed in index order starting from 1.0f.
 
+#include <atomic>
 #include <cfloat>
 #include <map>
 
@@ -359,10 +360,32 @@ void decompress(const uint8_t* desc, NeedleF* out) {  // DescriptorColor::get, c
   }
 }
 
+// "color_chunk_scores": the most score elements (needles x entries) one chunk of cbh_color_find_batch,
+// cbh_color_find_all_batch or cbh_color_distances may hold; 0 (default) = 2^28 / 2^27 / 2^27.  At least one needle per
+// chunk.  Forced (tests): the second and later chunks of the needle loops on a small index.  Results do not depend on it.
+std::atomic<int> g_color_chunk_scores{0};
+// "color_full_sorts" / "color_window_cuts": needles of cbh_color_find_batch that went through color_full_sort_one / were
+// answered from the candidate list (needles without a match, and k == 0, count as neither)
+std::atomic<long long> g_color_full_sorts{0}, g_color_window_cuts{0};
+
+// needles per chunk of a loop whose default budget is `dflt` score elements
+size_t color_chunk(size_t nq, size_t n, size_t dflt) {
+  const int forced = g_color_chunk_scores.load();
+  return std::max<size_t>(1, std::min<size_t>(nq, (forced > 0 ? (size_t)forced : dflt) / n));
+}
+
 }  // namespace
 
 namespace cbh {
 void set_color_fma(int on) { g_color_fma = on ? 1 : 0; }
+int set_color_chunk_scores(int v) {
+  if (v < 0) return CBH_E_INVAL;
+  g_color_chunk_scores.store(v);
+  return CBH_OK;
+}
+int get_color_chunk_scores() { return g_color_chunk_scores.load(); }
+long long get_color_full_sorts() { return g_color_full_sorts.load(); }
+long long get_color_window_cuts() { return g_color_window_cuts.load(); }
 }  // namespace cbh
 
 struct cbh_color {
@@ -677,7 +700,7 @@ int cbh_color_find_all_batch(cbh_color* c, const void* needle_descs, size_t nq, 
   cbh::DeviceGuard g(c->device);
   if (!g.ok) return CBH_E_NODEVICE;
   std::lock_guard<std::mutex> lk(c->mu);
-  const size_t chunk = std::max<size_t>(1, std::min<size_t>(nq, ((size_t)1 << 27) / c->n));
+  const size_t chunk = color_chunk(nq, c->n, (size_t)1 << 27);
   int rc = ensure_scratch(c, chunk, false);
   if (rc) return rc;
   std::vector<int> sc(chunk * c->n);
@@ -712,7 +735,7 @@ int cbh_color_distances(cbh_color* c, const void* needle_descs, size_t nq, float
   cbh::DeviceGuard g(c->device);
   if (!g.ok) return CBH_E_NODEVICE;
   std::lock_guard<std::mutex> lk(c->mu);
-  const size_t chunk = std::max<size_t>(1, std::min<size_t>(nq, ((size_t)1 << 27) / c->n));
+  const size_t chunk = color_chunk(nq, c->n, (size_t)1 << 27);
   int rc = ensure_scratch(c, chunk, false);
   if (rc) return rc;
   float* d_raw = nullptr;
@@ -759,7 +782,7 @@ int cbh_color_find_batch(cbh_color* c, const void* needle_descs, size_t nq, int 
   cbh::DeviceGuard g(c->device);
   if (!g.ok) return CBH_E_NODEVICE;
   std::lock_guard<std::mutex> lk(c->mu);
-  const size_t chunk = std::max<size_t>(1, std::min<size_t>(nq, ((size_t)1 << 28) / c->n));  // <= 1 GiB of scores
+  const size_t chunk = color_chunk(nq, c->n, (size_t)1 << 28);  // <= 1 GiB of scores
   int rc = ensure_scratch(c, chunk, true);
   if (rc) return rc;
   if (chunk > c->topk_cap) {
@@ -822,9 +845,11 @@ int cbh_color_find_batch(cbh_color* c, const void* needle_descs, size_t nq, int 
         std::sort(cq, cq + h_ncand[q]);  // (score, id): Database::searchIndex order with ties by id
         const size_t take = std::min<size_t>((size_t)k, h_ncand[q]);
         for (size_t j = 0; j < take; ++j) oq[j] = cbh_match{(uint32_t)cq[j], (int32_t)(cq[j] >> 32)};
+        g_color_window_cuts++;
       } else {
         rc = color_full_sort_one(c, q, k, oq, h_valid[q]);
         if (rc) return rc;
+        g_color_full_sorts++;
       }
     }
   }

@@ -802,7 +802,7 @@ int cbh_color_distances(cbh_color*, const void* needle_descs, size_t nq, float* 
 int cbh_color_find_batch(cbh_color*, const void* needle_descs, size_t nq, int k, cbh_match* out,
                          uint32_t* counts);
 
-/* Knobs (28).  Results never change with any of them except "color_fma".  Unknown keys return CBH_E_INVAL.
+/* Knobs (29).  Results never change with any of them except "color_fma".  Unknown keys return CBH_E_INVAL.
  * Which kernel serves a call:
  *   "scan_mfma"     64-bit scan on the matrix cores (k_hamm64_mfma*): 0 = never (the popcount kernel k_hamm64_scan), 1 = calls
  *                   with >= 256 needles and >= 4096 slots (default), 2 = always; 3 = as 1, and calls with thresholds <= 8 and
@@ -867,6 +867,10 @@ int cbh_color_find_batch(cbh_color*, const void* needle_descs, size_t nq, int k,
  * Memory:
  *   "color_create_chunk_mb" scratch one launch of ColorDescriptor::create may take, in MB (default 32768): larger batches
  *                   are worked off in chunks of that many images (1.6 MB per 256 x 192 image)
+ *   "color_chunk_scores" the most score elements (needles x entries) one chunk of the needle loops of
+ *                   cbh_color_find_batch, cbh_color_find_all_batch and cbh_color_distances may hold: 0 (default) = 2^28 /
+ *                   2^27 / 2^27; at least one needle per chunk (tests: the later chunks on a small index).  Negative
+ *                   values return CBH_E_INVAL and leave the knob as it was
  *   "quality_chunk_mb" what one upload of cbh_quality_scores, and the working planes of one group of launches of
  *                   cbh_quality_scores_dev, may take, in MB (default 1024; at least one image each)
  *   "pool_keep_mb"  cached scratch that may outlive its stream, per device, in MB (default 16384; < 0: everything)
@@ -911,7 +915,10 @@ int cbh_set_tuning(const char* key, int value);
  * a sharded handle notes one launch per shard, a buffer that had to grow one per attempt); "slices_on_device" (the
  * cbh_idx256_slice and cbh_color_slice calls so far that succeeded on the device route, the one that
  * runs the kernels of slice.hip; a call that had nothing to move -- an empty list, an empty index, nothing kept --
- * counts too, although it launches none of them); "quality_chunk_mb" (the knob's value); "quality_strip_rows" (rows of
+ * counts too, although it launches none of them); "color_chunk_scores" (the knob's value); "color_full_sorts" / "color_window_cuts" (needles of
+ * cbh_color_find_batch sent through the full sort -- k above 4096, or more than 4096 candidates at or under the k-th score
+ * -- / answered from the candidate list, since the library loaded; needles without a match, and k = 0, count as neither;
+ * read-only); "quality_chunk_mb" (the knob's value); "quality_strip_rows" (rows of
  * the working plane one thread of the quality kernels walks: their strips start at every multiple of it; read-only). */
 int cbh_get_tuning(const char* key, long long* value);
 

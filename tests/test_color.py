@@ -4,37 +4,14 @@ oracle against an independent numpy float32 statement and hand-made cases; the G
 import numpy as np
 import pytest
 
+from color_search_cases import synth_descriptors  # (shared with tests/test_color_search*.py)
+
 
 @pytest.fixture(scope="module")
 def co():
     from oracle import ColorOracle
 
     return ColorOracle()
-
-
-def synth_descriptors(n, seed, dup_frac=0.3):
-    from cbird_amd.colordesc import COLOR_DTYPE
-
-    rng = np.random.default_rng(seed)
-    d = np.zeros(n, COLOR_DTYPE)
-    num = rng.integers(0, 33, n)
-    num[rng.random(n) < 0.05] = 0  # grayscale images: stored with no colours (colordescindex.cpp:73-75)
-    for i in range(n):
-        if i and rng.random() < dup_frac:  # near-duplicate palette of an earlier entry
-            src = int(rng.integers(0, i))
-            d[i] = d[src]
-            k = int(d[i]["numColors"])
-            if k:
-                jit = rng.integers(-600, 601, (k, 4))
-                d[i]["colors"][:k] = np.clip(d[i]["colors"][:k].astype(np.int64) + jit, 0, 65535)
-                drop = int(rng.integers(0, 3))
-                d[i]["numColors"] = max(0, k - drop)
-        else:
-            k = int(num[i])
-            d[i]["colors"][:k] = rng.integers(0, 65536, (k, 4))
-            d[i]["numColors"] = k
-    ids = np.arange(1, n + 1, dtype=np.uint32)
-    return d, ids
 
 
 def np_distance(a, b):
