@@ -201,6 +201,14 @@ _SIGS = {
                                       C.c_int]),
     "cbh_template_hashes_dev": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, _vp, _sz, C.c_int, _vp, _vp,
                                           C.c_int, _vp]),
+    "cbh_estimate_rigid": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, C.c_int]),
+    "cbh_estimate_rigid_dev": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "cbh_warp_affine_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int,
+                                      _vp]),
+    "cbh_template_match": (C.c_int, [_vp, C.c_int, C.c_int, _sz, C.c_int, _vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "cbh_template_match_dev": (C.c_int, [_vp, C.c_int, C.c_int, _sz, C.c_int, _vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "cbh_vindexer_create": (_vp, [C.c_int, C.c_int, C.c_int]),
     "cbh_vindexer_destroy": (None, [_vp]),
     "cbh_vindexer_resume": (C.c_int, [_vp, _vp, _vp, _sz]),

@@ -287,6 +287,61 @@ inline int gpuTemplateScore(const cv::Mat& img, const cv::Mat& tmplImg, uint64_t
   return score;
 }
 
+// TemplateMatcher::match from the point lists to the score, src/templatematcher.cpp:264-374, for ALL candidates of one
+// template in one call that does not leave the device.  Per candidate i: tmplPoints[i] / matchPoints[i] as the loop at
+// :243-250 fills them, candImgs[i] the candidate image the keypoints were taken from (8-bit, one channel count for the
+// group), candScales[i] its candScale.  Replaces, inside the loop over the candidates,
+//     cv::Mat transform = cv::estimateRigidTransform(tmplPoints, matchPoints, false);            (:264)
+//     cv::transform(tmplRect, candRect, transform); roi.append(QPoint(int(candRect[i].x / candScale), ...)); (:284-300)
+//     for (cv::Point2f& p : matchPoints) { p.x /= candScale; p.y /= candScale; }
+//     const cv::Mat tx = cv::estimateRigidTransform(tmplPoints, matchPoints, false);             (:304-309)
+//     cv::invertAffineTransform(transform, transform);
+//     cv::warpAffine(img, img, transform, tmplImg.size(), cv::INTER_AREA, cv::BORDER_CONSTANT, cv::Scalar(0,0,0,255)); (:331-333)
+//     ... the masking loop, the two dctHash64 and hamm64                                          (:337-374)
+// by one call after the loop has gathered the lists:
+//     std::vector<cbh_template_result> results;
+//     cbird_gpu::gpuTemplateMatch(tmplImg, candImgs, tmplPoints, matchPoints, candScales, results);
+// results[i].found == 0 is the reference's "no transform found" (score INT_MAX, :271); otherwise .roi holds the four
+// QPoints of :299, .tx the matrix for QTransform (:315-316, valid when .tx_found), .score what m.setScore takes (:378).
+// (OpenCV parity of the estimate and the warp is unpinned: see include/cbird_hip.h.)
+inline void gpuTemplateMatch(const cv::Mat& tmplImg, const std::vector<cv::Mat>& candImgs,
+                             const std::vector<std::vector<cv::Point2f>>& tmplPoints,
+                             const std::vector<std::vector<cv::Point2f>>& matchPoints, const std::vector<float>& candScales,
+                             std::vector<cbh_template_result>& results) {
+  const size_t n = candImgs.size();
+  if (tmplPoints.size() != n || matchPoints.size() != n || candScales.size() != n)
+    qFatal("gpuTemplateMatch: one point list pair and one scale per candidate");
+  results.assign(n, cbh_template_result());
+  if (n == 0) return;
+  if (tmplImg.depth() != CV_8U || tmplImg.rows <= 0 || tmplImg.cols <= 0)
+    qFatal("gpuTemplateMatch: expected a non-empty 8-bit template");
+  const int cn = candImgs[0].channels();
+  std::vector<uint64_t> off, first(1, 0);
+  std::vector<uint32_t> w, h, step;
+  std::vector<uint8_t> buf;
+  std::vector<float> a, b;
+  for (size_t i = 0; i < n; ++i) {
+    const cv::Mat& m = candImgs[i];
+    if (m.rows <= 0 || m.cols <= 0 || m.depth() != CV_8U || m.channels() != cn)
+      qFatal("gpuTemplateMatch: expected non-empty 8-bit candidates of one channel count");
+    if (tmplPoints[i].size() != matchPoints[i].size()) qFatal("gpuTemplateMatch: the point lists of a candidate differ in length");
+    const size_t row = size_t(m.cols) * size_t(cn);
+    off.push_back((buf.size() + 15) / 16 * 16);
+    buf.resize(size_t(off.back()) + row * size_t(m.rows));
+    for (int y = 0; y < m.rows; ++y) memcpy(buf.data() + off.back() + size_t(y) * row, m.ptr<uint8_t>(y), row);
+    w.push_back(uint32_t(m.cols)), h.push_back(uint32_t(m.rows)), step.push_back(uint32_t(row));
+    for (size_t k = 0; k < tmplPoints[i].size(); ++k) {
+      a.push_back(tmplPoints[i][k].x), a.push_back(tmplPoints[i][k].y);
+      b.push_back(matchPoints[i][k].x), b.push_back(matchPoints[i][k].y);
+    }
+    first.push_back(first.back() + tmplPoints[i].size());
+  }
+  const int rc = cbh_template_match(tmplImg.data, tmplImg.cols, tmplImg.rows, size_t(tmplImg.step), tmplImg.channels(),
+                                    buf.data(), buf.size(), n, off.data(), w.data(), h.data(), step.data(), cn, a.data(),
+                                    b.data(), first.data(), candScales.data(), results.data(), nullptr, hashDevice());
+  if (rc) qFatal("gpuTemplateMatch: %s (%s)", cbh_strerror(rc), cbh_last_error());
+}
+
 // qualityScore(const Media&) (src/cimgops.cpp:313-596) for images that are already decoded: 8-bit cv::Mat of 1, 3 (BGR)
 // or 4 (BGRA) channels, the layout loadImage / qImageToCvImg give.  Only the red channel takes part, as in the
 // reference (its crop keeps channel 0 of qImageToCImg's planes).  INT32_MIN = no score (no edges at all, or a side of 1,

@@ -1379,6 +1379,7 @@ int cbh_set_tuning(const char* key, int value) {
       {"color_fma", [](int v) { set_color_fma(v); }},
       {"color_create_chunk_mb", [](int v) { set_cd_chunk_mb(v); }},
       {"quality_chunk_mb", [](int v) { set_quality_chunk_mb(v); }},
+      {"tmatch_chunk_mb", [](int v) { set_tmatch_chunk_mb(v); }},
       {"fdct_host_vote", [](int v) { g_fdct_host_vote = v; }},
       {"video_host_reduce", [](int v) { g_video_host_reduce = v; }},
       {"orb_retain_order", [](int v) { set_orb_retain_order(v); }},
@@ -1434,6 +1435,7 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strcmp(key, "color_window_cuts")) return *value = get_color_window_cuts(), CBH_OK;
   if (!strcmp(key, "quality_chunk_mb")) return *value = get_quality_chunk_mb(), CBH_OK;
   if (!strcmp(key, "quality_strip_rows")) return *value = get_quality_strip_rows(), CBH_OK;
+  if (!strcmp(key, "tmatch_chunk_mb")) return *value = get_tmatch_chunk_mb(), CBH_OK;
   if (!strcmp(key, "scan_probes")) return *value = get_scan_probes(), CBH_OK;
   if (!strcmp(key, "scan_joins")) return *value = get_scan_joins(), CBH_OK;
   if (!strcmp(key, "join_needle_preps")) return *value = get_join_needle_preps(), CBH_OK;

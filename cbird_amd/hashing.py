@@ -167,3 +167,113 @@ def size_longest_side(imgs: np.ndarray, size: int = 400, device: int = 0) -> np.
     check(L.cbh_size_longest_side(imgs.ctypes.data, n, w, h, imgs.strides[1], imgs.strides[0] if n else 0, int(size),
                                   out.ctypes.data, C.byref(ow), C.byref(oh), device), "size_longest_side")
     return out
+
+
+# ---- TemplateMatcher::match between the descriptor match and the score (src/templatematcher.cpp:264-333) -------------
+RIGID_DETAIL_DTYPE = np.dtype([("iterations", np.int32), ("good_count", np.int32), ("draws", np.uint32),
+                               ("reserved", np.uint32)])
+TEMPLATE_RESULT_DTYPE = np.dtype([("m", np.float64, 6), ("tx", np.float64, 6), ("cand_hash", np.uint64),
+                                  ("tmpl_hash", np.uint64), ("roi", np.int32, 8), ("found", np.int32),
+                                  ("tx_found", np.int32), ("score", np.int32), ("iterations", np.int32),
+                                  ("good_count", np.int32), ("reserved", np.int32)])
+assert RIGID_DETAIL_DTYPE.itemsize == 16 and TEMPLATE_RESULT_DTYPE.itemsize == 168
+NO_TRANSFORM_SCORE = (1 << 31) - 1  # INT_MAX, what the reference caches for a candidate without a transform
+
+
+def pack_point_lists(a_lists, b_lists):
+    """lists of [k_i, 2] float32 point arrays -> (a_xy, b_xy float32 [total, 2], first uint64 [n + 1])"""
+    if len(a_lists) != len(b_lists):
+        raise ValueError("one list of B points per list of A points")
+    a = [np.ascontiguousarray(p, np.float32).reshape(-1, 2) for p in a_lists]
+    b = [np.ascontiguousarray(p, np.float32).reshape(-1, 2) for p in b_lists]
+    if any(len(p) != len(q) for p, q in zip(a, b)):
+        raise ValueError("A and B of a list hold the same number of points")
+    first = np.zeros(len(a) + 1, np.uint64)
+    first[1:] = np.cumsum([len(p) for p in a], dtype=np.uint64)
+    cat = lambda ps: np.concatenate(ps) if ps and first[-1] else np.zeros((1, 2), np.float32)  # noqa: E731
+    return cat(a), cat(b), first
+
+
+def estimate_rigid(a_lists, b_lists, detail: bool = False, device: int = 0):
+    """cv::estimateRigidTransform(A, B, fullAffine=false) (src/templatematcher.cpp:264, 309) for n point-pair lists in one
+    call.  Returns (m float64 [n, 2, 3], found bool [n]) and, with detail=True, RIGID_DETAIL_DTYPE [n] (outer iterations
+    run, inliers of the stopping iteration, RNG values drawn)."""
+    a, b, first = pack_point_lists(a_lists, b_lists)
+    n = len(first) - 1
+    m = np.zeros((n, 2, 3), np.float64)
+    found = np.zeros(n, np.uint8)
+    det = np.zeros(n, RIGID_DETAIL_DTYPE)
+    if n:
+        check(_lib.lib().cbh_estimate_rigid(a.ctypes.data, b.ctypes.data, n, first.ctypes.data, m.ctypes.data,
+                                            found.ctypes.data, det.ctypes.data if detail else None, device),
+              "estimate_rigid")
+    return (m, found.astype(bool), det) if detail else (m, found.astype(bool))
+
+
+def warp_affine(images, m, tw: int, th: int, found=None, device: int = 0):
+    """invertAffineTransform(m) + warpAffine(img, m, (tw, th), INTER_AREA, BORDER_CONSTANT, (0,0,0,255))
+    (src/templatematcher.cpp:331-333) for a list of uint8 images of one channel count (1, 3 or 4) and any sizes: m
+    [n, 2, 3] maps the template to each candidate.  Returns (patches uint8 [n, th, tw(, ch)], warped bool [n]) -- for an empty list ([0, th, tw], []); the patch
+    of a candidate that is not found, or whose coordinates leave the reference's integer range, is zero."""
+    import torch
+
+    from .quality import pack_images
+
+    imgs = [np.ascontiguousarray(im, np.uint8) for im in images]
+    n = len(imgs)
+    chs = {1 if im.ndim == 2 else im.shape[2] for im in imgs}
+    if n == 0:  # nothing to do, as in the C entry (no image says how many channels: the patches have no channel axis)
+        return np.zeros((0, th, tw), np.uint8), np.zeros(0, bool)
+    if len(chs) != 1 or not chs <= {1, 3, 4} or any(im.size == 0 for im in imgs):
+        raise ValueError("expected non-empty uint8 images of one channel count: [h, w], [h, w, 3] or [h, w, 4]")
+    ch = chs.pop()
+    m = np.ascontiguousarray(m, np.float64).reshape(n, 6)
+    found = np.ones(n, np.uint8) if found is None else np.ascontiguousarray(found).astype(np.uint8).reshape(n)
+    buf, off, w, h, stride = pack_images(imgs)
+    dev = torch.device("cuda", device)
+    d_img, d_m, d_found = (torch.from_numpy(v).to(dev) for v in (buf, m, found))
+    d_out = torch.zeros(n * th * tw * ch, dtype=torch.uint8, device=dev)
+    d_ok = torch.zeros(n, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    check(_lib.lib().cbh_warp_affine_dev(d_img.data_ptr(), n, off.ctypes.data, w.ctypes.data, h.ctypes.data,
+                                         stride.ctypes.data, ch, d_m.data_ptr(), d_found.data_ptr(), int(tw), int(th),
+                                         d_out.data_ptr(), d_ok.data_ptr(), device, None), "warp_affine")
+    torch.cuda.synchronize(dev)
+    shape = (n, th, tw) if imgs[0].ndim == 2 else (n, th, tw, ch)
+    return d_out.cpu().numpy().reshape(shape), d_ok.cpu().numpy().astype(bool)
+
+
+def template_match(tmpl, cands, tmpl_points, match_points, cand_scales=None, patches: bool = False, device: int = 0):
+    """TemplateMatcher::match from the point lists to the score (src/templatematcher.cpp:264-374) for ONE template and n
+    candidate images (a list of uint8 images of one channel count, any sizes): both rigid estimates, the roi, the warp,
+    the masked hashes and their distance, in one call that does not leave the device.  tmpl_points[i] / match_points[i]:
+    [k_i, 2] float32, the matched keypoints of candidate i in the caller's order (:243-250); cand_scales[i]: candScale.
+    Returns TEMPLATE_RESULT_DTYPE [n] (score = NO_TRANSFORM_SCORE where found is 0) and, with patches=True, the warped
+    patches uint8 [n, th, tw(, ch)]."""
+    from .quality import pack_images
+
+    tmpl = np.ascontiguousarray(tmpl, np.uint8)
+    imgs = [np.ascontiguousarray(im, np.uint8) for im in cands]
+    n = len(imgs)
+    res = np.zeros(n, TEMPLATE_RESULT_DTYPE)
+    if tmpl.ndim not in (2, 3) or tmpl.size == 0:
+        raise ValueError("expected a uint8 template [h, w] or [h, w, c]")
+    th, tw = tmpl.shape[:2]
+    tc = 1 if tmpl.ndim == 2 else tmpl.shape[2]
+    if n == 0:  # (no candidate says how many channels: the empty patches take the template's layout)
+        return (res, np.zeros((0,) + tmpl.shape, np.uint8)) if patches else res
+    chs = {1 if im.ndim == 2 else im.shape[2] for im in imgs}
+    if len(chs) != 1 or not chs <= {1, 3, 4} or tc not in (1, 3, 4) or any(im.size == 0 for im in imgs):
+        raise ValueError("expected non-empty uint8 images of one channel count: [h, w], [h, w, 3] or [h, w, 4]")
+    ch = chs.pop()
+    a, b, first = pack_point_lists(tmpl_points, match_points)
+    if len(first) - 1 != n:
+        raise ValueError("one point list per candidate")
+    scales = np.ones(n, np.float32) if cand_scales is None else np.ascontiguousarray(cand_scales, np.float32).reshape(n)
+    buf, off, w, h, stride = pack_images(imgs)
+    out = np.zeros((n, th, tw) if imgs[0].ndim == 2 else (n, th, tw, ch), np.uint8)
+    check(_lib.lib().cbh_template_match(tmpl.ctypes.data, tw, th, tw * tc, tc, buf.ctypes.data, buf.size, n,
+                                        off.ctypes.data, w.ctypes.data, h.ctypes.data, stride.ctypes.data, ch,
+                                        a.ctypes.data, b.ctypes.data, first.ctypes.data, scales.ctypes.data,
+                                        res.ctypes.data, out.ctypes.data if patches else None, device), "template_match")
+    return (res, out) if patches else res

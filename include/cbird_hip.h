@@ -699,13 +699,67 @@ long long cbh_vindexer_finish(const cbh_vindexer*, int32_t* frames, uint64_t* ha
  * it is 0 the template's pixel is zeroed too, a BGRA template is premultiplied by its alpha (and scales the candidate's
  * grey value by it) (:343-364); candHash = dctHash64(cand), tmplHash = dctHash64(tmplMasked); score = hamm64 of the two
  * (:366-371; the caller compares with tmThresh, :373).  The descriptor match in front of it is cbh_idx256_radius_match;
- * estimateRigidTransform / warpAffine between the two stay with the caller (OpenCV). */
+ * estimateRigidTransform / warpAffine between the two are cbh_estimate_rigid / cbh_warp_affine_dev below, and
+ * cbh_template_match runs transform -> warp -> these hashes -> score for a batch without leaving the device. */
 int cbh_template_scores(const uint8_t* cands, size_t n, int w, int h, size_t cand_row_stride, size_t cand_img_stride,
                         int cand_channels, const uint8_t* tmpl, size_t tmpl_row_stride, int tmpl_channels,
                         uint64_t* cand_hashes, uint64_t* tmpl_hashes, int32_t* scores, int device);
 int cbh_template_hashes_dev(const void* d_cands, size_t n, int w, int h, size_t cand_row_stride, size_t cand_img_stride,
                             int cand_channels, const void* d_tmpl, size_t tmpl_row_stride, int tmpl_channels,
                             void* d_cand_hashes, void* d_tmpl_hashes, int device, void* stream);
+
+/* ---- TemplateMatcher::match between the descriptor match and the score (src/templatematcher.cpp:264-333) ----------
+ * UNPINNED: OpenCV is not available to this repository; estimateRigidTransform, cv::transform, invertAffineTransform and
+ * warpAffine are restated as recalled from OpenCV 2.4.13 (cbird_amd/csrc/tmatch.hip; tests/template_match_rules.py is the
+ * numpy model the device is held to) until tools/pin_with_opencv.sh has written tests/golden/opencv_tmatch.npz.
+ *
+ * estimateRigidTransform(A, B, fullAffine = false) on point sets (:264, :309) for n ragged lists: list i = pairs
+ * first[i] .. first[i + 1] of a_xy / b_xy (x, y floats; first[0] = 0; `first` is host memory in both entries).  RANSAC
+ * with cv::RNG((uint64)-1), at most 500 outer iterations of three draws, inlier threshold 0.05 * the larger side of
+ * boundingRect(B), stop at half the pairs, final getRTMatrix over the inliers in order.  m[6 * i ..] = the 2 x 3 matrix in
+ * row order (zeros when found[i] == 0: fewer than three pairs, or no iteration stopped); detail (NULL or n): outer
+ * iterations run (0 below three pairs, 500 when none stopped), inliers of the stopping iteration (0 when not found), RNG
+ * values drawn.  Any count up to 2^31 - 1 pairs per list. */
+typedef struct cbh_rigid_detail {
+  int32_t iterations, good_count;
+  uint32_t draws, reserved;
+} cbh_rigid_detail;
+int cbh_estimate_rigid(const float* a_xy, const float* b_xy, size_t n, const uint64_t* first, double* m, uint8_t* found,
+                       cbh_rigid_detail* detail, int device);
+int cbh_estimate_rigid_dev(const void* d_a_xy, const void* d_b_xy, size_t n, const uint64_t* first, void* d_m /* f64 6n */,
+                           void* d_found /* u8 n */, void* d_detail /* NULL or n */, int device, void* stream);
+/* invertAffineTransform(m) + warpAffine(img, m, Size(tw, th), INTER_AREA -> INTER_LINEAR, BORDER_CONSTANT, (0,0,0,255))
+ * (:331-333) for n ragged candidate images (the img_off / img_w / img_h / img_row_stride host tables and the channel
+ * counts 1 / 3 / 4 of cbh_quality_scores_dev; sides up to 32767) into packed n x th x tw x channels patches: d_m[6 * i ..]
+ * maps the template to the candidate, as estimateRigidTransform returned it.  The patch of a candidate with
+ * d_found[i] == 0 is zero; so is one whose coordinate integers would reach 2^30 (|M (x, y)| * 1024, where the reference's
+ * arithmetic is undefined) -- d_warped (NULL or u8 n) tells: 1 = warped.  d_patches is 16-byte aligned. */
+int cbh_warp_affine_dev(const void* d_imgs, size_t n, const uint64_t* img_off, const uint32_t* img_w, const uint32_t* img_h,
+                        const uint32_t* img_row_stride, int channels, const void* d_m, const void* d_found, int tw, int th,
+                        void* d_patches, void* d_warped, int device, void* stream);
+/* The chain for ONE template and n candidates: both estimates (the second on matchPoints / cand_scale[i], :304-309), the
+ * corners and the roi (:284-300), the warp, cbh_template_hashes_dev, hamm64.  tmpl_xy / match_xy / first: the point lists
+ * of the candidates in the caller's order (:243-250).  A candidate without a transform, or outside the warp's domain, has
+ * found = 0, score = INT32_MAX (the reference's INT_MAX, :233, :258, :271) and zeros elsewhere but iterations /
+ * good_count.  patches (NULL or n x th x tw x channels; the device entry's 16-byte aligned) receives the warped patches.
+ * Host images go up in pieces of at most "tmatch_chunk_mb" (cbh_set_tuning). */
+typedef struct cbh_template_result {
+  double m[6];   /* template -> candidate (:264) */
+  double tx[6];  /* template -> unscaled candidate (:309); zeros unless tx_found */
+  uint64_t cand_hash, tmpl_hash;
+  int32_t roi[8]; /* x, y of the four corners / candScale (:299) */
+  int32_t found, tx_found, score, iterations, good_count, reserved;
+} cbh_template_result;
+int cbh_template_match(const uint8_t* tmpl, int tw, int th, size_t tmpl_row_stride, int tmpl_channels, const uint8_t* imgs,
+                       size_t imgs_bytes, size_t n, const uint64_t* img_off, const uint32_t* img_w, const uint32_t* img_h,
+                       const uint32_t* img_row_stride, int channels, const float* tmpl_xy, const float* match_xy,
+                       const uint64_t* first, const float* cand_scale, cbh_template_result* results, uint8_t* patches,
+                       int device);
+int cbh_template_match_dev(const void* d_tmpl, int tw, int th, size_t tmpl_row_stride, int tmpl_channels, const void* d_imgs,
+                           size_t n, const uint64_t* img_off, const uint32_t* img_w, const uint32_t* img_h,
+                           const uint32_t* img_row_stride, int channels, const void* d_tmpl_xy, const void* d_match_xy,
+                           const uint64_t* first, const float* cand_scale, void* d_results, void* d_patches, int device,
+                           void* stream);
 
 /* ---- CvFeaturesIndex: src/cvfeaturesindex.{h,cpp} ---------------------------------------------------
  * N x 32-byte ORB/BRIEF descriptor rows (cv::Mat CV_8U, cvfeaturesindex.h:73) + the first-row -> mediaId
@@ -761,7 +815,8 @@ int cbh_idx256_find_batch(cbh_idx256*, const uint8_t* needle_rows, const uint64_
  * the index rows as the train set (load the template's descriptors with cbh_idx256_add): every (query, train) pair
  * with distance <= max_dist, grouped by query, each group in ascending (distance, train row) order (OpenCV: by
  * distance, ties unspecified).  out_first has nq + 1 entries; returns CBH_E_OVERFLOW (with out_first complete) when
- * cap is too small.  The steps after it (estimateRigidTransform's RANSAC, warpAffine) are OpenCV's and stay there. */
+ * cap is too small.  The steps after it (estimateRigidTransform's RANSAC, warpAffine, the score) are
+ * cbh_template_match; gathering its point lists from these records and the keypoints is the caller's (:241-250). */
 typedef struct {
   int32_t query_idx, train_idx, distance; /* cv::DMatch::queryIdx, trainIdx, distance */
 } cbh_dmatch;
@@ -873,6 +928,8 @@ int cbh_color_find_batch(cbh_color*, const void* needle_descs, size_t nq, int k,
  *                   values return CBH_E_INVAL and leave the knob as it was
  *   "quality_chunk_mb" what one upload of cbh_quality_scores, and the working planes of one group of launches of
  *                   cbh_quality_scores_dev, may take, in MB (default 1024; at least one image each)
+ *   "tmatch_chunk_mb" what one upload of cbh_template_match, and the patches of one group of candidates of
+ *                   cbh_template_match_dev when the caller does not take them, may take, in MB (default 1024)
  *   "pool_keep_mb"  cached scratch that may outlive its stream, per device, in MB (default 16384; < 0: everything)
  *   "pool_live_keep_mb" what the cache of a LIVE stream may hold, in MB (0 = default: a quarter of the device's memory, at
  *                   least 16384; < 0: everything).  Beyond it the blocks freed longest ago go back to the driver once the
@@ -919,7 +976,8 @@ int cbh_set_tuning(const char* key, int value);
  * cbh_color_find_batch sent through the full sort -- k above 4096, or more than 4096 candidates at or under the k-th score
  * -- / answered from the candidate list, since the library loaded; needles without a match, and k = 0, count as neither;
  * read-only); "quality_chunk_mb" (the knob's value); "quality_strip_rows" (rows of
- * the working plane one thread of the quality kernels walks: their strips start at every multiple of it; read-only). */
+ * the working plane one thread of the quality kernels walks: their strips start at every multiple of it; read-only);
+ * "tmatch_chunk_mb" (the knob's value). */
 int cbh_get_tuning(const char* key, long long* value);
 
 /* ---- measurement support ---------------------------------------------------------------- */

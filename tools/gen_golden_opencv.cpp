@@ -6,10 +6,16 @@
 //   g++ -O2 -std=c++11 tools/gen_golden_opencv.cpp -o gen_golden_opencv `pkg-config --cflags --libs opencv`   (core, imgproc, features2d)
 //   ./gen_golden_opencv > opencv_hash.txt
 //   python tools/opencv_golden_to_npz.py opencv_hash.txt tests/golden/opencv_hash.npz
+// and, for TemplateMatcher's estimateRigidTransform / warpAffine (needs the video module as well):
+//   python tools/tmatch_cases.py > tmatch_cases.txt          (the numpy model's own cases, tests/template_match_rules.py)
+//   ./gen_golden_opencv tmatch_cases.txt > opencv_tmatch.txt
+//   python tools/opencv_golden_to_npz.py --tmatch opencv_tmatch.txt tests/golden/opencv_tmatch.npz
+// (tools/pin_with_opencv.sh does all of it.)
 //
 // Everything OpenCV-free (the image generator, the geometry list) can be built with -DNO_OPENCV, which is how
 // tests/test_opencv_golden.py checks here that this file and its Python twin (tools/opencv_golden_to_npz.py)
-// generate identical inputs.
+// generate identical inputs; with a cases file it echoes what it read (records T and Y below with found = -1 and the
+// image's checksums in place of the patch), which is how tests/test_opencv_golden_tmatch.py checks the cases' path.
 //
 // The calls below are the ones the reference makes, in its order, written from its description in SURVEY.md 8(a1):
 //   dctHash64        src/cvutil.cpp:435-545   blur (kernel by area) -> resize 32x32 INTER_AREA -> CV_32F -> cv::dct
@@ -37,9 +43,21 @@
 //   K <N> <iterations-unknown:0> <N labels> <96 centre bit patterns :08x>
 //                                                         cv::kmeans(N x 3 samples, 32, (ITER|EPS, 100, 10), 1, PP) with
 //                                                         theRNG().state = 0xffffffff; samples = Luv of gen_image planes
+// With a cases file (argv[1]; src/templatematcher.cpp:264, 331-333), whose lines are
+//   E <name> <count> {<ax:08x> <ay:08x> <bx:08x> <by:08x>}*count
+//   W <name> <w> <h> <channels> <seed> <tw> <th> <6 matrix entries :016x>     (image: channel c = gen_image(w, h, seed + c))
+// the output is V and
+//   T <name> <count> {the points as read}*count <found> <6 matrix entries :016x>
+//                                                         cv::estimateRigidTransform(A, B, false); not called below three
+//                                                         pairs, as the reference does not (:255)
+//   Y <name> <w> <h> <channels> <seed> <tw> <th> <6 matrix entries :016x> <tw*th*channels bytes hex>
+//                                                         invertAffineTransform(M) + warpAffine(img, M, Size(tw, th),
+//                                                         INTER_AREA, BORDER_CONSTANT, Scalar(0, 0, 0, 255))
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 // ---- deterministic integer-only image generator (twin: gen_image in tools/opencv_golden_to_npz.py) ----------------
@@ -93,9 +111,83 @@ static void put_hex(const uint8_t* p, size_t n) {
   for (size_t i = 0; i < n; ++i) std::printf("%02x", p[i]);
 }
 
+
+// ---- the cases file of the template-match records (written by tools/tmatch_cases.py) -----------------------------------
+struct TmCase {
+  char kind;  // 'E' or 'W'
+  std::string name;
+  std::vector<uint32_t> pts;  // E: ax ay bx by bit patterns
+  int w, h, ch, tw, th;       // W
+  uint32_t seed;
+  uint64_t m[6];
+};
+static bool read_tm_cases(const char* path, std::vector<TmCase>& out) {
+  FILE* f = std::fopen(path, "r");
+  if (!f) return false;
+  char kind[4], name[128];
+  while (std::fscanf(f, "%3s %127s", kind, name) == 2) {
+    TmCase c;
+    c.kind = kind[0], c.name = name, c.w = c.h = c.ch = c.tw = c.th = 0, c.seed = 0;
+    std::memset(c.m, 0, sizeof(c.m));
+    if (c.kind == 'E') {
+      int count = 0;
+      if (std::fscanf(f, "%d", &count) != 1 || count < 0) return false;
+      c.pts.resize((size_t)count * 4);
+      for (size_t i = 0; i < c.pts.size(); ++i)
+        if (std::fscanf(f, "%x", &c.pts[i]) != 1) return false;
+    } else if (c.kind == 'W') {
+      if (std::fscanf(f, "%d %d %d %u %d %d", &c.w, &c.h, &c.ch, &c.seed, &c.tw, &c.th) != 6) return false;
+      for (int k = 0; k < 6; ++k) {
+        unsigned long long v;
+        if (std::fscanf(f, "%llx", &v) != 1) return false;
+        c.m[k] = v;
+      }
+    } else {
+      return false;
+    }
+    out.push_back(c);
+  }
+  std::fclose(f);
+  return true;
+}
+// interleaved w x h x ch image: channel c = gen_image(w, h, seed + c)
+static std::vector<uint8_t> tm_image(const TmCase& c) {
+  std::vector<uint8_t> img((size_t)c.w * c.h * c.ch);
+  for (int k = 0; k < c.ch; ++k) {
+    std::vector<uint8_t> plane = gen_image(c.w, c.h, c.seed + (uint32_t)k);
+    for (size_t i = 0; i < plane.size(); ++i) img[i * c.ch + k] = plane[i];
+  }
+  return img;
+}
+static void put_tm_head(const TmCase& c) {
+  if (c.kind == 'E') {
+    std::printf("T %s %d", c.name.c_str(), (int)(c.pts.size() / 4));
+    for (size_t i = 0; i < c.pts.size(); ++i) std::printf(" %08x", c.pts[i]);
+  } else {
+    std::printf("Y %s %d %d %d %u %d %d", c.name.c_str(), c.w, c.h, c.ch, c.seed, c.tw, c.th);
+    for (int k = 0; k < 6; ++k) std::printf(" %016llx", (unsigned long long)c.m[k]);
+  }
+}
+
 #ifdef NO_OPENCV
-// generator self-test: print checksums the Python twin must reproduce
-int main() {
+// generator self-test: print checksums the Python twin must reproduce; with a cases file, what was read from it
+int main(int argc, char** argv) {
+  if (argc > 1) {
+    std::vector<TmCase> cases;
+    if (!read_tm_cases(argv[1], cases)) return 2;
+    for (size_t i = 0; i < cases.size(); ++i) {
+      put_tm_head(cases[i]);
+      if (cases[i].kind == 'E') {
+        std::printf(" -1\n");
+      } else {
+        std::vector<uint8_t> img = tm_image(cases[i]);
+        uint64_t sum = 0, wsum = 0;
+        for (size_t k = 0; k < img.size(); ++k) sum += img[k], wsum += (uint64_t)img[k] * (uint64_t)(k % 251 + 1);
+        std::printf(" %llu %llu\n", (unsigned long long)sum, (unsigned long long)wsum);
+      }
+    }
+    return 0;
+  }
   for (int g = 0; g < kNGeom; ++g) {
     std::vector<uint8_t> img = gen_image(kGeom[g][0], kGeom[g][1], 100u + (uint32_t)g);
     uint64_t sum = 0, wsum = 0;
@@ -110,6 +202,7 @@ int main() {
 #include <opencv2/core/version.hpp>
 #include <opencv2/features2d/features2d.hpp>
 #include <opencv2/imgproc/imgproc.hpp>
+#include <opencv2/video/tracking.hpp>  // estimateRigidTransform
 
 static const char kZigZag[81] = {0,  9,  1,  2,  10, 18, 27, 19, 11, 3,  4,  12, 20, 28, 36, 45, 37, 29, 21, 13, 5,
                                  6,  14, 22, 30, 38, 46, 54, 63, 55, 47, 39, 31, 23, 15, 7,  8,  16, 24, 32, 40, 48,
@@ -168,7 +261,50 @@ static void emit_hash(int w, int h, uint32_t seed) {
   std::printf("\n");
 }
 
-int main() {
+// the template-match records for the cases of argv[1]
+static int emit_tmatch(const char* path) {
+  std::vector<TmCase> cases;
+  if (!read_tm_cases(path, cases)) return 2;
+  std::printf("V %s\n", CV_VERSION);
+  for (size_t i = 0; i < cases.size(); ++i) {
+    const TmCase& c = cases[i];
+    put_tm_head(c);
+    if (c.kind == 'E') {
+      std::vector<cv::Point2f> A, B;
+      for (size_t k = 0; k + 3 < c.pts.size(); k += 4) {
+        float v[4];
+        std::memcpy(v, &c.pts[k], 16);
+        A.push_back(cv::Point2f(v[0], v[1])), B.push_back(cv::Point2f(v[2], v[3]));
+      }
+      cv::Mat M;
+      if (A.size() >= 3) M = cv::estimateRigidTransform(A, B, false);  // (:255: never called with fewer)
+      const bool found = !M.empty() && M.rows == 2 && M.cols == 3 && M.type() == CV_64F;
+      std::printf(" %d", found ? 1 : 0);
+      for (int k = 0; k < 6; ++k) {
+        const double d = found ? M.at<double>(k / 3, k % 3) : 0.0;
+        uint64_t b;
+        std::memcpy(&b, &d, 8);
+        std::printf(" %016llx", (unsigned long long)b);
+      }
+      std::printf("\n");
+    } else {
+      std::vector<uint8_t> bytes = tm_image(c);
+      cv::Mat img(c.h, c.w, CV_8UC(c.ch), bytes.data());
+      cv::Mat M(2, 3, CV_64F);
+      for (int k = 0; k < 6; ++k) std::memcpy(&M.at<double>(k / 3, k % 3), &c.m[k], 8);
+      cv::invertAffineTransform(M, M);
+      cv::Mat out;
+      cv::warpAffine(img, out, M, cv::Size(c.tw, c.th), cv::INTER_AREA, cv::BORDER_CONSTANT, cv::Scalar(0, 0, 0, 255));
+      std::printf(" ");
+      for (int y = 0; y < out.rows; ++y) put_hex(out.ptr(y), (size_t)out.cols * c.ch);
+      std::printf("\n");
+    }
+  }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1) return emit_tmatch(argv[1]);
   std::printf("V %s\n", CV_VERSION);
   for (int g = 0; g < kNGeom; ++g) emit_hash(kGeom[g][0], kGeom[g][1], 100u + (uint32_t)g);
   for (int i = 0; i < kBatch256; ++i) emit_hash(256, 256, 1000u + (uint32_t)i);

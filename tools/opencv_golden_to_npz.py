@@ -3,7 +3,9 @@
 tests/golden/opencv_hash.npz, which tests/test_opencv_golden.py consumes when present.
 
     python tools/opencv_golden_to_npz.py opencv_hash.txt tests/golden/opencv_hash.npz
+    python tools/opencv_golden_to_npz.py --tmatch opencv_tmatch.txt tests/golden/opencv_tmatch.npz
 
+(the second form: the records T and Y the tool prints for a cases file, consumed by tests/test_opencv_golden_tmatch.py).
 Also home of gen_image(), the Python twin of the C++ tool's integer-only image generator: the npz stores outputs
 only, the tests regenerate the inputs from (w, h, seed)."""
 from __future__ import annotations
@@ -125,7 +127,52 @@ def parse(path: str) -> dict:
     return out
 
 
+def gen_image_channels(w: int, h: int, ch: int, seed: int) -> np.ndarray:
+    """u8 [h, w] (ch 1) or [h, w, ch]: channel c = gen_image(w, h, seed + c) -- tm_image() of the C++ tool"""
+    planes = [gen_image(w, h, seed + c) for c in range(ch)]
+    return planes[0] if ch == 1 else np.stack(planes, -1)
+
+
+def _f64(tokens):
+    return np.array([int(v, 16) for v in tokens], np.uint64).view(np.float64)
+
+
+def parse_tmatch(path: str) -> dict:
+    """records T (estimateRigidTransform) and Y (invertAffineTransform + warpAffine) -> a_k, b_k, m_k ([2, 3], or [0]
+    when no transform came back), ename_k; imgspec_k (w, h, channels, seed), wm_k, size_k (tw, th), patch_k, wname_k"""
+    out, ne, nw = {}, 0, 0
+    for line in open(path):
+        t = line.split()
+        if not t:
+            continue
+        if t[0] == "V":
+            out["cv_version"] = np.array(t[1])
+        elif t[0] == "T":
+            count = int(t[2])
+            pts = np.array([int(v, 16) for v in t[3: 3 + 4 * count]], np.uint32).view(np.float32).reshape(count, 4)
+            found = int(t[3 + 4 * count])
+            out[f"ename_{ne}"] = np.array(t[1])
+            out[f"a_{ne}"], out[f"b_{ne}"] = pts[:, :2].copy(), pts[:, 2:].copy()
+            out[f"m_{ne}"] = _f64(t[4 + 4 * count: 10 + 4 * count]).reshape(2, 3) if found == 1 else np.zeros(0)
+            ne += 1
+        elif t[0] == "Y":
+            w, h, ch, seed, tw, th = (int(v) for v in t[2:8])
+            out[f"wname_{nw}"] = np.array(t[1])
+            out[f"imgspec_{nw}"] = np.array([w, h, ch, seed], np.int64)  # the image: gen_image_channels(w, h, ch, seed)
+            out[f"wm_{nw}"] = _f64(t[8:14]).reshape(2, 3)
+            out[f"size_{nw}"] = np.array([tw, th], np.int32)
+            patch = np.frombuffer(bytes.fromhex(t[14]), np.uint8)
+            out[f"patch_{nw}"] = patch.reshape(th, tw) if ch == 1 else patch.reshape(th, tw, ch)
+            nw += 1
+    return out
+
+
 if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--tmatch":
+        d = parse_tmatch(sys.argv[2])
+        np.savez_compressed(sys.argv[3], **d)
+        print(f"{sum(k.startswith('a_') for k in d)} estimates, {sum(k.startswith('patch_') for k in d)} patches")
+        sys.exit(0)
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     d = parse(sys.argv[1])
