@@ -209,6 +209,14 @@ _SIGS = {
                                      _vp, _vp, _vp, _vp, _vp, C.c_int]),
     "cbh_template_match_dev": (C.c_int, [_vp, C.c_int, C.c_int, _sz, C.c_int, _vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp,
                                          _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "cbh_template_match_images": (C.c_int, [_vp, C.c_int, C.c_int, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp,
+                                            _vp, C.c_int]),
+    "cbh_template_match_images_dev": (C.c_int, [_vp, C.c_int, C.c_int, _sz, _vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp,
+                                                _vp, C.c_int, _vp]),
+    "cbh_resize_lanczos4_ragged_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "cbh_bgr2gray_ragged_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]),
+    "cbh_tm_match_points_dev": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, C.c_int, C.c_int, _vp, _vp, _vp, _sz, _vp,
+                                          C.c_int, _vp]),
     "cbh_vindexer_create": (_vp, [C.c_int, C.c_int, C.c_int]),
     "cbh_vindexer_destroy": (None, [_vp]),
     "cbh_vindexer_resume": (C.c_int, [_vp, _vp, _vp, _sz]),

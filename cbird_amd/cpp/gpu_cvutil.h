@@ -342,6 +342,55 @@ inline void gpuTemplateMatch(const cv::Mat& tmplImg, const std::vector<cv::Mat>&
   if (rc) qFatal("gpuTemplateMatch: %s (%s)", cbh_strerror(rc), cbh_last_error());
 }
 
+// TemplateMatcher::match from the decoded images to the score, src/templatematcher.cpp:113-374, for ALL candidates of one
+// template in one call that does not come back to the host between the upload and the results.  tmplImg / candImgs[i]:
+// what qImageToCvImg gave (:114, :173), 8-bit, one channel count for the template and the group; params: SearchParams
+// (any type with needleFeatures, haystackFeatures, cvThresh, tmScalePct).  Replaces
+//     tmplMedia.makeKeyPoints(tmplImg, params.needleFeatures, ...); makeKeyPointDescriptors(...)         (:118-121)
+//     cv::BFMatcher matcher(cv::NORM_HAMMING, true); matcher.add(haystack);                              (:134-138)
+// and, inside the loop over the candidates, everything from
+//     float candScale = 1.0; ... sizeScaleFactor(img, candScale);                                        (:182-192)
+//     m.makeKeyPoints(img, params.haystackFeatures, ...); m.makeKeyPointDescriptors(...)                  (:196-202)
+//     matcher.radiusMatch(queryDescriptors, dmatch, params.cvThresh);                                     (:217)
+//     ... the loops that fill matches, tmplPoints and matchPoints                                         (:221-250)
+// to hamm64(candHash, tmplHash) (:374; gpuTemplateMatch above lists :264-374) by one call in front of the loop:
+//     std::vector<cbh_tm_image_result> results;
+//     cbird_gpu::gpuTemplateMatchImages(tmplImg, candImgs, params, results);
+// The loop keeps what is the caller's: loading (:166-170), and per results[i].status the exits -- CBH_TM_NO_KEYPOINTS
+// continues without caching (:210-213); NO_MATCHES / FEW_POINTS / NO_TRANSFORM cache INT_MAX (:230-235, :255-260,
+// :268-273); SCORED takes .r.roi, .r.tx and .r.score (:294-320, :378-413); CBH_TM_NO_TEMPLATE_KEYPOINTS on every
+// candidate is the return of :127-130.  cbh_orb_set_pattern must have been called (ORB's test pairs are OpenCV's table).
+// (OpenCV parity of ORB, the estimate and the warp is unpinned: see include/cbird_hip.h.)
+template <class Params>
+inline void gpuTemplateMatchImages(const cv::Mat& tmplImg, const std::vector<cv::Mat>& candImgs, const Params& params,
+                                   std::vector<cbh_tm_image_result>& results) {
+  const size_t n = candImgs.size();
+  results.assign(n, cbh_tm_image_result());
+  if (n == 0) return;
+  if (tmplImg.depth() != CV_8U || tmplImg.rows <= 0 || tmplImg.cols <= 0)
+    qFatal("gpuTemplateMatchImages: expected a non-empty 8-bit template");
+  const int cn = tmplImg.channels();
+  std::vector<uint64_t> off;
+  std::vector<uint32_t> w, h, step;
+  std::vector<uint8_t> buf;
+  for (size_t i = 0; i < n; ++i) {
+    const cv::Mat& m = candImgs[i];
+    if (m.rows <= 0 || m.cols <= 0 || m.depth() != CV_8U || m.channels() != cn)
+      qFatal("gpuTemplateMatchImages: expected non-empty 8-bit candidates of the template's channel count");
+    const size_t row = size_t(m.cols) * size_t(cn);
+    off.push_back((buf.size() + 15) / 16 * 16);
+    buf.resize(size_t(off.back()) + row * size_t(m.rows));
+    for (int y = 0; y < m.rows; ++y) memcpy(buf.data() + off.back() + size_t(y) * row, m.ptr<uint8_t>(y), row);
+    w.push_back(uint32_t(m.cols)), h.push_back(uint32_t(m.rows)), step.push_back(uint32_t(row));
+  }
+  const cbh_tm_params p = {int32_t(params.needleFeatures), int32_t(params.haystackFeatures), int32_t(params.cvThresh),
+                           int32_t(params.tmScalePct)};
+  const int rc = cbh_template_match_images(tmplImg.data, tmplImg.cols, tmplImg.rows, size_t(tmplImg.step), buf.data(),
+                                           buf.size(), n, off.data(), w.data(), h.data(), step.data(), cn, &p,
+                                           results.data(), nullptr, hashDevice());
+  if (rc) qFatal("gpuTemplateMatchImages: %s (%s)", cbh_strerror(rc), cbh_last_error());
+}
+
 // qualityScore(const Media&) (src/cimgops.cpp:313-596) for images that are already decoded: 8-bit cv::Mat of 1, 3 (BGR)
 // or 4 (BGRA) channels, the layout loadImage / qImageToCvImg give.  Only the red channel takes part, as in the
 // reference (its crop keeps channel 0 of qImageToCImg's planes).  INT32_MIN = no score (no edges at all, or a side of 1,

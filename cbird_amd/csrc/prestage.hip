@@ -420,6 +420,13 @@ __global__ __launch_bounds__(256) void k_tm_mask(const unsigned char* __restrict
 
 }  // namespace
 
+namespace cbh {
+// the same tables for tmimages.hip's ragged resize: one host routine, so both kernels read identical coefficients
+void lanczos4_table(int ssize, int dsize, std::vector<int>* ofs, std::vector<short>* coef) {
+  lanczos4_tab(ssize, dsize, ofs, coef);
+}
+}  // namespace cbh
+
 extern "C" {
 
 int cbh_bgr2gray_dev(const void* d_src, size_t n, int w, int h, size_t row_stride, size_t img_stride,

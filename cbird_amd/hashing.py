@@ -277,3 +277,57 @@ def template_match(tmpl, cands, tmpl_points, match_points, cand_scales=None, pat
                                         a.ctypes.data, b.ctypes.data, first.ctypes.data, scales.ctypes.data,
                                         res.ctypes.data, out.ctypes.data if patches else None, device), "template_match")
     return (res, out) if patches else res
+
+
+# ---- TemplateMatcher::match from the decoded images to the score (src/templatematcher.cpp:105-374) --------------------
+TEMPLATE_IMAGE_RESULT_DTYPE = np.dtype([("r", TEMPLATE_RESULT_DTYPE), ("cand_scale", np.float32), ("status", np.int32),
+                                        ("w", np.int32), ("h", np.int32), ("n_keypoints", np.uint32),
+                                        ("n_matches", np.uint32)])  # struct cbh_tm_image_result
+TM_PARAMS_DTYPE = np.dtype([("needle_features", np.int32), ("haystack_features", np.int32), ("cv_thresh", np.int32),
+                            ("tm_scale_pct", np.int32)])  # struct cbh_tm_params
+assert TEMPLATE_IMAGE_RESULT_DTYPE.itemsize == 192 and TM_PARAMS_DTYPE.itemsize == 16
+(TM_SCORED, TM_NO_TEMPLATE_KEYPOINTS, TM_NO_KEYPOINTS, TM_NO_MATCHES, TM_FEW_POINTS, TM_NO_TRANSFORM,
+ TM_EMPTY_RESIZE) = range(7)  # CBH_TM_*
+
+
+def tm_params(params=None) -> np.ndarray:
+    """struct cbh_tm_params from a SearchParams (or anything with its template matcher fields); None = the defaults"""
+    from .index import SearchParams
+
+    p = SearchParams() if params is None else params
+    out = np.zeros(1, TM_PARAMS_DTYPE)
+    out[0] = (p.needleFeatures, p.haystackFeatures, p.cvThresh, p.tmScalePct)
+    return out
+
+
+def template_match_images(tmpl, cands, params=None, patches: bool = False, device: int = 0):
+    """TemplateMatcher::match from the decoded images to the score (src/templatematcher.cpp:105-374) for ONE template and
+    n candidate images (uint8, one channel count, the template's included; any sizes) in one call that does not come back
+    to the host between the upload and the results: the candidate's resize, ORB on both sides, the descriptor match, the
+    point lists, both rigid estimates, the warp, the masked hashes and their distance.  params: a SearchParams
+    (needleFeatures, haystackFeatures, cvThresh, tmScalePct).  Needs orb.set_pattern.  Returns
+    TEMPLATE_IMAGE_RESULT_DTYPE [n] (status TM_*; r.score = NO_TRANSFORM_SCORE unless TM_SCORED) and, with patches=True, the
+    warped patches uint8 [n, th, tw(, ch)]."""
+    from .quality import pack_images
+
+    tmpl = np.ascontiguousarray(tmpl, np.uint8)
+    imgs = [np.ascontiguousarray(im, np.uint8) for im in cands]
+    n = len(imgs)
+    res = np.zeros(n, TEMPLATE_IMAGE_RESULT_DTYPE)
+    if tmpl.ndim not in (2, 3) or tmpl.size == 0:
+        raise ValueError("expected a uint8 template [h, w] or [h, w, c]")
+    th, tw = tmpl.shape[:2]
+    tc = 1 if tmpl.ndim == 2 else tmpl.shape[2]
+    if n == 0:
+        return (res, np.zeros((0,) + tmpl.shape, np.uint8)) if patches else res
+    chs = {1 if im.ndim == 2 else im.shape[2] for im in imgs}
+    if chs != {tc} or tc not in (1, 3, 4) or any(im.size == 0 for im in imgs):
+        raise ValueError("expected non-empty uint8 images of the template's channel count: 1, 3 (BGR) or 4 (BGRA)")
+    p = tm_params(params)
+    buf, off, w, h, stride = pack_images(imgs)
+    out = np.zeros((n,) + tmpl.shape, np.uint8)
+    check(_lib.lib().cbh_template_match_images(tmpl.ctypes.data, tw, th, tw * tc, buf.ctypes.data, buf.size, n,
+                                               off.ctypes.data, w.ctypes.data, h.ctypes.data, stride.ctypes.data, tc,
+                                               p.ctypes.data, res.ctypes.data, out.ctypes.data if patches else None,
+                                               device), "template_match_images")
+    return (res, out) if patches else res

@@ -89,6 +89,12 @@ class SearchParams:
     expandGroups: bool = False
     mergeGroups: int = 0
     mirrorMask: int = 0       # Mirror* flags: also search the needle's reflections (-p.refl; database.query)
+    # the template matcher (src/index.h:79-91, defaults identical; cbird_amd/templatematcher.py reads them)
+    needleFeatures: int = 100     # number of needle / template features
+    haystackFeatures: int = 1000  # number of haystack / candidate features
+    tmThresh: int = 7             # threshold for match validation
+    tmScalePct: int = 200         # max scale factor between template and candidate
+    templateMatch: bool = False   # remove results that don't pass the template matcher
 
 
 def _as_u64(a) -> np.ndarray:

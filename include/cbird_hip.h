@@ -761,6 +761,78 @@ int cbh_template_match_dev(const void* d_tmpl, int tw, int th, size_t tmpl_row_s
                            const uint64_t* first, const float* cand_scale, void* d_results, void* d_patches, int device,
                            void* stream);
 
+/* ---- TemplateMatcher::match from the decoded images to the score (src/templatematcher.cpp:105-374) -------------------
+ * One template and n candidate images (8-bit, channels 1 / 3 = BGR / 4 = BGRA, one channel count per call, the template's
+ * included; ragged: the img_off / img_w / img_h / img_row_stride host tables of cbh_warp_affine_dev, sides up to 32767) ->
+ * one cbh_tm_image_result each, with no host round trip between the upload and the results but the keypoint counts and
+ * the match counts (cbh_orb_dev's and cbh_template_match_dev's host tables).  cbird_amd/csrc/tmimages.hip.
+ * UNPINNED where its parts are: the estimate, the warp (cbh_template_match above) and ORB (cbh_orb) are restated as
+ * recalled from OpenCV 2.4.13; the resize, the grey conversion, the descriptor match and the gather are integer / copy
+ * steps held to the oracle bit for bit.
+ * Per candidate (:161-414): candScale and the target size (:182-192; sizeScaleFactor, src/cvutil.cpp:1951-1956: areas
+ * compared as integers, maxSize = int(tSize * tm_scale_pct / 100.0), candScale = float(maxSize) / cSize, sides
+ * int(cols * candScale)); cv::resize(INTER_LANCZOS4) of every channel -- the resized image replaces the candidate for
+ * everything after it, the warp included (:190, :332); ORB of the grey view with haystack_features (:197-202; the template:
+ * needle_features, :120-121; ORB's own limit of 8192 pixels per side applies to the template and to the candidates as they
+ * reach it, CBH_E_INVAL beyond; needs cbh_orb_set_pattern); radiusMatch against the template's rows within cv_thresh
+ * (:217); the point lists (:221-250, from the keypoints as compute() left them); then cbh_template_match_dev.
+ * Host images go up, and device images are worked on, in runs of candidates that span at most "tmatch_chunk_mb". */
+typedef struct cbh_tm_params {
+  int32_t needle_features, haystack_features, cv_thresh, tm_scale_pct; /* src/index.h:76-84: 100, 1000, 25, 200 */
+} cbh_tm_params;
+enum {                              /* the exits of the reference's loop */
+  CBH_TM_SCORED = 0,
+  CBH_TM_NO_TEMPLATE_KEYPOINTS = 1, /* :127-130, every candidate of the call; cand_scale 1 and the candidate's own size */
+  CBH_TM_NO_KEYPOINTS = 2,          /* :210-213 (the reference continues without caching) */
+  CBH_TM_NO_MATCHES = 3,            /* :230-235 */
+  CBH_TM_FEW_POINTS = 4,            /* :255-260 */
+  CBH_TM_NO_TRANSFORM = 5,          /* :268-273; also a candidate outside the warp's domain (cbh_template_match) */
+  CBH_TM_EMPTY_RESIZE = 6           /* a resize target side of 0: the reference's cv::resize throws */
+};
+typedef struct cbh_tm_image_result {
+  cbh_template_result r;        /* as cbh_template_match gives it; score INT32_MAX unless status == CBH_TM_SCORED */
+  float cand_scale;             /* 1 when not resized */
+  int32_t status;
+  int32_t w, h;                 /* the candidate's size after the resize */
+  uint32_t n_keypoints, n_matches;
+} cbh_tm_image_result;
+/* images in host memory; patches: NULL or n x th x tw x channels */
+int cbh_template_match_images(const uint8_t* tmpl, int tw, int th, size_t tmpl_row_stride, const uint8_t* imgs,
+                              size_t imgs_bytes, size_t n, const uint64_t* img_off, const uint32_t* img_w,
+                              const uint32_t* img_h, const uint32_t* img_row_stride, int channels,
+                              const cbh_tm_params* params, cbh_tm_image_result* results, uint8_t* patches, int device);
+/* images (and d_patches: NULL or 16-byte aligned) in device memory; the size tables and the results are host memory.
+ * Returns with the stream synchronised. */
+int cbh_template_match_images_dev(const void* d_tmpl, int tw, int th, size_t tmpl_row_stride, const void* d_imgs, size_t n,
+                                  const uint64_t* img_off, const uint32_t* img_w, const uint32_t* img_h,
+                                  const uint32_t* img_row_stride, int channels, const cbh_tm_params* params,
+                                  cbh_tm_image_result* results, void* d_patches, int device, void* stream);
+/* Its stages.  All return with the stream synchronised (their tables are host memory).
+ * sizeScaleFactor's cv::resize(INTER_LANCZOS4) (src/cvutil.cpp:1955) for n ragged images, image i from img_w[i] x
+ * img_h[i] to dst_w[i] x dst_h[i], every channel with cbh_resize_lanczos4_dev's arithmetic; the results are packed
+ * (pitch dst_w * channels) at d_dst + dst_off[i], 16-byte aligned offsets the caller lays out. */
+int cbh_resize_lanczos4_ragged_dev(const void* d_src, size_t n, const uint64_t* img_off, const uint32_t* img_w,
+                                   const uint32_t* img_h, const uint32_t* img_row_stride, int channels,
+                                   const uint64_t* dst_off, const uint32_t* dst_w, const uint32_t* dst_h, void* d_dst,
+                                   int device, void* stream);
+/* cvtColor(BGR2GRAY / BGRA2GRAY) as ORB applies it to a colour input (channels 3 / 4; a grey image needs no copy): grey
+ * planes with pitch img_w[i] at d_dst + dst_off[i] (16-byte aligned) */
+int cbh_bgr2gray_ragged_dev(const void* d_src, size_t n, const uint64_t* img_off, const uint32_t* img_w, const uint32_t* img_h,
+                            const uint32_t* img_row_stride, int channels, const uint64_t* dst_off, void* d_dst, int device,
+                            void* stream);
+/* radiusMatch (:134, :217) and the point lists (:221-250) for n candidates as cbh_orb_dev left them: candidate i has
+ * min(d_counts[i], kp_cap) descriptor rows d_desc[(i * kp_cap + j) * 32] and points d_xy[2 * (i * kp_cap + j)] (kp_after);
+ * the train set is n_train template rows d_tmpl_desc / points d_tmpl_xy.  Every (query, train) pair with distance <=
+ * max_dist (0..256), grouped by candidate, inside a candidate by query row, inside a query ascending (distance, train
+ * row) -- cbh_idx256_radius_match's order.  first (host, n + 1): candidate i owns entries first[i] .. first[i + 1] of
+ * d_tmpl_pts / d_match_pts (x, y floats) and of d_records (NULL, or cbh_dmatch with query_idx = the row inside its
+ * candidate).  CBH_E_OVERFLOW with first complete and nothing written when first[n] > points_cap.  kp_cap <= 2^23,
+ * n_train <= 2^20, kp_cap * n_train < 2^32. */
+int cbh_tm_match_points_dev(const void* d_tmpl_desc, const void* d_tmpl_xy, size_t n_train, const void* d_desc,
+                            const void* d_xy, const void* d_counts, size_t n, int kp_cap, int max_dist, void* d_records,
+                            void* d_tmpl_pts, void* d_match_pts, size_t points_cap, uint64_t* first, int device,
+                            void* stream);
+
 /* ---- CvFeaturesIndex: src/cvfeaturesindex.{h,cpp} ---------------------------------------------------
  * N x 32-byte ORB/BRIEF descriptor rows (cv::Mat CV_8U, cvfeaturesindex.h:73) + the first-row -> mediaId
  * map (_indexMap/_idMap, :77-81).  Searches are exact brute force (the reference asks a FLANN LSH index,
@@ -816,7 +888,8 @@ int cbh_idx256_find_batch(cbh_idx256*, const uint8_t* needle_rows, const uint64_
  * with distance <= max_dist, grouped by query, each group in ascending (distance, train row) order (OpenCV: by
  * distance, ties unspecified).  out_first has nq + 1 entries; returns CBH_E_OVERFLOW (with out_first complete) when
  * cap is too small.  The steps after it (estimateRigidTransform's RANSAC, warpAffine, the score) are
- * cbh_template_match; gathering its point lists from these records and the keypoints is the caller's (:241-250). */
+ * cbh_template_match; gathering its point lists from these records and the keypoints is the caller's (:241-250) --
+ * or cbh_tm_match_points_dev's, which matches and gathers for a batch of candidates on the device. */
 typedef struct {
   int32_t query_idx, train_idx, distance; /* cv::DMatch::queryIdx, trainIdx, distance */
 } cbh_dmatch;
