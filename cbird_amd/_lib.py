@@ -96,6 +96,14 @@ _SIGS = {
     "cbh_quality_dims": (None, [C.c_int, C.c_int, _vp, _vp]),
     "cbh_quality_scores": (C.c_int, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int]),
     "cbh_quality_scores_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "cbh_gray_cuts": (C.c_int, [_vp, _sz, C.c_float, _vp, _vp]),
+    "cbh_auto_contrast_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int, _vp]),
+    "cbh_auto_contrast": (C.c_int, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int]),
+    "cbh_difference_dims": (C.c_int, [C.c_int, C.c_int, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cbh_difference_images_dev": (C.c_int, [_vp, C.c_int, C.c_int, _sz, C.c_int, _vp, _sz, _vp, _vp, _vp, _vp, C.c_int,
+                                            _vp, _vp, C.c_float, _vp, _vp, _vp, C.c_int, _vp]),
+    "cbh_difference_images": (C.c_int, [_vp, C.c_int, C.c_int, _sz, C.c_int, _vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int,
+                                        _vp, _vp, C.c_float, _vp, _sz, _vp, _vp, C.c_int]),
     "cbh_index_images": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, C.c_int]),
     "cbh_index_images_views": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,

@@ -10,6 +10,9 @@
 //                                                                                                  src/media.cpp:925-1037
 //   the scoring block of TemplateMatcher::match (mask, two dctHash64, hamm64)                     src/templatematcher.cpp:331-371
 //   int qualityScore(const Media&, QVector<QImage>* visuals = nullptr)   (decoded images, one or a group)   src/cimgops.cpp:313-596
+//   void brightnessAndContrastAuto(const cv::Mat& src, cv::Mat& dst, float clipHistPercent = 0)       src/cvutil.cpp:657-665
+//   static QImage differenceImage(const Media& ml, const Media& mr, ...)   (decoded images, one pair or a group)
+//                                                                                 src/gui/mediagrouplistwidget.cpp:106-208
 //
 // Same arguments and effects as the originals for 8-bit single-channel images (what Scanner::processImage passes
 // after grayscale(), src/scanner.cpp:859,876-889): the hash is returned, and with inPlace = true the blurred pixels
@@ -435,6 +438,105 @@ inline int gpuQualityScore(const cv::Mat& img) {
                                     &step, img.channels(), &score, nullptr, hashDevice());
   if (rc) qFatal("gpuQualityScore: %s (%s)", cbh_strerror(rc), cbh_last_error());
   return score;
+}
+
+// void brightnessAndContrastAuto(const cv::Mat& src, cv::Mat& dst, float clipHistPercent = 0)   src/cvutil.cpp:657-665
+// for CV_8UC1 / CV_8UC3 / CV_8UC4, read where it lies (a view's rows are read from its parent).  dst is replaced by a new
+// image of src's size and type; when no adjustment is possible (minGray >= maxGray) it is a copy where the reference
+// shares src's storage.  minGray / maxGray: what grayLevel found.  (convertTo's rounding is unpinned against OpenCV: see
+// include/cbird_hip.h.)
+inline void gpuBrightnessAndContrastAuto(const cv::Mat& src, cv::Mat& dst, float clipHistPercent = 0, int* minGray = nullptr,
+                                         int* maxGray = nullptr) {
+  if (src.rows <= 0 || src.cols <= 0 || (src.type() != CV_8UC1 && src.type() != CV_8UC3 && src.type() != CV_8UC4))
+    qFatal("gpuBrightnessAndContrastAuto: expected a non-empty 8-bit image of 1, 3 or 4 channels");
+  const uint64_t off = 0;
+  const uint32_t w = uint32_t(src.cols), h = uint32_t(src.rows), step = uint32_t(src.step);
+  const size_t row = size_t(w) * size_t(src.channels()), bytes = size_t(h - 1) * step + row;
+  std::vector<uint8_t> out(bytes);
+  int32_t cuts[2] = {0, 0};
+  const int rc = cbh_auto_contrast(src.data, bytes, 1, &off, &w, &h, &step, src.channels(), clipHistPercent, out.data(), cuts,
+                                   nullptr, hashDevice());
+  if (rc) qFatal("gpuBrightnessAndContrastAuto: %s (%s)", cbh_strerror(rc), cbh_last_error());
+  cv::Mat res(src.rows, src.cols, src.type());
+  for (int y = 0; y < src.rows; ++y) memcpy(res.ptr<uint8_t>(y), out.data() + size_t(y) * step, row);
+  dst = res;
+  if (minGray) *minGray = cuts[0];
+  if (maxGray) *maxGray = cuts[1];
+}
+
+// static QImage differenceImage(const Media& ml, const Media& mr, ...)   src/gui/mediagrouplistwidget.cpp:106-208
+// for images that are already decoded (8-bit cv::Mat of 1, 3 = BGR or 4 = BGRA channels, what qImageToCvImg gives), ONE
+// left image against all the right images of a group in one call.  results: NULL, or per right image the record the
+// template matcher returned (gpuTemplateMatch / gpuTemplateMatchImages' .r): .tx is the matrix Media::transform() holds
+// (:315-316; for a QTransform t: {t.m11(), t.m21(), t.dx(), t.m12(), t.m22(), t.dy()}) and is used where .tx_found is set
+// and it is not the identity (:114).  images[i] becomes a CV_8UC4 BGRA image, the bytes of the reference's Format_RGB32
+// picture; details[i] the record to rank the group by (include/cbird_hip.h).  The clip of 5 % is the reference's (:135).
+// (The aligned right image and QImage::scaled are unpinned against Qt, convertTo against OpenCV: see include/cbird_hip.h.)
+inline void gpuDifferenceImages(const cv::Mat& left, const std::vector<cv::Mat>& rights, const cbh_template_result* results,
+                                std::vector<cv::Mat>& images, std::vector<cbh_diff_detail>& details,
+                                float clipHistPercent = 5) {
+  images.assign(rights.size(), cv::Mat());
+  details.assign(rights.size(), cbh_diff_detail());
+  if (left.rows <= 0 || left.cols <= 0 || (left.type() != CV_8UC1 && left.type() != CV_8UC3 && left.type() != CV_8UC4))
+    qFatal("gpuDifferenceImages: expected a non-empty 8-bit left image of 1, 3 or 4 channels");
+  for (int cn : {1, 3, 4}) {
+    std::vector<size_t> which;
+    std::vector<uint64_t> off, outOff;
+    std::vector<uint32_t> w, h, step;
+    std::vector<uint8_t> buf, has;
+    std::vector<double> tx;
+    for (size_t i = 0; i < rights.size(); ++i) {
+      const cv::Mat& m = rights[i];
+      if (m.rows <= 0 || m.cols <= 0 || (m.type() != CV_8UC1 && m.type() != CV_8UC3 && m.type() != CV_8UC4))
+        qFatal("gpuDifferenceImages: expected non-empty 8-bit images of 1, 3 or 4 channels");
+      if (m.channels() != cn) continue;
+      const size_t row = size_t(m.cols) * size_t(cn);
+      off.push_back((buf.size() + 15) / 16 * 16);
+      buf.resize(size_t(off.back()) + row * size_t(m.rows));
+      for (int y = 0; y < m.rows; ++y) memcpy(buf.data() + off.back() + size_t(y) * row, m.ptr<uint8_t>(y), row);
+      which.push_back(i), w.push_back(uint32_t(m.cols)), h.push_back(uint32_t(m.rows)), step.push_back(uint32_t(row));
+      has.push_back(results && results[i].tx_found ? 1 : 0);
+      for (int k = 0; k < 6; ++k) tx.push_back(results ? results[i].tx[k] : 0.0);
+    }
+    if (which.empty()) continue;
+    const size_t n = which.size();
+    std::vector<uint32_t> ow(n), oh(n);
+    int rc = cbh_difference_dims(left.cols, left.rows, n, w.data(), h.data(), tx.data(), has.data(), ow.data(), oh.data(),
+                                 nullptr);
+    if (rc) qFatal("gpuDifferenceImages: %s", cbh_strerror(rc));
+    size_t total = 0;
+    for (size_t k = 0; k < n; ++k) {
+      outOff.push_back(total);
+      total += (size_t(ow[k]) * oh[k] * 4 + 15) / 16 * 16;
+    }
+    std::vector<uint8_t> out(total);
+    std::vector<cbh_diff_detail> det(n);
+    rc = cbh_difference_images(left.data, left.cols, left.rows, size_t(left.step), left.channels(), buf.data(), buf.size(), n,
+                               off.data(), w.data(), h.data(), step.data(), cn, tx.data(), has.data(), clipHistPercent,
+                               out.data(), out.size(), outOff.data(), det.data(), hashDevice());
+    if (rc) qFatal("gpuDifferenceImages: %s (%s)", cbh_strerror(rc), cbh_last_error());
+    for (size_t k = 0; k < n; ++k) {
+      cv::Mat img(int(oh[k]), int(ow[k]), CV_8UC4);
+      memcpy(img.data, out.data() + outOff[k], size_t(ow[k]) * oh[k] * 4);
+      images[which[k]] = img;
+      details[which[k]] = det[k];
+    }
+  }
+}
+
+// one pair; tx: NULL, or the six numbers of the right image's transform as above
+inline cv::Mat gpuDifferenceImage(const cv::Mat& left, const cv::Mat& right, const double* tx = nullptr,
+                                  cbh_diff_detail* detail = nullptr, float clipHistPercent = 5) {
+  cbh_template_result r = cbh_template_result();
+  if (tx) {
+    r.tx_found = 1;
+    for (int k = 0; k < 6; ++k) r.tx[k] = tx[k];
+  }
+  std::vector<cv::Mat> images;
+  std::vector<cbh_diff_detail> details;
+  gpuDifferenceImages(left, std::vector<cv::Mat>(1, right), tx ? &r : nullptr, images, details, clipHistPercent);
+  if (detail) *detail = details[0];
+  return images[0];
 }
 
 }  // namespace cbird_gpu

@@ -336,6 +336,7 @@ int get_quality_chunk_mb();
 int get_quality_strip_rows();      // "quality_strip_rows": rows one thread of the quality kernels walks
 void set_tmatch_chunk_mb(int v);   // tmatch.hip "tmatch_chunk_mb": MB one upload / one group's patches may take
 int get_tmatch_chunk_mb();
+int get_diff_block_pixels();       // diffimage.hip "diff_block_pixels": pixels of one grid a workgroup of its passes takes
 void set_color_fma(int on);        // color.hip "color_fma": fused squares in k_color_dist3 (default off: not bit-identical)
 int set_color_chunk_scores(int v);  // color.hip "color_chunk_scores": most score elements per chunk of the needle loops, 0 (default) = 2^28 / 2^27 / 2^27; < 0: CBH_E_INVAL, knob unchanged
 int get_color_chunk_scores();

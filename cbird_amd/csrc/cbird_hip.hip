@@ -1436,6 +1436,7 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strcmp(key, "quality_chunk_mb")) return *value = get_quality_chunk_mb(), CBH_OK;
   if (!strcmp(key, "quality_strip_rows")) return *value = get_quality_strip_rows(), CBH_OK;
   if (!strcmp(key, "tmatch_chunk_mb")) return *value = get_tmatch_chunk_mb(), CBH_OK;
+  if (!strcmp(key, "diff_block_pixels")) return *value = get_diff_block_pixels(), CBH_OK;
   if (!strcmp(key, "scan_probes")) return *value = get_scan_probes(), CBH_OK;
   if (!strcmp(key, "scan_joins")) return *value = get_scan_joins(), CBH_OK;
   if (!strcmp(key, "join_needle_preps")) return *value = get_join_needle_preps(), CBH_OK;

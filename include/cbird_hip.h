@@ -238,6 +238,78 @@ int cbh_quality_scores_dev(const void* d_imgs, size_t n, const uint64_t* img_off
                            void* d_detail /* NULL or n */, void* d_planes /* NULL or see above */,
                            const uint64_t* plane_off /* n, with d_planes */, int device, void* stream);
 
+/* ---- brightnessAndContrastAuto (src/cvutil.cpp:578-665) and differenceImage (src/gui/mediagrouplistwidget.cpp:98-208) --
+ * cbird_amd/csrc/diffimage.hip; tests/difference_rules.py is the numpy model the device is held to, bit for bit.  Images
+ * as everywhere above: the img_off / img_w / img_h / img_row_stride host tables of cbh_warp_affine_dev, channels 1 / 3 =
+ * BGR / 4 = BGRA, one channel count per call, sides 1 .. 32767, at most 2^20 images per call.  clip_pct >= 0, finite.
+ *
+ * EXACT restatements of the reference's own arithmetic: the cut rule (grayLevel, :578-626), the colour map (:173-206)
+ * and the size rule (:153-161: which side is scaled).  UNPINNED, restated without the library they come from:
+ *   - the stretch, Mat::convertTo(dst, -1, alpha, beta), as recalled from OpenCV 2.4.13: saturate_cast<uchar>(cvRound(
+ *     float(s) * alpha + beta)) with a float32 multiply, a float32 add and round-half-to-even;
+ *   - the aligned right image (QPainter::drawImage under QTransform::inverted): nearest neighbour at pixel centres in
+ *     f64 where Qt's raster engine samples in 16.16 fixed point, and B = G = R = 0 where the right image does not cover
+ *     the canvas, which the reference leaves uninitialised -- both are this library's definitions;
+ *   - QImage::scaled(size): nearest neighbour, aspect ignored, src = ((2 * dst + 1) * ssize) / (2 * dsize) in integers.
+ *
+ * The cut rule on given counts, in host memory and without a device: hist = n x 256 counts, count[j] = pixels of grey
+ * value j.  clip_pct == 0: the lowest and highest value present (256 / -1 when all counts are 0).  Otherwise acc[0] =
+ * float(count[0]), acc[i] = acc[i-1] + float(count[i]) in float32, max = acc[255], clip = (clip_pct * (max / 100.0f)) /
+ * 2.0f; min_gray = the first i with !(acc[i] < clip), 256 if none; max_gray = the last i with !(acc[i] >= max - clip),
+ * -1 if none.  The device runs the same function. */
+int cbh_gray_cuts(const uint32_t* hist, size_t n, float clip_pct, int32_t* min_gray, int32_t* max_gray);
+/* brightnessAndContrastAuto(src, dst, clip_pct) per image.  The histogram is that of the grey view (a one-channel image
+ * itself, cvtColor's fixed-point weights otherwise, alpha ignored); min_gray >= max_gray copies the image, otherwise
+ * alpha = 255 / float(max_gray - min_gray), beta = -min_gray * alpha and EVERY byte of every channel, alpha included
+ * (the reference's alpha restore is commented out, :647-653), goes through the stretch above.  UNPINNED: convertTo.
+ * d_out: NULL, or a buffer of d_imgs' layout that receives the pixels' bytes (nothing between them is written; it may be
+ * d_imgs); d_cuts: int32 2n, {min_gray, max_gray} per image; d_hist: NULL or u32 256 n.  Synchronises the stream. */
+int cbh_auto_contrast_dev(const void* d_imgs, size_t n, const uint64_t* img_off, const uint32_t* img_w,
+                          const uint32_t* img_h, const uint32_t* img_row_stride, int channels, float clip_pct, void* d_out,
+                          void* d_cuts, void* d_hist /* NULL or 256 n */, int device, void* stream);
+/* the same from and to host memory; out: NULL or imgs_bytes bytes, the bytes between the images copied from imgs */
+int cbh_auto_contrast(const uint8_t* imgs, size_t imgs_bytes, size_t n, const uint64_t* img_off, const uint32_t* img_w,
+                      const uint32_t* img_h, const uint32_t* img_row_stride, int channels, float clip_pct, uint8_t* out,
+                      int32_t* cuts /* 2n */, uint32_t* hist /* NULL or 256 n */, int device);
+/* differenceImage(left, right_i) for ONE left image (the needle or template) and n right images (the candidates).
+ *  1. Both sides as RGB32: grey replicated into B, G, R; the alpha of BGRA dropped (not premultiplied), alpha = 255.
+ *  2. Pair i is WARPED when tx != NULL, has_tx (NULL = all set) [i] != 0 and tx[6 * i ..], the 2 x 3 matrix template ->
+ *     right image that cbh_template_result.tx holds, is not exactly the identity: the right image is redrawn on a canvas
+ *     of the left image's size, canvas pixel (x, y) = the right image's pixel (sx, sy), sx = floor((a * (x + 0.5) + b *
+ *     (y + 0.5)) + c) in f64 without fusing, sy from the second row; 0 outside.  A matrix whose determinant a * e - b * d
+ *     is exactly 0 samples through the identity (QTransform::inverted returns it).  UNPINNED against Qt, see above.
+ *  3. cbh_auto_contrast's rule with clip_pct (the reference passes 5) on the left image and on the aligned right image
+ *     -- the zero fill of a canvas counts in its histogram, as in the reference.
+ *  4. area(aligned right) < area(left): the right side is scaled to the left's size, else the left side to the right's
+ *     (nearest neighbour as above; UNPINNED against QImage::scaled).
+ *  5. Per pixel sum = dr^2 + dg^2 + db^2; r = ((sum >> 10) << 1) & 255 (it wraps above 131071, as qRgb masks it),
+ *     g = ((sum >> 5) & 31) << 3, b = (sum & 31) << 3; the picture is BGRA, alpha 255.
+ * cbh_difference_dims gives each pair's output size (and whether it is warped) for the caller to lay out out_off.  The
+ * record has no counterpart in the reference: it ranks the pairs of a group without fetching n pictures. */
+typedef struct cbh_diff_detail {
+  uint64_t sum_total;                 /* sum over all output pixels */
+  uint32_t sum_max, n_ge32, n_ge1024; /* the largest sum; pixels with green set ("noticeable") / red set ("obvious") */
+  int32_t w, h, warped;               /* the output's size; 1 = the right image was redrawn through tx */
+  int32_t left_min, left_max, right_min, right_max; /* the cuts of both sides */
+} cbh_diff_detail;
+int cbh_difference_dims(int left_w, int left_h, size_t n, const uint32_t* img_w, const uint32_t* img_h,
+                        const double* tx /* NULL or 6n */, const uint8_t* has_tx /* NULL or n */, uint32_t* out_w,
+                        uint32_t* out_h, uint8_t* warped /* NULL or n */);
+/* images in device memory; the tables, tx and has_tx are host memory.  d_images: NULL (the record alone), or 16-byte
+ * aligned, picture i packed (pitch 4 * w) at out_off[i], a multiple of 16; d_detail: NULL or n records.  Synchronises
+ * the stream. */
+int cbh_difference_images_dev(const void* d_left, int left_w, int left_h, size_t left_row_stride, int left_channels,
+                              const void* d_rights, size_t n, const uint64_t* img_off, const uint32_t* img_w,
+                              const uint32_t* img_h, const uint32_t* img_row_stride, int channels, const double* tx,
+                              const uint8_t* has_tx, float clip_pct, void* d_images, const uint64_t* out_off,
+                              void* d_detail, int device, void* stream);
+/* the same from and to host memory; images: NULL or images_bytes bytes of which only the pictures are written */
+int cbh_difference_images(const uint8_t* left, int left_w, int left_h, size_t left_row_stride, int left_channels,
+                          const uint8_t* rights, size_t rights_bytes, size_t n, const uint64_t* img_off,
+                          const uint32_t* img_w, const uint32_t* img_h, const uint32_t* img_row_stride, int channels,
+                          const double* tx, const uint8_t* has_tx, float clip_pct, uint8_t* images, size_t images_bytes,
+                          const uint64_t* out_off, cbh_diff_detail* detail /* NULL or n */, int device);
+
 /* ---- the steps in front of dctHash64 in Scanner::processImage (src/scanner.cpp:852-862) -------------------
  * grayscale(): cv::cvtColor(BGR2GRAY/BGRA2GRAY) on 8-bit data (src/cvutil.cpp:1265-1283); d_gray is packed
  * n*w*h bytes. */
@@ -1050,7 +1122,8 @@ int cbh_set_tuning(const char* key, int value);
  * -- / answered from the candidate list, since the library loaded; needles without a match, and k = 0, count as neither;
  * read-only); "quality_chunk_mb" (the knob's value); "quality_strip_rows" (rows of
  * the working plane one thread of the quality kernels walks: their strips start at every multiple of it; read-only);
- * "tmatch_chunk_mb" (the knob's value). */
+ * "tmatch_chunk_mb" (the knob's value); "diff_block_pixels" (consecutive pixels of one image a workgroup of the
+ * difference-image passes takes: an image above it spans several workgroups; read-only). */
 int cbh_get_tuning(const char* key, long long* value);
 
 /* ---- measurement support ---------------------------------------------------------------- */
