@@ -514,6 +514,8 @@ int arena_counter(const char* name, long long* value) {
 }  // namespace cbh
 
 #include "cbh_index.h"
+#include "cbh_runs.h"
+#include "cbh_staging.h"
 
 namespace cbh {  // sharded.hip
 int sharded_load(cbh_idx64* idx, const void* hashes, const void* ids, size_t n, bool on_device, hipStream_t stream);
@@ -632,38 +634,22 @@ int cbh_dcthash_batch(const uint8_t* imgs, size_t n, int w, int h, size_t row_st
   size_t per_chunk = std::max<size_t>(1, ((size_t)256 << 20) / std::max<size_t>(img_stride, span1));
   per_chunk = std::min(per_chunk, n);
   const size_t chunk_bytes = (per_chunk - 1) * img_stride + span1;
-  uint8_t* d_imgs = nullptr;
-  uint64_t* d_out = nullptr;
-  hipStream_t s = nullptr;
-  int rc = CBH_OK;
-  hipError_t e;
-  if ((e = hipMalloc(&d_imgs, chunk_bytes)) != hipSuccess ||
-      (e = hipMalloc(&d_out, per_chunk * sizeof(uint64_t))) != hipSuccess ||
-      (e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess) {
-    set_last_error("dcthash_batch setup", e);
-    rc = e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-  }
+  Staging st("dcthash_batch");
+  uint8_t* d_imgs;
+  uint64_t* d_out;
+  st.alloc(&d_imgs, chunk_bytes);
+  st.alloc(&d_out, per_chunk * sizeof(uint64_t));
+  int rc = st.status();
   for (size_t i0 = 0; rc == CBH_OK && i0 < n; i0 += per_chunk) {
     const size_t m = std::min(per_chunk, n - i0);
-    const size_t bytes = (m - 1) * img_stride + span1;
-    if ((e = hipMemcpyAsync(d_imgs, imgs + i0 * img_stride, bytes, hipMemcpyHostToDevice, s)) !=
-        hipSuccess) {
-      set_last_error("hipMemcpyAsync(H2D images)", e);
-      rc = CBH_E_HIP;
-      break;
-    }
-    rc = launch_dcthash(d_imgs, m, w, h, row_stride, img_stride, d_out, s);
+    st.up(d_imgs, imgs + i0 * img_stride, (m - 1) * img_stride + span1);
+    if ((rc = st.status())) break;
+    rc = launch_dcthash(d_imgs, m, w, h, row_stride, img_stride, d_out, st.s);
     if (rc) break;
-    if ((e = hipMemcpyAsync(out + i0, d_out, m * sizeof(uint64_t), hipMemcpyDeviceToHost, s)) !=
-            hipSuccess ||
-        (e = hipStreamSynchronize(s)) != hipSuccess) {
-      set_last_error("dcthash_batch D2H", e);
-      rc = CBH_E_HIP;
-    }
+    st.down(out + i0, d_out, m * sizeof(uint64_t));
+    st.sync();
+    rc = st.status();
   }
-  if (s) cbh::stream_destroy(s);
-  if (d_imgs) (void)hipFree(d_imgs);
-  if (d_out) (void)hipFree(d_out);
   return rc;
 }
 
@@ -722,31 +708,19 @@ int rect_hashes_host(const uint8_t* imgs, size_t imgs_bytes, const std::vector<c
   }
   DeviceGuard g(device);
   if (!g.ok) return CBH_E_NODEVICE;
-  uint8_t* d_imgs = nullptr;
-  uint64_t* d_out = nullptr;
-  hipStream_t s = nullptr;
-  hipError_t e;
-  int rc = CBH_OK;
-  if ((e = hipMalloc(&d_imgs, imgs_bytes)) != hipSuccess ||
-      (e = hipMalloc(&d_out, total * sizeof(uint64_t))) != hipSuccess ||
-      (e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipMemcpyAsync(d_imgs, imgs, imgs_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) {
-    set_last_error("rect hashes setup", e);
-    rc = e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-  }
-  if (rc == CBH_OK) rc = launch_rect_hashes(d_imgs, images, rects, write_back, d_out, s);
-  if (rc == CBH_OK) {
-    if ((e = hipMemcpyAsync(out_hashes, d_out, total * sizeof(uint64_t), hipMemcpyDeviceToHost, s)) != hipSuccess ||
-        (imgs_after && (e = hipMemcpyAsync(imgs_after, d_imgs, imgs_bytes, hipMemcpyDeviceToHost, s)) != hipSuccess) ||
-        (e = hipStreamSynchronize(s)) != hipSuccess) {
-      set_last_error("rect hashes D2H", e);
-      rc = CBH_E_HIP;
-    }
-  }
-  if (s) cbh::stream_destroy(s);
-  if (d_imgs) (void)hipFree(d_imgs);
-  if (d_out) (void)hipFree(d_out);
-  return rc;
+  Staging st("rect hashes");
+  uint8_t* d_imgs;
+  uint64_t* d_out;
+  st.alloc(&d_imgs, imgs_bytes);
+  st.alloc(&d_out, total * sizeof(uint64_t));
+  st.up(d_imgs, imgs, imgs_bytes);
+  int rc = st.status();
+  if (rc == CBH_OK) rc = launch_rect_hashes(d_imgs, images, rects, write_back, d_out, st.s);
+  if (rc != CBH_OK) return rc;
+  st.down(out_hashes, d_out, total * sizeof(uint64_t));
+  if (imgs_after) st.down(imgs_after, d_imgs, imgs_bytes);
+  st.sync();
+  return st.status();
 }
 
 int check_images(size_t n, size_t imgs_bytes, const uint64_t* img_off, const uint32_t* img_w, const uint32_t* img_h,
@@ -754,8 +728,7 @@ int check_images(size_t n, size_t imgs_bytes, const uint64_t* img_off, const uin
   for (size_t i = 0; i < n; ++i) {
     if (img_w[i] == 0 || img_h[i] == 0 || img_w[i] > 8192 || img_h[i] > 8192 || img_row_stride[i] < img_w[i])
       return CBH_E_INVAL;
-    const unsigned long long end = img_off[i] + (unsigned long long)(img_h[i] - 1) * img_row_stride[i] + img_w[i];
-    if (end > imgs_bytes) return CBH_E_INVAL;
+    if (image_end(img_off[i], img_w[i], img_h[i], img_row_stride[i], 1) > imgs_bytes) return CBH_E_INVAL;
   }
   return CBH_OK;
 }
@@ -781,33 +754,21 @@ int cbh_keypoint_hashes(const uint8_t* imgs, size_t imgs_bytes, size_t n, const 
   if (nkp && !out_hashes) return CBH_E_INVAL;
   DeviceGuard g(device);
   if (!g.ok) return CBH_E_NODEVICE;
-  uint8_t* d_imgs = nullptr;
-  uint64_t* d_out = nullptr;
-  hipStream_t s = nullptr;
-  hipError_t e;
-  if ((e = hipMalloc(&d_imgs, imgs_bytes)) != hipSuccess ||
-      (e = hipMalloc(&d_out, std::max<size_t>(nkp, 1) * sizeof(uint64_t))) != hipSuccess ||
-      (e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipMemcpyAsync(d_imgs, imgs, imgs_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) {
-    set_last_error("keypoint_hashes setup", e);
-    rc = e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-  }
+  Staging st("keypoint_hashes");
+  uint8_t* d_imgs;
+  uint64_t* d_out;
+  st.alloc(&d_imgs, imgs_bytes);
+  st.alloc(&d_out, std::max<size_t>(nkp, 1) * sizeof(uint64_t));
+  st.up(d_imgs, imgs, imgs_bytes);
+  rc = st.status();
   if (rc == CBH_OK)
-    rc = launch_keypoint_hashes(d_imgs, n, img_off, img_w, img_h, img_row_stride, kp, kp_first, d_out, out_first, s);
-  if (rc == CBH_OK) {
-    const size_t total = out_first[n];
-    if ((total && (e = hipMemcpyAsync(out_hashes, d_out, total * sizeof(uint64_t), hipMemcpyDeviceToHost, s)) !=
-                      hipSuccess) ||
-        (imgs_after && (e = hipMemcpyAsync(imgs_after, d_imgs, imgs_bytes, hipMemcpyDeviceToHost, s)) != hipSuccess) ||
-        (e = hipStreamSynchronize(s)) != hipSuccess) {
-      set_last_error("keypoint_hashes D2H", e);
-      rc = CBH_E_HIP;
-    }
-  }
-  if (s) cbh::stream_destroy(s);
-  if (d_imgs) (void)hipFree(d_imgs);
-  if (d_out) (void)hipFree(d_out);
-  return rc;
+    rc = launch_keypoint_hashes(d_imgs, n, img_off, img_w, img_h, img_row_stride, kp, kp_first, d_out, out_first, st.s);
+  if (rc != CBH_OK) return rc;
+  const size_t total = out_first[n];
+  if (total) st.down(out_hashes, d_out, total * sizeof(uint64_t));
+  if (imgs_after) st.down(imgs_after, d_imgs, imgs_bytes);
+  st.sync();
+  return st.status();
 }
 
 int cbh_dcthash_rects(const uint8_t* imgs, size_t imgs_bytes, size_t n, const uint64_t* img_off,

@@ -26,6 +26,8 @@
 #include <vector>
 
 #include "cbh_index.h"
+#include "cbh_runs.h"
+#include "cbh_staging.h"
 
 namespace cbh {
 namespace {
@@ -1110,36 +1112,24 @@ int cbh_color_descriptors(const uint8_t* imgs, size_t imgs_bytes, size_t n, cons
     return CBH_E_INVAL;
   for (size_t i = 0; i < n; ++i)
     if (img_w[i] == 0 || img_h[i] == 0 ||
-        img_off[i] + (uint64_t)(img_h[i] - 1) * img_row_stride[i] + (uint64_t)img_w[i] * channels > imgs_bytes)
+        cbh::image_end(img_off[i], img_w[i], img_h[i], img_row_stride[i], channels) > imgs_bytes)
       return CBH_E_INVAL;
   cbh::DeviceGuard g(device);
   if (!g.ok) return CBH_E_NODEVICE;
-  hipStream_t s = nullptr;
-  uint8_t *d_imgs = nullptr, *d_descs = nullptr, *d_ok = nullptr;
-  hipError_t e;
-  int rc = CBH_OK;
-  if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipMalloc(&d_imgs, imgs_bytes)) != hipSuccess || (e = hipMalloc(&d_descs, n * 258)) != hipSuccess ||
-      (e = hipMalloc(&d_ok, n)) != hipSuccess ||
-      (e = hipMemcpyAsync(d_imgs, imgs, imgs_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) {
-    cbh::set_last_error("color descriptors setup", e);
-    rc = e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-  }
+  cbh::Staging st("color descriptors");
+  uint8_t *d_imgs, *d_descs, *d_ok;
+  st.alloc(&d_imgs, imgs_bytes);
+  st.alloc(&d_descs, n * 258);
+  st.alloc(&d_ok, n);
+  st.up(d_imgs, imgs, imgs_bytes);
+  int rc = st.status();
   if (rc == CBH_OK)
-    rc = cbh_color_descriptors_dev(d_imgs, n, img_off, img_w, img_h, img_row_stride, channels, d_descs, d_ok, device, s);
-  if (rc == CBH_OK) {
-    if ((e = hipMemcpyAsync(descs, d_descs, n * 258, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-        (e = hipStreamSynchronize(s)) != hipSuccess) {
-      cbh::set_last_error("color descriptors fetch", e);
-      rc = CBH_E_HIP;
-    }
-  }
-  if (s) (void)hipStreamSynchronize(s);
-  for (void* p : {(void*)d_imgs, (void*)d_descs, (void*)d_ok})
-    if (p) (void)hipFree(p);
-  if (s) cbh::stream_destroy(s);
-  return rc;
+    rc = cbh_color_descriptors_dev(d_imgs, n, img_off, img_w, img_h, img_row_stride, channels, d_descs, d_ok, device, st.s);
+  if (rc != CBH_OK) return rc;
+  st.down(descs, d_descs, n * 258);
+  st.down(ok, d_ok, n);
+  st.sync();
+  return st.status();
 }
 
 }  // extern "C"

@@ -23,6 +23,8 @@
 #include <vector>
 
 #include "cbh_index.h"
+#include "cbh_runs.h"
+#include "cbh_staging.h"
 #include "gray_px.h"
 
 namespace cbh {
@@ -324,7 +326,6 @@ __global__ __launch_bounds__(kBlock) void k_diff_color(const unsigned char* __re
 bool side_ok(uint32_t w, uint32_t h, uint32_t stride, int channels) {
   return w >= 1 && h >= 1 && w <= kMaxSide && h <= kMaxSide && stride >= w * (uint32_t)channels;
 }
-bool channels_ok(int c) { return c == 1 || c == 3 || c == 4; }
 bool clip_ok(float c) { return c >= 0.0f && std::isfinite(c); }
 
 DView direct_view(uint64_t off, uint32_t w, uint32_t h, uint32_t stride) {
@@ -361,13 +362,6 @@ DView on_grid(DView v, uint32_t ow, uint32_t oh) {
   return v;
 }
 
-template <class T>
-hipError_t upload(Scratch& scratch, T** d, const std::vector<T>& h, hipStream_t s) {
-  hipError_t e = scratch.get(d, std::max<size_t>(h.size(), 1) * sizeof(T));
-  if (e == hipSuccess && !h.empty()) e = hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s);
-  return e;
-}
-
 template <int CH>
 void launch_hist(const uint8_t* src, const DView* views, const DItem* items, size_t n_items, unsigned* hist, hipStream_t s) {
   if (n_items) hipLaunchKernelGGL(k_diff_hist<CH>, dim3((unsigned)n_items), dim3(kBlock), 0, s, src, views, items, hist);
@@ -384,11 +378,6 @@ void launch_color(int chr, unsigned ni, hipStream_t s, const uint8_t* l, const u
   if (chr == 1) hipLaunchKernelGGL((k_diff_color<CHL, 1>), dim3(ni), dim3(kBlock), 0, s, l, r, pairs, items, tables, images, detail);
   else if (chr == 3) hipLaunchKernelGGL((k_diff_color<CHL, 3>), dim3(ni), dim3(kBlock), 0, s, l, r, pairs, items, tables, images, detail);
   else hipLaunchKernelGGL((k_diff_color<CHL, 4>), dim3(ni), dim3(kBlock), 0, s, l, r, pairs, items, tables, images, detail);
-}
-
-int fail(const char* where, hipError_t e) {
-  set_last_error(where, e);
-  return e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
 }
 
 }  // namespace
@@ -462,36 +451,29 @@ int cbh_auto_contrast(const uint8_t* imgs, size_t imgs_bytes, size_t n, const ui
   if (!imgs || !img_off || !img_w || !img_h || !img_row_stride || !cuts) return CBH_E_INVAL;
   for (size_t i = 0; i < n; ++i)
     if (!side_ok(img_w[i], img_h[i], img_row_stride[i], channels) ||
-        img_off[i] + (uint64_t)(img_h[i] - 1) * img_row_stride[i] + (uint64_t)img_w[i] * channels > imgs_bytes)
+        image_end(img_off[i], img_w[i], img_h[i], img_row_stride[i], channels) > imgs_bytes)
       return CBH_E_INVAL;
   DeviceGuard g(device);
   if (!g.ok) return CBH_E_NODEVICE;
-  hipStream_t s = nullptr;
-  uint8_t* d_imgs = nullptr;
-  int32_t* d_cuts = nullptr;
+  Staging st("auto contrast");
+  uint8_t* d_imgs;
+  int32_t* d_cuts;
   uint32_t* d_hist = nullptr;
-  hipError_t e;
-  int rc = CBH_OK;
-  if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipMalloc(&d_imgs, imgs_bytes)) != hipSuccess || (e = hipMalloc(&d_cuts, n * 2 * sizeof(int32_t))) != hipSuccess ||
-      (hist && (e = hipMalloc(&d_hist, n * 256 * sizeof(uint32_t))) != hipSuccess) ||
-      (e = hipMemcpyAsync(d_imgs, imgs, imgs_bytes, hipMemcpyHostToDevice, s)) != hipSuccess)
-    rc = fail("auto contrast setup", e);
+  st.alloc(&d_imgs, imgs_bytes);
+  st.alloc(&d_cuts, n * 2 * sizeof(int32_t));
+  if (hist) st.alloc(&d_hist, n * 256 * sizeof(uint32_t));
+  st.up(d_imgs, imgs, imgs_bytes);
+  int rc = st.status();
   // (in place on the device copy: the bytes between the images come back as they went up)
   if (rc == CBH_OK)
     rc = cbh_auto_contrast_dev(d_imgs, n, img_off, img_w, img_h, img_row_stride, channels, clip_pct, out ? d_imgs : nullptr,
-                               d_cuts, d_hist, device, s);
-  if (rc == CBH_OK &&
-      ((out && (e = hipMemcpyAsync(out, d_imgs, imgs_bytes, hipMemcpyDeviceToHost, s)) != hipSuccess) ||
-       (e = hipMemcpyAsync(cuts, d_cuts, n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess ||
-       (hist && (e = hipMemcpyAsync(hist, d_hist, n * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s)) != hipSuccess) ||
-       (e = hipStreamSynchronize(s)) != hipSuccess))
-    rc = fail("auto contrast fetch", e);
-  if (s) (void)hipStreamSynchronize(s);
-  for (void* p : {(void*)d_imgs, (void*)d_cuts, (void*)d_hist})
-    if (p) (void)hipFree(p);
-  if (s) stream_destroy(s);
-  return rc;
+                               d_cuts, d_hist, device, st.s);
+  if (rc != CBH_OK) return rc;
+  if (out) st.down(out, d_imgs, imgs_bytes);
+  st.down(cuts, d_cuts, n * 2 * sizeof(int32_t));
+  if (hist) st.down(hist, d_hist, n * 256 * sizeof(uint32_t));
+  st.sync();
+  return st.status();
 }
 
 int cbh_difference_dims(int left_w, int left_h, size_t n, const uint32_t* img_w, const uint32_t* img_h, const double* tx,
@@ -598,7 +580,7 @@ int cbh_difference_images(const uint8_t* left, int left_w, int left_h, size_t le
   std::vector<uint32_t> ow(n), oh(n);
   for (size_t i = 0; i < n; ++i)
     if (!side_ok(img_w[i], img_h[i], img_row_stride[i], channels) ||
-        img_off[i] + (uint64_t)(img_h[i] - 1) * img_row_stride[i] + (uint64_t)img_w[i] * channels > rights_bytes)
+        image_end(img_off[i], img_w[i], img_h[i], img_row_stride[i], channels) > rights_bytes)
       return CBH_E_INVAL;
   if (cbh_difference_dims(left_w, left_h, n, img_w, img_h, tx, has_tx, ow.data(), oh.data(), nullptr) != CBH_OK)
     return CBH_E_INVAL;
@@ -608,36 +590,26 @@ int cbh_difference_images(const uint8_t* left, int left_w, int left_h, size_t le
   DeviceGuard g(device);
   if (!g.ok) return CBH_E_NODEVICE;
   const size_t left_bytes = (size_t)(left_h - 1) * left_row_stride + (size_t)left_w * left_channels;
-  hipStream_t s = nullptr;
-  uint8_t *d_left = nullptr, *d_rights = nullptr, *d_images = nullptr;
+  Staging st("difference images");
+  uint8_t *d_left, *d_rights, *d_images = nullptr;
   cbh_diff_detail* d_detail = nullptr;
-  hipError_t e;
-  int rc = CBH_OK;
-  if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipMalloc(&d_left, left_bytes)) != hipSuccess || (e = hipMalloc(&d_rights, rights_bytes)) != hipSuccess ||
-      (images && (e = hipMalloc(&d_images, std::max<size_t>(images_bytes, 16))) != hipSuccess) ||
-      (detail && (e = hipMalloc(&d_detail, n * sizeof(cbh_diff_detail))) != hipSuccess) ||
-      (e = hipMemcpyAsync(d_left, left, left_bytes, hipMemcpyHostToDevice, s)) != hipSuccess ||
-      (e = hipMemcpyAsync(d_rights, rights, rights_bytes, hipMemcpyHostToDevice, s)) != hipSuccess)
-    rc = fail("difference images setup", e);
+  st.alloc(&d_left, left_bytes);
+  st.alloc(&d_rights, rights_bytes);
+  if (images) st.alloc(&d_images, std::max<size_t>(images_bytes, 16));
+  if (detail) st.alloc(&d_detail, n * sizeof(cbh_diff_detail));
+  st.up(d_left, left, left_bytes);
+  st.up(d_rights, rights, rights_bytes);
+  int rc = st.status();
   if (rc == CBH_OK)
     rc = cbh_difference_images_dev(d_left, left_w, left_h, left_row_stride, left_channels, d_rights, n, img_off, img_w,
                                    img_h, img_row_stride, channels, tx, has_tx, clip_pct, d_images, out_off, d_detail,
-                                   device, s);
-  if (rc == CBH_OK) {
-    // each picture where the caller laid it out: the bytes between them are the caller's
-    for (size_t i = 0; i < n && images && e == hipSuccess; ++i)
-      e = hipMemcpyAsync(images + out_off[i], d_images + out_off[i], (size_t)ow[i] * oh[i] * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && detail)
-      e = hipMemcpyAsync(detail, d_detail, n * sizeof(cbh_diff_detail), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) rc = fail("difference images fetch", e);
-  }
-  if (s) (void)hipStreamSynchronize(s);
-  for (void* p : {(void*)d_left, (void*)d_rights, (void*)d_images, (void*)d_detail})
-    if (p) (void)hipFree(p);
-  if (s) stream_destroy(s);
-  return rc;
+                                   device, st.s);
+  if (rc != CBH_OK) return rc;
+  // each picture where the caller laid it out: the bytes between them are the caller's
+  for (size_t i = 0; i < n && images; ++i) st.down(images + out_off[i], d_images + out_off[i], (size_t)ow[i] * oh[i] * 4);
+  if (detail) st.down(detail, d_detail, n * sizeof(cbh_diff_detail));
+  st.sync();
+  return st.status();
 }
 
 }  // extern "C"

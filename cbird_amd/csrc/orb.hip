@@ -39,6 +39,8 @@
 #include <vector>
 
 #include "cbh_index.h"
+#include "cbh_runs.h"
+#include "cbh_staging.h"
 
 namespace cbh {
 namespace {
@@ -1374,45 +1376,33 @@ int cbh_orb(const uint8_t* imgs, size_t imgs_bytes, size_t n, const uint64_t* im
   if (!imgs || !kp || !counts || kp_cap < 1) return CBH_E_INVAL;
   for (size_t i = 0; i < n; ++i)
     if (!img_off || !img_w || !img_h || !img_row_stride ||
-        img_off[i] + (uint64_t)(img_h[i] - 1) * img_row_stride[i] + img_w[i] > imgs_bytes)
+        cbh::image_end(img_off[i], img_w[i], img_h[i], img_row_stride[i], 1) > imgs_bytes)
       return CBH_E_INVAL;
   cbh::DeviceGuard g(device);
   if (!g.ok) return CBH_E_NODEVICE;
-  hipStream_t s = nullptr;
-  uint8_t *d_imgs = nullptr, *d_desc = nullptr;
-  cbh_keypoint* d_kp = nullptr;
+  cbh::Staging st("orb");
+  uint8_t *d_imgs, *d_desc = nullptr;
+  cbh_keypoint* d_kp;
   float* d_after = nullptr;
-  uint32_t* d_counts = nullptr;
+  uint32_t* d_counts;
   const size_t slots = n * (size_t)kp_cap;
-  hipError_t e;
-  int rc = CBH_OK;
-  if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipMalloc(&d_imgs, imgs_bytes)) != hipSuccess || (e = hipMalloc(&d_kp, slots * sizeof(cbh_keypoint))) != hipSuccess ||
-      (kp_after && (e = hipMalloc(&d_after, slots * 2 * sizeof(float))) != hipSuccess) ||
-      (desc && (e = hipMalloc(&d_desc, slots * 32)) != hipSuccess) ||
-      (e = hipMalloc(&d_counts, n * sizeof(uint32_t))) != hipSuccess ||
-      (e = hipMemcpyAsync(d_imgs, imgs, imgs_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) {
-    cbh::set_last_error("orb setup", e);
-    rc = e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-  }
+  st.alloc(&d_imgs, imgs_bytes);
+  st.alloc(&d_kp, slots * sizeof(cbh_keypoint));
+  if (kp_after) st.alloc(&d_after, slots * 2 * sizeof(float));
+  if (desc) st.alloc(&d_desc, slots * 32);
+  st.alloc(&d_counts, n * sizeof(uint32_t));
+  st.up(d_imgs, imgs, imgs_bytes);
+  int rc = st.status();
   if (rc == CBH_OK)
     rc = cbh_orb_dev(d_imgs, n, img_off, img_w, img_h, img_row_stride, nfeatures, kp_cap, d_kp, d_after, d_desc, d_counts,
-                     device, s);
-  if (rc == CBH_OK) {
-    if ((e = hipMemcpyAsync(kp, d_kp, slots * sizeof(cbh_keypoint), hipMemcpyDeviceToHost, s)) != hipSuccess ||
-        (kp_after && (e = hipMemcpyAsync(kp_after, d_after, slots * 2 * sizeof(float), hipMemcpyDeviceToHost, s)) != hipSuccess) ||
-        (desc && (e = hipMemcpyAsync(desc, d_desc, slots * 32, hipMemcpyDeviceToHost, s)) != hipSuccess) ||
-        (e = hipMemcpyAsync(counts, d_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s)) != hipSuccess ||
-        (e = hipStreamSynchronize(s)) != hipSuccess) {
-      cbh::set_last_error("orb fetch", e);
-      rc = CBH_E_HIP;
-    }
-  }
-  if (s) (void)hipStreamSynchronize(s);
-  for (void* p : {(void*)d_imgs, (void*)d_kp, (void*)d_after, (void*)d_desc, (void*)d_counts})
-    if (p) (void)hipFree(p);
-  if (s) cbh::stream_destroy(s);
-  return rc;
+                     device, st.s);
+  if (rc != CBH_OK) return rc;
+  st.down(kp, d_kp, slots * sizeof(cbh_keypoint));
+  if (kp_after) st.down(kp_after, d_after, slots * 2 * sizeof(float));
+  if (desc) st.down(desc, d_desc, slots * 32);
+  st.down(counts, d_counts, n * sizeof(uint32_t));
+  st.sync();
+  return st.status();
 }
 
 int cbh_orb_describe(const uint8_t* imgs, size_t imgs_bytes, size_t n, const uint64_t* img_off, const uint32_t* img_w,
@@ -1426,26 +1416,18 @@ int cbh_orb_describe(const uint8_t* imgs, size_t imgs_bytes, size_t n, const uin
   if (kp_first[n] && (!kp || !out_kp || !out_desc)) return CBH_E_INVAL;
   for (size_t i = 0; i < n; ++i)
     if (kp_first[i + 1] < kp_first[i] || img_w[i] == 0 || img_h[i] == 0 || img_w[i] > 8192 || img_h[i] > 8192 ||
-        img_row_stride[i] < img_w[i] || img_off[i] + (uint64_t)(img_h[i] - 1) * img_row_stride[i] + img_w[i] > imgs_bytes)
+        img_row_stride[i] < img_w[i] || cbh::image_end(img_off[i], img_w[i], img_h[i], img_row_stride[i], 1) > imgs_bytes)
       return CBH_E_INVAL;
   cbh::DeviceGuard g(device);
   if (!g.ok) return CBH_E_NODEVICE;
-  hipStream_t s = nullptr;
-  uint8_t* d_imgs = nullptr;
-  hipError_t e;
-  int rc = CBH_OK;
-  if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipMalloc(&d_imgs, imgs_bytes)) != hipSuccess ||
-      (e = hipMemcpyAsync(d_imgs, imgs, imgs_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) {
-    cbh::set_last_error("orb describe setup", e);
-    rc = e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-  }
+  cbh::Staging st("orb describe");
+  uint8_t* d_imgs;
+  st.alloc(&d_imgs, imgs_bytes);
+  st.up(d_imgs, imgs, imgs_bytes);
+  int rc = st.status();
   if (rc == CBH_OK)
     rc = cbh::launch_orb_describe(d_imgs, n, img_off, img_w, img_h, img_row_stride, kp, kp_first, out_kp, out_desc,
-                                  out_first, s);
-  if (s) (void)hipStreamSynchronize(s);
-  if (d_imgs) (void)hipFree(d_imgs);
-  if (s) cbh::stream_destroy(s);
+                                  out_first, st.s);
   return rc;
 }
 

@@ -8,6 +8,8 @@
 #include <vector>
 
 #include "cbh_index.h"
+#include "cbh_runs.h"
+#include "cbh_staging.h"
 #include "gray_px.h"
 
 namespace {
@@ -494,7 +496,7 @@ int cbh_process_images_ex(const uint8_t* imgs, size_t n, int w, int h, size_t ro
   if (resize_size < 0 || resize_size > 8192 || (resize_size > 0 && n && (!resized || !resized_dims))) return CBH_E_INVAL;
   if (!cbh::device_usable(device)) return CBH_E_NODEVICE;
   if (n == 0) return CBH_OK;
-  if (!imgs || !out || w <= 0 || h <= 0 || (channels != 1 && channels != 3 && channels != 4) ||
+  if (!imgs || !out || w <= 0 || h <= 0 || !cbh::channels_ok(channels) ||
       row_stride < (size_t)w * channels)
     return CBH_E_INVAL;
   cbh::DeviceGuard g(device);
@@ -502,36 +504,23 @@ int cbh_process_images_ex(const uint8_t* imgs, size_t n, int w, int h, size_t ro
   const size_t span1 = (size_t)(h - 1) * row_stride + (size_t)w * channels;
   size_t per_chunk = std::max<size_t>(1, ((size_t)256 << 20) / std::max(img_stride, span1));
   per_chunk = std::min(per_chunk, n);
-  uint8_t *d_src = nullptr, *d_gray = nullptr, *d_res = nullptr;
-  uint64_t* d_out = nullptr;
-  int* d_rects = nullptr;
-  hipStream_t s = nullptr;
-  int rc = CBH_OK;
+  cbh::Staging st("process images");
+  hipStream_t s = st.s;
+  uint8_t *d_src, *d_gray = nullptr, *d_res = nullptr;
+  uint64_t* d_out;
+  int* d_rects;
   const size_t slot = (size_t)resize_size * (size_t)resize_size;
-  auto cleanup = [&]() {
-    if (s) cbh::stream_destroy(s);
-    for (void* p : {(void*)d_src, (void*)d_gray, (void*)d_out, (void*)d_rects, (void*)d_res})
-      if (p) (void)hipFree(p);
-  };
-#define CBH_TRY(call)                       \
-  do {                                      \
-    hipError_t e_ = (call);                 \
-    if (e_ != hipSuccess) {                 \
-      cbh::set_last_error(#call, e_);       \
-      cleanup();                            \
-      return e_ == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP; \
-    }                                       \
-  } while (0)
-  CBH_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  CBH_TRY(hipMalloc(&d_src, (per_chunk - 1) * img_stride + span1));
-  if (channels != 1) CBH_TRY(hipMalloc(&d_gray, per_chunk * (size_t)w * h));
-  CBH_TRY(hipMalloc(&d_out, per_chunk * sizeof(uint64_t)));
-  CBH_TRY(hipMalloc(&d_rects, per_chunk * 4 * sizeof(int)));
-  if (resize_size > 0) CBH_TRY(hipMalloc(&d_res, per_chunk * slot));
+  st.alloc(&d_src, (per_chunk - 1) * img_stride + span1);
+  if (channels != 1) st.alloc(&d_gray, per_chunk * (size_t)w * h);
+  st.alloc(&d_out, per_chunk * sizeof(uint64_t));
+  st.alloc(&d_rects, per_chunk * 4 * sizeof(int));
+  if (resize_size > 0) st.alloc(&d_res, per_chunk * slot);
+  int rc = st.status();
   std::vector<int> hr(per_chunk * 4);
   for (size_t i0 = 0; rc == CBH_OK && i0 < n; i0 += per_chunk) {
     const size_t m = std::min(per_chunk, n - i0);
-    CBH_TRY(hipMemcpyAsync(d_src, imgs + i0 * img_stride, (m - 1) * img_stride + span1, hipMemcpyHostToDevice, s));
+    st.up(d_src, imgs + i0 * img_stride, (m - 1) * img_stride + span1);
+    if ((rc = st.status())) break;
     const uint8_t* gray = d_src;
     size_t gs = row_stride, gi = img_stride;
     if (channels != 1) {
@@ -545,8 +534,9 @@ int cbh_process_images_ex(const uint8_t* imgs, size_t n, int w, int h, size_t ro
     if (autocrop_range >= 0) {
       rc = cbh_autocrop_dev(gray, m, w, h, gs, gi, autocrop_range, d_rects, device, s);
       if (rc) break;
-      CBH_TRY(hipMemcpyAsync(hr.data(), d_rects, m * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-      CBH_TRY(hipStreamSynchronize(s));
+      st.down(hr.data(), d_rects, m * 4 * sizeof(int));
+      st.sync();
+      if ((rc = st.status())) break;
       for (size_t i = 0; i < m; ++i)
         cropped |= hr[i * 4] != 0 || hr[i * 4 + 1] != 0 || hr[i * 4 + 2] != w || hr[i * 4 + 3] != h;
     } else {
@@ -590,17 +580,18 @@ int cbh_process_images_ex(const uint8_t* imgs, size_t n, int w, int h, size_t ro
         rc = cbh_resize_lanczos4_dev(gray + i * gi + (size_t)r[1] * gs + r[0], run, r[2] - r[0], r[3] - r[1], gs, gi,
                                      dw, dh, d_res + i * slot, device, s);
         if (rc) break;
-        CBH_TRY(hipMemcpy2DAsync(resized + (i0 + i) * slot, slot, d_res + i * slot, (size_t)dw * dh, (size_t)dw * dh,
-                                 run, hipMemcpyDeviceToHost, s));
+        // (a pitched copy, which Staging does not have: slot i of the caller's buffer gets its image packed)
+        const hipError_t e = hipMemcpy2DAsync(resized + (i0 + i) * slot, slot, d_res + i * slot, (size_t)dw * dh,
+                                              (size_t)dw * dh, run, hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) rc = cbh::fail("process images fetch", e);
       }
       if (rc) break;
     }
-    CBH_TRY(hipMemcpyAsync(out + i0, d_out, m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    CBH_TRY(hipStreamSynchronize(s));
+    st.down(out + i0, d_out, m * sizeof(uint64_t));
+    st.sync();
+    if ((rc = st.status())) break;
     if (rects) memcpy(rects + i0 * 4, hr.data(), m * 4 * sizeof(int));
   }
-#undef CBH_TRY
-  cleanup();
   return rc;
 }
 
@@ -611,9 +602,8 @@ int cbh_template_hashes_dev(const void* d_cands, size_t n, int w, int h, size_t 
                             void* d_cand_hashes, void* d_tmpl_hashes, int device, void* stream) {
   if (!cbh::device_usable(device)) return CBH_E_NODEVICE;
   if (n == 0) return CBH_OK;
-  auto ch_ok = [](int c) { return c == 1 || c == 3 || c == 4; };
-  if (!d_cands || !d_tmpl || !d_cand_hashes || !d_tmpl_hashes || w <= 0 || h <= 0 || !ch_ok(cand_channels) ||
-      !ch_ok(tmpl_channels) || cand_row_stride < (size_t)w * cand_channels || tmpl_row_stride < (size_t)w * tmpl_channels)
+  if (!d_cands || !d_tmpl || !d_cand_hashes || !d_tmpl_hashes || w <= 0 || h <= 0 || !cbh::channels_ok(cand_channels) ||
+      !cbh::channels_ok(tmpl_channels) || cand_row_stride < (size_t)w * cand_channels || tmpl_row_stride < (size_t)w * tmpl_channels)
     return CBH_E_INVAL;
   cbh::DeviceGuard g(device);
   if (!g.ok) return CBH_E_NODEVICE;
@@ -657,47 +647,32 @@ int cbh_template_scores(const uint8_t* cands, size_t n, int w, int h, size_t can
   const size_t tspan = (size_t)(h - 1) * tmpl_row_stride + (size_t)w * tmpl_channels;
   cbh::DeviceGuard g(device);
   if (!g.ok) return CBH_E_NODEVICE;
-  hipStream_t s = nullptr;
-  unsigned char *d_c = nullptr, *d_t = nullptr;
-  uint64_t* d_h = nullptr;
-  auto cleanup = [&]() {
-    if (s) cbh::stream_destroy(s);
-    for (void* p : {(void*)d_c, (void*)d_t, (void*)d_h})
-      if (p) (void)hipFree(p);
-  };
-#define CBH_TRY(call)                       \
-  do {                                      \
-    hipError_t e_ = (call);                 \
-    if (e_ != hipSuccess) {                 \
-      cbh::set_last_error(#call, e_);       \
-      cleanup();                            \
-      return e_ == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP; \
-    }                                       \
-  } while (0)
-  CBH_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  cbh::Staging st("template scores");
+  unsigned char *d_c, *d_t;
+  uint64_t* d_h;
   const size_t per = std::min(n, std::max<size_t>(1, ((size_t)256 << 20) / std::max(cis, cspan)));
-  CBH_TRY(hipMalloc(&d_c, (per - 1) * cis + cspan));
-  CBH_TRY(hipMalloc(&d_t, tspan));
-  CBH_TRY(hipMalloc(&d_h, 2 * per * sizeof(uint64_t)));
-  CBH_TRY(hipMemcpyAsync(d_t, tmpl, tspan, hipMemcpyHostToDevice, s));
+  st.alloc(&d_c, (per - 1) * cis + cspan);
+  st.alloc(&d_t, tspan);
+  st.alloc(&d_h, 2 * per * sizeof(uint64_t));
+  st.up(d_t, tmpl, tspan);
   std::vector<uint64_t> hh(2 * per);
-  int rc = CBH_OK;
-  for (size_t i0 = 0; i0 < n; i0 += per) {
+  int rc = st.status();
+  for (size_t i0 = 0; rc == CBH_OK && i0 < n; i0 += per) {
     const size_t m = std::min(per, n - i0);
-    CBH_TRY(hipMemcpyAsync(d_c, cands + i0 * cis, (m - 1) * cis + cspan, hipMemcpyHostToDevice, s));
+    st.up(d_c, cands + i0 * cis, (m - 1) * cis + cspan);
+    if ((rc = st.status())) break;
     rc = cbh_template_hashes_dev(d_c, m, w, h, cand_row_stride, cis, cand_channels, d_t, tmpl_row_stride, tmpl_channels,
-                                 d_h, d_h + per, device, s);
+                                 d_h, d_h + per, device, st.s);
     if (rc) break;
-    CBH_TRY(hipMemcpyAsync(hh.data(), d_h, 2 * per * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    CBH_TRY(hipStreamSynchronize(s));
+    st.down(hh.data(), d_h, 2 * per * sizeof(uint64_t));
+    st.sync();
+    if ((rc = st.status())) break;
     for (size_t i = 0; i < m; ++i) {
       scores[i0 + i] = __builtin_popcountll(hh[i] ^ hh[per + i]);
       if (cand_hashes) cand_hashes[i0 + i] = hh[i];
       if (tmpl_hashes) tmpl_hashes[i0 + i] = hh[per + i];
     }
   }
-#undef CBH_TRY
-  cleanup();
   return rc;
 }
 
@@ -771,38 +746,22 @@ int cbh_size_longest_side(const uint8_t* imgs, size_t n, int w, int h, size_t ro
   const size_t span1 = (size_t)(h - 1) * row_stride + (size_t)w;
   size_t per_chunk = std::max<size_t>(1, ((size_t)256 << 20) / std::max(img_stride, span1));
   per_chunk = std::min<size_t>(std::min(per_chunk, n), 65535);
-  uint8_t *d_src = nullptr, *d_dst = nullptr;
-  hipStream_t s = nullptr;
-  int rc = CBH_OK;
-  hipError_t e;
-  if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipMalloc(&d_src, (per_chunk - 1) * img_stride + span1)) != hipSuccess ||
-      (e = hipMalloc(&d_dst, per_chunk * (size_t)dw * dh)) != hipSuccess) {
-    cbh::set_last_error("size_longest_side setup", e);
-    rc = e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-  }
+  cbh::Staging st("size_longest_side");
+  uint8_t *d_src, *d_dst;
+  st.alloc(&d_src, (per_chunk - 1) * img_stride + span1);
+  st.alloc(&d_dst, per_chunk * (size_t)dw * dh);
+  int rc = st.status();
   for (size_t i0 = 0; rc == CBH_OK && i0 < n; i0 += per_chunk) {
     const size_t m = std::min(per_chunk, n - i0);
-    if ((e = hipMemcpyAsync(d_src, imgs + i0 * img_stride, (m - 1) * img_stride + span1, hipMemcpyHostToDevice, s)) !=
-        hipSuccess) {
-      cbh::set_last_error("size_longest_side H2D", e);
-      rc = CBH_E_HIP;
-      break;
-    }
-    rc = cbh_resize_lanczos4_dev(d_src, m, w, h, row_stride, img_stride, dw, dh, d_dst, device, s);
+    st.up(d_src, imgs + i0 * img_stride, (m - 1) * img_stride + span1);
+    if ((rc = st.status())) break;
+    rc = cbh_resize_lanczos4_dev(d_src, m, w, h, row_stride, img_stride, dw, dh, d_dst, device, st.s);
     if (rc) break;
-    if ((e = hipMemcpyAsync(out + i0 * (size_t)dw * dh, d_dst, m * (size_t)dw * dh, hipMemcpyDeviceToHost, s)) !=
-            hipSuccess ||
-        (e = hipStreamSynchronize(s)) != hipSuccess) {
-      cbh::set_last_error("size_longest_side D2H", e);
-      rc = CBH_E_HIP;
-    }
+    st.down(out + i0 * (size_t)dw * dh, d_dst, m * (size_t)dw * dh);
+    st.sync();
+    rc = st.status();
   }
-  if (s) cbh::stream_destroy(s);
-  if (d_src) (void)hipFree(d_src);
-  if (d_dst) (void)hipFree(d_dst);
   return rc;
 }
-
 
 }  // extern "C"

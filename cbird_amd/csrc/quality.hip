@@ -24,6 +24,8 @@
 #include <vector>
 
 #include "cbh_index.h"
+#include "cbh_runs.h"
+#include "cbh_staging.h"
 
 namespace cbh {
 namespace {
@@ -394,11 +396,7 @@ int launch_quality_group(const uint8_t* d_imgs, size_t m, const uint64_t* img_of
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(s);  // the host tables above must outlive the copies
-  if (e != hipSuccess) {
-    set_last_error("quality scores", e);
-    return e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-  }
-  return CBH_OK;
+  return e == hipSuccess ? CBH_OK : fail("quality scores", e);
 }
 
 bool quality_shape_ok(uint32_t w, uint32_t h, uint32_t stride, int channels) {
@@ -434,7 +432,7 @@ int cbh_quality_scores_dev(const void* d_imgs, size_t n, const uint64_t* img_off
   if (!cbh::device_usable(device)) return CBH_E_NODEVICE;
   if (n == 0) return CBH_OK;
   if (!d_imgs || !img_off || !img_w || !img_h || !img_row_stride || !d_scores || (d_planes && !plane_off) ||
-      (channels != 1 && channels != 3 && channels != 4) || n > (1u << 24))
+      !cbh::channels_ok(channels) || n > (1u << 24))
     return CBH_E_INVAL;
   for (size_t i = 0; i < n; ++i)
     if (!cbh::quality_shape_ok(img_w[i], img_h[i], img_row_stride[i], channels)) return CBH_E_INVAL;
@@ -467,75 +465,43 @@ int cbh_quality_scores(const uint8_t* imgs, size_t imgs_bytes, size_t n, const u
   if (!cbh::device_usable(device)) return CBH_E_NODEVICE;
   if (n == 0) return CBH_OK;
   if (!imgs || !scores || !img_off || !img_w || !img_h || !img_row_stride ||
-      (channels != 1 && channels != 3 && channels != 4))
+      !cbh::channels_ok(channels))
     return CBH_E_INVAL;
   std::vector<uint64_t> end(n);
   for (size_t i = 0; i < n; ++i) {
     if (!cbh::quality_shape_ok(img_w[i], img_h[i], img_row_stride[i], channels)) return CBH_E_INVAL;
-    end[i] = img_off[i] + (uint64_t)(img_h[i] - 1) * img_row_stride[i] + (uint64_t)img_w[i] * channels;
+    end[i] = cbh::image_end(img_off[i], img_w[i], img_h[i], img_row_stride[i], channels);
     if (end[i] > imgs_bytes) return CBH_E_INVAL;
   }
   cbh::DeviceGuard g(device);
   if (!g.ok) return CBH_E_NODEVICE;
   // uploads of at most "quality_chunk_mb" each: runs of images whose bytes span no more than that (at least one image)
-  const size_t budget = cbh::quality_budget();
-  struct Run {
-    size_t i0, m;
-    uint64_t lo, hi;
-  };
-  std::vector<Run> runs;
+  const std::vector<cbh::Run> runs = cbh::make_runs(n, img_off, end.data(), cbh::quality_budget(), SIZE_MAX);
   size_t span = 0;
-  for (size_t i0 = 0; i0 < n;) {
-    Run r{i0, 1, img_off[i0], end[i0]};
-    while (r.i0 + r.m < n) {
-      const uint64_t lo = std::min(r.lo, img_off[r.i0 + r.m]), hi = std::max(r.hi, end[r.i0 + r.m]);
-      if (hi - lo > budget) break;
-      r.lo = lo, r.hi = hi, ++r.m;
-    }
-    span = std::max<size_t>(span, r.hi - r.lo);
-    runs.push_back(r);
-    i0 += r.m;
-  }
-  hipStream_t s = nullptr;
-  uint8_t* d_imgs = nullptr;
-  int32_t* d_scores = nullptr;
+  for (const cbh::Run& r : runs) span = std::max<size_t>(span, r.hi - r.lo);
+  cbh::Staging st("quality scores");
+  uint8_t* d_imgs;
+  int32_t* d_scores;
   cbh_quality_detail* d_detail = nullptr;
-  hipError_t e;
-  int rc = CBH_OK;
-  if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipMalloc(&d_imgs, span)) != hipSuccess || (e = hipMalloc(&d_scores, n * sizeof(int32_t))) != hipSuccess ||
-      (detail && (e = hipMalloc(&d_detail, n * sizeof(cbh_quality_detail))) != hipSuccess)) {
-    cbh::set_last_error("quality scores setup", e);
-    rc = e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-  }
+  st.alloc(&d_imgs, span);
+  st.alloc(&d_scores, n * sizeof(int32_t));
+  if (detail) st.alloc(&d_detail, n * sizeof(cbh_quality_detail));
+  int rc = st.status();
   std::vector<uint64_t> off;
   for (size_t k = 0; k < runs.size() && rc == CBH_OK; ++k) {
-    const Run& r = runs[k];
-    off.assign(img_off + r.i0, img_off + r.i0 + r.m);
-    for (uint64_t& o : off) o -= r.lo;
+    const cbh::Run& r = runs[k];
+    cbh::rebase(r, img_off, &off);
     // (the group's kernels have finished: cbh_quality_scores_dev synchronises the stream before it returns)
-    if ((e = hipMemcpyAsync(d_imgs, imgs + r.lo, r.hi - r.lo, hipMemcpyHostToDevice, s)) != hipSuccess) {
-      cbh::set_last_error("quality scores upload", e);
-      rc = CBH_E_HIP;
-      break;
-    }
-    rc = cbh_quality_scores_dev(d_imgs, r.m, off.data(), img_w + r.i0, img_h + r.i0, img_row_stride + r.i0, channels,
-                                d_scores + r.i0, d_detail ? d_detail + r.i0 : nullptr, nullptr, nullptr, device, s);
+    st.up(d_imgs, imgs + r.lo, r.hi - r.lo);
+    if ((rc = st.status()) == CBH_OK)
+      rc = cbh_quality_scores_dev(d_imgs, r.m, off.data(), img_w + r.i0, img_h + r.i0, img_row_stride + r.i0, channels,
+                                  d_scores + r.i0, d_detail ? d_detail + r.i0 : nullptr, nullptr, nullptr, device, st.s);
   }
-  if (rc == CBH_OK) {
-    if ((e = hipMemcpyAsync(scores, d_scores, n * sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess ||
-        (detail && (e = hipMemcpyAsync(detail, d_detail, n * sizeof(cbh_quality_detail), hipMemcpyDeviceToHost, s)) !=
-                       hipSuccess) ||
-        (e = hipStreamSynchronize(s)) != hipSuccess) {
-      cbh::set_last_error("quality scores fetch", e);
-      rc = CBH_E_HIP;
-    }
-  }
-  if (s) (void)hipStreamSynchronize(s);
-  for (void* p : {(void*)d_imgs, (void*)d_scores, (void*)d_detail})
-    if (p) (void)hipFree(p);
-  if (s) cbh::stream_destroy(s);
-  return rc;
+  if (rc != CBH_OK) return rc;
+  st.down(scores, d_scores, n * sizeof(int32_t));
+  if (detail) st.down(detail, d_detail, n * sizeof(cbh_quality_detail));
+  st.sync();
+  return st.status();
 }
 
 }  // extern "C"

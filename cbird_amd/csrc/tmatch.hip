@@ -31,6 +31,8 @@
 #include <vector>
 
 #include "cbh_index.h"
+#include "cbh_runs.h"
+#include "cbh_staging.h"
 
 namespace cbh {
 namespace {
@@ -421,24 +423,12 @@ __global__ __launch_bounds__(64) void k_tm_finish(const double* __restrict__ m, 
   out[i] = r;
 }
 
-int fail(const char* where, hipError_t e) {
-  set_last_error(where, e);
-  return e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-}
-
 bool lists_ok(const uint64_t* first, size_t n) {
   if (first[0] != 0) return false;
   for (size_t i = 0; i < n; ++i)
     if (first[i + 1] < first[i] || first[i + 1] - first[i] > 0x7fffffffull) return false;
   return first[n] < (1ull << 40);
 }
-
-bool image_ok(uint32_t w, uint32_t h, uint32_t stride, int channels) {
-  // remap addresses its source with shorts
-  return w >= 1 && h >= 1 && w <= 32767 && h <= 32767 && stride >= w * (uint32_t)channels;
-}
-
-bool channels_ok(int c) { return c == 1 || c == 3 || c == 4; }
 
 // queues the RANSAC of `np` lists: list j = pairs first[j / per] .. first[j / per + 1], `per` lists per entry of first (the
 // chain: 2, the second with B divided by scale[j / 2]).  The table is host memory: the caller synchronises.
@@ -450,8 +440,7 @@ int queue_ransac(Scratch& scratch, std::vector<RProblem>& probs, const float* d_
     for (int k = 0; k < per; ++k)
       probs[i * per + k] = {first[i], (unsigned)(first[i + 1] - first[i]), k ? scale[i] : 1.f};
   RProblem* d_probs = nullptr;
-  hipError_t e = scratch.get(&d_probs, probs.size() * sizeof(RProblem));
-  if (e == hipSuccess) e = hipMemcpyAsync(d_probs, probs.data(), probs.size() * sizeof(RProblem), hipMemcpyHostToDevice, s);
+  const hipError_t e = upload(scratch, &d_probs, probs, s);
   if (e != hipSuccess) return fail("rigid transform tables", e);
   // LDS for the longest list of the launch, up to kLdsPoints pairs (a 100-pair batch keeps its occupancy); longer lists
   // are drawn from global memory
@@ -469,8 +458,7 @@ int queue_warp(Scratch& scratch, std::vector<WImage>& images, const uint8_t* d_i
   images.resize(n);
   for (size_t i = 0; i < n; ++i) images[i] = {img_off[i], img_w[i], img_h[i], img_row_stride[i], 0u};
   WImage* d_images = nullptr;
-  hipError_t e = scratch.get(&d_images, n * sizeof(WImage));
-  if (e == hipSuccess) e = hipMemcpyAsync(d_images, images.data(), n * sizeof(WImage), hipMemcpyHostToDevice, s);
+  const hipError_t e = upload(scratch, &d_images, images, s);
   if (e != hipSuccess) return fail("warp tables", e);
   const size_t npx = (size_t)tw * th;
   // launches of at most 2^32 pixels, a multiple of four candidates each (the stores stay aligned)
@@ -535,34 +523,25 @@ int cbh_estimate_rigid(const float* a_xy, const float* b_xy, size_t n, const uin
   cbh::DeviceGuard g(device);
   if (!g.ok) return CBH_E_NODEVICE;
   const size_t pts = std::max<size_t>(first[n], 1) * 2 * sizeof(float);
-  hipStream_t s = nullptr;
-  float *d_a = nullptr, *d_b = nullptr;
-  double* d_m = nullptr;
-  uint8_t* d_found = nullptr;
+  cbh::Staging st("rigid transform");
+  float *d_a, *d_b;
+  double* d_m;
+  uint8_t* d_found;
   cbh_rigid_detail* d_detail = nullptr;
-  hipError_t e;
-  int rc = CBH_OK;
-  if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess || (e = hipMalloc(&d_a, pts)) != hipSuccess ||
-      (e = hipMalloc(&d_b, pts)) != hipSuccess || (e = hipMalloc(&d_m, n * 6 * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&d_found, n)) != hipSuccess ||
-      (detail && (e = hipMalloc(&d_detail, n * sizeof(cbh_rigid_detail))) != hipSuccess))
-    rc = cbh::fail("rigid transform setup", e);
-  if (rc == CBH_OK && first[n] &&
-      ((e = hipMemcpyAsync(d_a, a_xy, first[n] * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
-       (e = hipMemcpyAsync(d_b, b_xy, first[n] * 8, hipMemcpyHostToDevice, s)) != hipSuccess))
-    rc = cbh::fail("rigid transform upload", e);
-  if (rc == CBH_OK) rc = cbh_estimate_rigid_dev(d_a, d_b, n, first, d_m, d_found, d_detail, device, s);
-  if (rc == CBH_OK &&
-      ((e = hipMemcpyAsync(m, d_m, n * 6 * sizeof(double), hipMemcpyDeviceToHost, s)) != hipSuccess ||
-       (e = hipMemcpyAsync(found, d_found, n, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-       (detail && (e = hipMemcpyAsync(detail, d_detail, n * sizeof(cbh_rigid_detail), hipMemcpyDeviceToHost, s)) != hipSuccess) ||
-       (e = hipStreamSynchronize(s)) != hipSuccess))
-    rc = cbh::fail("rigid transform fetch", e);
-  if (s) (void)hipStreamSynchronize(s);
-  for (void* p : {(void*)d_a, (void*)d_b, (void*)d_m, (void*)d_found, (void*)d_detail})
-    if (p) (void)hipFree(p);
-  if (s) cbh::stream_destroy(s);
-  return rc;
+  st.alloc(&d_a, pts);
+  st.alloc(&d_b, pts);
+  st.alloc(&d_m, n * 6 * sizeof(double));
+  st.alloc(&d_found, n);
+  if (detail) st.alloc(&d_detail, n * sizeof(cbh_rigid_detail));
+  if (first[n]) st.up(d_a, a_xy, first[n] * 8), st.up(d_b, b_xy, first[n] * 8);
+  int rc = st.status();
+  if (rc == CBH_OK) rc = cbh_estimate_rigid_dev(d_a, d_b, n, first, d_m, d_found, d_detail, device, st.s);
+  if (rc != CBH_OK) return rc;
+  st.down(m, d_m, n * 6 * sizeof(double));
+  st.down(found, d_found, n);
+  if (detail) st.down(detail, d_detail, n * sizeof(cbh_rigid_detail));
+  st.sync();
+  return st.status();
 }
 
 int cbh_warp_affine_dev(const void* d_imgs, size_t n, const uint64_t* img_off, const uint32_t* img_w, const uint32_t* img_h,
@@ -693,7 +672,7 @@ int cbh_template_match(const uint8_t* tmpl, int tw, int th, size_t tmpl_row_stri
   for (size_t i = 0; i < n; ++i) {
     if (!cbh::image_ok(img_w[i], img_h[i], img_row_stride[i], channels) || !(cand_scale[i] > 0.f) || std::isinf(cand_scale[i]))
       return CBH_E_INVAL;
-    end[i] = img_off[i] + (uint64_t)(img_h[i] - 1) * img_row_stride[i] + (uint64_t)img_w[i] * channels;
+    end[i] = cbh::image_end(img_off[i], img_w[i], img_h[i], img_row_stride[i], channels);
     if (end[i] > imgs_bytes) return CBH_E_INVAL;
   }
   cbh::DeviceGuard g(device);
@@ -701,69 +680,47 @@ int cbh_template_match(const uint8_t* tmpl, int tw, int th, size_t tmpl_row_stri
   // uploads of at most "tmatch_chunk_mb" each: runs of candidates whose image bytes span no more than that, and whose
   // patches fit it as well (at least one candidate, then multiples of four)
   const size_t budget = cbh::tmatch_budget(), patch = (size_t)tw * th * channels;
-  const size_t most = std::max<size_t>(4, (budget / patch) & ~(size_t)3);
-  struct Run {
-    size_t i0, m;
-    uint64_t lo, hi;
-  };
-  std::vector<Run> runs;
+  const std::vector<cbh::Run> runs =
+      cbh::make_runs(n, img_off, end.data(), budget, std::max<size_t>(4, (budget / patch) & ~(size_t)3));
   size_t span = 0, most_m = 0;
-  for (size_t i0 = 0; i0 < n;) {
-    Run r{i0, 1, img_off[i0], end[i0]};
-    while (r.i0 + r.m < n && r.m < most) {
-      const uint64_t lo = std::min(r.lo, img_off[r.i0 + r.m]), hi = std::max(r.hi, end[r.i0 + r.m]);
-      if (hi - lo > budget) break;
-      r.lo = lo, r.hi = hi, ++r.m;
-    }
-    span = std::max<size_t>(span, r.hi - r.lo), most_m = std::max(most_m, r.m);
-    runs.push_back(r);
-    i0 += r.m;
-  }
+  for (const cbh::Run& r : runs) span = std::max<size_t>(span, r.hi - r.lo), most_m = std::max(most_m, r.m);
   const size_t tspan = (size_t)(th - 1) * tmpl_row_stride + (size_t)tw * tmpl_channels;
   const size_t pts = std::max<size_t>(first[n], 1) * 2 * sizeof(float);
-  hipStream_t s = nullptr;
-  uint8_t *d_imgs = nullptr, *d_tmpl = nullptr, *d_patches = nullptr;
-  float *d_a = nullptr, *d_b = nullptr;
-  cbh_template_result* d_res = nullptr;
-  hipError_t e;
-  int rc = CBH_OK;
-  if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess || (e = hipMalloc(&d_imgs, span)) != hipSuccess ||
-      (e = hipMalloc(&d_tmpl, tspan)) != hipSuccess || (e = hipMalloc(&d_a, pts)) != hipSuccess ||
-      (e = hipMalloc(&d_b, pts)) != hipSuccess || (e = hipMalloc(&d_res, n * sizeof(cbh_template_result))) != hipSuccess ||
-      (patches && (e = hipMalloc(&d_patches, most_m * patch)) != hipSuccess))
-    rc = cbh::fail("template match setup", e);
-  if (rc == CBH_OK && ((e = hipMemcpyAsync(d_tmpl, tmpl, tspan, hipMemcpyHostToDevice, s)) != hipSuccess ||
-                       (first[n] && ((e = hipMemcpyAsync(d_a, tmpl_xy, first[n] * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
-                                     (e = hipMemcpyAsync(d_b, match_xy, first[n] * 8, hipMemcpyHostToDevice, s)) != hipSuccess))))
-    rc = cbh::fail("template match upload", e);
+  cbh::Staging st("template match");
+  uint8_t *d_imgs, *d_tmpl, *d_patches = nullptr;
+  float *d_a, *d_b;
+  cbh_template_result* d_res;
+  st.alloc(&d_imgs, span);
+  st.alloc(&d_tmpl, tspan);
+  st.alloc(&d_a, pts);
+  st.alloc(&d_b, pts);
+  st.alloc(&d_res, n * sizeof(cbh_template_result));
+  if (patches) st.alloc(&d_patches, most_m * patch);
+  st.up(d_tmpl, tmpl, tspan);
+  if (first[n]) st.up(d_a, tmpl_xy, first[n] * 8), st.up(d_b, match_xy, first[n] * 8);
+  int rc = st.status();
   std::vector<uint64_t> off, rel;
   for (size_t k = 0; k < runs.size() && rc == CBH_OK; ++k) {
-    const Run& r = runs[k];
-    off.assign(img_off + r.i0, img_off + r.i0 + r.m);
-    for (uint64_t& o : off) o -= r.lo;
+    const cbh::Run& r = runs[k];
+    cbh::rebase(r, img_off, &off);
     rel.assign(first + r.i0, first + r.i0 + r.m + 1);
     for (uint64_t& v : rel) v -= first[r.i0];
     // (the run before has finished: cbh_template_match_dev synchronises the stream before it returns)
-    if ((e = hipMemcpyAsync(d_imgs, imgs + r.lo, r.hi - r.lo, hipMemcpyHostToDevice, s)) != hipSuccess) {
-      rc = cbh::fail("template match upload", e);
-      break;
-    }
+    st.up(d_imgs, imgs + r.lo, r.hi - r.lo);
+    if ((rc = st.status()) != CBH_OK) break;
     rc = cbh_template_match_dev(d_tmpl, tw, th, tmpl_row_stride, tmpl_channels, d_imgs, r.m, off.data(), img_w + r.i0,
                                 img_h + r.i0, img_row_stride + r.i0, channels, d_a + 2 * first[r.i0], d_b + 2 * first[r.i0],
-                                rel.data(), cand_scale + r.i0, d_res + r.i0, d_patches, device, s);
-    if (rc == CBH_OK && patches &&
-        ((e = hipMemcpyAsync(patches + r.i0 * patch, d_patches, r.m * patch, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-         (e = hipStreamSynchronize(s)) != hipSuccess))
-      rc = cbh::fail("template match fetch", e);
+                                rel.data(), cand_scale + r.i0, d_res + r.i0, d_patches, device, st.s);
+    if (rc == CBH_OK && patches) {  // before the next run warps into d_patches
+      st.down(patches + r.i0 * patch, d_patches, r.m * patch);
+      st.sync();
+      rc = st.status();
+    }
   }
-  if (rc == CBH_OK && ((e = hipMemcpyAsync(results, d_res, n * sizeof(cbh_template_result), hipMemcpyDeviceToHost, s)) != hipSuccess ||
-                       (e = hipStreamSynchronize(s)) != hipSuccess))
-    rc = cbh::fail("template match fetch", e);
-  if (s) (void)hipStreamSynchronize(s);
-  for (void* p : {(void*)d_imgs, (void*)d_tmpl, (void*)d_patches, (void*)d_a, (void*)d_b, (void*)d_res})
-    if (p) (void)hipFree(p);
-  if (s) cbh::stream_destroy(s);
-  return rc;
+  if (rc != CBH_OK) return rc;
+  st.down(results, d_res, n * sizeof(cbh_template_result));
+  st.sync();
+  return st.status();
 }
 
 }  // extern "C"

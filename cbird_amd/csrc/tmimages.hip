@@ -29,6 +29,8 @@
 #include <vector>
 
 #include "cbh_index.h"
+#include "cbh_runs.h"
+#include "cbh_staging.h"
 #include "gray_px.h"
 
 namespace cbh {
@@ -294,17 +296,6 @@ __global__ __launch_bounds__(kBlock) void k_tm_gather(const unsigned long long* 
   }
 }
 
-int fail(const char* where, hipError_t e) {
-  set_last_error(where, e);
-  return e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-}
-
-bool channels_ok(int c) { return c == 1 || c == 3 || c == 4; }
-
-bool image_ok(uint32_t w, uint32_t h, uint32_t stride, int channels) {
-  return w >= 1 && h >= 1 && w <= 32767 && h <= 32767 && stride >= w * (uint32_t)channels;
-}
-
 // ---- resize / grey launchers.  The tables they upload live in `keep` (host memory the caller holds until it has
 // synchronised the stream) and in `scratch` ----------------------------------------------------------------------------
 struct ResizeTables {
@@ -343,13 +334,9 @@ int queue_resize(Scratch& scratch, ResizeTables& keep, const uint8_t* d_src, siz
   RImage* d_images = nullptr;
   int* d_ofs = nullptr;
   short* d_coef = nullptr;
-  hipError_t e = scratch.get(&d_images, n * sizeof(RImage));
-  if (e == hipSuccess) e = scratch.get(&d_ofs, keep.ofs.size() * sizeof(int));
-  if (e == hipSuccess) e = scratch.get(&d_coef, keep.coef.size() * sizeof(short));
-  if (e == hipSuccess) e = hipMemcpyAsync(d_images, keep.images.data(), n * sizeof(RImage), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_ofs, keep.ofs.data(), keep.ofs.size() * sizeof(int), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_coef, keep.coef.data(), keep.coef.size() * sizeof(short), hipMemcpyHostToDevice, s);
+  hipError_t e = upload(scratch, &d_images, keep.images, s);
+  if (e == hipSuccess) e = upload(scratch, &d_ofs, keep.ofs, s);
+  if (e == hipSuccess) e = upload(scratch, &d_coef, keep.coef, s);
   if (e != hipSuccess) return fail("ragged resize tables", e);
   const unsigned gx = (unsigned)std::min<unsigned long long>((most + 4 * kBlock - 1) / (4 * kBlock), 4096);
   for (size_t i0 = 0; i0 < n; i0 += 65535) {
@@ -375,8 +362,7 @@ int queue_gray(Scratch& scratch, std::vector<RImage>& keep, const uint8_t* d_src
     most = std::max<unsigned long long>(most, (unsigned long long)w[i] * h[i]);
   }
   RImage* d_images = nullptr;
-  hipError_t e = scratch.get(&d_images, n * sizeof(RImage));
-  if (e == hipSuccess) e = hipMemcpyAsync(d_images, keep.data(), n * sizeof(RImage), hipMemcpyHostToDevice, s);
+  hipError_t e = upload(scratch, &d_images, keep, s);
   if (e != hipSuccess) return fail("ragged grey tables", e);
   const unsigned gx = (unsigned)std::min<unsigned long long>((most + 4 * kBlock - 1) / (4 * kBlock), 4096);
   for (size_t i0 = 0; i0 < n; i0 += 65535) {
@@ -695,31 +681,12 @@ bool images_args_ok(const void* tmpl, int tw, int th, size_t tstride, const void
   return true;
 }
 
-uint64_t image_end(uint64_t off, uint32_t w, uint32_t h, uint32_t stride, int channels) {
-  return off + (uint64_t)(h - 1) * stride + (uint64_t)w * channels;
-}
-
 // runs of candidates whose bytes span at most "tmatch_chunk_mb" (at least one candidate, at most 32768)
-struct Run {
-  size_t i0, m;
-  uint64_t lo, hi;
-};
-std::vector<Run> make_runs(size_t n, const uint64_t* off, const uint32_t* w, const uint32_t* h, const uint32_t* stride,
-                           int channels) {
-  const uint64_t budget = (uint64_t)std::max(get_tmatch_chunk_mb(), 1) << 20;
-  std::vector<Run> runs;
-  for (size_t i0 = 0; i0 < n;) {
-    Run r{i0, 1, off[i0], image_end(off[i0], w[i0], h[i0], stride[i0], channels)};
-    while (r.i0 + r.m < n && r.m < 32768) {
-      const size_t j = r.i0 + r.m;
-      const uint64_t lo = std::min(r.lo, off[j]), hi = std::max(r.hi, image_end(off[j], w[j], h[j], stride[j], channels));
-      if (hi - lo > budget) break;
-      r.lo = lo, r.hi = hi, ++r.m;
-    }
-    runs.push_back(r);
-    i0 += r.m;
-  }
-  return runs;
+std::vector<Run> candidate_runs(size_t n, const uint64_t* off, const uint32_t* w, const uint32_t* h, const uint32_t* stride,
+                                int channels) {
+  std::vector<uint64_t> end(n);
+  for (size_t i = 0; i < n; ++i) end[i] = image_end(off[i], w[i], h[i], stride[i], channels);
+  return make_runs(n, off, end.data(), (uint64_t)std::max(get_tmatch_chunk_mb(), 1) << 20, 32768);
 }
 
 }  // namespace
@@ -820,7 +787,7 @@ int cbh_template_match_images_dev(const void* d_tmpl, int tw, int th, size_t tmp
   int rc = cbh::prepare_template(t, params, s);
   if (rc != CBH_OK) return rc;
   const size_t patch = (size_t)tw * th * channels;
-  for (const cbh::Run& r : cbh::make_runs(n, img_off, img_w, img_h, img_row_stride, channels)) {
+  for (const cbh::Run& r : cbh::candidate_runs(n, img_off, img_w, img_h, img_row_stride, channels)) {
     rc = cbh::run_group(t, (const uint8_t*)d_imgs, r.m, img_off + r.i0, img_w + r.i0, img_h + r.i0, img_row_stride + r.i0,
                         params, results + r.i0, d_patches ? (uint8_t*)d_patches + r.i0 * patch : nullptr, device, s);
     if (rc != CBH_OK) return rc;
@@ -841,46 +808,37 @@ int cbh_template_match_images(const uint8_t* tmpl, int tw, int th, size_t tmpl_r
     if (cbh::image_end(img_off[i], img_w[i], img_h[i], img_row_stride[i], channels) > imgs_bytes) return CBH_E_INVAL;
   cbh::DeviceGuard g(device);
   if (!g.ok) return CBH_E_NODEVICE;
-  const std::vector<cbh::Run> runs = cbh::make_runs(n, img_off, img_w, img_h, img_row_stride, channels);
+  const std::vector<cbh::Run> runs = cbh::candidate_runs(n, img_off, img_w, img_h, img_row_stride, channels);
   size_t span = 0, most_m = 0;
   for (const cbh::Run& r : runs) span = std::max<size_t>(span, r.hi - r.lo), most_m = std::max(most_m, r.m);
   const size_t tspan = (size_t)(th - 1) * tmpl_row_stride + (size_t)tw * channels;
   const size_t patch = (size_t)tw * th * channels;
-  hipStream_t s = nullptr;
-  uint8_t *d_imgs = nullptr, *d_tmpl = nullptr, *d_patches = nullptr;
-  hipError_t e;
-  int rc = CBH_OK;
-  if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess || (e = hipMalloc(&d_imgs, span)) != hipSuccess ||
-      (e = hipMalloc(&d_tmpl, tspan)) != hipSuccess || (patches && (e = hipMalloc(&d_patches, most_m * patch)) != hipSuccess))
-    rc = cbh::fail("template match images setup", e);
-  if (rc == CBH_OK && (e = hipMemcpyAsync(d_tmpl, tmpl, tspan, hipMemcpyHostToDevice, s)) != hipSuccess)
-    rc = cbh::fail("template match images upload", e);
-  if (rc == CBH_OK) {
-    cbh::Template t{d_tmpl, tw, th, channels, tmpl_row_stride};
-    rc = cbh::prepare_template(t, params, s);
-    std::vector<uint64_t> off;
-    for (size_t k = 0; k < runs.size() && rc == CBH_OK; ++k) {
-      const cbh::Run& r = runs[k];
-      off.assign(img_off + r.i0, img_off + r.i0 + r.m);
-      for (uint64_t& o : off) o -= r.lo;
-      // (the run before has finished: run_group returns with the stream synchronised)
-      if ((e = hipMemcpyAsync(d_imgs, imgs + r.lo, r.hi - r.lo, hipMemcpyHostToDevice, s)) != hipSuccess) {
-        rc = cbh::fail("template match images upload", e);
-        break;
-      }
-      rc = cbh::run_group(t, d_imgs, r.m, off.data(), img_w + r.i0, img_h + r.i0, img_row_stride + r.i0, params,
-                          results + r.i0, d_patches, device, s);
-      if (rc == CBH_OK && patches &&
-          ((e = hipMemcpyAsync(patches + r.i0 * patch, d_patches, r.m * patch, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-           (e = hipStreamSynchronize(s)) != hipSuccess))
-        rc = cbh::fail("template match images fetch", e);
+  cbh::Staging st("template match images");
+  uint8_t *d_imgs, *d_tmpl, *d_patches = nullptr;
+  st.alloc(&d_imgs, span);
+  st.alloc(&d_tmpl, tspan);
+  if (patches) st.alloc(&d_patches, most_m * patch);
+  st.up(d_tmpl, tmpl, tspan);
+  int rc = st.status();
+  if (rc != CBH_OK) return rc;
+  cbh::Template t{d_tmpl, tw, th, channels, tmpl_row_stride};
+  rc = cbh::prepare_template(t, params, st.s);
+  std::vector<uint64_t> off;
+  for (size_t k = 0; k < runs.size() && rc == CBH_OK; ++k) {
+    const cbh::Run& r = runs[k];
+    cbh::rebase(r, img_off, &off);
+    // (the run before has finished: run_group returns with the stream synchronised)
+    st.up(d_imgs, imgs + r.lo, r.hi - r.lo);
+    if ((rc = st.status()) != CBH_OK) break;
+    rc = cbh::run_group(t, d_imgs, r.m, off.data(), img_w + r.i0, img_h + r.i0, img_row_stride + r.i0, params,
+                        results + r.i0, d_patches, device, st.s);
+    if (rc == CBH_OK && patches) {  // before the next run warps into d_patches
+      st.down(patches + r.i0 * patch, d_patches, r.m * patch);
+      st.sync();
+      rc = st.status();
     }
-    if (s) (void)hipStreamSynchronize(s);  // before the template's scratch goes back
   }
-  if (s) (void)hipStreamSynchronize(s);
-  for (void* p : {(void*)d_imgs, (void*)d_tmpl, (void*)d_patches})
-    if (p) (void)hipFree(p);
-  if (s) cbh::stream_destroy(s);
+  (void)hipStreamSynchronize(st.s);  // before the template's scratch goes back
   return rc;
 }
 
