@@ -6,6 +6,7 @@ load the shared library; the first call does, and fails loudly when it (or a gfx
 missing.
 """
 from ._lib import CbhError, lib, require_device  # noqa: F401
+from .alignment import align_spatial, align_temporal, alignment_transform  # noqa: F401
 from .difference import auto_contrast, difference_images  # noqa: F401
 from .hashing import dct_hash64, dct_hash64_batch, estimate_rigid, template_match, warp_affine  # noqa: F401
 from .index import DctFeaturesIndex, DctHashIndex, Match, MatchRange, Media, SearchParams  # noqa: F401
@@ -13,5 +14,5 @@ from .quality import quality_planes, quality_scores  # noqa: F401
 
 __all__ = ["CbhError", "lib", "require_device", "dct_hash64", "dct_hash64_batch", "DctHashIndex",
            "DctFeaturesIndex", "quality_scores", "quality_planes", "estimate_rigid", "warp_affine", "template_match",
-           "auto_contrast", "difference_images",
+           "auto_contrast", "difference_images", "align_spatial", "align_temporal", "alignment_transform",
            "Match", "MatchRange", "Media", "SearchParams"]

@@ -104,6 +104,14 @@ _SIGS = {
                                             _vp, _vp, C.c_float, _vp, _vp, _vp, C.c_int, _vp]),
     "cbh_difference_images": (C.c_int, [_vp, C.c_int, C.c_int, _sz, C.c_int, _vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int,
                                         _vp, _vp, C.c_float, _vp, _sz, _vp, _vp, C.c_int]),
+    "cbh_align_spatial_dev": (C.c_int, [_vp, C.c_int, C.c_int, _sz, C.c_int, _vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp,
+                                        C.c_int, _vp]),
+    "cbh_align_spatial": (C.c_int, [_vp, C.c_int, C.c_int, _sz, C.c_int, _vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp,
+                                    C.c_int]),
+    "cbh_align_temporal_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _sz, _vp, _vp, _vp, _vp, C.c_int, C.c_int,
+                                         _vp, _vp, _vp, C.c_int, _vp]),
+    "cbh_align_temporal": (C.c_int, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int,
+                                     C.c_int, _vp, _vp, _vp, C.c_int]),
     "cbh_index_images": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, C.c_int]),
     "cbh_index_images_views": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,

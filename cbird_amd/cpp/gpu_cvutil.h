@@ -13,6 +13,8 @@
 //   void brightnessAndContrastAuto(const cv::Mat& src, cv::Mat& dst, float clipHistPercent = 0)       src/cvutil.cpp:657-665
 //   static QImage differenceImage(const Media& ml, const Media& mr, ...)   (decoded images, one pair or a group)
 //                                                                                 src/gui/mediagrouplistwidget.cpp:106-208
+//   void VideoCompareWidget::alignSpatially() / alignTemporally()   (decoded frames, one pair, a group or a clip)
+//                                                                                 src/gui/videocomparewidget.cpp:590-680
 //
 // Same arguments and effects as the originals for 8-bit single-channel images (what Scanner::processImage passes
 // after grayscale(), src/scanner.cpp:859,876-889): the hash is returned, and with inPlace = true the blurred pixels
@@ -537,6 +539,96 @@ inline cv::Mat gpuDifferenceImage(const cv::Mat& left, const cv::Mat& right, con
   gpuDifferenceImages(left, std::vector<cv::Mat>(1, right), tx ? &r : nullptr, images, details, clipHistPercent);
   if (detail) *detail = details[0];
   return images[0];
+}
+
+namespace detail {
+// 8-bit images of ONE channel count behind each other in `buf`, rows packed, 16-byte aligned starts
+inline void packMats(const std::vector<cv::Mat>& mats, const std::vector<size_t>& which, int cn, std::vector<uint8_t>& buf,
+                     std::vector<uint64_t>& off, std::vector<uint32_t>& w, std::vector<uint32_t>& h,
+                     std::vector<uint32_t>& step) {
+  for (size_t i : which) {
+    const cv::Mat& m = mats[i];
+    const size_t row = size_t(m.cols) * size_t(cn);
+    off.push_back((buf.size() + 15) / 16 * 16);
+    buf.resize(size_t(off.back()) + row * size_t(m.rows));
+    for (int y = 0; y < m.rows; ++y) memcpy(buf.data() + off.back() + size_t(y) * row, m.ptr<uint8_t>(y), row);
+    w.push_back(uint32_t(m.cols)), h.push_back(uint32_t(m.rows)), step.push_back(uint32_t(row));
+  }
+}
+inline bool is8bit(const cv::Mat& m) {
+  return m.rows > 0 && m.cols > 0 && (m.type() == CV_8UC1 || m.type() == CV_8UC3 || m.type() == CV_8UC4);
+}
+}  // namespace detail
+
+// void VideoCompareWidget::alignSpatially()   src/gui/videocomparewidget.cpp:590-627
+// for frames that are already decoded (8-bit cv::Mat of 1, 3 or 4 channels), ONE left image against all the right images
+// of a group in one call: out[i] is the shift of +-8 pixels at 256 x 256 with the smallest sum of absolute differences,
+// ties as the reference's loops break them (include/cbird_hip.h).  (QImage::scaled is unpinned against Qt.)
+inline void gpuAlignSpatial(const cv::Mat& left, const std::vector<cv::Mat>& rights, std::vector<cbh_align_spatial_result>& out) {
+  out.assign(rights.size(), cbh_align_spatial_result());
+  if (!detail::is8bit(left)) qFatal("gpuAlignSpatial: expected a non-empty 8-bit left image of 1, 3 or 4 channels");
+  for (const cv::Mat& m : rights)
+    if (!detail::is8bit(m)) qFatal("gpuAlignSpatial: expected non-empty 8-bit images of 1, 3 or 4 channels");
+  for (int cn : {1, 3, 4}) {
+    std::vector<size_t> which;
+    for (size_t i = 0; i < rights.size(); ++i)
+      if (rights[i].channels() == cn) which.push_back(i);
+    if (which.empty()) continue;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> w, h, step;
+    std::vector<uint8_t> buf;
+    detail::packMats(rights, which, cn, buf, off, w, h, step);
+    std::vector<cbh_align_spatial_result> res(which.size());
+    const int rc = cbh_align_spatial(left.data, left.cols, left.rows, size_t(left.step), left.channels(), buf.data(), buf.size(),
+                                     which.size(), off.data(), w.data(), h.data(), step.data(), cn, res.data(), nullptr,
+                                     hashDevice());
+    if (rc) qFatal("gpuAlignSpatial: %s (%s)", cbh_strerror(rc), cbh_last_error());
+    for (size_t k = 0; k < which.size(); ++k) out[which[k]] = res[k];
+  }
+}
+
+// one pair: the reference's _alignX, _alignY (:624-625), fractions of the frame's sides; returns the record
+inline cbh_align_spatial_result gpuAlignSpatial(const cv::Mat& left, const cv::Mat& right, float* alignX, float* alignY) {
+  std::vector<cbh_align_spatial_result> out;
+  gpuAlignSpatial(left, std::vector<cv::Mat>(1, right), out);
+  if (alignX) *alignX = float(out[0].min_x) / 256.0f;
+  if (alignY) *alignY = float(out[0].min_y) / 256.0f;
+  return out[0];
+}
+
+// void VideoCompareWidget::alignTemporally()   src/gui/videocomparewidget.cpp:629-680
+// the window `right` (the reference: 5 frames) against `left` (64) at every placement d = 0 .. left.size() - right.size():
+// right[i] on left[d + i].  start: the placement that is kept unless another has a strictly smaller mean SAD (the
+// reference's current offset, 30 of 60); -1 = the middle, (P - 1) / 2 + (P - 1) % 2.  The frames of a side share a channel
+// count.  Which frame stands in for an index outside the video is the caller's business, as it is FrameCache's.
+inline cbh_align_temporal_result gpuAlignTemporal(const std::vector<cv::Mat>& left, const std::vector<cv::Mat>& right,
+                                                  int start = -1) {
+  if (right.empty() || right.size() > 64 || left.size() < right.size() || left.size() > 65535)
+    qFatal("gpuAlignTemporal: expected 1 .. 64 right frames and at least as many, at most 65535, left frames");
+  const int placements = int(left.size() - right.size()) + 1;
+  if (start < 0) start = (placements - 1) / 2 + (placements - 1) % 2;
+  if (start >= placements) qFatal("gpuAlignTemporal: start is no placement");
+  std::vector<uint8_t> buf[2];
+  std::vector<uint64_t> off[2];
+  std::vector<uint32_t> w[2], h[2], step[2];
+  int cn[2];
+  for (int side = 0; side < 2; ++side) {
+    const std::vector<cv::Mat>& frames = side ? right : left;
+    cn[side] = frames[0].channels();
+    std::vector<size_t> which;
+    for (size_t i = 0; i < frames.size(); ++i) {
+      if (!detail::is8bit(frames[i]) || frames[i].channels() != cn[side])
+        qFatal("gpuAlignTemporal: expected non-empty 8-bit frames of 1, 3 or 4 channels, one channel count per side");
+      which.push_back(i);
+    }
+    detail::packMats(frames, which, cn[side], buf[side], off[side], w[side], h[side], step[side]);
+  }
+  cbh_align_temporal_result res = cbh_align_temporal_result();
+  const int rc = cbh_align_temporal(buf[0].data(), buf[0].size(), left.size(), off[0].data(), w[0].data(), h[0].data(),
+                                    step[0].data(), cn[0], buf[1].data(), buf[1].size(), right.size(), off[1].data(),
+                                    w[1].data(), h[1].data(), step[1].data(), cn[1], start, &res, nullptr, nullptr, hashDevice());
+  if (rc) qFatal("gpuAlignTemporal: %s (%s)", cbh_strerror(rc), cbh_last_error());
+  return res;
 }
 
 }  // namespace cbird_gpu

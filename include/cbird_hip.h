@@ -310,6 +310,64 @@ int cbh_difference_images(const uint8_t* left, int left_w, int left_h, size_t le
                           const double* tx, const uint8_t* has_tx, float clip_pct, uint8_t* images, size_t images_bytes,
                           const uint64_t* out_off, cbh_diff_detail* detail /* NULL or n */, int device);
 
+/* ---- alignSpatially (src/gui/videocomparewidget.cpp:590-627) and alignTemporally with sad128 (:629-680) -------------------
+ * cbird_amd/csrc/align.hip; tests/alignment_rules.py is the numpy model the device is held to, bit for bit (everything is
+ * integer arithmetic).  Images as above: the img_off / img_w / img_h / img_row_stride host tables, channels 1 / 3 / 4, one
+ * channel count per table, sides 1 .. 32767, at most 2^20 images per call.  The three bytes of a pixel are the grey byte
+ * three times, the three bytes, or the first three of four (alpha ignored); their order does not matter to a sum.
+ *
+ * EXACT restatements of the reference's own arithmetic: the SAD windows, the scan order and the tie rules, the integer
+ * mean and the start rule.  UNPINNED, as for the difference image: QImage::scaled(S, S) -- nearest neighbour, aspect
+ * ignored, src = ((2 * dst + 1) * ssize) / (2 * dsize) in integers -- restated without Qt.
+ *
+ * Spatial, S = 256, ONE left image A against n right images B_i.  For xo = -8 .. 8 (outer loop) and yo = -8 .. 8 (inner):
+ *   sad(xo, yo) = sum over y = 8 .. 247, x = 8 .. 247, c of |A[y + yo][x + xo][c] - B[y][x][c]|   (<= 44 064 000)
+ * and the answer is the first shift in that order whose sad is strictly below every earlier one: on a tie the smaller
+ * xo, then the smaller yo; (-8, -8) when all are equal.  The table is uint32 [n][289], entry (xo + 8) * 17 + (yo + 8).
+ * The reference's _alignX, _alignY are min_x / 256.0f, min_y / 256.0f. */
+typedef struct cbh_align_spatial_result {
+  int32_t min_x, min_y;          /* the shift: left pixel (x + min_x, y + min_y) lies on right pixel (x, y) at 256 x 256 */
+  uint32_t min_sad, sad_at_zero; /* its sad; the sad of (0, 0) */
+} cbh_align_spatial_result;
+/* images in device memory, the tables in host memory; d_results: n records; d_table: NULL or 289 n words.  n == 0
+ * returns CBH_OK and touches nothing.  CBH_E_INVAL (with a cbh_last_error text): a side of 0 or above 32767, rows shorter
+ * than their pixels, a channel count other than 1 / 3 / 4, n above 2^20.  Synchronises the stream. */
+int cbh_align_spatial_dev(const void* d_left, int left_w, int left_h, size_t left_row_stride, int left_channels,
+                          const void* d_rights, size_t n, const uint64_t* img_off, const uint32_t* img_w,
+                          const uint32_t* img_h, const uint32_t* img_row_stride, int channels, void* d_results,
+                          void* d_table /* NULL or 289 n */, int device, void* stream);
+/* the same from and to host memory */
+int cbh_align_spatial(const uint8_t* left, int left_w, int left_h, size_t left_row_stride, int left_channels,
+                      const uint8_t* rights, size_t rights_bytes, size_t n, const uint64_t* img_off, const uint32_t* img_w,
+                      const uint32_t* img_h, const uint32_t* img_row_stride, int channels, cbh_align_spatial_result* results,
+                      uint32_t* table /* NULL or 289 n */, int device);
+/* Temporal, S = 128: left frames F_0 .. F_{nL-1} against the window of right frames G_0 .. G_{W-1}, 1 <= W <= 64,
+ * W <= nL <= 65535, P = nL - W + 1 placements.  cell(d, i) = the SAD of all 128 * 128 * 3 bytes of F_{d+i} and G_i
+ * (<= 12 533 760); mean(d) = (sum over i of cell(d, i)) / W in integer division.  With start in [0, P): best = start,
+ * min = mean(start); then for d = 0 .. P - 1 ascending, mean(d) < min replaces both -- a placement that only equals the
+ * start's mean never wins, among equal better ones the earliest does.  The reference's call is nL = 64, W = 5, start = 30:
+ * offsets -30 .. +29 around the current frame.  Which frame stands in for an index outside the video is the caller's
+ * business (FrameCache's in the reference). */
+typedef struct cbh_align_temporal_result {
+  int32_t placement, offset;     /* the placement kept; placement - start */
+  uint32_t min_mean, start_mean; /* its mean; the mean at start */
+} cbh_align_temporal_result;
+/* frames in device memory, the tables in host memory, one channel count per side; d_result: one record; d_means: NULL or
+ * P words; d_cells: NULL or P * W words, cell(d, i) at d * W + i.  CBH_E_INVAL (with a cbh_last_error text): as above, W
+ * outside 1 .. 64, W > nL, nL above 65535, start outside [0, P).  Synchronises the stream. */
+int cbh_align_temporal_dev(const void* d_left, size_t n_left, const uint64_t* left_off, const uint32_t* left_w,
+                           const uint32_t* left_h, const uint32_t* left_row_stride, int left_channels, const void* d_right,
+                           size_t n_right, const uint64_t* right_off, const uint32_t* right_w, const uint32_t* right_h,
+                           const uint32_t* right_row_stride, int right_channels, int start, void* d_result,
+                           void* d_means /* NULL or P */, void* d_cells /* NULL or P * W */, int device, void* stream);
+/* the same from and to host memory */
+int cbh_align_temporal(const uint8_t* left, size_t left_bytes, size_t n_left, const uint64_t* left_off, const uint32_t* left_w,
+                       const uint32_t* left_h, const uint32_t* left_row_stride, int left_channels, const uint8_t* right,
+                       size_t right_bytes, size_t n_right, const uint64_t* right_off, const uint32_t* right_w,
+                       const uint32_t* right_h, const uint32_t* right_row_stride, int right_channels, int start,
+                       cbh_align_temporal_result* result, uint32_t* means /* NULL or P */,
+                       uint32_t* cells /* NULL or P * W */, int device);
+
 /* ---- the steps in front of dctHash64 in Scanner::processImage (src/scanner.cpp:852-862) -------------------
  * grayscale(): cv::cvtColor(BGR2GRAY/BGRA2GRAY) on 8-bit data (src/cvutil.cpp:1265-1283); d_gray is packed
  * n*w*h bytes. */
