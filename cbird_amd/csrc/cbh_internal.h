@@ -319,7 +319,7 @@ int launch_hamm256_mfma(Scan256Kernel kernel, const uint8_t* d_rows, size_t n, c
                         hipStream_t stream);
 
 // ---- setters behind cbh_set_tuning (include/cbird_hip.h documents every knob) ---------------------------------------
-int g_hash_mfma_set(int v);        // dcthash.hip "hash_mfma": 256 x 256 tiles on k_dcthash_256_band (non-zero) or k_dcthash_256 (0)
+void set_hash_mfma(int v);         // dcthash.hip "hash_mfma": 256 x 256 tiles on k_dcthash_256_band (non-zero) or k_dcthash_256 (0)
 void set_hash_band_area(int v);    // dcthash.hip "hash_band_area": k_band_area for fractional ratios up to 1920 columns (1) or never (0)
 void set_hash_stream(int v);       // dcthash.hip "hash_stream": k_blur_area_regs on strips -- 0 never, 1 by batch size, >= 2 always, of v steps
 void set_hash_fuse(int v);         // dcthash.hip "hash_fuse": vertical INTER_AREA pass + tile inside k_blur_area_regs (0 never, 1 auto, 2 always)

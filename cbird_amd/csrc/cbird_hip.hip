@@ -1331,7 +1331,7 @@ int cbh_set_tuning(const char* key, int value) {
       {"scan_mfma_pre_max", [](int v) { set_scan_pre_max(v); }},
       {"scan_pre_rate_e9", [](int v) { set_scan_pre_rate(v); }},
       {"scan_pre48", [](int v) { set_scan_pre48(v); }},
-      {"hash_mfma", [](int v) { (void)g_hash_mfma_set(v); }},
+      {"hash_mfma", [](int v) { set_hash_mfma(v); }},
       {"hash_band_area", [](int v) { set_hash_band_area(v); }},
       {"hash_fuse", [](int v) { set_hash_fuse(v); }},
       {"hash_stream", [](int v) { set_hash_stream(v); }},

@@ -215,9 +215,7 @@ typedef int v4i_lds __attribute__((ext_vector_type(4), may_alias));
 typedef unsigned int v2u_lds __attribute__((ext_vector_type(2), may_alias));
 typedef unsigned int v4u_lds __attribute__((ext_vector_type(4), may_alias));
 
-struct BandTables {
-  unsigned int w[1][64][4];  // the B operand (i8 x 16 per lane) of an interior column tile: the only one (see "borders")
-};
+// (BandTables, the B operand: dcthash_tables.h)
 
 constexpr int kBandPitch = 272;  // 8 + 256 + 8
 
@@ -428,34 +426,7 @@ __global__ __launch_bounds__(64) void k_dcthash_256_band(
 // per pixel): ~2.5 + ~2.2 -- see DESIGN a1.  Preconditions (launcher): whole images, or views whose vertical edges are
 // the parent's or lie >= 8 (left) / >= 3 (right) columns inside it (oy, ph, ox, inner), 7 x 7 blur, fractional ratios,
 // strips of at least 4 cells within 240 columns (w <= 1920), four images' strides below 2^32.
-struct BaStrip {
-  int xs;       // first source column of the strip's first cell
-  int T;        // 16-column tiles (<= 15)
-  int cell0;    // first output cell
-  int ncell;    // cells (<= 16)
-  int amax;     // longest cell walk
-  int amin;     // shortest: entries 1 .. amin - 2 of EVERY cell weigh its wmid (checked on the host)
-  int tp;       // dwords between the images' planes of sT: chosen on the host so that the cells' walks (lane = image, cell
-                // reads column si0[cell] + k of its image's plane) meet in as few LDS banks as possible
-  int rotm;     // integer ratios with 16 or 32 columns per cell (512, 1024 px): cell width - 1, else 0 -- see rot
-  int si0[16];             // first source column of cell c, relative to xs
-  // the block-sum walk of cell c starts at its column rot[c] and wraps (a sum has no order): cells a multiple of 16 columns
-  // apart would otherwise read the same LDS bank in every step of the walk, 8 lanes a bank at 512 px
-  int rot[16];
-  // weights of cell c in table order: wfirst, then wmid for entries 1 .. amin - 2, then wtail[j] for entry amin - 1 + j
-  // (+0.0f past the cell's end; amax - amin + 1 <= 4 of them)
-  float wfirst[16], wmid[16], wtail[16][4];
-  unsigned band[3][64][4]; // B operands: the plain band, the strip's first tile, its last tile
-};
-
-// Row bands: a small batch has too few (group, strip) pairs to fill the machine (256 frames of 1920 x 1080: 512 waves for 2560
-// slots, each walking 270 steps), so the 32 output ROWS are dealt to up to 8 waves per (group, strip) as well: band b makes
-// the output rows [c0, c1) and walks the source rows [ra, rb] that feed them (+ two warm-up steps for the blur's seven-row
-// window; a source row that straddles two bands' cells is walked by both).
-struct BaBands {
-  int n;
-  int ra[8], rb[8], c0[8], c1[8];
-};
+// (BaStrip, one strip of a geometry, and BaBands, the row bands of a launch: dcthash_tables.h)
 
 // T = 16-column tiles per strip (the same for every strip of a geometry).  RS = rows of a step one lane carries through the
 // area walk: 4 (strips of <= 16 cells: lane = image, cell), 2 (<= 8 cells: lane = image, cell, row pair) or 1 (<= 4 cells:
@@ -1517,62 +1488,47 @@ __global__ __launch_bounds__(kThreads) void k_tile_hash(const float* __restrict_
   hash_from_tile(tile, sZ, sT, sY, out + blockIdx.x, tabs);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host side.  dcthash_tables.h builds every table and sizes the strips (no device involved); here the tables are cached
+// per device, and launch_dcthash routes a call to one of the kernel paths.
+
+// The device buffers of one cache entry: all are allocated (hipMalloc here is the gated one, called in the order given),
+// then filled.  All or nothing: a table that could not be made leaves nothing behind -- what was allocated is freed, the
+// error is reported, the caller inserts no entry and the next call starts over.
+struct Upload {
+  void** dst;  // null before the call
+  const void* src;
+  size_t bytes;
+  template <class T>
+  Upload(T** d, const std::vector<T>& host) : dst(reinterpret_cast<void**>(d)), src(host.data()), bytes(host.size() * sizeof(T)) {}
+};
+int upload_entry(const std::vector<Upload>& parts) {
+  hipError_t e = hipSuccess;
+  for (const Upload& p : parts)
+    if (e == hipSuccess) e = hipMalloc(p.dst, p.bytes);
+  for (const Upload& p : parts)
+    if (e == hipSuccess) e = hipMemcpy(*p.dst, p.src, p.bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    for (const Upload& p : parts)
+      if (*p.dst) (void)hipFree(*p.dst), *p.dst = nullptr;
+    CBH_HIP(e);
+  }
+  return CBH_OK;
+}
 
 struct TableCache {
   std::mutex mu;
   DctTables* d[16] = {};  // [device]
 } g_tabs;
 
-}  // namespace
-
-namespace {
-
-// computeResizeAreaTab (OpenCV 2.4 imgwarp.cpp, as recalled): see oracle/cbird_oracle.c for the prose
-// cv::resize: inv_scale = (double)dsize/ssize; scale = 1./inv_scale (two roundings -- it is not ssize/dsize), and the
-// integer "area fast" path only when |scale - round(scale)| < DBL_EPSILON on both axes: for ssize = 32*m with
-// m = 49, 93, 98, 99, 103 ... the double rounding misses m by an ulp and the weighted tables are used instead.
-double cv_resize_scale(int ssize, int dsize) {
-  const double inv_scale = (double)dsize / ssize;
-  return 1. / inv_scale;
-}
-}  // namespace
-bool area_fast(int w, int h) {
-  const double sx = cv_resize_scale(w, 32), sy = cv_resize_scale(h, 32);
-  return std::fabs(sx - std::nearbyint(sx)) < DBL_EPSILON && std::fabs(sy - std::nearbyint(sy)) < DBL_EPSILON;
-}
-
-std::vector<AreaTab> make_area_tab(int ssize, int dsize, std::vector<int>* first) {
-  std::vector<AreaTab> tab;
-  const double scale = cv_resize_scale(ssize, dsize);
-  first->assign((size_t)dsize + 1, 0);
-  for (int dx = 0; dx < dsize; dx++) {
-    (*first)[(size_t)dx] = (int)tab.size();
-    const double fsx1 = dx * scale, fsx2 = fsx1 + scale;
-    const double cellWidth = std::min(scale, ssize - fsx1);
-    int sx1 = (int)__builtin_ceil(fsx1), sx2 = (int)__builtin_floor(fsx2);
-    sx2 = std::min(sx2, ssize - 1);
-    sx1 = std::min(sx1, sx2);
-    if (sx1 - fsx1 > 1e-3) tab.push_back(AreaTab{sx1 - 1, dx, (float)((sx1 - fsx1) / cellWidth)});
-    for (int sx = sx1; sx < sx2; sx++) tab.push_back(AreaTab{sx, dx, (float)(1.0 / cellWidth)});
-    if (fsx2 - sx2 > 1e-3)
-      tab.push_back(AreaTab{sx2, dx, (float)(std::min(std::min(fsx2 - sx2, 1.), cellWidth) / cellWidth)});
-  }
-  (*first)[(size_t)dsize] = (int)tab.size();
-  return tab;
-}
-
-namespace {
-
 struct AreaTabsDev {
   AreaTab *x = nullptr, *y = nullptr;
   int *xfirst = nullptr, *yfirst = nullptr;
   int xn = 0, yn = 0;
   YRow* yrow = nullptr;  // h entries, nullptr when some source row has more than two entries (never for h >= 32);
-                         // kYRowPad neutral entries before and behind them (k_band_area reads the four rows of a step
-                         // without clamping their indices)
+                         // kYRowPad neutral entries before and behind them (make_yrows)
   YRow* yrow_base = nullptr;
 };
-constexpr int kYRowPad = 8;
 std::mutex g_area_mu;
 std::map<std::tuple<int, int, int>, AreaTabsDev> g_area;  // (device, w, h)
 
@@ -1584,65 +1540,22 @@ int get_area_tabs(int w, int h, AreaTabsDev* out) {
   auto it = g_area.find(key);
   if (it == g_area.end()) {
     std::vector<int> xf, yf;
-    std::vector<AreaTab> xt = make_area_tab(w, 32, &xf), yt = make_area_tab(h, 32, &yf);
+    const std::vector<AreaTab> xt = make_area_tab(w, 32, &xf), yt = make_area_tab(h, 32, &yf);
+    const std::vector<YRow> yr = make_yrows(h, yt, yf);
     AreaTabsDev d;
     d.xn = (int)xt.size();
     d.yn = (int)yt.size();
-    // all or nothing: a table that could not be made leaves nothing behind (the next call starts over)
-    hipError_t e = hipMalloc(&d.x, xt.size() * sizeof(AreaTab));
-    if (e == hipSuccess) e = hipMalloc(&d.y, yt.size() * sizeof(AreaTab));
-    if (e == hipSuccess) e = hipMalloc(&d.xfirst, 33 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&d.yfirst, 33 * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(d.x, xt.data(), xt.size() * sizeof(AreaTab), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d.y, yt.data(), yt.size() * sizeof(AreaTab), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d.xfirst, xf.data(), 33 * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d.yfirst, yf.data(), 33 * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-      std::vector<YRow> yr_all((size_t)h + 2 * kYRowPad, YRow{0.f, 0.f, 0, 1.f});
-      YRow* const yr = yr_all.data() + kYRowPad;
-      std::vector<int> cnt((size_t)h, 0);
-      bool ok = true;
-      for (size_t j = 0; j < yt.size() && ok; ++j) {
-        const AreaTab& en = yt[j];
-        if (en.si < 0 || en.si >= h || en.di < 0 || en.di > 31) {
-          ok = false;
-          break;
-        }
-        const bool opens = (int)j == yf[(size_t)en.di], closes = (int)j + 1 == yf[(size_t)en.di + 1];
-        YRow& r = yr[(size_t)en.si];
-        if (cnt[(size_t)en.si] == 0) {
-          r.a0 = en.alpha;
-          r.info = en.di | (opens ? 0x100 : 0) | (closes ? 0x200 : 0);
-          r.k0 = opens ? 0.f : 1.f;
-        } else if (cnt[(size_t)en.si] == 1 && en.di == (r.info & 0xff) + 1) {
-          r.a1 = en.alpha;
-          r.info |= 0x400 | (opens ? 0x800 : 0) | (closes ? 0x1000 : 0);
-        } else {
-          ok = false;
-        }
-        cnt[(size_t)en.si]++;
-      }
-      for (int y = 0; y < h && ok; ++y) ok = cnt[(size_t)y] >= 1;
-      if (ok) {
-        e = hipMalloc(&d.yrow_base, yr_all.size() * sizeof(YRow));
-        if (e == hipSuccess) e = hipMemcpy(d.yrow_base, yr_all.data(), yr_all.size() * sizeof(YRow), hipMemcpyHostToDevice);
-        if (e == hipSuccess) d.yrow = d.yrow_base + kYRowPad;
-      }
-    }
-    if (e != hipSuccess) {
-      for (void* q : {(void*)d.x, (void*)d.y, (void*)d.xfirst, (void*)d.yfirst, (void*)d.yrow_base})
-        if (q) (void)hipFree(q);
-      CBH_HIP(e);
-    }
+    std::vector<Upload> parts = {{&d.x, xt}, {&d.y, yt}, {&d.xfirst, xf}, {&d.yfirst, yf}};
+    if (!yr.empty()) parts.push_back({&d.yrow_base, yr});
+    if (int rc = upload_entry(parts)) return rc;
+    if (d.yrow_base) d.yrow = d.yrow_base + kYRowPad;
     it = g_area.emplace(key, d).first;
   }
   *out = it->second;
   return CBH_OK;
 }
 
-// Column strips of an image wider than 2048 pixels (k_blur_area_regs spans a row with one workgroup of <= 256 lanes x 8
-// columns): strip s of ncol makes the output cells [s * 32 / ncol, (s + 1) * 32 / ncol); it covers the source columns of
-// exactly those cells (the blur's 3-pixel border comes from the parent through the view mechanism).
+// One column strip of an image wider than 2048 pixels (make_strip_geom)
 struct StripTabs {
   AreaTab* x = nullptr;  // fractional ratios: the cells' table entries, si relative to x0
   int* xfirst = nullptr;
@@ -1658,31 +1571,13 @@ int get_strip_tabs(int w, bool integer, int ncol, int s, StripTabs* out) {
   auto key = std::make_tuple(dev, integer ? -w : w, ncol, s);
   auto it = g_strips.find(key);
   if (it == g_strips.end()) {
-    const int cpw = 32 / ncol, c_lo = s * cpw, c_hi = c_lo + cpw;
+    const StripGeom g = make_strip_geom(w, integer, ncol, s);
     StripTabs d;
-    if (integer) {
-      d.x0 = c_lo * (w / 32);
-      d.ws = cpw * (w / 32);
-    } else {
-      std::vector<int> xf;
-      const std::vector<AreaTab> xt = make_area_tab(w, 32, &xf);
-      const int e0 = xf[(size_t)c_lo], e1 = xf[(size_t)c_hi];
-      d.x0 = xt[(size_t)e0].si;
-      d.ws = xt[(size_t)e1 - 1].si + 1 - d.x0;
-      std::vector<AreaTab> st(xt.begin() + e0, xt.begin() + e1);
-      for (AreaTab& e : st) e.si -= d.x0, e.di -= c_lo;
-      std::vector<int> sf(33);
-      for (int c = 0; c <= 32; ++c) sf[(size_t)c] = xf[(size_t)std::min(c_lo + c, c_hi)] - e0;
-      d.xn = (int)st.size();
-      hipError_t e = hipMalloc(&d.x, st.size() * sizeof(AreaTab));
-      if (e == hipSuccess) e = hipMalloc(&d.xfirst, 33 * sizeof(int));
-      if (e == hipSuccess) e = hipMemcpy(d.x, st.data(), st.size() * sizeof(AreaTab), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(d.xfirst, sf.data(), 33 * sizeof(int), hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        if (d.x) (void)hipFree(d.x);
-        if (d.xfirst) (void)hipFree(d.xfirst);
-        CBH_HIP(e);
-      }
+    d.x0 = g.x0;
+    d.ws = g.ws;
+    if (!integer) {
+      d.xn = (int)g.x.size();
+      if (int rc = upload_entry({{&d.x, g.x}, {&d.xfirst, g.xfirst}})) return rc;
     }
     it = g_strips.emplace(key, d).first;
   }
@@ -1690,19 +1585,8 @@ int get_strip_tabs(int w, bool integer, int ncol, int s, StripTabs* out) {
   return CBH_OK;
 }
 
-}  // namespace
-
-namespace {
-
-int reflect101_host(int p, int len);
-
-// Strips and band matrices of k_band_area for images of width w: n_strips >= 2 strips of cps = ceil(32 / n_strips) <= 16
-// cells, each at most 240 source columns wide with cells of at most 32 table entries.  *out = nullptr (and CBH_OK) when
-// the geometry does not fit (the caller takes k_blur_area_regs).
-// "hash_band_area": 1 (default) = fractional-ratio geometries whose strips hold >= 4 cells (w <= 1920) take k_band_area (blur
-// on the matrix cores, up to four rows per area walk), 0 = k_blur_area_regs as through round 4
-int g_hash_band_area = 1;
-
+// k_band_area's strips for images of width w (make_ba_strips); strips = nullptr (and CBH_OK) when the geometry does not
+// fit (the caller takes k_blur_area_regs)
 struct BaTabsDev {
   BaStrip* strips = nullptr;
   int n_strips = 0, T = 0, amax = 0, RS = 4;
@@ -1716,146 +1600,15 @@ int get_ba_tabs(int w, BaTabsDev* out) {
   auto key = std::make_pair(dev, w);
   auto it = g_ba_tabs.find(key);
   if (it == g_ba_tabs.end()) {
+    const BaStripList host = make_ba_strips(w);
     BaTabsDev d;
-    std::vector<int> xf;
-    const std::vector<AreaTab> xt = make_area_tab(w, 32, &xf);
-    std::vector<BaStrip> host;
-    auto band_of = [&](int xs0, int c, bool plain, unsigned (*dst)[4]) {
-      for (int l = 0; l < 64; ++l)
-        for (int j = 0; j < 16; ++j) {
-          const int k = 16 * (l >> 4) + j, kk = k & 31;
-          const int col = xs0 + 16 * c - 8 + kk, xo = xs0 + 16 * c + (l & 15);
-          int wgt = 0;
-          if (plain) {
-            wgt = std::abs(col - xo) <= 3 ? 1 : 0;
-          } else if (col >= 0 && col < w && xo < w) {
-            for (int dd = -3; dd <= 3; ++dd) wgt += reflect101_host(xo + dd, w) == col;
-          }
-          if (k >= 32) wgt = -wgt;
-          dst[l][j >> 2] |= (unsigned)(wgt & 0xff) << (8 * (j & 3));
-        }
-    };
-    // cells per strip, in order of preference: 16 or 11 (a lane carries the four rows of a step: RS 4), 8 (two rows: RS 2),
-    // 4 (one row: RS 1; w <= 1920).  Two cells per strip (w <= 3840) leave half the walk's lanes idle: measured 1.45 TB/s at
-    // 3840 x 2160 against k_blur_area_regs' 2.6 -- not offered.
-    // (fewer cells per strip than the geometry allows -- shorter rings, 15 instead of 10 waves per CU -- lose more to the
-    // strips' halos than the occupancy returns: 400 x 300 2.92 -> 2.72 TB/s with 8 cells, 160 x 120 2.03 -> 1.42;
-    // profiles/r06_band_area_cells_per_strip.txt)
-    const int cps_try[4] = {16, 11, 8, 4};
-    for (int ci = 0; ci < 4 && host.empty(); ++ci) {
-      const int cps = cps_try[ci];
-      bool ok = true;
-      // one tile count for every strip: the widest strip's
-      int Tc = 0;
-      for (int c0 = 0; c0 < 32 && ok; c0 += cps) {
-        const int c1 = std::min(32, c0 + cps);
-        Tc = std::max(Tc, (xt[(size_t)xf[(size_t)c1] - 1].si + 1 - xt[(size_t)xf[(size_t)c0]].si + 15) / 16);
-      }
-      ok = ok && Tc >= 2 && Tc <= 15 && 16 * Tc + 8 <= w;
-      if (!ok) continue;
-      d.RS = cps > 8 ? 4 : cps == 8 ? 2 : 1;
-      std::vector<BaStrip> cand;
-      for (int c0 = 0; c0 < 32 && ok; c0 += cps) {
-        const int c1 = std::min(32, c0 + cps);
-        BaStrip b;
-        memset(&b, 0, sizeof b);
-        const int xs_cells = xt[(size_t)xf[(size_t)c0]].si;
-        // the strip's tiles start at its first cell -- or further left, so that the LAST strip's tiles end exactly at
-        // column w - 1 (then only its last tile sees the right edge) and no strip reaches past it
-        b.xs = c0 == 0 ? 0 : std::min(xs_cells, w - 16 * Tc);
-        b.T = Tc;
-        b.cell0 = c0;
-        b.ncell = c1 - c0;
-        ok = b.xs == 0 || b.xs >= 8;
-        if (c1 == 32) ok = ok && b.xs == w - 16 * Tc;
-        for (int c = c0; c < c1 && ok; ++c) {
-          const int e0 = xf[(size_t)c], e1 = xf[(size_t)c + 1];
-          ok = e1 - e0 >= 2;
-          b.amax = std::max(b.amax, e1 - e0);
-          b.amin = c == c0 ? e1 - e0 : std::min(b.amin, e1 - e0);
-          b.si0[c - c0] = xt[(size_t)e0].si - b.xs;
-          ok = ok && b.si0[c - c0] >= 0 && b.si0[c - c0] + (e1 - e0) <= 16 * Tc;
-          for (int e = e0; e < e1 && ok; ++e) {
-            ok = xt[(size_t)e].si == xt[(size_t)e0].si + (e - e0) && xt[(size_t)e].di == c;  // consecutive columns, in order
-          }
-        }
-        ok = ok && b.amax - b.amin + 1 <= 4;
-        for (int c = c0; c < c1 && ok; ++c) {  // the walk's weights: first, mid (entries 1 .. amin - 2), tail
-          const int e0 = xf[(size_t)c], nn = xf[(size_t)c + 1] - e0;
-          b.wfirst[c - c0] = xt[(size_t)e0].alpha;
-          b.wmid[c - c0] = xt[(size_t)e0 + 1].alpha;
-          for (int k = 1; k <= b.amin - 2 && ok; ++k) ok = xt[(size_t)(e0 + k)].alpha == b.wmid[c - c0];
-          for (int j = 0; j < 4; ++j) b.wtail[c - c0][j] = b.amin - 1 + j < nn ? xt[(size_t)(e0 + b.amin - 1 + j)].alpha : 0.f;
-        }
-        if (b.amin == b.amax && (b.amin == 16 || b.amin == 32)) {
-          b.rotm = b.amin - 1;
-          for (int c = 0; c < b.ncell; ++c) b.rot[c] = c * std::max(1, b.amin / b.ncell) & b.rotm;
-        }
-        {  // plane stride: the fewest lanes per LDS bank over the walk (every lane advances by one column per read)
-          int best = 1 << 30;
-          for (int cand_tp = 16 * Tc + 8; cand_tp <= 16 * Tc + 8 + 39; ++cand_tp) {
-            int cnt[32] = {0};
-            for (int im = 0; im < 4; ++im)
-              for (int c = 0; c < b.ncell; ++c) cnt[(b.si0[c] + b.rot[c] + im * cand_tp) & 31]++;
-            int worst = 0;
-            for (int k = 0; k < 32; ++k) worst = std::max(worst, cnt[k]);
-            // (ties: prefer strides that also keep the blur's stores -- 16 consecutive columns per image -- apart)
-            const int score = worst * 64 + ((cand_tp & 31) == 16 ? 0 : (cand_tp & 15) == 8 ? 1 : 2);
-            if (score < best) best = score, b.tp = cand_tp;
-          }
-        }
-        band_of(b.xs, 0, true, b.band[0]);
-        band_of(b.xs, 0, false, b.band[1]);
-        band_of(b.xs, Tc - 1, false, b.band[2]);
-        // every tile between must be the plain band: no image edge within three columns of it
-        for (int c = 1; c + 1 < Tc && ok; ++c) {
-          unsigned m[64][4];
-          memset(m, 0, sizeof m);
-          band_of(b.xs, c, false, m);
-          ok = memcmp(m, b.band[0], sizeof m) == 0;
-        }
-        cand.push_back(b);
-      }
-      if (ok) host.swap(cand);
-    }
-    if (!host.empty()) {
-      for (BaStrip& b : host) d.amax = std::max(d.amax, b.amax);
-      hipError_t e = hipMalloc(&d.strips, host.size() * sizeof(BaStrip));
-      if (e == hipSuccess) e = hipMemcpy(d.strips, host.data(), host.size() * sizeof(BaStrip), hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        if (d.strips) (void)hipFree(d.strips);
-        CBH_HIP(e);
-      }
-      d.n_strips = (int)host.size();
-      d.T = host[0].T;
-    }
+    d.n_strips = host.n_strips, d.T = host.T, d.amax = host.amax, d.RS = host.RS;
+    if (!host.strips.empty())
+      if (int rc = upload_entry({{&d.strips, host.strips}})) return rc;
     it = g_ba_tabs.emplace(key, d).first;
   }
   *out = it->second;
   return CBH_OK;
-}
-
-}  // namespace
-
-namespace {
-
-int reflect101_host(int p, int len) {
-  while (p < 0 || p >= len) p = p < 0 ? -p : 2 * (len - 1) - p;
-  return p;
-}
-
-// The B operand of k_dcthash_256_band: lane l = (column n = l & 15 of the tile, chunk q = l >> 4), byte j <-> k = 16 q + j.
-// k < 32: source column 16 c - 8 + k of the row, weight 1 on the 7 taps of output column 16 c + n (an interior tile: the
-// kernel mirrors the image's edge columns into the ring); k >= 32: the same columns of the row seven above, weights negated.
-void make_band_tables(BandTables* bt) {
-  memset(bt, 0, sizeof(*bt));
-  for (int l = 0; l < 64; ++l)
-    for (int j = 0; j < 16; ++j) {
-      const int k = 16 * (l >> 4) + j, kk = k & 31;
-      int wgt = std::abs((kk - 8) - (l & 15)) <= 3 ? 1 : 0;
-      if (k >= 32) wgt = -wgt;
-      bt->w[0][l][j >> 2] |= (unsigned)(wgt & 0xff) << (8 * (j & 3));
-    }
 }
 
 struct BandTabCache {
@@ -1871,82 +1624,15 @@ int get_band_tables(const BandTables** out) {
     std::vector<BandTables> host(1);
     make_band_tables(host.data());
     BandTables* d = nullptr;
-    CBH_HIP(hipMalloc(&d, sizeof(BandTables)));
-    hipError_t e = hipMemcpy(d, host.data(), sizeof(BandTables), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(d);
-      CBH_HIP(e);
-    }
+    if (int rc = upload_entry({{&d, host}})) return rc;
     g_band_tabs.d[dev] = d;
   }
   *out = g_band_tabs.d[dev];
   return CBH_OK;
 }
 
-}  // namespace
-
-// "hash_mfma": which kernel hashes 256 x 256 tiles -- non-zero (default 2) k_dcthash_256_band (horizontal box sums on the
-// matrix cores; needs 16-byte aligned rows, else 0 is taken), 0 k_dcthash_256 (all VALU: what runs when the band tables
-// cannot be made; the parity suite runs both).
-int g_hash_mfma = 2;
-int g_hash_mfma_set(int v) { return g_hash_mfma = v; }
-void set_hash_band_area(int v) { g_hash_band_area = v < 0 ? 0 : v > 2 ? 2 : v; }
-int g_hash_fuse = 1;  // "hash_fuse": 1 = k_blur_area_regs<.., FUSE> (vertical pass + tile in the strip kernel) when the batch
-                      // gives >= 512 workgroups, 2 = always, 0 = never (k_tile_hash reads the rows back)
-void set_hash_fuse(int v) {
-  if (v >= 0 && v <= 2) g_hash_fuse = v;
-}
-// "hash_stream": k_blur_area_regs on strips: 0 never (k_blur_area's 16-row bands for every batch), 1 = when
-                        // the batch is large enough (strips of 3..8 steps), v >= 2 = always, strips of v steps (the parity
-                        // suite's way to put a handful of images through the strip kernel)
-int g_hash_stream = 1;
-void set_hash_stream(int v) {
-  if (v >= 0) g_hash_stream = v;
-}
-// rows per step for a workgroup of T threads making ncell cells per row: a turn of the area phase has 2 T / ncell row
-// slots, and 14 rows fill a turn of 12 (T = 192), 24, 32, 48 or 64 slots badly -- 21 where that fills the turns better
-static int pick_rows_per_step(int K, unsigned T, int ncell, size_t lds_per_row, size_t lds_fixed) {
-  if (K != 7) return 15;
-  auto fits = [&](int ks) { return lds_fixed + (size_t)ks * lds_per_row <= (size_t)64 * 1024; };
-  const int cap = (int)(2 * T) / ncell;
-  int best = 14;
-  double best_u = 0.0;
-  for (int ks : {14, 21}) {  // (28 measured too: slower than 21 everywhere, 15-30 % slower than 14 on one-wave workgroups)
-    if (!fits(ks)) break;
-    const int turns = (ks + cap - 1) / cap;
-    const double u = (double)ks / ((double)turns * cap);
-    if (u > best_u + 0.05) best = ks, best_u = u;  // (more rows per step only for a real gain: they cost LDS)
-  }
-  return best;
-}
-// steps per strip of k_blur_area_regs: every strip re-reads the 6 rows of blur halo and its last step may be partly
-// empty, so the rows PROCESSED depend on how h divides: 960 rows in strips of 8 x 14 = 106 output rows are 10 strips =
-// 1120 rows, in strips of 9 x 14 = 120 they are 8 = 1008.  Around the target (which the batch size sets: enough
-// workgroups), the count that processes the fewest rows; ties go to the longer strip.  "hash_stream" >= 2 forces its value.
-static int pick_steps_per_strip(int h, int ks, int target, int halo) {
-  const int all = (h + halo + ks - 1) / ks;  // one strip spanning the image
-  if (g_hash_stream >= 2 || target >= all) return std::max(1, std::min(target, all));
-  int best = target;
-  long long best_rows = -1;
-  for (int st = std::max(2, target - 1); st <= std::min(all, target + 3); ++st) {
-    const int out = st * ks - halo;
-    if (out <= 0) continue;
-    const long long rows = (long long)((h + out - 1) / out) * st * ks;
-    if (best_rows < 0 || rows <= best_rows) best = st, best_rows = rows;
-  }
-  return best;
-}
-// integer ratios, cells of nd = isx / 4 dwords: the 32 lanes of a row group read dword u of their cells together, gcd(nd, 32)
-// to a bank -- one pad dword behind every cell of a blurred LDS row where that would be 4 ways or more (512, 1024, 1536 px ...)
-static int cell_pad_for(bool integer, int isx) {
-  if (!integer || (isx & 7)) return 0;  // (nd even: a blur lane's two dwords stay in one cell)
-  int g = 1;
-  while (g < 32 && ((isx >> 2) % (2 * g)) == 0) g *= 2;
-  return g >= 4 ? 1 : 0;
-}
-
 // Host-side table construction (same closed forms as the oracle, computed independently here).
-static void make_tables(DctTables* t) {
+void make_tables(DctTables* t) {
   // 9x9 zig-zag, first step downwards (equals the table at cvutil.cpp:491-495); keep 6..69
   int zz[81], n = 0;
   for (int s = 0; s <= 16; ++s) {
@@ -1960,26 +1646,437 @@ static void make_tables(DctTables* t) {
   cv_dct32_make_tabs(&t->cv);
 }
 
+// The image hash's knobs (cbh_set_tuning; include/cbird_hip.h documents them); each setter below holds its knob's one
+// clamping rule.
+struct HashKnobs {
+  // "hash_mfma": which kernel hashes 256 x 256 tiles -- non-zero (default 2) k_dcthash_256_band (horizontal box sums on
+  // the matrix cores; needs 16-byte aligned rows, else 0 is taken), 0 k_dcthash_256 (all VALU: what runs when the band
+  // tables cannot be made; the parity suite runs both).
+  int mfma = 2;
+  // "hash_band_area": 1 (default) = fractional-ratio geometries whose strips hold >= 4 cells (w <= 1920) take k_band_area
+  // (blur on the matrix cores, up to four rows per area walk), 0 = k_blur_area_regs as through round 4
+  int band_area = 1;
+  // "hash_fuse": 1 = k_blur_area_regs<.., FUSE> (vertical pass + tile in the strip kernel) when the batch gives >= 512
+  // workgroups, 2 = always, 0 = never (k_tile_hash reads the rows back)
+  int fuse = 1;
+  // "hash_stream": k_blur_area_regs on strips: 0 never (k_blur_area's 16-row bands for every batch), 1 = when the batch
+  // is large enough (strips of 3..8 steps), v >= 2 = always, strips of v steps (the parity suite's way to put a handful
+  // of images through the strip kernel)
+  int stream = 1;
+} g_hash;
+
+}  // namespace
+
+void set_hash_mfma(int v) { g_hash.mfma = v; }  // (any value: only zero / non-zero is read)
+void set_hash_band_area(int v) { g_hash.band_area = v < 0 ? 0 : v > 2 ? 2 : v; }
+void set_hash_fuse(int v) {
+  if (v >= 0 && v <= 2) g_hash.fuse = v;
+}
+void set_hash_stream(int v) {
+  if (v >= 0) g_hash.stream = v;
+}
+
 int get_tables(const DctTables** out) {
   int dev = 0;
   CBH_HIP(hipGetDevice(&dev));
   if (dev < 0 || dev >= 16) return CBH_E_INVAL;
   std::lock_guard<std::mutex> lk(g_tabs.mu);
   if (!g_tabs.d[dev]) {
-    DctTables host;
-    make_tables(&host);
+    std::vector<DctTables> host(1);
+    make_tables(host.data());
     DctTables* d = nullptr;
-    CBH_HIP(hipMalloc(&d, sizeof(DctTables)));
-    hipError_t e = hipMemcpy(d, &host, sizeof(DctTables), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(d);
-      CBH_HIP(e);
-    }
+    if (int rc = upload_entry({{&d, host}})) return rc;
     g_tabs.d[dev] = d;
   }
   *out = g_tabs.d[dev];
   return CBH_OK;
 }
+
+namespace {
+
+// One launch_dcthash call after validation: n images of w x h, image i at imgs + i * img_stride, rows row_stride apart.
+struct HashCall {
+  const uint8_t* imgs;
+  size_t n;
+  int w, h;
+  size_t row_stride, img_stride;
+  // a view: the w x h images are sub-rectangles at (ox, oy) of pw x ph parents that start at imgs (+ i * img_stride); the
+  // blur takes its border from the parent.  Normalised: whole images have view == false and vw = {w, h, 0, 0}.
+  HashView vw;
+  bool view;
+  hipStream_t stream;
+  uint64_t* out;
+  uint8_t* tiles;                  // optional: a copy of every image's 32 x 32 tile
+  const DctTables* tabs = nullptr;
+  // the general paths (everything but the rectangle kernel and 256 x 256)
+  int K = 7;  // blur kernel
+  AreaTabsDev at;
+  bool integer = false;  // area_fast(w, h); then isx x isy pixels per cell
+  int isx = 0, isy = 0;
+
+  uint8_t* tiles_at(size_t i0) const { return tiles ? tiles + i0 * 1024 : nullptr; }
+};
+
+// f(std::integral_constant<int, V>{}) for the V in [LO, HI] that equals v; CBH_E_UNSUPPORTED when none does
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <int LO, int HI, class F>
+int with_int(int v, F&& f) {
+  if constexpr (LO <= HI) return v == LO ? f(int_c<LO>{}) : with_int<LO + 1, HI>(v, f);
+  return CBH_E_UNSUPPORTED;
+}
+
+// stages 3-6 of the images [i0, i0 + m) from their 32 x 32 tiles / from their 32-column rows (vertical INTER_AREA first)
+void hash_tiles(const HashCall& c, const unsigned char* d_tiles32, size_t i0, size_t m) {
+  hipLaunchKernelGGL(k_tiles_hash2, dim3((unsigned)((m + 1) / 2)), dim3(64), 0, c.stream, d_tiles32, (unsigned)m, c.tabs,
+                     c.out + i0, c.tiles_at(i0));
+}
+void hash_rows(const HashCall& c, const float* d_rowsf, size_t i0, size_t m) {
+  hipLaunchKernelGGL(k_tile_hash, dim3((unsigned)m), dim3(kThreads), 0, c.stream, d_rowsf, c.h, c.at.y, c.at.yfirst, c.isx,
+                     c.isy, 1, c.tabs, c.out + i0, c.tiles_at(i0));
+}
+
+// ---- 1. a side enlarges (cv::resize's bilinear emulation), or nothing is resized at all: the rectangle kernel, one
+// rectangle = the whole image
+int hash_rects(const HashCall& c) {
+  const size_t per_chunk = (size_t)1 << 20;
+  for (size_t i0 = 0; i0 < c.n; i0 += per_chunk) {
+    const size_t m = std::min(per_chunk, c.n - i0);
+    std::vector<RectImageDesc> images(m);
+    std::vector<int> rects(4 * m);
+    for (size_t i = 0; i < m; ++i) {
+      images[i] = RectImageDesc{(unsigned long long)(i * c.img_stride), c.vw.pw, c.vw.ph, (unsigned)c.row_stride,
+                                (unsigned)i, 1u};
+      rects[4 * i] = c.vw.ox, rects[4 * i + 1] = c.vw.oy, rects[4 * i + 2] = c.w, rects[4 * i + 3] = c.h;
+    }
+    int rc2 = launch_rect_hashes(const_cast<uint8_t*>(c.imgs) + i0 * c.img_stride, images, rects, 0, c.out + i0, c.stream,
+                                 c.tiles_at(i0));
+    if (rc2) return rc2;
+  }
+  return CBH_OK;
+}
+
+// ---- 2. 256 x 256 (8-byte aligned rows; anything else of that size takes the general kernels)
+bool is_256(const HashCall& c) {
+  return !c.view && c.w == 256 && c.h == 256 && ((uintptr_t)c.imgs % 8) == 0 && c.row_stride % 8 == 0 &&
+         c.img_stride % 8 == 0 && c.row_stride * 256 < (1u << 24) && c.img_stride < (1u << 28);
+}
+int hash_256(const HashCall& c) {
+  const unsigned n = (unsigned)c.n, rs = (unsigned)c.row_stride, is = (unsigned)c.img_stride;
+  const BandTables* btab = nullptr;
+  const bool band = g_hash.mfma != 0 && ((uintptr_t)c.imgs % 16) == 0 && c.row_stride % 16 == 0 &&
+                    c.img_stride % 16 == 0 && get_band_tables(&btab) == CBH_OK;
+  if (!band) cbh_clear_error();  // (no table on this device: the all-VALU kernel needs none)
+  auto launch = [&](auto dump) {  // DUMP: the kernels also write the tiles
+    if (band)
+      hipLaunchKernelGGL(k_dcthash_256_band<decltype(dump)::value>, dim3((unsigned)((c.n + 3) / 4)), dim3(64), 0, c.stream,
+                         c.imgs, n, rs, is, c.tabs, btab, c.out, c.tiles);
+    else
+      hipLaunchKernelGGL(k_dcthash_256<decltype(dump)::value>, dim3((unsigned)((c.n + 7) / 8)), dim3(kThreads), 0, c.stream,
+                         c.imgs, n, rs, is, c.tabs, c.out, c.tiles);
+  };
+  c.tiles ? launch(std::true_type{}) : launch(std::false_type{});
+  CBH_HIP(hipGetLastError());
+  return CBH_OK;
+}
+
+// ---- 3. k_band_area.  true: the call takes it, on the strips in *bat
+bool band_area_tabs(const HashCall& c, BaTabsDev* bat) {
+  const HashView& vw = c.vw;
+  // (views: a vertical edge is the parent's, or lies far enough inside it that the blur's three columns -- and on the left
+  // the staging chunk's eight -- are the parent's pixels: letterboxed and pillarboxed frames after autocrop)
+  // (integer ratios: every width but 1024 -- strips of 128 columns on rows a multiple of the cache line apart put every row's
+  // 144 staged bytes across three lines, 2.84 TB/s against k_blur_area_regs' 3.1; profiles/r06_band_area_int.txt)
+  const bool ba_view = !c.view || ((vw.ox == 0 || vw.ox >= 8) && (vw.ox + c.w == vw.pw || vw.ox + c.w + 3 <= vw.pw));
+  if (!(g_hash.band_area && ba_view && c.K == 7 && (c.integer ? c.isx >= 2 && c.w != 1024 : c.at.yrow != nullptr) &&
+        c.w >= 64 && 4ull * c.img_stride < (1ull << 32) && (size_t)vw.ph * c.row_stride < ((size_t)1 << 32)))
+    return false;
+  if (get_ba_tabs(c.w, bat) != CBH_OK) {  // (its table could not be made: k_blur_area_regs needs none)
+    cbh_clear_error();
+    bat->strips = nullptr;
+  }
+  return bat->strips != nullptr;
+}
+int hash_band_area(const HashCall& c, const BaTabsDev& bat) {
+  const HashView& vw = c.vw;
+  const size_t per_chunk_b = 200000;  // (grid y)
+  unsigned char* d_btiles = nullptr;
+  cbh::Scratch scratch(c.stream);
+  CBH_HIP(scratch.get(&d_btiles, std::min(per_chunk_b, c.n) * 1024));
+  for (size_t i0 = 0; i0 < c.n; i0 += per_chunk_b) {
+    const size_t m = std::min(per_chunk_b, c.n - i0);
+    const unsigned char* src = c.imgs + i0 * c.img_stride;
+    const unsigned long long bytes = (unsigned long long)(m - 1) * c.img_stride + (unsigned long long)(vw.ph - 1) * c.row_stride + (unsigned)vw.pw;
+    // row bands: enough waves for ~two rounds of the machine's 2560 slots, at least 4 output rows per band
+    BaBands bands;
+    bands.n = 1;
+    while (bands.n < 8 && (m + 3) / 4 * (size_t)bat.n_strips * (size_t)bands.n < 5120) bands.n *= 2;
+    std::vector<int> yf;
+    const std::vector<AreaTab> yt = c.integer ? std::vector<AreaTab>() : make_area_tab(c.h, 32, &yf);
+    for (int b_ = 0; b_ < bands.n; ++b_) {
+      const int c0_ = 32 * b_ / bands.n, c1_ = 32 * (b_ + 1) / bands.n;
+      bands.c0[b_] = c0_, bands.c1[b_] = c1_;
+      bands.ra[b_] = c.integer ? c0_ * c.isy : yt[(size_t)yf[(size_t)c0_]].si;
+      bands.rb[b_] = c.integer ? c1_ * c.isy - 1 : yt[(size_t)yf[(size_t)c1_] - 1].si;
+    }
+    const dim3 grid((unsigned)(((m + 3) / 4 + 7) / 8 * 8 * (size_t)bat.n_strips * (size_t)bands.n));
+    const int inner = (vw.ox > 0 ? 1 : 0) | (vw.ox + c.w < vw.pw ? 2 : 0);
+    // k_band_area<T 2..15, RS 4 / 2 / 1, integer ratios or not>
+    const int rc = with_int<2, 15>(bat.T, [&](auto tt) {
+      auto launch = [&](auto rs, auto ii) {
+        hipLaunchKernelGGL((k_band_area<decltype(tt)::value, decltype(rs)::value, decltype(ii)::value>), grid, dim3(64), 0,
+                           c.stream, src, (unsigned)m, c.w, c.h, (unsigned)c.row_stride, (unsigned)c.img_stride, bytes,
+                           bat.strips, bat.n_strips, c.at.yrow, d_btiles, vw.oy, vw.ph, vw.ox, inner, bands, c.isy);
+        return CBH_OK;
+      };
+      auto by_ratio = [&](auto rs) { return c.integer ? launch(rs, std::true_type{}) : launch(rs, std::false_type{}); };
+      return bat.RS == 4 ? by_ratio(int_c<4>{}) : bat.RS == 2 ? by_ratio(int_c<2>{}) : by_ratio(int_c<1>{});
+    });
+    if (rc) return rc;
+    hash_tiles(c, d_btiles, i0, m);
+    CBH_HIP(hipGetLastError());
+  }
+  return CBH_OK;
+}
+
+// One chunk of a call on the VALU kernels: the images [i0, i0 + m) at src, and the chunk's scratch
+struct Chunk {
+  const unsigned char* src;
+  size_t i0, m;
+  float* d_rowsf;           // m * h * 32: the rows after the horizontal INTER_AREA pass
+  unsigned char* d_ftiles;  // the fused kernel's 32 x 32 tiles (1 KB per image)
+  int target_rows;          // rows per strip that leave the batch enough workgroups (0: no strips)
+};
+
+// ---- 5. (ahead of 4., whose column strips fall back on it) k_blur_area: a workgroup per 16-row band, rows staged in
+// LDS, on ncol column strips: the fewest (1, 2, 4, 8) whose widest window -- first source column of a strip's first cell ..
+// last of its last -- fits 256 lanes x 8 columns.  (Fractional cells overlap by a pixel: 8191 columns need 8 strips.)
+struct BandPlan {
+  int ncol, cpw, Tf, fpitch;
+  size_t fsmem;
+};
+int plan_bands(const HashCall& c, BandPlan* bp) {
+  const int w = c.w;
+  int ncol = w <= 2048 ? 1 : w <= 4096 ? 2 : 4, cpw = 32 / ncol, win = 0;
+  std::vector<int> xf;
+  const std::vector<AreaTab> xt_full = c.integer ? std::vector<AreaTab>() : make_area_tab(w, 32, &xf);
+  for (;; ncol *= 2) {
+    cpw = 32 / ncol;
+    win = 0;
+    if (c.integer) {
+      win = cpw * c.isx;
+    } else {
+      for (int cell = 0; cell < 32; cell += cpw)
+        win = std::max(win, xt_full[(size_t)xf[(size_t)(cell + cpw)] - 1].si + 1 - xt_full[(size_t)xf[(size_t)cell]].si);
+    }
+    if ((win + 7) / 8 <= 256 || ncol == 8) break;
+  }
+  const int Tf = std::min(256, ((win + 7) / 8 + 63) / 64 * 64);
+  if ((win + 7) / 8 > 256) return CBH_E_UNSUPPORTED;  // cannot happen for w <= 8192
+  const int fpitch = Tf * 8 + 8;
+  *bp = BandPlan{ncol, cpw, Tf, fpitch,
+                 (size_t)(kBlurRB + c.K - 1) * fpitch + (size_t)(c.integer ? 0 : c.at.xn) * sizeof(float)};
+  return CBH_OK;
+}
+template <int K>
+int launch_bands(const HashCall& c, const Chunk& k, const BandPlan& bp) {
+  const dim3 gf((unsigned)bp.ncol, (unsigned)((c.h + kBlurRB - 1) / kBlurRB), (unsigned)k.m);
+  if (bp.fsmem > 64 * 1024)
+    CBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_blur_area<K>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)bp.fsmem));
+  hipLaunchKernelGGL(k_blur_area<K>, gf, dim3((unsigned)bp.Tf), bp.fsmem, c.stream, k.src, c.w, c.h, c.row_stride,
+                     c.img_stride, c.at.x, c.at.xfirst, c.isx, bp.cpw, bp.fpitch, k.d_rowsf, c.vw.pw, c.vw.ph, c.vw.ox,
+                     c.vw.oy);
+  return CBH_OK;
+}
+int hash_bands(const HashCall& c, const Chunk& k, const BandPlan& bp) {
+  const int rc = c.K == 3 ? launch_bands<3>(c, k, bp) : c.K == 5 ? launch_bands<5>(c, k, bp) : launch_bands<7>(c, k, bp);
+  if (rc) return rc;
+  hash_rows(c, k.d_rowsf, k.i0, k.m);
+  return CBH_OK;
+}
+
+// ---- 4. k_blur_area_regs on strips of rows.
+// f(K, GEN, KS) as integral constants for the k_blur_area_regs<K, GEN, .., KS> that serves blur K, general (unaligned)
+// loads or not, ks rows per step: K 3 / 5 / 7 at StreamK<K>::step, and K 7 at 21
+template <class F>
+int with_regs_variant(int K, bool gen, int ks, F&& f) {
+  auto by_gen = [&](auto kk, auto ksv) { return gen ? f(kk, std::true_type{}, ksv) : f(kk, std::false_type{}, ksv); };
+  if (K == 7 && ks == 21) return by_gen(int_c<7>{}, int_c<21>{});
+  switch (K) {
+    case 3: return by_gen(int_c<3>{}, int_c<StreamK<3>::step>{});
+    case 5: return by_gen(int_c<5>{}, int_c<StreamK<5>::step>{});
+    default: return by_gen(int_c<7>{}, int_c<StreamK<7>::step>{});
+  }
+}
+
+// One launch of the family: ipb images side by side in a workgroup, of each the ws columns from x0 on (a whole image, a
+// view, or a column strip of a wide image), making ncell of the 32 cells of a row from a table of xn entries.
+// inner_right: the last lane reads real pixels of the parent behind the columns -- any ws mod 8 takes the aligned loads.
+struct RegsPlan {
+  bool gen;            // unaligned loads
+  int cpad;            // cell_pad_for
+  size_t k_end, rowb;  // floats of LDS behind the rows (weights + per-cell edge weights); LDS bytes of one blurred row
+  unsigned T, gsy;     // workgroup size; strips per image
+  int ks, steps;       // rows per step, steps per strip
+  size_t smem;
+};
+RegsPlan plan_regs(const HashCall& c, const Chunk& k, int x0, int ws, bool inner_right, int xn, int ipb, int ncell) {
+  RegsPlan p;
+  const int L = (ws + 7) / 8, halo = 2 * (c.K / 2);
+  p.gen = !((ws % 8 == 0 || inner_right) && ((uintptr_t)(k.src + x0) % 8) == 0 && c.row_stride % 8 == 0 &&
+            c.img_stride % 8 == 0);
+  p.k_end = c.integer ? 0 : (((size_t)xn + 3) & ~(size_t)3) + 512;
+  p.cpad = cell_pad_for(c.integer, c.isx);
+  p.rowb = (size_t)(8 * L) + (p.cpad ? 128 : 0);
+  p.T = (unsigned)std::max(64, (ipb * L + 63) / 64 * 64);
+  // rows per step (14 / 21) by how they fill the area phase's turns (a launch that makes ncell of the 32 cells has
+  // 2 T / ncell row slots per turn); the strips keep their length in rows
+  p.ks = pick_rows_per_step(c.K, p.T, ncell, (size_t)ipb * p.rowb, p.k_end * sizeof(float) + 16);
+  p.steps = pick_steps_per_strip(c.h, p.ks, (k.target_rows + p.ks - 1) / p.ks, halo, g_hash.stream);
+  const int strip_out = p.steps * p.ks - halo;
+  p.gsy = (unsigned)((c.h + strip_out - 1) / strip_out);
+  p.smem = (size_t)ipb * p.ks * p.rowb + p.k_end * sizeof(float) +
+           16;  // the area walk reads whole words: up to 7 bytes past the last blurred row
+  return p;
+}
+// parent = {pw, ph, ox, oy} as the kernel takes them (all 0: whole images).  FUSE: the vertical pass runs in the kernel,
+// which then writes tiles (k.d_ftiles) instead of rows (k.d_rowsf)
+template <bool FUSE>
+int launch_regs(const HashCall& c, const Chunk& k, const RegsPlan& p, int ws, const AreaTab* x, const int* xfirst, int ipb,
+                const HashView& parent, int cell0, int ncell) {
+  return with_regs_variant(c.K, p.gen, p.ks, [&](auto kk, auto gg, auto ksv) -> int {
+    const auto kernel = k_blur_area_regs<decltype(kk)::value, decltype(gg)::value, FUSE, decltype(ksv)::value>;
+    if (p.smem > 64 * 1024)
+      CBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)p.smem));
+    hipLaunchKernelGGL(kernel, dim3(1, p.gsy, (unsigned)((k.m + ipb - 1) / ipb)), dim3(p.T), p.smem, c.stream, k.src, ws, c.h,
+                       (unsigned)c.row_stride, c.img_stride, x, xfirst, c.isx, p.steps, FUSE ? (float*)nullptr : k.d_rowsf,
+                       ipb, (unsigned)k.m, FUSE ? c.at.yrow : (const YRow*)nullptr, FUSE ? c.isy : 0,
+                       FUSE ? k.d_ftiles : (unsigned char*)nullptr, parent.oy, parent.ph, parent.ox, parent.pw, cell0, ncell,
+                       p.cpad);
+    return CBH_OK;
+  });
+}
+
+// Whole images and views of at most 2048 columns: one strip of columns, images packed side by side, and the vertical pass
+// fused into the kernel where that pays.
+// a view whose vertical edges are the parent's or lie >= 4 pixels inside it (letterboxed / pillarboxed frames
+// after autocrop) differs from a whole image in the row mapping and in which lanes mirror: the
+// register-streaming kernel takes it; other views (a margin of 1..3 pixels) stay on the band kernel
+bool row_strips_fit(const HashCall& c) {
+  const HashView& vw = c.vw;
+  const int Lv = (c.w + 7) / 8;
+  const bool lbox = c.view && (vw.ox == 0 || vw.ox >= 4) && (vw.ox + c.w == vw.pw || vw.ox + 8 * Lv + 4 <= vw.pw);
+  return (!c.view || lbox) && (size_t)vw.ph * c.row_stride < ((size_t)1 << 31);
+}
+int hash_row_strips(const HashCall& c, const Chunk& k) {
+  const HashView parent = c.view ? c.vw : HashView{0, 0, 0, 0};
+  // lanes per image = w / 8.  Images whose last wave would be mostly empty share a 256-lane workgroup side by
+  // side (640 px: 80 of 128 lanes busy alone, 240 of 256 as three: +12 %) where that puts 15 % more of the lanes to
+  // work (400 px: 50 of 64 alone, 250 of 256 as five: +3..4 %; 720 / 800 px: two images fill 256 lanes no better than one
+  // fills 128: -2 % packed); where the lanes are already well used the larger workgroup only costs (more waves per
+  // barrier: -5..-9 % measured at 400, 512, 1024 px).  Integer ratios (cheap area phase: the blur lanes decide) count
+  // the packed workgroup's own size -- 704 x 576: 176 of 192 lanes as two against 88 of 128 alone, +10 % --
+  // fractional ones count it as 256 lanes: 720 x 540 and 688 x 516 run 4-5 % faster alone in 128 lanes than as two in 192.
+  const int Lr = (c.w + 7) / 8, Lw = (Lr + 63) / 64 * 64;
+  const int ipb_try = Lr <= 128 ? 256 / Lr : 1;
+  const int Tp = c.integer ? (ipb_try * Lr + 63) / 64 * 64 : 256;
+  const bool pack = ipb_try > 1 && (long long)ipb_try * Lr * Lw * 100 >= 115LL * Lr * Tp;
+  const int ipb = (pack && (unsigned long long)ipb_try * c.img_stride < (1ull << 32)) ? ipb_try : 1;
+  const bool inner_right = c.view && c.vw.ox + 8 * Lr + 4 <= c.vw.pw;  // the last lane reads real pixels: any w mod 8
+  const RegsPlan p = plan_regs(c, k, parent.ox, c.w, inner_right, c.at.xn, ipb, 32);
+  // whole image per workgroup, vertical pass and tile inside the kernel (FUSE) when the batch still fills
+  // the machine that way: at least two workgroups per CU
+  const int ipb_f = std::min(ipb, 8);
+  const unsigned Tf_ = (unsigned)std::max(64, (ipb_f * std::max(Lr, 32) + 63) / 64 * 64);
+  RegsPlan f = p;  // one strip that spans the image
+  f.T = std::min(256u, Tf_), f.gsy = 1;
+  f.ks = pick_rows_per_step(c.K, f.T, 32, (size_t)ipb_f * (p.rowb + 32 * sizeof(float)),
+                            p.k_end * sizeof(float) + (size_t)ipb_f * 1024);
+  f.steps = (c.h + 2 * (c.K / 2) + f.ks - 1) / f.ks;
+  f.smem = (size_t)ipb_f * f.ks * p.rowb + p.k_end * sizeof(float) + (size_t)ipb_f * f.ks * 32 * sizeof(float) +
+           (size_t)ipb_f * 1024;
+  // (measured, hash_fuse 0 -> 2: 320x240 +30 %, 400x300 +22 %, 533x400 +19 %, 640x480 +8 %, 800x600 +6 %,
+  // 1366x768 +6 %, 1024x768 -2 %, 1280x960 -8 %, 1080p -7 %: large images spend little in k_tile_hash and
+  // lose occupancy to the extra LDS; fractional ratios gain up to ~1 MP)
+  // a fused workgroup walks its whole image alone: with one or two waves per workgroup the machine needs
+  // thousands of them before that beats strips of 8 steps (tools/ab/hash_small_batches.py: 400x300, one wave per
+  // image, 1024 images 137 us fused / 86 split, 2048: 160 / 148, 4096: 289 / 298; 800x600, two waves:
+  // 2048 images 553 / 483, 4096: 945 / 951; four-wave workgroups of 3-6 images pay from ~600 up)
+  const size_t fuse_min_wgs = Tf_ <= 64 ? 4096 : Tf_ <= 128 ? 3072 : 512;
+  const bool fuse = g_hash.fuse && f.smem <= 160 * 1024 - 1024 && (c.integer || c.at.yrow) &&
+                    (g_hash.fuse >= 2 ||
+                     ((k.m + (size_t)ipb_f - 1) / (size_t)ipb_f >= fuse_min_wgs &&
+                      (size_t)c.w * (size_t)c.h <= (c.integer ? 1000000u : 1100000u)));
+  if (int rc = fuse ? launch_regs<true>(c, k, f, c.w, c.at.x, c.at.xfirst, ipb_f, parent, 0, 32)
+                    : launch_regs<false>(c, k, p, c.w, c.at.x, c.at.xfirst, ipb, parent, 0, 32))
+    return rc;
+  fuse ? hash_tiles(c, k.d_ftiles, k.i0, k.m) : hash_rows(c, k.d_rowsf, k.i0, k.m);
+  return CBH_OK;
+}
+
+// images wider than 2048 pixels: the register-streaming kernel on ncol column strips, each a view of the
+// parent that makes its share of the 32 output cells; 16-row bands when a strip's geometry does not fit
+int hash_column_strips(const HashCall& c, const Chunk& k, const BandPlan& bp) {
+  const int w = c.w, ncol = bp.ncol, cpw = bp.cpw;
+  StripTabs stt[8];
+  for (int sidx = 0; sidx < ncol; ++sidx) {
+    if (int rc = get_strip_tabs(w, c.integer, ncol, sidx, &stt[sidx])) return rc;
+    const StripTabs& S_ = stt[sidx];
+    const int Ls = (S_.ws + 7) / 8;
+    if (!(S_.ws >= 64 && Ls <= 256 && (S_.x0 == 0 || S_.x0 >= 4) && (S_.x0 + S_.ws == w || S_.x0 + 8 * Ls + 4 <= w)))
+      return hash_bands(c, k, bp);
+  }
+  for (int sidx = 0; sidx < ncol; ++sidx) {
+    const StripTabs& S_ = stt[sidx];
+    const bool inner_right = S_.x0 + 8 * ((S_.ws + 7) / 8) + 4 <= w;
+    // a strip makes cpw of the 32 cells: 2 T / cpw row slots per turn of the area phase, 14 rows fill them badly
+    const RegsPlan p = plan_regs(c, k, S_.x0, S_.ws, inner_right, S_.xn, 1, cpw);
+    if (int rc = launch_regs<false>(c, k, p, S_.ws, c.integer ? c.at.x : S_.x, c.integer ? c.at.xfirst : S_.xfirst, 1,
+                                    HashView{w, c.h, S_.x0, 0}, sidx * cpw, cpw))
+      return rc;
+  }
+  hash_rows(c, k.d_rowsf, k.i0, k.m);
+  return CBH_OK;
+}
+
+// ---- 4 and 5, chunk by chunk: k_blur_area_regs on strips (batches that fill the machine that way), k_blur_area on
+// 16-row bands for everything else -- small batches, views with a margin of 1..3 pixels, views of more than 2048 columns
+int hash_valu(const HashCall& c) {
+  const int h = c.h;
+  BandPlan bp;
+  if (int rc = plan_bands(c, &bp)) return rc;
+  const size_t per_chunk_f = std::max<size_t>(1, ((size_t)1 << 30) / ((size_t)h * 128));
+  float* d_rowsf = nullptr;
+  unsigned char* d_ftiles = nullptr;
+  cbh::Scratch scratch(c.stream);
+  CBH_HIP(scratch.get(&d_rowsf, std::min(per_chunk_f, c.n) * (size_t)h * 32 * sizeof(float)));
+  CBH_HIP(scratch.get(&d_ftiles, std::min(per_chunk_f, c.n) * 1024));
+  for (size_t i0 = 0; i0 < c.n; i0 += per_chunk_f) {
+    const size_t m = std::min(per_chunk_f, c.n - i0);
+    // strips of `steps` steps when the batch leaves enough workgroups ("hash_stream": 0 never, >= 2 always, of that many)
+    const int kstep = c.K == 7 ? 14 : 15;
+    const long long band_wgs = (long long)bp.ncol * ((h + kBlurRB - 1) / kBlurRB) * (long long)m;
+    int steps = (int)std::min<long long>(8, band_wgs / 3072);
+    steps = std::min(steps, (h + 2 * (c.K / 2) + kstep - 1) / kstep);
+    if (g_hash.stream >= 2) steps = g_hash.stream;
+    if (!g_hash.stream) steps = 0;
+    const Chunk k{c.imgs + i0 * c.img_stride, i0, m, d_rowsf, d_ftiles, steps * kstep};
+    int rc;
+    if (steps >= 3 && bp.ncol == 1 && row_strips_fit(c))
+      rc = hash_row_strips(c, k);
+    else if (steps >= 3 && bp.ncol > 1 && !c.view && c.K == 7 && (size_t)h * c.row_stride < ((size_t)1 << 31))
+      rc = hash_column_strips(c, k, bp);
+    else
+      rc = hash_bands(c, k, bp);
+    if (rc) return rc;
+  }
+  CBH_HIP(hipGetLastError());
+  return CBH_OK;
+}
+
+}  // namespace
 
 int launch_dcthash(const uint8_t* d_imgs, size_t n, int w, int h, size_t row_stride,
                    size_t img_stride, uint64_t* d_out, hipStream_t stream, uint8_t* d_tiles, const HashView* view) {
@@ -1998,345 +2095,20 @@ int launch_dcthash(const uint8_t* d_imgs, size_t n, int w, int h, size_t row_str
   if (view && w == 32 && h == 32)  // no blur: nothing is read outside the view
     return launch_dcthash(d_imgs + (size_t)vw.oy * row_stride + vw.ox, n, w, h, row_stride, img_stride, d_out, stream,
                           d_tiles, nullptr);
-  if (w < 32 || h < 32 || (w == 32 && h == 32)) {
-    // a side enlarges (cv::resize's bilinear emulation), or nothing is resized at all: the rectangle kernel, one
-    // rectangle = the whole image
-    const size_t per_chunk = (size_t)1 << 20;
-    for (size_t i0 = 0; i0 < n; i0 += per_chunk) {
-      const size_t m = std::min(per_chunk, n - i0);
-      std::vector<RectImageDesc> images(m);
-      std::vector<int> rects(4 * m);
-      for (size_t i = 0; i < m; ++i) {
-        images[i] = RectImageDesc{(unsigned long long)(i * img_stride), vw.pw, vw.ph, (unsigned)row_stride, (unsigned)i,
-                                  1u};
-        rects[4 * i] = vw.ox, rects[4 * i + 1] = vw.oy, rects[4 * i + 2] = w, rects[4 * i + 3] = h;
-      }
-      int rc2 = launch_rect_hashes(const_cast<uint8_t*>(d_imgs) + i0 * img_stride, images, rects, 0, d_out + i0, stream,
-                                   d_tiles ? d_tiles + i0 * 1024 : nullptr);
-      if (rc2) return rc2;
-    }
-    return CBH_OK;
-  }
-  const DctTables* tabs = nullptr;
-  int rc = get_tables(&tabs);
+  HashCall c{d_imgs, n, w, h, row_stride, img_stride, vw, view != nullptr, stream, d_out, d_tiles};
+  if (w < 32 || h < 32 || (w == 32 && h == 32)) return hash_rects(c);
+  int rc = get_tables(&c.tabs);
   if (rc) return rc;
-  // ---- 256 x 256 (8-byte aligned rows; anything else of that size takes the general kernels)
-  if (!view && w == 256 && h == 256 && ((uintptr_t)d_imgs % 8) == 0 && row_stride % 8 == 0 && img_stride % 8 == 0 &&
-      row_stride * 256 < (1u << 24) && img_stride < (1u << 28)) {
-    const BandTables* btab = nullptr;
-    if (g_hash_mfma != 0 && ((uintptr_t)d_imgs % 16) == 0 && row_stride % 16 == 0 && img_stride % 16 == 0 &&
-        get_band_tables(&btab) == CBH_OK) {  // (no table on this device: the all-VALU kernel needs none)
-      dim3 gridb((unsigned)((n + 3) / 4));
-      if (d_tiles)
-        hipLaunchKernelGGL(k_dcthash_256_band<true>, gridb, dim3(64), 0, stream, d_imgs, (unsigned)n, (unsigned)row_stride,
-                           (unsigned)img_stride, tabs, btab, d_out, d_tiles);
-      else
-        hipLaunchKernelGGL(k_dcthash_256_band<false>, gridb, dim3(64), 0, stream, d_imgs, (unsigned)n, (unsigned)row_stride,
-                           (unsigned)img_stride, tabs, btab, d_out, d_tiles);
-    } else {
-      cbh_clear_error();
-      dim3 grid((unsigned)((n + 7) / 8)), block(kThreads);
-      if (d_tiles)
-        hipLaunchKernelGGL(k_dcthash_256<true>, grid, block, 0, stream, d_imgs, (unsigned)n, (unsigned)row_stride,
-                           (unsigned)img_stride, tabs, d_out, d_tiles);
-      else
-        hipLaunchKernelGGL(k_dcthash_256<false>, grid, block, 0, stream, d_imgs, (unsigned)n, (unsigned)row_stride,
-                           (unsigned)img_stride, tabs, d_out, d_tiles);
-    }
-    CBH_HIP(hipGetLastError());
-    return CBH_OK;
-  }
+  if (is_256(c)) return hash_256(c);
   // ---- every other geometry
   const long long area_ = (long long)w * h;
-  const int K_ = area_ <= 64 * 64 ? 3 : area_ <= 128 * 128 ? 5 : 7;  // (area <= 32*32 is only 32x32 itself)
-  AreaTabsDev at;
-  if ((rc = get_area_tabs(w, h, &at))) return rc;
-  const bool integer = area_fast(w, h);
-  const int isx = integer ? w / 32 : 0, isy = integer ? h / 32 : 0;
-  // (views: a vertical edge is the parent's, or lies far enough inside it that the blur's three columns -- and on the left
-  // the staging chunk's eight -- are the parent's pixels: letterboxed and pillarboxed frames after autocrop)
-  // (integer ratios: every width but 1024 -- strips of 128 columns on rows a multiple of the cache line apart put every row's
-  // 144 staged bytes across three lines, 2.84 TB/s against k_blur_area_regs' 3.1; profiles/r06_band_area_int.txt)
-  const bool ba_view = !view || ((vw.ox == 0 || vw.ox >= 8) && (vw.ox + w == vw.pw || vw.ox + w + 3 <= vw.pw));
-  if (g_hash_band_area && ba_view && K_ == 7 && (integer ? isx >= 2 && w != 1024 : at.yrow != nullptr) && w >= 64 &&
-      4ull * img_stride < (1ull << 32) && (size_t)vw.ph * row_stride < ((size_t)1 << 32)) {
-    BaTabsDev bat;
-    if (get_ba_tabs(w, &bat) != CBH_OK) {  // (its table could not be made: k_blur_area_regs needs none)
-      cbh_clear_error();
-      bat.strips = nullptr;
-    }
-    if (bat.strips) {
-      const size_t per_chunk_b = 200000;  // (grid y)
-      unsigned char* d_btiles = nullptr;
-      cbh::Scratch scratch(stream);
-      CBH_HIP(scratch.get(&d_btiles, std::min(per_chunk_b, n) * 1024));
-      for (size_t i0 = 0; i0 < n; i0 += per_chunk_b) {
-        const size_t m = std::min(per_chunk_b, n - i0);
-        const unsigned char* src = d_imgs + i0 * img_stride;
-        const unsigned long long bytes = (unsigned long long)(m - 1) * img_stride + (unsigned long long)(vw.ph - 1) * row_stride + (unsigned)vw.pw;
-        // row bands: enough waves for ~two rounds of the machine's 2560 slots, at least 4 output rows per band
-        BaBands bands;
-        bands.n = 1;
-        while (bands.n < 8 && (m + 3) / 4 * (size_t)bat.n_strips * (size_t)bands.n < 5120) bands.n *= 2;
-        if (integer) {
-          for (int b_ = 0; b_ < bands.n; ++b_) {
-            const int c0_ = 32 * b_ / bands.n, c1_ = 32 * (b_ + 1) / bands.n;
-            bands.c0[b_] = c0_, bands.c1[b_] = c1_;
-            bands.ra[b_] = c0_ * isy, bands.rb[b_] = c1_ * isy - 1;
-          }
-        } else {
-          std::vector<int> yf;
-          const std::vector<AreaTab> yt = make_area_tab(h, 32, &yf);
-          for (int b_ = 0; b_ < bands.n; ++b_) {
-            const int c0_ = 32 * b_ / bands.n, c1_ = 32 * (b_ + 1) / bands.n;
-            bands.c0[b_] = c0_, bands.c1[b_] = c1_;
-            bands.ra[b_] = yt[(size_t)yf[(size_t)c0_]].si;
-            bands.rb[b_] = yt[(size_t)yf[(size_t)c1_] - 1].si;
-          }
-        }
-#define CBH_BA_(TT, RR)                                                                                                  \
-  if (integer) CBH_BA__(TT, RR, true); else CBH_BA__(TT, RR, false)
-#define CBH_BA__(TT, RR, II)                                                                                             \
-  hipLaunchKernelGGL((k_band_area<TT, RR, II>), dim3((unsigned)(((m + 3) / 4 + 7) / 8 * 8 * (size_t)bat.n_strips * (size_t)bands.n)), dim3(64), 0, \
-                     stream, src, (unsigned)m, w, h, (unsigned)row_stride, (unsigned)img_stride, bytes, bat.strips,      \
-                     bat.n_strips, at.yrow, d_btiles, view ? vw.oy : 0, view ? vw.ph : h, view ? vw.ox : 0,                \
-                     view ? (vw.ox > 0 ? 1 : 0) | (vw.ox + w < vw.pw ? 2 : 0) : 0, bands, isy)
-#define CBH_BA(TT)                         \
-  case TT:                                 \
-    if (bat.RS == 4) { CBH_BA_(TT, 4); }   \
-    else if (bat.RS == 2) { CBH_BA_(TT, 2); } \
-    else { CBH_BA_(TT, 1); }               \
-    break
-        switch (bat.T) {
-          CBH_BA(2); CBH_BA(3); CBH_BA(4); CBH_BA(5); CBH_BA(6); CBH_BA(7); CBH_BA(8); CBH_BA(9); CBH_BA(10); CBH_BA(11);
-          CBH_BA(12); CBH_BA(13); CBH_BA(14); CBH_BA(15);
-          default: return CBH_E_UNSUPPORTED;
-        }
-#undef CBH_BA__
-#undef CBH_BA_
-#undef CBH_BA
-        hipLaunchKernelGGL(k_tiles_hash2, dim3((unsigned)((m + 1) / 2)), dim3(64), 0, stream, d_btiles, (unsigned)m, tabs,
-                           d_out + i0, d_tiles ? d_tiles + i0 * 1024 : nullptr);
-        CBH_HIP(hipGetLastError());
-      }
-      return CBH_OK;
-    }
-  }
-  // ---- the VALU kernels: k_blur_area_regs on strips (batches that fill the machine that way), k_blur_area on 16-row bands
-  // column strips: the fewest (1, 2, 4, 8) whose widest window -- first source column of a strip's first cell .. last of
-  // its last -- fits 256 lanes x 8 columns.  (Fractional cells overlap by a pixel: 8191 columns need 8 strips.)
-  int ncol = w <= 2048 ? 1 : w <= 4096 ? 2 : 4, cpw = 32 / ncol, win = 0;
-  std::vector<int> xf;
-  const std::vector<AreaTab> xt_full = integer ? std::vector<AreaTab>() : make_area_tab(w, 32, &xf);
-  for (;; ncol *= 2) {
-    cpw = 32 / ncol;
-    win = 0;
-    if (integer) {
-      win = cpw * isx;
-    } else {
-      for (int c = 0; c < 32; c += cpw)
-        win = std::max(win, xt_full[(size_t)xf[(size_t)(c + cpw)] - 1].si + 1 - xt_full[(size_t)xf[(size_t)c]].si);
-    }
-    if ((win + 7) / 8 <= 256 || ncol == 8) break;
-  }
-  const int Tf = std::min(256, ((win + 7) / 8 + 63) / 64 * 64);
-  if ((win + 7) / 8 > 256) return CBH_E_UNSUPPORTED;  // cannot happen for w <= 8192
-  const int fpitch = Tf * 8 + 8;
-  const size_t fsmem = (size_t)(kBlurRB + K_ - 1) * fpitch + (size_t)(integer ? 0 : at.xn) * sizeof(float);
-  const size_t per_chunk_f = std::max<size_t>(1, ((size_t)1 << 30) / ((size_t)h * 128));
-  float* d_rowsf = nullptr;
-  unsigned char* d_ftiles = nullptr;  // the fused kernel's 32 x 32 tiles (1 KB per image)
-  cbh::Scratch scratch(stream);
-  CBH_HIP(scratch.get(&d_rowsf, std::min(per_chunk_f, n) * (size_t)h * 32 * sizeof(float)));
-  CBH_HIP(scratch.get(&d_ftiles, std::min(per_chunk_f, n) * 1024));
-  for (size_t i0 = 0; i0 < n; i0 += per_chunk_f) {
-    const size_t m = std::min(per_chunk_f, n - i0);
-    const unsigned char* src = d_imgs + i0 * img_stride;
-    unsigned char* tcopy = d_tiles ? d_tiles + i0 * 1024 : nullptr;
-    // strips of `steps` steps when the batch leaves enough workgroups ("hash_stream": 0 never, >= 2 always, of that many)
-    const int kstep = K_ == 7 ? 14 : 15;
-    const long long band_wgs = (long long)ncol * ((h + kBlurRB - 1) / kBlurRB) * (long long)m;
-    int steps = (int)std::min<long long>(8, band_wgs / 3072);
-    steps = std::min(steps, (h + 2 * (K_ / 2) + kstep - 1) / kstep);
-    if (g_hash_stream >= 2) steps = g_hash_stream;
-    if (!g_hash_stream) steps = 0;
-    // a view whose vertical edges are the parent's or lie >= 4 pixels inside it (letterboxed / pillarboxed frames
-    // after autocrop) differs from a whole image in the row mapping and in which lanes mirror: the
-    // register-streaming kernel takes it; other views (a margin of 1..3 pixels) stay on the band kernel
-    const int Lv = (w + 7) / 8;
-    const bool lbox = view && (vw.ox == 0 || vw.ox >= 4) && (vw.ox + w == vw.pw || vw.ox + 8 * Lv + 4 <= vw.pw);
-    if (steps >= 3 && ncol == 1 && (!view || lbox) && (size_t)vw.ph * row_stride < ((size_t)1 << 31)) {
-      const int v_oy = view ? vw.oy : 0, v_ph = view ? vw.ph : 0, v_ox = view ? vw.ox : 0, v_pw = view ? vw.pw : 0;
-      const bool v_ri = view && vw.ox + 8 * Lv + 4 <= vw.pw;  // the last lane reads real pixels: any w mod 8
-      const bool gen = !((w % 8 == 0 || v_ri) && ((uintptr_t)(src + v_ox) % 8) == 0 && row_stride % 8 == 0 &&
-                         img_stride % 8 == 0);
-      // lanes per image = w / 8.  Images whose last wave would be mostly empty share a 256-lane workgroup side by
-      // side (640 px: 80 of 128 lanes busy alone, 240 of 256 as three: +12 %) where that puts 15 % more of the lanes to
-      // work (400 px: 50 of 64 alone, 250 of 256 as five: +3..4 %; 720 / 800 px: two images fill 256 lanes no better than one
-      // fills 128: -2 % packed); where the lanes are already well used the larger workgroup only costs (more waves per
-      // barrier: -5..-9 % measured at 400, 512, 1024 px).  Integer ratios (cheap area phase: the blur lanes decide) count
-      // the packed workgroup's own size -- 704 x 576: 176 of 192 lanes as two against 88 of 128 alone, +10 % --
-      // fractional ones count it as 256 lanes: 720 x 540 and 688 x 516 run 4-5 % faster alone in 128 lanes than as two in 192.
-      const int Lr = (w + 7) / 8, Lw = (Lr + 63) / 64 * 64;
-      const int ipb_try = Lr <= 128 ? 256 / Lr : 1;
-      const int Tp = integer ? (ipb_try * Lr + 63) / 64 * 64 : 256;
-      const bool pack = ipb_try > 1 && (long long)ipb_try * Lr * Lw * 100 >= 115LL * Lr * Tp;
-      const int ipb = (pack && (unsigned long long)ipb_try * img_stride < (1ull << 32)) ? ipb_try : 1;
-      const size_t k_end_r = integer ? 0 : (((size_t)at.xn + 3) & ~(size_t)3) + 512;  // weights + per-cell edge weights
-      const int cpad = cell_pad_for(integer, isx);
-      const size_t rowb = (size_t)(8 * Lr) + (cpad ? 128 : 0);  // LDS bytes of one blurred row
-      const unsigned Tr = (unsigned)std::max(64, (ipb * Lr + 63) / 64 * 64);
-      // rows per step (14 / 21) by how they fill the area phase's turns; the strips keep their length in rows
-      const int ks_r = pick_rows_per_step(K_, Tr, 32, (size_t)ipb * rowb, k_end_r * sizeof(float) + 16);
-      const int steps_r = pick_steps_per_strip(h, ks_r, (steps * kstep + ks_r - 1) / ks_r, 2 * (K_ / 2));
-      const int strip_out_r = steps_r * ks_r - 2 * (K_ / 2);
-      const unsigned gsy_r = (unsigned)((h + strip_out_r - 1) / strip_out_r);
-      const size_t rsmem = (size_t)ipb * ks_r * rowb + k_end_r * sizeof(float) +
-                           16;  // the area walk reads whole words: up to 7 bytes past the last blurred row
-      // whole image per workgroup, vertical pass and tile inside the kernel (FUSE) when the batch still fills
-      // the machine that way: at least two workgroups per CU
-      const int ipb_f = std::min(ipb, 8);
-      const size_t k_end_f = k_end_r;
-      const unsigned Tf_ = (unsigned)std::max(64, (ipb_f * std::max(Lr, 32) + 63) / 64 * 64);
-      const int ks_f = pick_rows_per_step(K_, std::min(256u, Tf_), 32, (size_t)ipb_f * (rowb + 32 * sizeof(float)),
-                                          k_end_f * sizeof(float) + (size_t)ipb_f * 1024);
-      const int steps_f = (h + 2 * (K_ / 2) + ks_f - 1) / ks_f;
-      const size_t fsm = (size_t)ipb_f * ks_f * rowb + k_end_f * sizeof(float) +
-                         (size_t)ipb_f * ks_f * 32 * sizeof(float) + (size_t)ipb_f * 1024;
-      // (measured, hash_fuse 0 -> 2: 320x240 +30 %, 400x300 +22 %, 533x400 +19 %, 640x480 +8 %, 800x600 +6 %,
-      // 1366x768 +6 %, 1024x768 -2 %, 1280x960 -8 %, 1080p -7 %: large images spend little in k_tile_hash and
-      // lose occupancy to the extra LDS; fractional ratios gain up to ~1 MP)
-      // a fused workgroup walks its whole image alone: with one or two waves per workgroup the machine needs
-      // thousands of them before that beats strips of 8 steps (tools/ab/hash_small_batches.py: 400x300, one wave per
-      // image, 1024 images 137 us fused / 86 split, 2048: 160 / 148, 4096: 289 / 298; 800x600, two waves:
-      // 2048 images 553 / 483, 4096: 945 / 951; four-wave workgroups of 3-6 images pay from ~600 up)
-      const size_t fuse_min_wgs = Tf_ <= 64 ? 4096 : Tf_ <= 128 ? 3072 : 512;
-      const bool fuse = g_hash_fuse && fsm <= 160 * 1024 - 1024 && (integer || at.yrow) &&
-                        (g_hash_fuse >= 2 ||
-                         ((m + (size_t)ipb_f - 1) / (size_t)ipb_f >= fuse_min_wgs &&
-                          (size_t)w * (size_t)h <= (integer ? 1000000u : 1100000u)));
-#define CBH_REGS_L(KK, GG, KSV)                                                                              \
-  do {                                                                                                       \
-    if (fuse) {                                                                                              \
-      if (fsm > 64 * 1024)                                                                                   \
-        CBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_blur_area_regs<KK, GG, true, KSV>),      \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)fsm));                  \
-      hipLaunchKernelGGL((k_blur_area_regs<KK, GG, true, KSV>), dim3(1, 1, (unsigned)((m + ipb_f - 1) / ipb_f)), \
-                         dim3(std::min(256u, Tf_)), fsm, stream, src, w, h, (unsigned)row_stride, img_stride, at.x,       \
-                         at.xfirst, isx, steps_f, (float*)nullptr, ipb_f, (unsigned)m, at.yrow, isy, d_ftiles,       \
-                         v_oy, v_ph, v_ox, v_pw, 0, 32, cpad);                                               \
-      break;                                                                                                 \
-    }                                                                                                        \
-    if (rsmem > 64 * 1024)                                                                                   \
-      CBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_blur_area_regs<KK, GG, false, KSV>),       \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)rsmem));                  \
-    hipLaunchKernelGGL((k_blur_area_regs<KK, GG, false, KSV>), dim3(1, gsy_r, (unsigned)((m + ipb - 1) / ipb)), dim3(Tr), rsmem, \
-                       stream, src, w, h, (unsigned)row_stride, img_stride, at.x, at.xfirst, isx, steps_r, d_rowsf, \
-                       ipb, (unsigned)m, (const YRow*)nullptr, 0, (unsigned char*)nullptr, v_oy, v_ph, v_ox, \
-                       v_pw, 0, 32, cpad);                                                                   \
-  } while (0)
-#define CBH_REGS_(KK, GG)                                    \
-  do {                                                       \
-    const int ks_ = fuse ? ks_f : ks_r;                      \
-    if (KK == 7 && ks_ == 21) CBH_REGS_L(7, GG, 21);         \
-    else CBH_REGS_L(KK, GG, StreamK<KK>::step);              \
-  } while (0)
-#define CBH_REGS(KK)              \
-  do {                            \
-    if (gen) CBH_REGS_(KK, true); \
-    else CBH_REGS_(KK, false);    \
-  } while (0)
-      switch (K_) {
-        case 3: CBH_REGS(3); break;
-        case 5: CBH_REGS(5); break;
-        default: CBH_REGS(7); break;
-      }
-#undef CBH_REGS_L
-#undef CBH_REGS_
-#undef CBH_REGS
-      if (fuse)
-        hipLaunchKernelGGL(k_tiles_hash2, dim3((unsigned)((m + 1) / 2)), dim3(64), 0, stream, d_ftiles, (unsigned)m, tabs,
-                           d_out + i0, tcopy);
-      else
-        hipLaunchKernelGGL(k_tile_hash, dim3((unsigned)m), dim3(kThreads), 0, stream, d_rowsf, h, at.y, at.yfirst,
-                           isx, isy, 1, tabs, d_out + i0, tcopy);
-      continue;
-    }
-    // images wider than 2048 pixels: the register-streaming kernel on ncol column strips, each a view of the
-    // parent that makes its share of the 32 output cells
-    if (steps >= 3 && ncol > 1 && !view && K_ == 7 && (size_t)h * row_stride < ((size_t)1 << 31)) {
-      StripTabs stt[8];
-      bool ok = true;
-      for (int sidx = 0; sidx < ncol && ok; ++sidx) {
-        if ((rc = get_strip_tabs(w, integer, ncol, sidx, &stt[sidx]))) return rc;
-        const StripTabs& S_ = stt[sidx];
-        const int Ls = (S_.ws + 7) / 8;
-        ok = S_.ws >= 64 && Ls <= 256 && (S_.x0 == 0 || S_.x0 >= 4) &&
-             (S_.x0 + S_.ws == w || S_.x0 + 8 * Ls + 4 <= w);
-      }
-      if (ok) {
-        for (int sidx = 0; sidx < ncol; ++sidx) {
-          const StripTabs& S_ = stt[sidx];
-          const int ws = S_.ws, Ls = (ws + 7) / 8;
-          const bool s_ri = S_.x0 + 8 * Ls + 4 <= w;
-          const bool gen = !((ws % 8 == 0 || s_ri) && ((uintptr_t)(src + S_.x0) % 8) == 0 && row_stride % 8 == 0 &&
-                             img_stride % 8 == 0);
-          const size_t k_end_s = integer ? 0 : (((size_t)S_.xn + 3) & ~(size_t)3) + 512;
-          const int cpad_s = cell_pad_for(integer, isx);
-          const unsigned Ts = (unsigned)std::max(64, (Ls + 63) / 64 * 64);
-          // a strip makes cpw of the 32 cells: 2 Ts / cpw row slots per turn of the area phase, 14 rows fill them badly
-          const int ks_s = pick_rows_per_step(7, Ts, cpw, (size_t)(8 * Ls + (cpad_s ? 128 : 0)), k_end_s * sizeof(float) + 16);
-          const int steps_s = pick_steps_per_strip(h, ks_s, (steps * kstep + ks_s - 1) / ks_s, 6);
-          const int strip_out_s = steps_s * ks_s - 6;
-          const unsigned gsy_s = (unsigned)((h + strip_out_s - 1) / strip_out_s);
-          const size_t smem_s = (size_t)ks_s * (size_t)(8 * Ls + (cpad_s ? 128 : 0)) + k_end_s * sizeof(float) + 16;
-#define CBH_STRIP_L(GG, KSV)                                                                                      \
-  do {                                                                                                            \
-    if (smem_s > 64 * 1024)                                                                                       \
-      CBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_blur_area_regs<7, GG, false, KSV>),             \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_s));                      \
-    hipLaunchKernelGGL((k_blur_area_regs<7, GG, false, KSV>), dim3(1, gsy_s, (unsigned)m), dim3(Ts), smem_s, stream, src, \
-                       ws, h, (unsigned)row_stride, img_stride, integer ? at.x : S_.x, integer ? at.xfirst : S_.xfirst, \
-                       isx, steps_s, d_rowsf, 1, (unsigned)m, (const YRow*)nullptr, 0, (unsigned char*)nullptr, 0, h,  \
-                       S_.x0, w, sidx * cpw, cpw, cpad_s);                                                        \
-  } while (0)
-#define CBH_STRIP(GG)                               \
-  do {                                              \
-    if (ks_s == 21) CBH_STRIP_L(GG, 21);            \
-    else CBH_STRIP_L(GG, 14);                       \
-  } while (0)
-          if (gen) CBH_STRIP(true);
-          else CBH_STRIP(false);
-#undef CBH_STRIP_L
-#undef CBH_STRIP
-        }
-        hipLaunchKernelGGL(k_tile_hash, dim3((unsigned)m), dim3(kThreads), 0, stream, d_rowsf, h, at.y, at.yfirst,
-                           isx, isy, 1, tabs, d_out + i0, tcopy);
-        continue;
-      }
-    }
-    // everything else -- small batches, views with a margin of 1..3 pixels, views of more than 2048 columns: a workgroup
-    // per 16-row band, rows staged in LDS
-    dim3 gf((unsigned)ncol, (unsigned)((h + kBlurRB - 1) / kBlurRB), (unsigned)m);
-#define CBH_FUSED(KK)                                                                                    \
-  do {                                                                                                   \
-    if (fsmem > 64 * 1024)                                                                               \
-      CBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_blur_area<KK>),                        \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)fsmem));              \
-    hipLaunchKernelGGL(k_blur_area<KK>, gf, dim3((unsigned)Tf), fsmem, stream, src, w, h, row_stride,    \
-                       img_stride, at.x, at.xfirst, isx, cpw, fpitch, d_rowsf, vw.pw, vw.ph, vw.ox, vw.oy);  \
-  } while (0)
-    switch (K_) {
-      case 3: CBH_FUSED(3); break;
-      case 5: CBH_FUSED(5); break;
-      default: CBH_FUSED(7); break;
-    }
-#undef CBH_FUSED
-    hipLaunchKernelGGL(k_tile_hash, dim3((unsigned)m), dim3(kThreads), 0, stream, d_rowsf, h, at.y, at.yfirst, isx,
-                       isy, 1, tabs, d_out + i0, tcopy);
-  }
-  CBH_HIP(hipGetLastError());
-  return CBH_OK;
+  c.K = area_ <= 64 * 64 ? 3 : area_ <= 128 * 128 ? 5 : 7;  // (area <= 32*32 is only 32x32 itself)
+  if ((rc = get_area_tabs(w, h, &c.at))) return rc;
+  c.integer = area_fast(w, h);
+  c.isx = c.integer ? w / 32 : 0, c.isy = c.integer ? h / 32 : 0;
+  BaTabsDev bat;
+  if (band_area_tabs(c, &bat)) return hash_band_area(c, bat);
+  return hash_valu(c);
 }
 
 }  // namespace cbh

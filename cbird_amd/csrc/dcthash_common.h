@@ -16,27 +16,13 @@
 
 #include "cbh_internal.h"
 #include "cv_dct32_dev.h"
+#include "dcthash_tables.h"  // AreaTab, YRow and the other table entry types; area_fast, make_area_tab
 
 namespace cbh {
 
 struct DctTables {
   unsigned char zz[64];  // zig-zag positions 6..69 -> index into the 9x9 block (row*9+col)
   CvDct32Tabs cv;        // stages 3 / 5: cv::dct / cv::sum as OpenCV 2.4 evaluates them (cv_dct32_dev.h)
-};
-
-struct AreaTab {
-  int si, di;
-  float alpha;
-};
-// the y table of make_area_tab seen from a SOURCE row (k_blur_area_regs<.., FUSE>): a row contributes to one or two
-// consecutive output rows (scale >= 1).  info: bits 0..7 di of the first entry, bit 8 = that entry opens its cell,
-// bit 9 = it closes it, bit 10 = a second entry exists (cell di + 1), bit 11 / 12 = opens / closes for that one
-// k0 = 0.f when the first entry opens its cell, 1.f when it continues one: sum = fma(sum, k0, a0 * v) is `t0` or `sum + t0`
-// (one rounding either way) without a select (k_band_area)
-struct YRow {
-  float a0, a1;
-  int info;
-  float k0;
 };
 
 namespace {
@@ -251,9 +237,7 @@ typedef unsigned u32_any_align __attribute__((aligned(1)));
 
 }  // namespace
 
-// host side (dcthash.hip)
-bool area_fast(int w, int h);  // cv::resize takes its integer-ratio INTER_AREA path for this geometry
-std::vector<AreaTab> make_area_tab(int ssize, int dsize, std::vector<int>* first);  // computeResizeAreaTab
+// host side: area_fast() and make_area_tab() (computeResizeAreaTab) come with dcthash_tables.h; dcthash.hip has
 int get_tables(const DctTables** out);  // the current device's copy of the stage 3-6 tables
 
 }  // namespace cbh
