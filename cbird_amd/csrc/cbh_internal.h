@@ -407,6 +407,23 @@ struct HashView {
 int launch_dcthash(const uint8_t* d_imgs, size_t n, int w, int h, size_t row_stride,
                    size_t img_stride, uint64_t* d_out, hipStream_t stream,
                    uint8_t* d_tiles = nullptr, const HashView* view = nullptr);
+// The per-geometry steps of the callers that hash autocropped images (cbh_regions.h plans their launches).  rect: the
+// kept region {left, top, right, bottom} that the n grey w x h images at d_gray share.
+// dctHash64 of the kept VIEW: the blur sees the cropped-away margins (a view that is the whole image is none)
+inline int launch_dcthash_kept(const uint8_t* d_gray, size_t n, int w, int h, size_t row_stride, size_t img_stride,
+                               const int* rect, uint64_t* d_out, hipStream_t stream) {
+  const HashView view{w, h, rect[0], rect[1]};
+  return launch_dcthash(d_gray, n, rect[2] - rect[0], rect[3] - rect[1], row_stride, img_stride, d_out, stream, nullptr,
+                        &view);
+}
+// prestage.hip: sizeLongestSide(kept region, size) packed at d_dst (a view: cv::resize does not look outside it).
+// *dw x *dh: the size of each; 0 x 0 and nothing launched where the reference throws
+int resize_kept(const uint8_t* d_gray, size_t n, size_t row_stride, size_t img_stride, const int* rect, int size,
+                uint8_t* d_dst, int device, hipStream_t stream, int* dw, int* dh);
+// prestage.hip: the kept regions of n grey images on the host (rects, n x 4), which has synchronised `stream` when they
+// come from autocrop (range >= 0, through d_rects); range < 0: the whole frames
+int fetch_kept_regions(const uint8_t* d_gray, size_t n, int w, int h, size_t row_stride, size_t img_stride, int range,
+                       int* d_rects, int* rects, int device, hipStream_t stream);
 // rectangles of images hashed one after the other, optionally in place (Media::makeKeyPointHashes); also the path of
 // images with a side < 32
 struct RectImageDesc {

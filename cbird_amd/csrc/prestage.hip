@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "cbh_index.h"
+#include "cbh_regions.h"
 #include "cbh_runs.h"
 #include "cbh_staging.h"
 #include "gray_px.h"
@@ -427,6 +428,26 @@ namespace cbh {
 void lanczos4_table(int ssize, int dsize, std::vector<int>* ofs, std::vector<short>* coef) {
   lanczos4_tab(ssize, dsize, ofs, coef);
 }
+
+int resize_kept(const uint8_t* d_gray, size_t n, size_t row_stride, size_t img_stride, const int* rect, int size,
+                uint8_t* d_dst, int device, hipStream_t stream, int* dw, int* dh) {
+  if (!kept_region_dims(rect, size, dw, dh)) return CBH_OK;  // the reference throws: no image
+  return cbh_resize_lanczos4_dev(d_gray + (size_t)rect[1] * row_stride + rect[0], n, rect[2] - rect[0], rect[3] - rect[1],
+                                 row_stride, img_stride, *dw, *dh, d_dst, device, stream);
+}
+
+int fetch_kept_regions(const uint8_t* d_gray, size_t n, int w, int h, size_t row_stride, size_t img_stride, int range,
+                       int* d_rects, int* rects, int device, hipStream_t stream) {
+  if (range < 0) {
+    fill_whole(rects, n, w, h);
+    return CBH_OK;
+  }
+  const int rc = cbh_autocrop_dev(d_gray, n, w, h, row_stride, img_stride, range, d_rects, device, stream);
+  if (rc) return rc;
+  CBH_HIP(hipMemcpyAsync(rects, d_rects, n * 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
+  CBH_HIP(hipStreamSynchronize(stream));
+  return CBH_OK;
+}
 }  // namespace cbh
 
 extern "C" {
@@ -517,6 +538,7 @@ int cbh_process_images_ex(const uint8_t* imgs, size_t n, int w, int h, size_t ro
   if (resize_size > 0) st.alloc(&d_res, per_chunk * slot);
   int rc = st.status();
   std::vector<int> hr(per_chunk * 4);
+  std::vector<cbh::RegionRun> runs;
   for (size_t i0 = 0; rc == CBH_OK && i0 < n; i0 += per_chunk) {
     const size_t m = std::min(per_chunk, n - i0);
     st.up(d_src, imgs + i0 * img_stride, (m - 1) * img_stride + span1);
@@ -530,63 +552,31 @@ int cbh_process_images_ex(const uint8_t* imgs, size_t n, int w, int h, size_t ro
       gs = (size_t)w;
       gi = (size_t)w * h;
     }
-    bool cropped = false;
-    if (autocrop_range >= 0) {
-      rc = cbh_autocrop_dev(gray, m, w, h, gs, gi, autocrop_range, d_rects, device, s);
-      if (rc) break;
-      st.down(hr.data(), d_rects, m * 4 * sizeof(int));
-      st.sync();
-      if ((rc = st.status())) break;
-      for (size_t i = 0; i < m; ++i)
-        cropped |= hr[i * 4] != 0 || hr[i * 4 + 1] != 0 || hr[i * 4 + 2] != w || hr[i * 4 + 3] != h;
-    } else {
-      for (size_t i = 0; i < m; ++i) {
-        hr[i * 4] = hr[i * 4 + 1] = 0;
-        hr[i * 4 + 2] = w;
-        hr[i * 4 + 3] = h;
-      }
+    if ((rc = cbh::fetch_kept_regions(gray, m, w, h, gs, gi, autocrop_range, d_rects, hr.data(), device, s))) break;
+    // cropped images have their own geometry: one launch per run of images with the same kept region (frames of one
+    // letterboxed video all share it)
+    cbh::region_runs(hr.data(), m, &runs);
+    for (size_t k = 0; k < runs.size() && rc == CBH_OK; ++k) {
+      const cbh::RegionRun& r = runs[k];
+      rc = cbh::launch_dcthash_kept(gray + r.first * gi, r.count, w, h, gs, gi, r.rect, d_out + r.first, s);
     }
-    if (!cropped) {
-      rc = cbh::launch_dcthash(gray, m, w, h, gs, gi, d_out, s);
-    } else {
-      // cropped images have their own geometry: one launch per run of images with the same kept region
-      // (frames of one letterboxed video all share it)
-      for (size_t i = 0, run = 1; i < m && rc == CBH_OK; i += run) {
-        const int* r = &hr[i * 4];
-        run = 1;
-        while (i + run < m && !memcmp(r, &hr[(i + run) * 4], 4 * sizeof(int))) ++run;
-        // autocrop() narrows cvGray to a VIEW of the full image (cvutil.cpp:1397-1401): dctHash64's blur still
-        // sees the cropped-away margins at the view's edges
-        const cbh::HashView view{w, h, r[0], r[1]};
-        rc = cbh::launch_dcthash(gray + i * gi, run, r[2] - r[0], r[3] - r[1], gs, gi, d_out + i, s, nullptr, &view);
+    for (size_t k = 0; k < runs.size() && rc == CBH_OK && resize_size > 0; ++k) {
+      const cbh::RegionRun& r = runs[k];
+      int dw, dh;
+      rc = cbh::resize_kept(gray + r.first * gi, r.count, gs, gi, r.rect, resize_size, d_res + r.first * slot, device, s,
+                            &dw, &dh);
+      if (rc) break;
+      for (size_t t = 0; t < r.count; ++t) {
+        resized_dims[2 * (i0 + r.first + t)] = dw;
+        resized_dims[2 * (i0 + r.first + t) + 1] = dh;
       }
+      if (dw == 0) continue;
+      // (a pitched copy, which Staging does not have: slot i of the caller's buffer gets its image packed)
+      const hipError_t e = hipMemcpy2DAsync(resized + (i0 + r.first) * slot, slot, d_res + r.first * slot, (size_t)dw * dh,
+                                            (size_t)dw * dh, r.count, hipMemcpyDeviceToHost, s);
+      if (e != hipSuccess) rc = cbh::fail("process images fetch", e);
     }
     if (rc) break;
-    if (resize_size > 0) {
-      // sizeLongestSide of each kept region (a view: cv::resize does not look outside it), one launch per run of
-      // images with the same kept region
-      for (size_t i = 0, run = 1; i < m && rc == CBH_OK; i += run) {
-        const int* r = &hr[i * 4];
-        run = 1;
-        while (i + run < m && !memcmp(r, &hr[(i + run) * 4], 4 * sizeof(int))) ++run;
-        int dw = 0, dh = 0;
-        cbh_longest_side_dims(r[2] - r[0], r[3] - r[1], resize_size, &dw, &dh);
-        if (dw <= 0 || dh <= 0 || dw > resize_size || dh > resize_size) dw = dh = 0;
-        for (size_t t = 0; t < run; ++t) {
-          resized_dims[2 * (i0 + i + t)] = dw;
-          resized_dims[2 * (i0 + i + t) + 1] = dh;
-        }
-        if (dw == 0) continue;
-        rc = cbh_resize_lanczos4_dev(gray + i * gi + (size_t)r[1] * gs + r[0], run, r[2] - r[0], r[3] - r[1], gs, gi,
-                                     dw, dh, d_res + i * slot, device, s);
-        if (rc) break;
-        // (a pitched copy, which Staging does not have: slot i of the caller's buffer gets its image packed)
-        const hipError_t e = hipMemcpy2DAsync(resized + (i0 + i) * slot, slot, d_res + i * slot, (size_t)dw * dh,
-                                              (size_t)dw * dh, run, hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) rc = cbh::fail("process images fetch", e);
-      }
-      if (rc) break;
-    }
     st.down(out + i0, d_out, m * sizeof(uint64_t));
     st.sync();
     if ((rc = st.status())) break;
@@ -678,14 +668,7 @@ int cbh_template_scores(const uint8_t* cands, size_t n, int w, int h, size_t can
 
 /* sizeLongestSide's target size (src/cvutil.cpp:1933-1942): float aspect ratio, truncation */
 void cbh_longest_side_dims(int w, int h, int size, int* out_w, int* out_h) {
-  const float aspect = (float)w / (float)h;
-  if (w > h) {
-    *out_w = size;
-    *out_h = (int)((float)size / aspect);
-  } else {
-    *out_h = size;
-    *out_w = (int)(aspect * (float)size);
-  }
+  cbh::longest_side_dims(w, h, size, out_w, out_h);
 }
 
 int cbh_resize_lanczos4_dev(const void* d_src, size_t n, int w, int h, size_t row_stride, size_t img_stride, int dw,

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "cbh_index.h"
+#include "cbh_regions.h"
 
 namespace {
 constexpr int kMaxFramesPerVideo = 1 << 24;  // MAX_FRAMES_PER_VIDEO, src/dctvideoindex.h:32,50 (VINDEX_FRAME_BITS 24)
@@ -41,6 +42,7 @@ struct cbh_vindexer {
   uint64_t last_hash = 0;
   long long near_frames = 0;
   int spec[4] = {0, 0, 0, 0}, spec_w = 0, spec_h = 0;  // the kept region the last chunk ended on
+  std::vector<cbh::RegionRun> runs;                    // of the chunk in flight (kept here: no allocation per chunk)
 };
 
 namespace {
@@ -123,30 +125,23 @@ int hash_chunk(cbh_vindexer* v, const uint8_t* d_gray, size_t m, int w, int h, s
     v->spec_w = w, v->spec_h = h;
   }
   if (crop && v->spec_w == w && v->spec_h == h) memcpy(spec, v->spec, sizeof spec);
-  auto launch = [&](size_t i, size_t run, const int* r, uint64_t* d_out) {
-    if (r[0] == 0 && r[1] == 0 && r[2] == w && r[3] == h) return cbh::launch_dcthash(d_gray + i * gi, run, w, h, gs, gi, d_out, s);
-    const cbh::HashView view{w, h, r[0], r[1]};
-    return cbh::launch_dcthash(d_gray + i * gi, run, r[2] - r[0], r[3] - r[1], gs, gi, d_out, s, nullptr, &view);
-  };
   if (crop) {
     rc = cbh_autocrop_dev(d_gray, m, w, h, gs, gi, v->autocrop, v->d_rects, v->device, s);
     if (rc) return rc;
   }
-  rc = launch(0, m, spec, v->d_out);
+  rc = cbh::launch_dcthash_kept(d_gray, m, w, h, gs, gi, spec, v->d_out, s);
   if (rc) return rc;
   if (crop) CBH_HIP(hipMemcpyAsync(hr, v->d_rects, m * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   CBH_HIP(hipMemcpyAsync(v->h_hashes, v->d_out, m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   CBH_HIP(hipStreamSynchronize(s));
   if (!crop) return CBH_OK;
   bool again = false;
-  for (size_t i = 0, run = 1; i < m; i += run) {
-    const int* r = &hr[i * 4];
-    run = 1;
-    while (i + run < m && !memcmp(r, &hr[(i + run) * 4], 4 * sizeof(int))) ++run;
-    if (!memcmp(r, spec, sizeof spec)) continue;
-    rc = launch(i, run, r, v->d_out + i);
+  cbh::region_runs(hr, m, &v->runs);
+  for (const cbh::RegionRun& r : v->runs) {
+    if (cbh::same_rect(r.rect, spec)) continue;
+    rc = cbh::launch_dcthash_kept(d_gray + r.first * gi, r.count, w, h, gs, gi, r.rect, v->d_out + r.first, s);
     if (rc) return rc;
-    CBH_HIP(hipMemcpyAsync(v->h_hashes + i, v->d_out + i, run * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    CBH_HIP(hipMemcpyAsync(v->h_hashes + r.first, v->d_out + r.first, r.count * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     again = true;
   }
   if (again) CBH_HIP(hipStreamSynchronize(s));

@@ -132,3 +132,81 @@ def test_mixed_geometries_are_grouped_and_returned_in_input_order(gpu):
         if r.colorDescriptor is not None:
             assert r.colorDescriptor.tobytes() == one.colorDescriptor.tobytes()
     assert process_image_list([], p) == []
+
+
+# ---- kept regions: the launch plan shared by the three callers that hash autocropped images (cbh_regions.h) ----------
+
+_W, _H = 160, 120
+_WHOLE, _A, _B, _C = (0, 0, _W, _H), (0, 16, _W, _H - 16), (24, 0, _W - 24, _H), (0, 10, _W, _H - 10)
+
+
+def _framed(rng, rect, channels=None):
+    """content inside `rect`, bars of a flat colour within the autocrop range around it"""
+    shape = (_H, _W) if channels is None else (_H, _W, channels)
+    img = (16 + rng.integers(0, 4, shape)).astype(np.uint8)
+    l, t, r, b = rect
+    img[t:b, l:r] = rng.integers(60, 256, (b - t, r - l) + shape[2:], dtype=np.uint8)
+    img[0, 0] = 16
+    return img
+
+
+def _frames(rng, regions, channels=None):
+    from oracle import PrestageOracle
+
+    po = PrestageOracle()
+    imgs = np.stack([_framed(rng, r, channels) for r in regions])
+    for img, r in zip(imgs, regions):  # the oracle's autocrop keeps what the frame was built to keep
+        assert tuple(po.autocrop(img if channels is None else po.bgr2gray(img), 20).tolist()) == r
+    return imgs, po
+
+
+def test_the_three_callers_of_the_kept_region_plan_agree(gpu):
+    """process_images, the scanner pipeline and the video indexer (one chunk; chunks of 1) hash the same kept views:
+    hashes and rectangles equal one another and the oracle's, on a chunk whose regions change and come back"""
+    from cbird_amd import hashing
+    from cbird_amd.scanner import IndexParams, process_images
+    from cbird_amd.video import VideoIndexer
+
+    regions = [_WHOLE, _A, _A, _B, _WHOLE, _B]
+    gray, po = _frames(np.random.default_rng(160), regions)
+    assert len(set(regions)) == 3
+    want = [po.process_image(g, 20) for g in gray]
+    want_h = [int(h) for h, _ in want]
+    assert [tuple(int(v) for v in r) for _, r in want] == regions
+    assert len(set(want_h)) == len(want_h)
+    h1, r1 = hashing.process_images(gray, 20)
+    assert [int(x) for x in h1] == want_h and [tuple(r) for r in r1.tolist()] == regions
+    res = process_images(gray, IndexParams(algos=1))
+    assert [r.dctHash for r in res] == want_h and [r.cropRect for r in res] == regions
+    ix = VideoIndexer(threshold=0)
+    ix.push(gray)
+    assert ix.finish().hashes == want_h
+    ix = VideoIndexer(threshold=0)
+    for g in gray:
+        ix.push(g[None])
+    assert ix.finish().hashes == want_h
+
+
+def _same_result(a, b):
+    assert a.dctHash == b.dctHash and a.cropRect == b.cropRect and a.resizedDims == b.resizedDims
+    assert (a.keyPoints == b.keyPoints).all() and (a.keyPointDescriptors == b.keyPointDescriptors).all()
+    assert (a.keyPointHashes == b.keyPointHashes).all()
+
+
+def test_pipeline_plans_with_cropping_equal_the_images_alone(gpu):
+    """hash, resize, ORB and keypoint hashes of cropped images in one chunk, on both launch plans: runs ([A, A, B, B]:
+    two runs, and 1 + 2 odd images is not less than 2) and mode first ([A, B, A, C, A]: A over the chunk, B and C redone).
+    Every field equals the same image processed alone, bit for bit"""
+    from cbird_amd import orb
+    from cbird_amd.scanner import IndexParams, process_images
+
+    orb.set_pattern(orb.synthetic_pattern())
+    p = IndexParams(algos=7, numFeatures=40)
+    for seed, regions in ((4, [_A, _A, _B, _B]), (5, [_A, _B, _A, _C, _A])):
+        imgs, _ = _frames(np.random.default_rng(seed), regions, channels=3)
+        got = process_images(imgs, p)
+        assert [r.cropRect for r in got] == regions
+        for img, r in zip(imgs, got):
+            _same_result(r, process_images(img[None], p)[0])
+        assert min(len(r.keyPoints) for r in got) > 10 and min(len(r.keyPointHashes) for r in got) > 0
+        assert len({r.dctHash for r in got}) == len(got)
