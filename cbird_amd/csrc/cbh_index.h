@@ -354,12 +354,12 @@ inline int scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t n
 // first k by (distance, id) of each of the nq needles into d_out / d_counts
 inline int records_topk(Workspace* ws, size_t nq, int k, unsigned long long total, cbh_match* d_out, uint32_t* d_counts,
                         hipStream_t s) {
-  void* scratch = nullptr;
+  Scratch scratch(s);
+  char* block = nullptr;
   const size_t ncap = std::min<size_t>(ws->rec_cap, (size_t)total + 1);  // slots past the count are never read
-  CBH_HIP(cbh::malloc_async(&scratch, topk_scratch_bytes(nq, ncap) + 16, s));
-  unsigned* d_status = (unsigned*)((char*)scratch + topk_scratch_bytes(nq, ncap));
-  int rc = topk_scratch_init(scratch, nq, s);
-  if (!rc) rc = launch_records_topk(ws->d_total, 1, 0, ncap, nq, k, d_out, d_counts, d_status, scratch, s);
-  (void)cbh::free_async(scratch, s);
+  CBH_HIP(scratch.get(&block, topk_scratch_bytes(nq, ncap) + 16));
+  unsigned* d_status = (unsigned*)(block + topk_scratch_bytes(nq, ncap));
+  int rc = topk_scratch_init(block, nq, s);
+  if (!rc) rc = launch_records_topk(ws->d_total, 1, 0, ncap, nq, k, d_out, d_counts, d_status, block, s);
   return rc;
 }

@@ -6,8 +6,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include <cstring>
+#include <algorithm>
 #include <atomic>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -28,8 +29,9 @@ void set_last_error_code(int code);  // keeps the text (a successful fall-back l
 void* fail_handle(int code, const char* why);  // sets code + text (text kept if `why` is null and a text exists), returns nullptr
 
 // ---- stream-ordered scratch memory (cbird_hip.hip) ------------------------------------------------------------------
-// Every kernel launcher takes its scratch with malloc_async(&p, bytes, stream) and gives it back with
-// free_async(p, stream) right behind the last kernel that uses it (the contract of hipMallocAsync / hipFreeAsync).
+// malloc_async(&p, bytes, stream) takes a block and free_async(p, stream) gives it back behind the last kernel that uses
+// it (the contract of hipMallocAsync / hipFreeAsync).  Launchers do both through the Scratch guard below; only blocks
+// that outlive the function that takes them are freed by hand (DESIGN.md names them).
 // The source is the library's own arena: hipMalloc'ed blocks cached per (device, stream), reused only by the stream that
 // freed them; bounded ("pool_live_keep_mb" per live stream, "pool_keep_mb" for blocks that outlive theirs, 32 stream
 // caches, cbh_trim).  (ROCm's hipMallocAsync pools hand out memory that is still in use on this stack:
@@ -106,14 +108,30 @@ static inline hipError_t gated_host_malloc(T** p, size_t bytes, unsigned flags =
 #define hipMalloc(...) ::cbh::gated_malloc(__VA_ARGS__)
 #define hipHostMalloc(...) ::cbh::gated_host_malloc(__VA_ARGS__)
 
-#define CBH_HIP(call)                          \
-  do {                                         \
-    hipError_t e_ = (call);                    \
-    if (e_ != hipSuccess) {                    \
-      ::cbh::set_last_error(#call, e_);        \
-      return e_ == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP; \
-    }                                          \
+// the code the C-ABI returns for a failed HIP call; fail() also leaves the error text
+inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP; }
+inline int fail(const char* where, hipError_t e) {
+  set_last_error(where, e);
+  return hip_code(e);
+}
+#define CBH_HIP(call)                                     \
+  do {                                                    \
+    hipError_t e_ = (call);                               \
+    if (e_ != hipSuccess) return ::cbh::fail(#call, e_);  \
   } while (0)
+
+// a host table into a block of the launcher's scratch (at least one element's worth, so that an empty table still has an
+// address).  The copy reads the host memory when the stream gets to it: the caller keeps it until it has synchronised
+template <class T>
+hipError_t upload(Scratch& scratch, T** d, const T* h, size_t count, hipStream_t s) {
+  hipError_t e = scratch.get(d, std::max<size_t>(count, 1) * sizeof(T));
+  if (e == hipSuccess && count) e = hipMemcpyAsync(*d, h, count * sizeof(T), hipMemcpyHostToDevice, s);
+  return e;
+}
+template <class T>
+hipError_t upload(Scratch& scratch, T** d, const std::vector<T>& h, hipStream_t s) {
+  return upload(scratch, d, h.data(), h.size(), s);
+}
 
 // ---- the 64-bit threshold search: hamm64_scan.hip decides, hamm64_join.hip / hamm64_mfma.hip launch what they are told --
 struct JoinCache;    // the resident slot tables of one index, below (hamm64_join.hip)

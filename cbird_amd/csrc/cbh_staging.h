@@ -2,28 +2,12 @@
 // its _dev twin (or a launcher) on a stream of the library's own, fetches the results and leaves nothing behind.
 // Include after cbh_internal.h: the allocations below go through its hipMalloc gate (fault injection).
 #pragma once
-#include <algorithm>
 #include <string>
 #include <vector>
 
 #include "cbh_internal.h"
 
 namespace cbh {
-
-// the error text of a failed HIP call and the code the C-ABI returns for it
-inline int fail(const char* where, hipError_t e) {
-  set_last_error(where, e);
-  return e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-}
-
-// a host table into a block of the launcher's scratch.  The copy reads `h` when the stream gets to it: the caller keeps
-// the vector until it has synchronised
-template <class T>
-hipError_t upload(Scratch& scratch, T** d, const std::vector<T>& h, hipStream_t s) {
-  hipError_t e = scratch.get(d, std::max<size_t>(h.size(), 1) * sizeof(T));
-  if (e == hipSuccess && !h.empty()) e = hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s);
-  return e;
-}
 
 // The life of one host-memory call: a non-blocking stream `s`, the device buffers taken with alloc(), and the first HIP
 // error.  After an error alloc / up / down / sync do nothing, so a body reads straight down and asks status() where it

@@ -27,7 +27,7 @@ void set_last_error(const char* where, hipError_t e) {
   char buf[512];
   snprintf(buf, sizeof buf, "%s: %s (%d)", where, hipGetErrorString(e), (int)e);
   t_last_error = buf;
-  t_last_code = e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
+  t_last_code = hip_code(e);
 }
 
 void set_last_error_text(const char* text) {
@@ -1263,17 +1263,17 @@ int cbh_records_topk_dev(const void* d_blocks, size_t n_blocks, size_t block_str
   DeviceGuard g(device);
   if (!g.ok) return CBH_E_NODEVICE;
   hipStream_t s = (hipStream_t)stream;
-  void* scratch = nullptr;  // stream-ordered, recycled by this stream's pool between calls
-  hipError_t e = cbh::malloc_async(&scratch, topk_scratch_bytes(nq, n_blocks * cap), s);
+  Scratch scratch(s);  // stream-ordered, recycled by this stream's pool between calls
+  void* block = nullptr;
+  hipError_t e = scratch.get(&block, topk_scratch_bytes(nq, n_blocks * cap));
   if (e != hipSuccess) {
     set_last_error("malloc_async(topk scratch)", e);
     return CBH_E_NOMEM;
   }
-  int rc = topk_scratch_init(scratch, nq, s);
+  int rc = topk_scratch_init(block, nq, s);
   if (!rc)
     rc = launch_records_topk((const unsigned long long*)d_blocks, (unsigned)n_blocks, block_stride, cap, nq,
-                             max_per_query, (cbh_match*)d_out, (uint32_t*)d_counts, (unsigned*)d_status, scratch, s);
-  (void)cbh::free_async(scratch, s);
+                             max_per_query, (cbh_match*)d_out, (uint32_t*)d_counts, (unsigned*)d_status, block, s);
   if (rc) return rc;
   if (!stream) CBH_HIP(hipStreamSynchronize(s));
   return CBH_OK;
@@ -1290,16 +1290,14 @@ int cbh_sort_records_dev(void* d_records, size_t n, size_t nq, int device, void*
   void* tmp = nullptr;
   const size_t tmp_bytes = sort_records_scratch_bytes(n);
   // stream-ordered scratch: no device-wide synchronisation, the pool recycles the blocks between calls
-  CBH_HIP(cbh::malloc_async((void**)&alt, n * sizeof(cbh_record), s));
-  hipError_t e = cbh::malloc_async(&tmp, tmp_bytes ? tmp_bytes : 16, s);
+  Scratch scratch(s);
+  CBH_HIP(scratch.get(&alt, n * sizeof(cbh_record)));
+  hipError_t e = scratch.get(&tmp, tmp_bytes ? tmp_bytes : 16);
   if (e != hipSuccess) {
-    (void)cbh::free_async(alt, s);
     set_last_error("cbh::malloc_async(sort scratch)", e);
     return CBH_E_NOMEM;
   }
   int rc = launch_sort_records((cbh_record*)d_records, alt, n, nq, tmp, tmp_bytes, s);
-  (void)cbh::free_async(alt, s);
-  (void)cbh::free_async(tmp, s);
   if (rc) return rc;
   if (!stream) CBH_HIP(hipStreamSynchronize(s));
   return CBH_OK;

@@ -955,25 +955,20 @@ static int launch_color_descriptors_chunk(const uint8_t* d_imgs, size_t n, const
   CdW* d_w = nullptr;
   unsigned* d_unfinished = nullptr;
   unsigned* h_unfinished = nullptr;
-  hipError_t e = hipSuccess;
-  auto alloc = [&](void** p, size_t bytes) {
-    if (e == hipSuccess) e = cbh::malloc_async(p, std::max<size_t>(bytes, 256), s);
-  };
-  alloc((void**)&d_images, n * sizeof(CdImage));
-  alloc((void**)&d_masks, masks.size());
-  alloc((void**)&d_tabs, sizeof(CdTables));
-  alloc((void**)&d_samples, slots * 3 * sizeof(float));
-  alloc((void**)&d_dists, slots * 4 * sizeof(float));
-  alloc((void**)&d_pos, slots * sizeof(unsigned));
-  alloc((void**)&d_labels, slots);
-  alloc((void**)&d_counts, n * sizeof(int));
-  alloc((void**)&d_w, n * sizeof(CdW));
-  alloc((void**)&d_unfinished, sizeof(unsigned));
+  Scratch scratch(s);
+  hipError_t e = scratch.get(&d_images, std::max<size_t>(n * sizeof(CdImage), 256));
+  if (e == hipSuccess) e = scratch.get(&d_masks, std::max<size_t>(masks.size(), 256));
+  if (e == hipSuccess) e = upload(scratch, &d_tabs, &tables(), 1, s);
+  if (e == hipSuccess) e = scratch.get(&d_samples, std::max<size_t>(slots * 3 * sizeof(float), 256));
+  if (e == hipSuccess) e = scratch.get(&d_dists, std::max<size_t>(slots * 4 * sizeof(float), 256));
+  if (e == hipSuccess) e = scratch.get(&d_pos, std::max<size_t>(slots * sizeof(unsigned), 256));
+  if (e == hipSuccess) e = scratch.get(&d_labels, std::max<size_t>(slots, 256));
+  if (e == hipSuccess) e = scratch.get(&d_counts, std::max<size_t>(n * sizeof(int), 256));
+  if (e == hipSuccess) e = scratch.get(&d_w, std::max<size_t>(n * sizeof(CdW), 256));
+  if (e == hipSuccess) e = scratch.get(&d_unfinished, std::max<size_t>(sizeof(unsigned), 256));
   if (e == hipSuccess) e = hipHostMalloc(&h_unfinished, sizeof(unsigned));
-  int rc = CBH_OK;
   if (e == hipSuccess) e = hipMemcpyAsync(d_images, images.data(), n * sizeof(CdImage), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(d_masks, masks.data(), masks.size(), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_tabs, &tables(), sizeof(CdTables), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) {
     const unsigned ni = (unsigned)n;
     const size_t slot_stride = slots;  // floats between two distance slots
@@ -1024,15 +1019,8 @@ static int launch_color_descriptors_chunk(const uint8_t* d_imgs, size_t n, const
     }
   }
   if (e == hipSuccess) e = hipStreamSynchronize(s);  // the host tables above must outlive the copies
-  if (e != hipSuccess) {
-    set_last_error("color descriptors", e);
-    rc = e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-  }
-  for (void* p : {(void*)d_images, (void*)d_masks, (void*)d_tabs, (void*)d_samples, (void*)d_dists, (void*)d_pos,
-                  (void*)d_labels, (void*)d_counts, (void*)d_w, (void*)d_unfinished})
-    if (p) (void)cbh::free_async(p, s);
-  if (h_unfinished) (void)hipHostFree(h_unfinished);
-  return rc;
+  if (h_unfinished) (void)hipHostFree(h_unfinished);  // (pinned, not scratch: this is the only way out past its allocation)
+  return e == hipSuccess ? CBH_OK : fail("color descriptors", e);
 }
 
 int launch_color_descriptors(const uint8_t* d_imgs, size_t n, const uint64_t* img_off, const uint32_t* img_w,

@@ -155,16 +155,11 @@ int fdct_core(cbh_idx64* idx, const uint64_t* hashes, const std::vector<Needle>&
     for (size_t j = needles[i].begin; j < needles[i].end; ++j) qneedle[j] = (uint32_t)i;
   }
   uint32_t *d_qneedle = nullptr, *d_nid = nullptr;
-  hipError_t e = cbh::malloc_async((void**)&d_qneedle, nq * 4, s);
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&d_nid, std::max<size_t>(1, nid.size()) * 4, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_qneedle, qneedle.data(), nq * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && !nid.empty()) e = hipMemcpyAsync(d_nid, nid.data(), nid.size() * 4, hipMemcpyHostToDevice, s);
+  Scratch scratch(s);
+  CBH_HIP(upload(scratch, &d_qneedle, qneedle, s));
+  CBH_HIP(upload(scratch, &d_nid, nid, s));
   std::vector<cbh_nmatch> flat;
-  if (e == hipSuccess) rc = launch_fdct_vote(ws->d_out, ws->d_counts, d_qneedle, nq, k, d_nid, nid.size(), &flat, s);
-  if (d_qneedle) (void)cbh::free_async(d_qneedle, s);
-  if (d_nid) (void)cbh::free_async(d_nid, s);
-  CBH_HIP(e);
-  if (rc) return rc;
+  if ((rc = launch_fdct_vote(ws->d_out, ws->d_counts, d_qneedle, nq, k, d_nid, nid.size(), &flat, s))) return rc;
   std::sort(flat.begin(), flat.end(), [](const cbh_nmatch& a, const cbh_nmatch& b) {
     return a.needle != b.needle ? a.needle < b.needle : a.id < b.id;  // QMap order: ascending mediaId
   });

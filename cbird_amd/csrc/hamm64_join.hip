@@ -531,8 +531,7 @@ std::shared_ptr<const JoinTables> JoinCache::get_or_build(int m, const uint64_t*
   if ((e = hipMalloc(&T->hist_h, entries * 4)) != hipSuccess || (e = hipMalloc(&T->start_h, entries * 4)) != hipSuccess ||
       (e = hipMalloc(&T->hx, (size_t)P.m * n * 8)) != hipSuccess || (e = hipMalloc(&T->hid, (size_t)P.m * n * 4)) != hipSuccess ||
       (e = scratch.get(&cursor, entries * 4)) != hipSuccess) {
-    set_last_error("join tables", e);
-    return give_up(e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP);
+    return give_up(fail("join tables", e));
   }
   if ((e = hipMemsetAsync(T->hist_h, 0, entries * 4, stream)) == hipSuccess && (e = hipMemsetAsync(cursor, 0, entries * 4, stream)) == hipSuccess) {
     launch_hist(d_hashes, n, P, T->hist_h, stream);
@@ -567,10 +566,7 @@ int join_prepare_needles(const uint64_t* d_q, size_t nq, int thresh, hipStream_t
   int rc = needles_alloc(P, nq, stream, out);
   if (!rc) {
     hipError_t e = scratch.get(&cursor, plan_entries(P) * 4);
-    if (e != hipSuccess) {
-      set_last_error("join needles", e);
-      rc = e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-    }
+    if (e != hipSuccess) rc = fail("join needles", e);
   }
   if (!rc) rc = needles_count(d_q, nq, P, cursor, stream, out);
   if (!rc) {

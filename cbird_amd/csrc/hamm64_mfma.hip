@@ -938,8 +938,9 @@ void probe_slot_put(uint32_t* p) {
 
 bool probe_fold_rates(const uint64_t* d_hashes, size_t n, const uint64_t* d_q, size_t nq, int thresh, hipStream_t stream,
                       double* r_cand, double* r_true, double* r_cand48, double* r_cand16) {
+  Scratch scratch(stream);
   uint32_t* d_cnt = nullptr;
-  if (cbh::malloc_async((void**)&d_cnt, 4 * kProbeT * sizeof(uint32_t), stream) != hipSuccess) {
+  if (scratch.get(&d_cnt, 4 * kProbeT * sizeof(uint32_t)) != hipSuccess) {
     (void)hipGetLastError();
     return false;
   }
@@ -957,7 +958,6 @@ bool probe_fold_rates(const uint64_t* d_hashes, size_t n, const uint64_t* d_q, s
            hipStreamSynchronize(stream) == hipSuccess;
     }
   }
-  (void)cbh::free_async(d_cnt, stream);
   if (ok) {
     const double pairs = (double)sh * (double)sq;
     *r_cand = (double)h_cnt[thresh - 1] / pairs;

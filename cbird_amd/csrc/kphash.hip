@@ -560,27 +560,17 @@ int launch_rect_hashes(uint8_t* d_base, const std::vector<RectImageDesc>& images
   AreaTab* d_apool = nullptr;
   int* d_ipool = nullptr;
   unsigned char* d_scr = nullptr;
-  hipError_t e = hipSuccess;
-  auto up = [&](void** dst, const void* src, size_t bytes) {
-    if (e != hipSuccess) return;
-    if ((e = cbh::malloc_async(dst, bytes, stream)) != hipSuccess) return;
-    e = hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, stream);
-  };
-  up((void**)&d_images, imgs.data(), imgs.size() * sizeof(RectImage));
-  up((void**)&d_jobs, jobs.data(), jobs.size() * sizeof(RectJob));
-  up((void**)&d_axes, rt.axes.data(), rt.axes.size() * sizeof(AxisTab));
-  up((void**)&d_apool, rt.apool.data(), rt.apool.size() * sizeof(AreaTab));
-  up((void**)&d_ipool, rt.ipool.data(), rt.ipool.size() * sizeof(int));
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&d_scr, (size_t)grid * max_blur, stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_rect_hashes, dim3(grid), dim3(kThreads), 0, stream, d_base, d_images, (unsigned)imgs.size(),
-                       d_jobs, d_axes, d_apool, d_ipool, d_scr, max_blur, tabs, write_back, d_out, d_tiles);
-    e = hipGetLastError();
-  }
-  for (void* p : {(void*)d_images, (void*)d_jobs, (void*)d_axes, (void*)d_apool, (void*)d_ipool, (void*)d_scr})
-    if (p) (void)cbh::free_async(p, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  CBH_HIP(e);
+  Scratch scratch(stream);
+  CBH_HIP(upload(scratch, &d_images, imgs, stream));
+  CBH_HIP(upload(scratch, &d_jobs, jobs, stream));
+  CBH_HIP(upload(scratch, &d_axes, rt.axes, stream));
+  CBH_HIP(upload(scratch, &d_apool, rt.apool, stream));
+  CBH_HIP(upload(scratch, &d_ipool, rt.ipool, stream));
+  CBH_HIP(scratch.get(&d_scr, (size_t)grid * max_blur));
+  hipLaunchKernelGGL(k_rect_hashes, dim3(grid), dim3(kThreads), 0, stream, d_base, d_images, (unsigned)imgs.size(), d_jobs,
+                     d_axes, d_apool, d_ipool, d_scr, max_blur, tabs, write_back, d_out, d_tiles);
+  CBH_HIP(hipGetLastError());
+  CBH_HIP(hipStreamSynchronize(stream));
   return CBH_OK;
 }
 
@@ -663,46 +653,32 @@ int launch_keypoint_hashes(uint8_t* d_base, size_t n, const uint64_t* img_off, c
   uint64_t* d_slots = nullptr;
   unsigned *d_counts = nullptr, *d_first = nullptr;
   std::vector<unsigned> counts(n);
-  hipError_t e = hipSuccess;
-  auto up = [&](void** dst, const void* src, size_t bytes) {
-    if (e != hipSuccess) return;
-    if ((e = cbh::malloc_async(dst, bytes, stream)) != hipSuccess) return;
-    e = hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, stream);
-  };
-  up((void**)&d_images, imgs.data(), imgs.size() * sizeof(KpImage));
-  up((void**)&d_kp, kp, nkp * 3 * sizeof(float));
-  up((void**)&d_sizes, sizes.data(), sizes.size() * sizeof(SizeInfo));
-  up((void**)&d_apool, apool.data(), apool.size() * sizeof(AreaTab));
-  up((void**)&d_ipool, ipool.data(), ipool.size() * sizeof(int));
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&d_scr, (size_t)grid * scratch_per_wg, stream);
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&d_slots, nkp * sizeof(uint64_t), stream);
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&d_counts, n * sizeof(unsigned), stream);
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&d_first, (n + 1) * sizeof(unsigned), stream);
-  if (e == hipSuccess && smem > 48 * 1024)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_kp_hashes), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_kp_hashes, dim3(grid), dim3(kThreads), smem, stream, d_base, d_images, (unsigned)n, d_kp,
-                       d_sizes, d_apool, d_ipool, lds_side, blur_side, tab_cap, d_scr, scratch_per_wg, tabs, d_slots,
-                       d_counts);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts, n * sizeof(unsigned), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (e == hipSuccess) {
-    for (size_t i = 0; i < n; ++i) out_first[i + 1] = out_first[i] + counts[i];
-    e = hipMemcpyAsync(d_first, out_first, (n + 1) * sizeof(unsigned), hipMemcpyHostToDevice, stream);
-  }
-  if (e == hipSuccess && out_first[n]) {
+  Scratch scratch(stream);
+  CBH_HIP(upload(scratch, &d_images, imgs, stream));
+  CBH_HIP(upload(scratch, &d_kp, kp, nkp * 3, stream));
+  CBH_HIP(upload(scratch, &d_sizes, sizes, stream));
+  CBH_HIP(upload(scratch, &d_apool, apool, stream));
+  CBH_HIP(upload(scratch, &d_ipool, ipool, stream));
+  CBH_HIP(scratch.get(&d_scr, (size_t)grid * scratch_per_wg));
+  CBH_HIP(scratch.get(&d_slots, nkp * sizeof(uint64_t)));
+  CBH_HIP(scratch.get(&d_counts, n * sizeof(unsigned)));
+  CBH_HIP(scratch.get(&d_first, (n + 1) * sizeof(unsigned)));
+  if (smem > 48 * 1024)
+    CBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_kp_hashes), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)smem));
+  hipLaunchKernelGGL(k_kp_hashes, dim3(grid), dim3(kThreads), smem, stream, d_base, d_images, (unsigned)n, d_kp, d_sizes,
+                     d_apool, d_ipool, lds_side, blur_side, tab_cap, d_scr, scratch_per_wg, tabs, d_slots, d_counts);
+  CBH_HIP(hipGetLastError());
+  CBH_HIP(hipMemcpyAsync(counts.data(), d_counts, n * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+  CBH_HIP(hipStreamSynchronize(stream));
+  for (size_t i = 0; i < n; ++i) out_first[i + 1] = out_first[i] + counts[i];
+  CBH_HIP(hipMemcpyAsync(d_first, out_first, (n + 1) * sizeof(unsigned), hipMemcpyHostToDevice, stream));
+  if (out_first[n]) {
     hipLaunchKernelGGL(k_kp_compact, dim3(grid), dim3(kThreads), 0, stream, d_slots, d_images, d_first, d_out,
                        (unsigned)n);
-    e = hipGetLastError();
+    CBH_HIP(hipGetLastError());
   }
-  for (void* p : {(void*)d_images, (void*)d_kp, (void*)d_sizes, (void*)d_apool, (void*)d_ipool, (void*)d_scr,
-                  (void*)d_slots, (void*)d_counts, (void*)d_first})
-    if (p) (void)cbh::free_async(p, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  CBH_HIP(e);
+  CBH_HIP(hipStreamSynchronize(stream));
   return CBH_OK;
 }
 

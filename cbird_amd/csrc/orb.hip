@@ -1047,13 +1047,8 @@ OrbPlan make_plan(size_t n, const uint64_t* img_off, const uint32_t* img_w, cons
                   const uint32_t* img_row_stride, const int* nper, const int* level_limit) {
   OrbPlan pl;
   pl.images.resize(n);
-  auto& images = pl.images;
-  unsigned long long &pyr_bytes = pl.pyr_bytes, &sc_bytes = pl.sc_bytes, &cands = pl.cands;
-  unsigned &max_tiles = pl.max_tiles, &max_bwg = pl.max_bwg, &max_pitch = pl.max_pitch;
-  int& max_lev = pl.max_lev;
-  int* max_h = pl.max_h;
   for (size_t i = 0; i < n; ++i) {
-    OrbImage& im = images[i];
+    OrbImage& im = pl.images[i];
     memset(&im, 0, sizeof im);
     im.src_off = img_off[i];
     im.src_stride = img_row_stride[i];
@@ -1068,16 +1063,16 @@ OrbPlan make_plan(size_t n, const uint64_t* img_off, const uint32_t* img_w, cons
       im.nfeat[l] = nper[l];
       const unsigned P = (unsigned)((lw + 3) & ~3) + 2 * kBorderX;
       im.pitch[l] = P;
-      im.poff[l] = pyr_bytes + (unsigned long long)kBorderY * P + kBorderX;
-      pyr_bytes += ((unsigned long long)P * (lh + 2 * kBorderY) + 15) & ~15ull;
-      max_pitch = std::max(max_pitch, P);
-      max_h[l] = std::max(max_h[l], lh);
+      im.poff[l] = pl.pyr_bytes + (unsigned long long)kBorderY * P + kBorderX;
+      pl.pyr_bytes += ((unsigned long long)P * (lh + 2 * kBorderY) + 15) & ~15ull;
+      pl.max_pitch = std::max(pl.max_pitch, P);
+      pl.max_h[l] = std::max(pl.max_h[l], lh);
       im.spitch[l] = (unsigned)((lw + 15) & ~15);
-      im.soff[l] = sc_bytes;
-      sc_bytes += (unsigned long long)im.spitch[l] * lh;
+      im.soff[l] = pl.sc_bytes;
+      pl.sc_bytes += (unsigned long long)im.spitch[l] * lh;
       const int iw = lw - 2 * kEdge, ih = lh - 2 * kEdge;
-      im.coff[l] = cands;
-      cands += (unsigned long long)((iw + 1) / 2) * ((ih + 1) / 2);  // strict 3x3 maxima cannot be neighbours
+      im.coff[l] = pl.cands;
+      pl.cands += (unsigned long long)((iw + 1) / 2) * ((ih + 1) / 2);  // strict 3x3 maxima cannot be neighbours
       im.tile_first[l] = tiles;
       tiles += (unsigned)((iw + kTileW - 1) / kTileW) * (unsigned)((ih + kTileH - 1) / kTileH);
       im.bwg_first[l] = bwg;
@@ -1087,11 +1082,50 @@ OrbPlan make_plan(size_t n, const uint64_t* img_off, const uint32_t* img_w, cons
     }
     for (int l = nl; l <= kLevels; ++l) im.tile_first[l] = tiles, im.bwg_first[l] = bwg;
     im.nlev = nl;
-    max_tiles = std::max(max_tiles, tiles);
-    max_bwg = std::max(max_bwg, bwg);
-    max_lev = std::max(max_lev, nl);
+    pl.max_tiles = std::max(pl.max_tiles, tiles);
+    pl.max_bwg = std::max(pl.max_bwg, bwg);
+    pl.max_lev = std::max(pl.max_lev, nl);
   }
   return pl;
+}
+
+// level 0 from the callers' images, then every further level from the one above it
+void build_pyramid(const OrbPlan& pl, const OrbImage* d_images, const uint8_t* d_imgs, unsigned char* d_pyr,
+                   hipStream_t s) {
+  const unsigned ny = (unsigned)pl.images.size();
+  if (pl.max_lev >= 1) hipLaunchKernelGGL(k_orb_level0, dim3(32, ny), dim3(256), 0, s, d_images, d_imgs, d_pyr);
+  if ((size_t)pl.max_pitch * 8 > 64 * 1024)  // images wider than 8184 pixels: the x tables pass the default LDS limit
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_orb_resize), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(pl.max_pitch * 8));
+  for (int l = 1; l < pl.max_lev; ++l)
+    hipLaunchKernelGGL(k_orb_resize, dim3((unsigned)((pl.max_h[l] + 2 * kBorderY + kResizeRows - 1) / kResizeRows), ny),
+                       dim3(256), (size_t)pl.max_pitch * 8, s, d_images, l, d_pyr);
+}
+
+// GaussianBlur(7 x 7, sigma 2) of the levels that hold keypoints (d_lc), into the score buffer
+void blur_levels(const OrbPlan& pl, const OrbImage* d_images, const unsigned char* d_pyr, const unsigned* d_lc,
+                 unsigned char* d_sc, hipStream_t s) {
+  GaussK g;
+  gauss7_kernel(g.k);
+  hipLaunchKernelGGL(k_orb_blur, dim3(pl.max_bwg, (unsigned)pl.images.size()), dim3(256), 0, s, d_images, d_pyr, d_lc, g,
+                     d_sc);
+}
+
+// the pattern of one launch; CBH_E_INVAL when it needs one and none is set (there is no built-in pattern: it is OpenCV's
+// learned table, an input), zeros when it needs none
+int pattern_copy(OrbPattern* pat, bool need) {
+  memset(pat, 0, sizeof *pat);
+  if (!need) return CBH_OK;
+  std::lock_guard<std::mutex> lk(g_pat_mu);
+  if (!g_have_pattern) return CBH_E_INVAL;
+  *pat = g_pattern;
+  return CBH_OK;
+}
+
+// the four lists of k_retain_best in one block of slots * 16 bytes
+RetainScratch retain_layout(void* block, size_t slots) {
+  unsigned* u = (unsigned*)block;
+  return RetainScratch{(float*)block, u + slots, u + 2 * slots, u + 3 * slots};
 }
 
 }  // namespace
@@ -1102,23 +1136,16 @@ void set_orb_retain_order(int v) {
 
 int launch_retain_best(const float* d_resp, uint32_t cnt, int n_points, int depth_limit, uint32_t* d_order,
                        uint32_t* d_count, hipStream_t s) {
-  RetainScratch rs = {nullptr, nullptr, nullptr, nullptr};
-  void* block = nullptr;
   const size_t slots = (size_t)cnt + 1;
-  hipError_t e = cbh::malloc_async(&block, slots * 16, s);
+  Scratch scratch(s);
+  void* block = nullptr;
+  hipError_t e = scratch.get(&block, slots * 16);
   if (e == hipSuccess) {
-    rs.key = (float*)block, rs.ref = (unsigned*)block + slots, rs.lp = (unsigned*)block + 2 * slots,
-    rs.ra = (unsigned*)block + 3 * slots;
-    hipLaunchKernelGGL(k_retain_best, dim3(1), dim3(256), 0, s, d_resp, (int)cnt, n_points, depth_limit, rs, d_order,
-                       d_count);
+    hipLaunchKernelGGL(k_retain_best, dim3(1), dim3(256), 0, s, d_resp, (int)cnt, n_points, depth_limit,
+                       retain_layout(block, slots), d_order, d_count);
     e = hipGetLastError();
   }
-  if (block) (void)cbh::free_async(block, s);
-  if (e != hipSuccess) {
-    set_last_error("orb retain_best", e);
-    return e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-  }
-  return CBH_OK;
+  return e == hipSuccess ? CBH_OK : fail("orb retain_best", e);
 }
 
 int orb_set_pattern(const int8_t* xy) {
@@ -1135,81 +1162,45 @@ int launch_orb(const uint8_t* d_imgs, size_t n, const uint64_t* img_off, const u
                const uint32_t* img_row_stride, int nfeatures, int kp_cap, cbh_keypoint* d_kp, float* d_kp_after,
                uint8_t* d_desc, uint32_t* d_counts, hipStream_t s) {
   OrbPattern pat;
-  if (d_desc) {
-    std::lock_guard<std::mutex> lk(g_pat_mu);
-    if (!g_have_pattern) return CBH_E_INVAL;  // no built-in pattern: it is OpenCV's learned table, an input
-    pat = g_pattern;
-  } else {
-    memset(&pat, 0, sizeof pat);
-  }
+  if (int rc = pattern_copy(&pat, d_desc != nullptr)) return rc;
   int nper[kLevels];
   features_per_level(nfeatures, nper);
-  OrbPlan pl = make_plan(n, img_off, img_w, img_h, img_row_stride, nper, nullptr);
-  const unsigned long long pyr_bytes = pl.pyr_bytes, sc_bytes = pl.sc_bytes, cands = pl.cands;
-  const unsigned max_tiles = pl.max_tiles, max_bwg = pl.max_bwg, max_pitch = pl.max_pitch;
-  const int max_lev = pl.max_lev;
-  const int* max_h = pl.max_h;
-  const std::vector<OrbImage>& images = pl.images;
+  const OrbPlan pl = make_plan(n, img_off, img_w, img_h, img_row_stride, nper, nullptr);
+  const int retain_order = g_retain_order;
+  const size_t slots = pl.cands + 1;
   OrbImage* d_images = nullptr;
   unsigned char *d_pyr = nullptr, *d_sc = nullptr;
   OrbCand *d_cand = nullptr, *d_cand_tmp = nullptr;
   unsigned* d_lc = nullptr;
-  int* d_pat = nullptr;
+  OrbPattern* d_pat = nullptr;
   void* d_retain = nullptr;
-  const int retain_order = g_retain_order;
   RetainScratch rs = {nullptr, nullptr, nullptr, nullptr};
-  hipError_t e = hipSuccess;
-  auto alloc = [&](void** p, size_t bytes) {
-    if (e == hipSuccess) e = cbh::malloc_async(p, std::max<size_t>(bytes, 256), s);
-  };
-  alloc((void**)&d_images, n * sizeof(OrbImage));
-  alloc((void**)&d_pyr, pyr_bytes + 64);
-  alloc((void**)&d_sc, sc_bytes + 64);
-  alloc((void**)&d_cand, (cands + 1) * sizeof(OrbCand));
-  if (retain_order == 1) {  // keys, raster positions and the two stop lists of every level + the gathered list
-    alloc((void**)&d_cand_tmp, (cands + 1) * sizeof(OrbCand));
-    alloc(&d_retain, (cands + 1) * 16);
-    if (e == hipSuccess)
-      rs.key = (float*)d_retain, rs.ref = (unsigned*)d_retain + (cands + 1), rs.lp = (unsigned*)d_retain + 2 * (cands + 1),
-      rs.ra = (unsigned*)d_retain + 3 * (cands + 1);
-  }
-  alloc((void**)&d_lc, n * kLevels * sizeof(unsigned));
-  alloc((void**)&d_pat, sizeof pat);
-  int rc = CBH_OK;
   // (pageable sources: hipMemcpyAsync has staged them when it returns)
-  if (e == hipSuccess) e = hipMemcpyAsync(d_images, images.data(), n * sizeof(OrbImage), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_pat, &pat, sizeof pat, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemsetAsync(d_sc, 0, sc_bytes + 64, s);  // k_orb_fast writes the non-zero scores only
+  Scratch scratch(s);
+  hipError_t e = upload(scratch, &d_images, pl.images, s);
+  if (e == hipSuccess) e = scratch.get(&d_pyr, std::max<size_t>(pl.pyr_bytes + 64, 256));
+  if (e == hipSuccess) e = scratch.get(&d_sc, std::max<size_t>(pl.sc_bytes + 64, 256));
+  if (e == hipSuccess) e = scratch.get(&d_cand, std::max<size_t>(slots * sizeof(OrbCand), 256));
+  if (retain_order == 1) {  // keys, raster positions and the two stop lists of every level + the gathered list
+    if (e == hipSuccess) e = scratch.get(&d_cand_tmp, std::max<size_t>(slots * sizeof(OrbCand), 256));
+    if (e == hipSuccess) e = scratch.get(&d_retain, std::max<size_t>(slots * 16, 256));
+    if (e == hipSuccess) rs = retain_layout(d_retain, slots);
+  }
+  if (e == hipSuccess) e = scratch.get(&d_lc, std::max<size_t>(n * kLevels * sizeof(unsigned), 256));
+  if (e == hipSuccess) e = upload(scratch, &d_pat, &pat, 1, s);
+  if (e == hipSuccess) e = hipMemsetAsync(d_sc, 0, pl.sc_bytes + 64, s);  // k_orb_fast writes the non-zero scores only
   if (e == hipSuccess) {
     const unsigned ny = (unsigned)n;
-    if (max_lev >= 1) hipLaunchKernelGGL(k_orb_level0, dim3(32, ny), dim3(256), 0, s, d_images, d_imgs, d_pyr);
-    if ((size_t)max_pitch * 8 > 64 * 1024)  // images wider than 8184 pixels: the x tables pass the default LDS limit
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_orb_resize), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(max_pitch * 8));
-    for (int l = 1; l < max_lev; ++l)
-      hipLaunchKernelGGL(k_orb_resize,
-                         dim3((unsigned)((max_h[l] + 2 * kBorderY + kResizeRows - 1) / kResizeRows), ny), dim3(256),
-                         (size_t)max_pitch * 8, s, d_images, l, d_pyr);
-    if (max_tiles) hipLaunchKernelGGL(k_orb_fast, dim3(max_tiles, ny), dim3(256), 0, s, d_images, d_pyr, d_sc);
+    build_pyramid(pl, d_images, d_imgs, d_pyr, s);
+    if (pl.max_tiles) hipLaunchKernelGGL(k_orb_fast, dim3(pl.max_tiles, ny), dim3(256), 0, s, d_images, d_pyr, d_sc);
     hipLaunchKernelGGL(k_orb_select, dim3(kLevels, ny), dim3(256), 0, s, d_images, d_pyr, d_sc, d_cand, d_lc,
                        retain_order, rs, d_cand_tmp);
-    if (d_desc && max_bwg) {
-      GaussK g;
-      gauss7_kernel(g.k);
-      hipLaunchKernelGGL(k_orb_blur, dim3(max_bwg, ny), dim3(256), 0, s, d_images, d_pyr, d_lc, g, d_sc);
-    }
+    if (d_desc && pl.max_bwg) blur_levels(pl, d_images, d_pyr, d_lc, d_sc, s);
     hipLaunchKernelGGL(k_orb_describe, dim3((unsigned)((std::max(kp_cap, 1) + 3) / 4), ny), dim3(256), 0, s, d_images,
-                       d_sc, d_cand, d_lc, d_pat, kp_cap, d_kp, d_kp_after, d_desc, d_counts);
+                       d_sc, d_cand, d_lc, (const int*)d_pat, kp_cap, d_kp, d_kp_after, d_desc, d_counts);
     e = hipGetLastError();
   }
-  if (e != hipSuccess) {
-    set_last_error("orb", e);
-    rc = e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-  }
-  for (void* p : {(void*)d_images, (void*)d_pyr, (void*)d_sc, (void*)d_cand, (void*)d_lc, (void*)d_pat,
-                  (void*)d_cand_tmp, d_retain})
-    if (p) (void)cbh::free_async(p, s);
-  return rc;
+  return e == hipSuccess ? CBH_OK : fail("orb", e);
 }
 
 // makeKeyPointDescriptors on provided keypoints (host arrays; d_imgs on the device).  out_kp: the keypoints as
@@ -1219,11 +1210,7 @@ int launch_orb_describe(const uint8_t* d_imgs, size_t n, const uint64_t* img_off
                         const uint32_t* kp_first, cbh_keypoint* out_kp, uint8_t* out_desc, uint32_t* out_first,
                         hipStream_t s) {
   OrbPattern pat;
-  {
-    std::lock_guard<std::mutex> lk(g_pat_mu);
-    if (!g_have_pattern) return CBH_E_INVAL;
-    pat = g_pattern;
-  }
+  if (int rc = pattern_copy(&pat, true)) return rc;
   // ORB::operator(): runByImageBorder(keypoints, image size, edgeThreshold) -- Rect::contains on the rounded point --
   // then one list per octave
   std::vector<OrbGivenKp> flat;
@@ -1260,61 +1247,38 @@ int launch_orb_describe(const uint8_t* d_imgs, size_t n, const uint64_t* img_off
   const size_t nk = flat.size();
   if (nk == 0) return CBH_OK;
   int nper[kLevels] = {0};
-  OrbPlan pl = make_plan(n, img_off, img_w, img_h, img_row_stride, nper, limit.data());
+  const OrbPlan pl = make_plan(n, img_off, img_w, img_h, img_row_stride, nper, limit.data());
+  std::vector<float> xy(nk * 2);
   OrbImage* d_images = nullptr;
   unsigned char *d_pyr = nullptr, *d_sc = nullptr, *d_desc = nullptr;
   unsigned* d_lc = nullptr;
-  int* d_pat = nullptr;
+  OrbPattern* d_pat = nullptr;
   OrbGivenKp* d_kps = nullptr;
   float* d_xy = nullptr;
-  hipError_t e = hipSuccess;
-  auto alloc = [&](void** p, size_t bytes) {
-    if (e == hipSuccess) e = cbh::malloc_async(p, std::max<size_t>(bytes, 256), s);
-  };
-  alloc((void**)&d_images, n * sizeof(OrbImage));
-  alloc((void**)&d_pyr, pl.pyr_bytes + 64);
-  alloc((void**)&d_sc, pl.sc_bytes + 64);
-  alloc((void**)&d_lc, n * kLevels * sizeof(unsigned));
-  alloc((void**)&d_pat, sizeof pat);
-  alloc((void**)&d_kps, nk * sizeof(OrbGivenKp));
-  alloc((void**)&d_xy, nk * 2 * sizeof(float));
-  alloc((void**)&d_desc, nk * 32);
-  std::vector<float> xy(nk * 2);
-  int rc = CBH_OK;
-  if (e == hipSuccess) e = hipMemcpyAsync(d_images, pl.images.data(), n * sizeof(OrbImage), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_pat, &pat, sizeof pat, hipMemcpyHostToDevice, s);
+  Scratch scratch(s);
+  hipError_t e = upload(scratch, &d_images, pl.images, s);
+  if (e == hipSuccess) e = scratch.get(&d_pyr, std::max<size_t>(pl.pyr_bytes + 64, 256));
+  if (e == hipSuccess) e = scratch.get(&d_sc, std::max<size_t>(pl.sc_bytes + 64, 256));
+  if (e == hipSuccess) e = scratch.get(&d_lc, std::max<size_t>(lc.size() * sizeof(unsigned), 256));
+  if (e == hipSuccess) e = upload(scratch, &d_pat, &pat, 1, s);
+  if (e == hipSuccess) e = scratch.get(&d_kps, std::max<size_t>(nk * sizeof(OrbGivenKp), 256));
+  if (e == hipSuccess) e = scratch.get(&d_xy, std::max<size_t>(nk * 2 * sizeof(float), 256));
+  if (e == hipSuccess) e = scratch.get(&d_desc, std::max<size_t>(nk * 32, 256));
   if (e == hipSuccess) e = hipMemcpyAsync(d_lc, lc.data(), lc.size() * sizeof(unsigned), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(d_kps, flat.data(), nk * sizeof(OrbGivenKp), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) {
-    const unsigned ny = (unsigned)n;
-    if (pl.max_lev >= 1) hipLaunchKernelGGL(k_orb_level0, dim3(32, ny), dim3(256), 0, s, d_images, d_imgs, d_pyr);
-    if ((size_t)pl.max_pitch * 8 > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_orb_resize), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(pl.max_pitch * 8));
-    for (int l = 1; l < pl.max_lev; ++l)
-      hipLaunchKernelGGL(k_orb_resize,
-                         dim3((unsigned)((pl.max_h[l] + 2 * kBorderY + kResizeRows - 1) / kResizeRows), ny), dim3(256),
-                         (size_t)pl.max_pitch * 8, s, d_images, l, d_pyr);
-    GaussK g;
-    gauss7_kernel(g.k);
-    if (pl.max_bwg) hipLaunchKernelGGL(k_orb_blur, dim3(pl.max_bwg, ny), dim3(256), 0, s, d_images, d_pyr, d_lc, g, d_sc);
+    build_pyramid(pl, d_images, d_imgs, d_pyr, s);
+    if (pl.max_bwg) blur_levels(pl, d_images, d_pyr, d_lc, d_sc, s);
     hipLaunchKernelGGL(k_orb_describe_given, dim3((unsigned)((nk + 3) / 4)), dim3(256), 0, s, d_images, d_sc, d_kps,
-                       (unsigned)nk, d_pat, d_xy, d_desc);
+                       (unsigned)nk, (const int*)d_pat, d_xy, d_desc);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(xy.data(), d_xy, nk * 2 * sizeof(float), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipMemcpyAsync(out_desc, d_desc, nk * 32, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) {
-    set_last_error("orb describe", e);
-    rc = e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-  } else {
-    for (size_t k = 0; k < nk; ++k) out_kp[k].x = xy[2 * k], out_kp[k].y = xy[2 * k + 1];
-  }
-  for (void* p : {(void*)d_images, (void*)d_pyr, (void*)d_sc, (void*)d_lc, (void*)d_pat, (void*)d_kps, (void*)d_xy,
-                  (void*)d_desc})
-    if (p) (void)cbh::free_async(p, s);
-  return rc;
+  if (e != hipSuccess) return fail("orb describe", e);
+  for (size_t k = 0; k < nk; ++k) out_kp[k].x = xy[2 * k], out_kp[k].y = xy[2 * k + 1];
+  return CBH_OK;
 }
 
 }  // namespace cbh
@@ -1332,14 +1296,9 @@ int cbh_orb_retain_best_dev(const void* d_responses, uint32_t count, int n_point
   hipStream_t s = (hipStream_t)stream;
   int rc = cbh::launch_retain_best((const float*)d_responses, count, n_points, depth_limit, (uint32_t*)d_order,
                                    (uint32_t*)d_count, s);
-  if (rc == CBH_OK && !s) {
-    hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-      cbh::set_last_error("orb retain_best sync", e);
-      rc = CBH_E_HIP;
-    }
-  }
-  return rc;
+  if (rc) return rc;
+  if (!stream) CBH_HIP(hipStreamSynchronize(s));
+  return CBH_OK;
 }
 
 int cbh_orb_dev(const void* d_imgs, size_t n, const uint64_t* img_off, const uint32_t* img_w, const uint32_t* img_h,
@@ -1358,14 +1317,9 @@ int cbh_orb_dev(const void* d_imgs, size_t n, const uint64_t* img_off, const uin
   hipStream_t s = (hipStream_t)stream;
   int rc = cbh::launch_orb((const uint8_t*)d_imgs, n, img_off, img_w, img_h, img_row_stride, nfeatures, kp_cap,
                            (cbh_keypoint*)d_kp, (float*)d_kp_after, (uint8_t*)d_desc, (uint32_t*)d_counts, s);
-  if (rc == CBH_OK && !s) {  // the NULL stream is synchronous by contract
-    hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-      cbh::set_last_error("orb sync", e);
-      rc = CBH_E_HIP;
-    }
-  }
-  return rc;
+  if (rc) return rc;
+  if (!stream) CBH_HIP(hipStreamSynchronize(s));  // the NULL stream is synchronous by contract
+  return CBH_OK;
 }
 
 int cbh_orb(const uint8_t* imgs, size_t imgs_bytes, size_t n, const uint64_t* img_off, const uint32_t* img_w,

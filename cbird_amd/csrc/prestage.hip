@@ -480,12 +480,13 @@ int cbh_autocrop_dev(const void* d_gray, size_t n, int w, int h, size_t row_stri
   cbh::DeviceGuard g(device);
   if (!g.ok) return CBH_E_NODEVICE;
   hipStream_t s = (hipStream_t)stream;
-  int* scratch = nullptr;
-  CBH_HIP(cbh::malloc_async((void**)&scratch, n * 2 * (size_t)(w + h) * sizeof(int), s));
+  cbh::Scratch scratch(s);
+  int* runs = nullptr;
+  CBH_HIP(scratch.get(&runs, n * 2 * (size_t)(w + h) * sizeof(int)));
   const int row_tasks = (h + kAcRowsPerWave - 1) / kAcRowsPerWave, col_tasks = 2 * ((w + kAcColChunk - 1) / kAcColChunk);
   for (size_t i0 = 0; i0 < n; i0 += 65535) {
     const size_t m = std::min<size_t>(65535, n - i0);
-    int* sc = scratch + i0 * 2 * (size_t)(w + h);
+    int* sc = runs + i0 * 2 * (size_t)(w + h);
     hipLaunchKernelGGL(k_autocrop_runs, dim3((unsigned)((row_tasks + 3) / 4), (unsigned)m), dim3(256), 0, s,
                        (const unsigned char*)d_gray + i0 * img_stride, w, h, row_stride, img_stride, range, sc, 0);
     hipLaunchKernelGGL(k_autocrop_runs, dim3((unsigned)((col_tasks + 3) / 4), (unsigned)m), dim3(256), 0, s,
@@ -494,7 +495,6 @@ int cbh_autocrop_dev(const void* d_gray, size_t n, int w, int h, size_t row_stri
                        (int*)d_rects + i0 * 4);
   }
   CBH_HIP(hipGetLastError());
-  CBH_HIP(cbh::free_async(scratch, s));
   if (!stream) CBH_HIP(hipStreamSynchronize(s));
   return CBH_OK;
 }
@@ -687,30 +687,19 @@ int cbh_resize_lanczos4_dev(const void* d_src, size_t n, int w, int h, size_t ro
   lanczos4_tab(h, dh, &yofs, &yb);
   int *d_xofs = nullptr, *d_yofs = nullptr;
   short *d_xa = nullptr, *d_yb = nullptr;
-  hipError_t e = hipSuccess;
-  auto up = [&](void** dst, const void* src, size_t bytes) {
-    if (e != hipSuccess) return;
-    if ((e = cbh::malloc_async(dst, bytes, s)) != hipSuccess) return;
-    e = hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, s);
-  };
-  up((void**)&d_xofs, xofs.data(), xofs.size() * sizeof(int));
-  up((void**)&d_yofs, yofs.data(), yofs.size() * sizeof(int));
-  up((void**)&d_xa, xa.data(), xa.size() * sizeof(short));
-  up((void**)&d_yb, yb.data(), yb.size() * sizeof(short));
+  cbh::Scratch scratch(s);
+  hipError_t e = cbh::upload(scratch, &d_xofs, xofs, s);
+  if (e == hipSuccess) e = cbh::upload(scratch, &d_yofs, yofs, s);
+  if (e == hipSuccess) e = cbh::upload(scratch, &d_xa, xa, s);
+  if (e == hipSuccess) e = cbh::upload(scratch, &d_yb, yb, s);
   if (e == hipSuccess) {
     const unsigned gx = (unsigned)std::min<long long>(((long long)dw * dh + 255) / 256, 4096);
     hipLaunchKernelGGL(k_resize_lanczos4, dim3(gx, (unsigned)n), dim3(256), 0, s, (const unsigned char*)d_src, w, h,
                        row_stride, img_stride, dw, dh, d_xofs, d_xa, d_yofs, d_yb, (unsigned char*)d_dst);
     e = hipGetLastError();
   }
-  for (void* p : {(void*)d_xofs, (void*)d_yofs, (void*)d_xa, (void*)d_yb})
-    if (p) (void)cbh::free_async(p, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);  // the tables came from pageable host vectors
-  if (e != hipSuccess) {
-    cbh::set_last_error("resize_lanczos4", e);
-    return e == hipErrorOutOfMemory ? CBH_E_NOMEM : CBH_E_HIP;
-  }
-  return CBH_OK;
+  return e == hipSuccess ? CBH_OK : cbh::fail("resize_lanczos4", e);
 }
 
 /* sizeLongestSide(img, size) for n grey images of one geometry in host memory; out receives n packed

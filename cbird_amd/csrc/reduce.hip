@@ -193,34 +193,26 @@ int launch_fdct_vote(const cbh_match* d_top, const uint32_t* d_counts, const uin
   FdctRun* runs = nullptr;
   unsigned* misc = nullptr;  // [0] = n_runs, [1..] = maxm[n_needles]
   cbh_nmatch* out = nullptr;
-  hipError_t e = cbh::malloc_async((void**)&keys, n * 8, s);
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&runs, n * sizeof(FdctRun), s);
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&misc, (1 + n_needles) * 4, s);
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&out, n * sizeof(cbh_nmatch), s);
-  int rc = CBH_OK;
+  Scratch scratch(s);
+  CBH_HIP(scratch.get(&keys, n * 8));
+  CBH_HIP(scratch.get(&runs, n * sizeof(FdctRun)));
+  CBH_HIP(scratch.get(&misc, (1 + n_needles) * 4));
+  CBH_HIP(scratch.get(&out, n * sizeof(cbh_nmatch)));
+  CBH_HIP(hipMemsetAsync(misc, 0, (1 + n_needles) * 4, s));
+  const unsigned g = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(k_fdct_pairs, dim3(g), dim3(256), 0, s, d_top, d_counts, d_qneedle, (unsigned)nq, k, keys);
+  if (int rc = sort_keys_u64(keys, n, 64, s)) return rc;
+  hipLaunchKernelGGL(k_fdct_runs, dim3(g), dim3(256), 0, s, keys, n, d_needle_id, runs, misc, misc + 1);
+  hipLaunchKernelGGL(k_fdct_score, dim3(g), dim3(256), 0, s, runs, misc, d_needle_id, misc + 1, out);
+  CBH_HIP(hipGetLastError());
   unsigned n_runs = 0;
-  if (e == hipSuccess) e = hipMemsetAsync(misc, 0, (1 + n_needles) * 4, s);
-  if (e == hipSuccess) {
-    const unsigned g = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(k_fdct_pairs, dim3(g), dim3(256), 0, s, d_top, d_counts, d_qneedle, (unsigned)nq, k, keys);
-    rc = sort_keys_u64(keys, n, 64, s);
-    if (!rc) {
-      hipLaunchKernelGGL(k_fdct_runs, dim3(g), dim3(256), 0, s, keys, n, d_needle_id, runs, misc, misc + 1);
-      hipLaunchKernelGGL(k_fdct_score, dim3(g), dim3(256), 0, s, runs, misc, d_needle_id, misc + 1, out);
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipMemcpyAsync(&n_runs, misc, 4, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);
-      if (e == hipSuccess && n_runs) {
-        h_out->resize(n_runs);
-        e = hipMemcpyAsync(h_out->data(), out, (size_t)n_runs * sizeof(cbh_nmatch), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-      }
-    }
+  CBH_HIP(hipMemcpyAsync(&n_runs, misc, 4, hipMemcpyDeviceToHost, s));
+  CBH_HIP(hipStreamSynchronize(s));
+  if (n_runs) {
+    h_out->resize(n_runs);
+    CBH_HIP(hipMemcpyAsync(h_out->data(), out, (size_t)n_runs * sizeof(cbh_nmatch), hipMemcpyDeviceToHost, s));
+    CBH_HIP(hipStreamSynchronize(s));
   }
-  for (void* p : {(void*)keys, (void*)runs, (void*)misc, (void*)out})
-    if (p) (void)cbh::free_async(p, s);
-  if (rc) return rc;
-  CBH_HIP(e);
   return CBH_OK;
 }
 
@@ -236,35 +228,27 @@ int launch_video_reduce(const unsigned* d_off, const unsigned long long* d_seg, 
   uint32_t* vals = nullptr;
   cbh_nvmatch* out = nullptr;
   unsigned* n_out = nullptr;
-  hipError_t e = cbh::malloc_async((void**)&keys, total * 8, s);
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&vals, total * 4, s);
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&out, total * sizeof(cbh_nvmatch), s);
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&n_out, 4, s);
-  if (e == hipSuccess) e = hipMemsetAsync(n_out, 0, 4, s);
-  int rc = CBH_OK;
+  Scratch scratch(s);
+  CBH_HIP(scratch.get(&keys, total * 8));
+  CBH_HIP(scratch.get(&vals, total * 4));
+  CBH_HIP(scratch.get(&out, total * sizeof(cbh_nvmatch)));
+  CBH_HIP(scratch.get(&n_out, 4));
+  CBH_HIP(hipMemsetAsync(n_out, 0, 4, s));
+  const unsigned g = (unsigned)((total + 255) / 256);
+  hipLaunchKernelGGL(k_video_winners, dim3(g), dim3(256), 0, s, d_seg, d_off, (unsigned)nq, d_egroup, d_vmedia, d_qneedle,
+                     d_needle_id, filter_self, keys, vals, total);
+  if (int rc = sort_pairs_u64_u32(keys, vals, total, 64, s)) return rc;
+  hipLaunchKernelGGL(k_video_score, dim3(g), dim3(256), 0, s, keys, vals, total, d_qneedle, d_qframe, d_eframe, d_vmedia,
+                     min_matched, min_near, out, n_out);
+  CBH_HIP(hipGetLastError());
   unsigned n = 0;
-  if (e == hipSuccess) {
-    const unsigned g = (unsigned)((total + 255) / 256);
-    hipLaunchKernelGGL(k_video_winners, dim3(g), dim3(256), 0, s, d_seg, d_off, (unsigned)nq, d_egroup, d_vmedia, d_qneedle,
-                       d_needle_id, filter_self, keys, vals, total);
-    rc = sort_pairs_u64_u32(keys, vals, total, 64, s);
-    if (!rc) {
-      hipLaunchKernelGGL(k_video_score, dim3(g), dim3(256), 0, s, keys, vals, total, d_qneedle, d_qframe, d_eframe,
-                         d_vmedia, min_matched, min_near, out, n_out);
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipMemcpyAsync(&n, n_out, 4, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);
-      if (e == hipSuccess && n) {
-        h_out->resize(n);
-        e = hipMemcpyAsync(h_out->data(), out, (size_t)n * sizeof(cbh_nvmatch), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-      }
-    }
+  CBH_HIP(hipMemcpyAsync(&n, n_out, 4, hipMemcpyDeviceToHost, s));
+  CBH_HIP(hipStreamSynchronize(s));
+  if (n) {
+    h_out->resize(n);
+    CBH_HIP(hipMemcpyAsync(h_out->data(), out, (size_t)n * sizeof(cbh_nvmatch), hipMemcpyDeviceToHost, s));
+    CBH_HIP(hipStreamSynchronize(s));
   }
-  for (void* p : {(void*)keys, (void*)vals, (void*)out, (void*)n_out})
-    if (p) (void)cbh::free_async(p, s);
-  if (rc) return rc;
-  CBH_HIP(e);
   return CBH_OK;
 }
 

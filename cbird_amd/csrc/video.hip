@@ -212,32 +212,24 @@ int reduce_on_device(cbh_vidx* v, const std::vector<uint64_t>& q, const std::vec
   if (total >= (1ull << 32)) return CBH_E_OVERFLOW;
   std::vector<uint32_t> nid(needles.size());
   for (size_t i = 0; i < needles.size(); ++i) nid[i] = needles[i].id;
-  void* scratch = nullptr;
+  char* block = nullptr;
   uint32_t *d_qneedle = nullptr, *d_nid = nullptr;
   int32_t* d_qframe = nullptr;
   const size_t sbytes = topk_scratch_bytes(nq, (size_t)total);
-  hipError_t e = cbh::malloc_async(&scratch, sbytes + 16, s);
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&d_qneedle, nq * 4, s);
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&d_qframe, nq * 4, s);
-  if (e == hipSuccess) e = cbh::malloc_async((void**)&d_nid, nid.size() * 4, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_qneedle, qneedle.data(), nq * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_qframe, qframe.data(), nq * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_nid, nid.data(), nid.size() * 4, hipMemcpyHostToDevice, s);
+  Scratch scratch(s);
+  CBH_HIP(scratch.get(&block, sbytes + 16));
+  CBH_HIP(upload(scratch, &d_qneedle, qneedle, s));
+  CBH_HIP(upload(scratch, &d_qframe, qframe, s));
+  CBH_HIP(upload(scratch, &d_nid, nid, s));
   std::vector<cbh_nvmatch> flat;
-  if (e == hipSuccess) {
-    const unsigned* d_off = nullptr;
-    const unsigned long long* d_seg = nullptr;
-    unsigned* d_status = (unsigned*)((char*)scratch + sbytes);
-    rc = topk_scratch_init(scratch, nq, s);
-    if (!rc) rc = launch_records_group(ws->d_total, 1, 0, (size_t)total, nq, d_status, scratch, &d_off, &d_seg, s);
-    if (!rc)
-      rc = launch_video_reduce(d_off, d_seg, (size_t)total, nq, v->d_egroup, v->d_eframe, v->d_vmedia, d_qneedle, d_qframe,
-                               d_nid, filter_self, min_matched, min_near, &flat, s);
-  }
-  for (void* p : {scratch, (void*)d_qneedle, (void*)d_qframe, (void*)d_nid})
-    if (p) (void)cbh::free_async(p, s);
-  CBH_HIP(e);
-  if (rc) return rc;
+  const unsigned* d_off = nullptr;
+  const unsigned long long* d_seg = nullptr;
+  unsigned* d_status = (unsigned*)(block + sbytes);
+  if ((rc = topk_scratch_init(block, nq, s))) return rc;
+  if ((rc = launch_records_group(ws->d_total, 1, 0, (size_t)total, nq, d_status, block, &d_off, &d_seg, s))) return rc;
+  if ((rc = launch_video_reduce(d_off, d_seg, (size_t)total, nq, v->d_egroup, v->d_eframe, v->d_vmedia, d_qneedle, d_qframe,
+                                d_nid, filter_self, min_matched, min_near, &flat, s)))
+    return rc;
   std::sort(flat.begin(), flat.end(), [](const cbh_nvmatch& a, const cbh_nvmatch& b) {
     return a.needle != b.needle ? a.needle < b.needle : a.m.id < b.m.id;  // std::map order: ascending mediaId
   });

@@ -274,13 +274,61 @@ def _cases(gpu):
         return list(vi.frames), [int(x) for x in vi.hashes]
 
     cases["video_indexer"] = vindexer
+
+    # launchers that take their scratch per call and that no case above reaches
+    (orb_kp, _, _), = orb.orb([scene], 150)
+    assert len(orb_kp) > 20
+
+    def orb_describe():
+        (k, d), = orb.make_keypoint_descriptors([scene], [orb_kp])
+        return np.asarray(k), np.asarray(d)
+
+    cases["orb_describe"] = orb_describe
+
+    # one 32 x 32 rectangle, one with a side below 32 (bilinear tables), one that is no multiple of 32 (area tables)
+    rects = np.array([[5, 7, 32, 32], [40, 50, 20, 45], [100, 60, 75, 50]], np.int32)
+    r_off, r_w, r_h = np.zeros(1, np.uint64), np.array([400], np.uint32), np.array([300], np.uint32)
+    r_first = np.array([0, len(rects)], np.uint32)
+
+    def dcthash_rects():
+        from cbird_amd import _lib
+
+        out = np.zeros(len(rects), np.uint64)
+        _lib.check(_lib.lib().cbh_dcthash_rects(photos[0].ctypes.data, photos[0].size, 1, r_off.ctypes.data, r_w.ctypes.data,
+                                                r_h.ctypes.data, r_w.ctypes.data, rects.ctypes.data, r_first.ctypes.data, 0,
+                                                out.ctypes.data, None, 0), "rects")
+        return out
+
+    cases["dcthash_rects"] = dcthash_rects
+    cases["resize_lanczos4"] = lambda: hashing.size_longest_side(photos[:2], 100)
+
+    import torch
+    from cbird_amd.dist import HipOps
+    from test_topk import make_records
+
+    ops = HipOps(0)
+    recs = make_records(rng, 200, 5000, dup_frac=0.05)
+
+    def sort_records():
+        r = torch.from_numpy(recs.view(np.int64).copy()).cuda()
+        ops.sort_records(r, len(recs), 200)
+        return r.cpu().numpy()
+
+    def records_topk():
+        blocks = torch.from_numpy(np.concatenate([[np.uint64(len(recs))], recs]).view(np.int64)).cuda()
+        status = torch.zeros(1, dtype=torch.int32, device="cuda")
+        i, s, c = ops.topk(blocks, 1, 0, len(recs), 200, 6, status)
+        return i.cpu().numpy(), s.cpu().numpy(), c.cpu().numpy(), int(status.item())
+
+    cases["sort_records"] = sort_records
+    cases["records_topk"] = records_topk
     return cases
 
 
 _CASE_NAMES = ["dcthash_256", "dcthash_general", "process_images", "idx64_mfma_full", "idx64_mfma_pre", "idx64_valu",
                "idx64_sharded", "idx64_sharded_regrow", "search_index_batch", "fdct_find_batch", "video_find_batch", "idx256_knn_small",
                "idx256_knn_batch", "idx256_radius", "idx256_sharded", "idx256_sharded_regrow", "color_find_batch", "orb", "color_descriptor_create", "keypoint_hashes",
-               "video_indexer"]
+               "video_indexer", "orb_describe", "dcthash_rects", "resize_lanczos4", "sort_records", "records_topk"]
 
 
 @pytest.fixture(scope="module")
