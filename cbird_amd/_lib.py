@@ -68,6 +68,14 @@ class cbh_quality_detail(C.Structure):
                 ("qh", C.c_int32), ("score", C.c_int32)]
 
 
+class cbh_demosaic_params(C.Structure):
+    _fields_ = [("clip_pct", C.c_float), ("pre_blur", C.c_int32), ("canny1", C.c_int32), ("canny2", C.c_int32),
+                ("post_blur", C.c_int32), ("h_margin", C.c_int32), ("v_margin", C.c_int32), ("hough_rho", C.c_float),
+                ("hough_theta", C.c_float), ("hough_thresh_factor", C.c_float), ("min_grid_spacing", C.c_int32),
+                ("grid_tolerance", C.c_int32), ("crop_margin", C.c_int32), ("max_aspect", C.c_float),
+                ("min_aspect", C.c_float)]
+
+
 class cbh_match(C.Structure):
     _fields_ = [("id", C.c_uint32), ("score", C.c_int32)]
 
@@ -112,6 +120,13 @@ _SIGS = {
                                          _vp, _vp, _vp, C.c_int, _vp]),
     "cbh_align_temporal": (C.c_int, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int,
                                      C.c_int, _vp, _vp, _vp, C.c_int]),
+    "cbh_demosaic_default_params": (None, [_vp]),
+    "cbh_grid_select": (C.c_int, [_vp, _sz, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "cbh_grid_rects": (C.c_int, [_vp, _sz, _vp, _sz, C.c_int, C.c_int, C.c_int, _vp, _sz, _vp]),
+    "cbh_edge_maps_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "cbh_grid_lines_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "cbh_demosaic_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _sz, _vp, C.c_int, _vp]),
+    "cbh_demosaic": (C.c_int, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _sz, _vp, C.c_int]),
     "cbh_index_images": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, C.c_int]),
     "cbh_index_images_views": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,

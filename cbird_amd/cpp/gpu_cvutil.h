@@ -15,6 +15,8 @@
 //                                                                                 src/gui/mediagrouplistwidget.cpp:106-208
 //   void VideoCompareWidget::alignSpatially() / alignTemporally()   (decoded frames, one pair, a group or a clip)
 //                                                                                 src/gui/videocomparewidget.cpp:590-680
+//   void demosaicHough(const cv::Mat& cvImg, QVector<QRect>& rects, const DemosaicParams& params = {})   (one sheet or a batch)
+//                                                                                 src/cvutil.cpp:1445-1688
 //
 // Same arguments and effects as the originals for 8-bit single-channel images (what Scanner::processImage passes
 // after grayscale(), src/scanner.cpp:859,876-889): the hash is returned, and with inPlace = true the blurred pixels
@@ -629,6 +631,59 @@ inline cbh_align_temporal_result gpuAlignTemporal(const std::vector<cv::Mat>& le
                                     w[1].data(), h[1].data(), step[1].data(), cn[1], start, &res, nullptr, nullptr, hashDevice());
   if (rc) qFatal("gpuAlignTemporal: %s (%s)", cbh_strerror(rc), cbh_last_error());
   return res;
+}
+
+// void demosaicHough(const cv::Mat& cvImg, QVector<QRect>& rects, const DemosaicParams& params, QList<QImage>*)
+//                                                                                 src/cvutil.cpp:1445-1688
+// for a batch of decoded contact sheets (8-bit cv::Mat of 1, 3 or 4 channels): rects[i] receives the tiles of sheets[i]
+// in the reference's order and replaces what it held.  (The reference appends to the caller's vector, counts what was
+// already there in its `rects.count() < 2` test and then assigns the subdivided list; for the empty vector that
+// -select-grid passes the two are the same.)  Templates, so that this header needs neither QRect
+// nor DemosaicParams until a caller names them: Params is cbird's DemosaicParams (borderThresh acts nowhere in the
+// reference and is not passed on), Rects a QVector<QRect>.  Blur kernels other than 0 and 3, houghRho other than 0.5
+// and houghTheta other than 45 are not implemented (include/cbird_hip.h); the outImages drawings are not produced.
+template <class Params, class Rects>
+inline void gpuDemosaicHough(const std::vector<cv::Mat>& sheets, std::vector<Rects>& rects, const Params& params) {
+  rects.assign(sheets.size(), Rects());
+  for (const cv::Mat& m : sheets)
+    if (!detail::is8bit(m)) qFatal("gpuDemosaicHough: expected non-empty 8-bit images of 1, 3 or 4 channels");
+  cbh_demosaic_params p;
+  cbh_demosaic_default_params(&p);
+  p.clip_pct = float(params.clipHistogramPercent), p.pre_blur = params.preBlurKernel, p.canny1 = params.cannyThresh1;
+  p.canny2 = params.cannyThresh2, p.post_blur = params.postBlurKernel, p.h_margin = params.hMargin, p.v_margin = params.vMargin;
+  p.hough_rho = params.houghRho, p.hough_theta = params.houghTheta, p.hough_thresh_factor = params.houghThreshFactor;
+  p.min_grid_spacing = params.minGridSpacing, p.grid_tolerance = params.gridTolerance, p.crop_margin = params.cropMargin;
+  p.max_aspect = params.maxAspectRatio, p.min_aspect = params.minAspectRatio;
+  for (int cn : {1, 3, 4}) {
+    std::vector<size_t> which;
+    for (size_t i = 0; i < sheets.size(); ++i)
+      if (sheets[i].channels() == cn) which.push_back(i);
+    if (which.empty()) continue;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> w, h, step, first(which.size() + 1);
+    std::vector<uint8_t> buf;
+    detail::packMats(sheets, which, cn, buf, off, w, h, step);
+    std::vector<int32_t> quads(4 * 64 * which.size());
+    int rc = cbh_demosaic(buf.data(), buf.size(), which.size(), off.data(), w.data(), h.data(), step.data(), cn, &p,
+                          quads.data(), quads.size() / 4, first.data(), hashDevice());
+    if (rc == CBH_E_OVERFLOW) {  // first[n] is the count it takes
+      quads.resize(4 * size_t(first.back()));
+      rc = cbh_demosaic(buf.data(), buf.size(), which.size(), off.data(), w.data(), h.data(), step.data(), cn, &p,
+                        quads.data(), quads.size() / 4, first.data(), hashDevice());
+    }
+    if (rc) qFatal("gpuDemosaicHough: %s (%s)", cbh_strerror(rc), cbh_last_error());
+    for (size_t k = 0; k < which.size(); ++k)
+      for (uint32_t r = first[k]; r < first[k + 1]; ++r)
+        rects[which[k]].append({quads[4 * r], quads[4 * r + 1], quads[4 * r + 2], quads[4 * r + 3]});
+  }
+}
+
+// one sheet, as -select-grid calls it (src/main.cpp:1320)
+template <class Params, class Rects>
+inline void gpuDemosaicHough(const cv::Mat& cvImg, Rects& rects, const Params& params) {
+  std::vector<Rects> all(1);
+  gpuDemosaicHough(std::vector<cv::Mat>(1, cvImg), all, params);
+  rects = all[0];
 }
 
 }  // namespace cbird_gpu

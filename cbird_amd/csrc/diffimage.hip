@@ -26,6 +26,7 @@
 #include "cbh_runs.h"
 #include "cbh_staging.h"
 #include "gray_px.h"
+#include "stretch_px.h"
 
 namespace cbh {
 namespace {
@@ -199,15 +200,7 @@ __global__ __launch_bounds__(256) void k_diff_tables(const unsigned* __restrict_
   }
   __syncthreads();
   const int lo = sh[0], hi = sh[1];
-  unsigned t = s;
-  if (lo < hi) {
-    const float alpha = 255.0f / (float)(hi - lo);
-    const float beta = (float)(-lo) * alpha;
-    const float prod = (float)s * alpha;
-    const float r = rintf(prod + beta);
-    t = r <= 0.0f ? 0u : r >= 255.0f ? 255u : (unsigned)r;
-  }
-  tables[(size_t)v * 256 + s] = (unsigned char)t;
+  tables[(size_t)v * 256 + s] = (unsigned char)cbh_stretch_px(lo, hi, s);
 }
 
 // every byte of the images' rows through the view's table (alpha included: the reference's restore is commented out);

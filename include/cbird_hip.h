@@ -368,6 +368,90 @@ int cbh_align_temporal(const uint8_t* left, size_t left_bytes, size_t n_left, co
                        cbh_align_temporal_result* result, uint32_t* means /* NULL or P */,
                        uint32_t* cells /* NULL or P * W */, int device);
 
+/* ---- demosaicHough (src/cvutil.cpp:1445-1688; -select-grid, src/main.cpp:1310-1332): contact sheets into tiles ------------
+ * cbird_amd/csrc/demosaic.hip; tests/demosaic_rules.py is the numpy model the device is held to, bit for bit.  Images as
+ * above: the img_off / img_w / img_h / img_row_stride host tables, channels 1 / 3 = BGR / 4 = BGRA, one channel count per
+ * call, sides 1 .. 32767, at most 2^20 images per call.  The working planes take two bytes per pixel of the batch.
+ *
+ * EXACT restatements of the reference's own arithmetic: the thresholds, the angle test, selectLines, the rectangles and the
+ * subdivision.  UNPINNED, restated as recalled from OpenCV 2.4.13 without the library: GaussianBlur, Canny, HoughLines
+ * (and convertTo inside step 1, as for cbh_auto_contrast).  Per image:
+ *  1. adjusted = brightnessAndContrastAuto(img, clip_pct) (cbh_auto_contrast's rule), g = the grey view of adjusted (a
+ *     one-channel image itself, cvtColor's fixed-point weights otherwise, alpha ignored).
+ *  2. pre_blur == 3: g through the 3 x 3 Gaussian on bytes, weights (1,2,1) x (1,2,1), border REFLECT_101 (a 1-pixel side
+ *     reflects onto itself): out = (S + 8) >> 4, S the weighted sum of the nine bytes.  0 skips it; other values are
+ *     CBH_E_UNSUPPORTED.  UNPINNED.
+ *  3. Canny(g, canny1, canny2), aperture 3, L1 norm: low = min, high = max of the two.  dx, dy = the 3 x 3 Sobel as
+ *     integers, border REPLICATE; m = |dx| + |dy|, 0 outside the image.  A pixel is a CANDIDATE when m > low and it passes
+ *     the suppression: with x = |dx|, y = |dy| << 15, t22 = x * 13573, t67 = t22 + (x << 16): y < t22 needs m > m(left)
+ *     && m >= m(right); otherwise y > t67 needs m > m(up) && m >= m(down); otherwise, with s = ((dx ^ dy) < 0) ? -1 : 1,
+ *     m > m(up, x - s) && m > m(down, x + s).  A candidate with m > high is STRONG.  edges = 255 on every candidate that is
+ *     8-connected, through candidates, to a strong pixel, 0 elsewhere.  UNPINNED.
+ *  4. post_blur == 3: the same Gaussian on edges.
+ *  5. HoughLines(edges, rho 0.5, theta 45 degrees, threshold), the standard transform; other rho / theta are
+ *     CBH_E_UNSUPPORTED.  numrho = 4 (w + h) + 2; theta = float(45 pi / 180), the four angles accumulated in float32,
+ *     tabCos[n] = float(cos(double(ang_n)) * 2), tabSin likewise; a non-zero pixel (row i, column j) votes at r =
+ *     rint_half_even(float(j * tabCos[n]) + float(i * tabSin[n])) + (numrho - 1) / 2, float32 and unfused.  Bin (n, r) is a
+ *     line when acc > threshold, acc > acc(n, r-1), acc >= acc(n, r+1), acc > acc(n-1, r), acc >= acc(n+1, r), missing
+ *     neighbours counting 0; its position is int(rho), rho = (float(r) - (numrho - 1) * 0.5f) * 0.5f.  The reference's angle
+ *     test keeps n = 2 as horizontal (threshold int(float(w) * factor)) and n = 0 as vertical (int(float(h) * factor)):
+ *     a row i with enough non-zero pixels gives y = i - 1 (0 for row 0), likewise columns; the diagonals only take part
+ *     as neighbours.  y is kept when h_margin <= y < h - h_margin, x when v_margin <= x < w - v_margin.  factor =
+ *     hough_thresh_factor for an image, 0.95f for every subdivision.  UNPINNED.
+ *  6. selectLines (:1552-1617) on the positions with 0 and the side appended, sorted, duplicates kept; the loops as they
+ *     stand, `s > img.cols` bounding both directions included.  Host code.
+ *  7. An empty grid becomes {0, side}.  Fewer than 3 lines both ways: one rectangle, the whole image.  Otherwise the
+ *     cells row by row, each shrunk by crop_margin on every side (a side may come out below 1, as in the reference).
+ *  8. With at least 2 rectangles, each whose float(w) / float(h) is above max_aspect or below min_aspect goes through
+ *     steps 1-8 again as an image of its own (a view of the ORIGINAL pixels, its own histogram and borders) and is
+ *     replaced by the answer, offset by its origin.  The reference would assert or throw on a rectangle with a side below
+ *     1 or one that leaves its image, and would recurse without end on one that is its whole image; this library does
+ *     not subdivide any of them.  One batched pass per level of subdivision.
+ * crop_margin < 0 and min_grid_spacing < 1 are CBH_E_INVAL: with them the cells of step 7 leave their image, or
+ * selectLines pairs a line with itself.  The other integer fields take any value. */
+typedef struct cbh_demosaic_params {
+  float clip_pct;                                        /* clipHistogramPercent 10 */
+  int32_t pre_blur, canny1, canny2, post_blur;           /* 3, 50, 0, 3 */
+  int32_t h_margin, v_margin;                            /* 0, 0 */
+  float hough_rho, hough_theta, hough_thresh_factor;     /* 0.5, 45, 0.8 */
+  int32_t min_grid_spacing, grid_tolerance, crop_margin; /* 96, 4, 2 */
+  float max_aspect, min_aspect;                          /* 2.5, 0.5 */
+} cbh_demosaic_params;
+void cbh_demosaic_default_params(cbh_demosaic_params* p);
+/* Step 6 on one list, host code, no device: lines = n_lines positions in 0 .. side, in any order; 0 and side are appended.
+ * cols = the image's width for both directions.  grid: room for n_lines + 2 entries; *n_grid = how many were written. */
+int cbh_grid_select(const int32_t* lines, size_t n_lines, int side, int cols, int min_grid_spacing, int grid_tolerance,
+                    int32_t* grid, size_t* n_grid);
+/* Step 7, host code, no device: rects = (x, y, w, h) quadruples, row by row.  *n_rects = how many there are;
+ * CBH_E_OVERFLOW with nothing written when that is above rects_cap. */
+int cbh_grid_rects(const int32_t* hgrid, size_t n_h, const int32_t* vgrid, size_t n_v, int w, int h, int crop_margin,
+                   int32_t* rects, size_t rects_cap, size_t* n_rects);
+/* Steps 1-4 of every image, no subdivision.  d_edges: the edge maps, image i packed (rows of img_w[i] bytes) behind
+ * image i - 1; d_classes: NULL, or in the same layout the classes before the hysteresis (0 none, 1 candidate, 2 strong);
+ * passes: NULL, or a host word that receives the number of hysteresis launches.  Synchronises the stream. */
+int cbh_edge_maps_dev(const void* d_imgs, size_t n, const uint64_t* img_off, const uint32_t* img_w, const uint32_t* img_h,
+                      const uint32_t* img_row_stride, int channels, const cbh_demosaic_params* params, void* d_edges,
+                      void* d_classes, uint32_t* passes, int device, void* stream);
+/* Steps 1-5 of every image with factor = hough_thresh_factor: the positions in host memory, ascending, duplicates kept;
+ * image i owns hor[hor_first[i] .. hor_first[i+1]) and ver likewise (n + 1 entries each).  hor needs room for the sum of
+ * img_h entries, ver for the sum of img_w. */
+int cbh_grid_lines_dev(const void* d_imgs, size_t n, const uint64_t* img_off, const uint32_t* img_w, const uint32_t* img_h,
+                       const uint32_t* img_row_stride, int channels, const cbh_demosaic_params* params, int32_t* hor,
+                       uint32_t* hor_first, int32_t* ver, uint32_t* ver_first, int device, void* stream);
+/* demosaicHough of every image.  rects (host memory) = (x, y, w, h) int32 quadruples in the reference's order, image i
+ * owns rects[4 * rect_first[i] .. 4 * rect_first[i+1]) as cbh_dcthash_rects takes them; rect_first has n + 1 entries.
+ * CBH_E_OVERFLOW with rect_first complete and nothing written to rects when rect_first[n] > rects_cap.  n == 0 returns
+ * CBH_OK.  CBH_E_INVAL (with a cbh_last_error text): a side of 0 or above 32767, rows shorter than their pixels, a channel
+ * count other than 1 / 3 / 4, n above 2^20, clip_pct negative or not finite, crop_margin negative, min_grid_spacing below 1.
+ * Synchronises the stream after every hysteresis launch and at the end. */
+int cbh_demosaic_dev(const void* d_imgs, size_t n, const uint64_t* img_off, const uint32_t* img_w, const uint32_t* img_h,
+                     const uint32_t* img_row_stride, int channels, const cbh_demosaic_params* params, int32_t* rects,
+                     size_t rects_cap, uint32_t* rect_first, int device, void* stream);
+/* the same from host memory */
+int cbh_demosaic(const uint8_t* imgs, size_t imgs_bytes, size_t n, const uint64_t* img_off, const uint32_t* img_w,
+                 const uint32_t* img_h, const uint32_t* img_row_stride, int channels, const cbh_demosaic_params* params,
+                 int32_t* rects, size_t rects_cap, uint32_t* rect_first, int device);
+
 /* ---- the steps in front of dctHash64 in Scanner::processImage (src/scanner.cpp:852-862) -------------------
  * grayscale(): cv::cvtColor(BGR2GRAY/BGRA2GRAY) on 8-bit data (src/cvutil.cpp:1265-1283); d_gray is packed
  * n*w*h bytes. */
