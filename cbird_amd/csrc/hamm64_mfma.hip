@@ -122,6 +122,19 @@ __device__ __forceinline__ void wave_order() {
 __device__ __forceinline__ uint32_t wave_rank(uint64_t m, uint32_t base = 0u) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, base));
 }
+// inclusive prefix sum of v over the 64 lanes (all active): six v_add_u32 with a DPP operand -- four shifts inside each
+// row of 16 lanes, then the last lane of rows 0 | 2 onto rows 1 | 3 and lane 31 onto rows 2 and 3.  (DPP controls
+// row_shr:n = 0x110 + n, row_bcast:15 = 0x142, row_bcast:31 = 0x143; lanes that a shift or a row mask leaves without a
+// source add the `old` operand, 0.)
+__device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
+  return v;
+}
 // C/D layout of the 32x32 MFMA: column = lane & 31 -> needle, accumulator register g of `lane` -> this haystack row of
 // the tile.  Register 16 t + g of a group of tiles counts on into tile t: the result gains 32 t.
 __device__ __forceinline__ uint32_t cd_row(uint32_t g, uint32_t lane) { return (g & 3u) + 8u * (g >> 2) + 4u * (lane >> 5); }
@@ -242,9 +255,9 @@ constexpr uint32_t kFieldOnes = 1u + (1u << 6) + (1u << 12) + (1u << 18);  // a 
 //   * when 64 descriptors are pending at the end of a step (and at the end of the wave's needle chunk) the wave drains
 //     the list: the descriptors become work items, one per flagged chain and candidate field, and the items are worked
 //     off 64 at a time, one per lane -- its needle from global memory (64 lanes' loads in flight together), then ALL 17
-//     or 15 haystack rows of its chain from LDS against it, popcount on 64 bits; real matches go to the wave's record
-//     buffer.  Every (row, needle) pair belongs to one (lane, group, step), one chain and one field, so a match is
-//     emitted once.
+//     or 15 haystack rows of its chain from LDS against it on their 32-bit fold, three instructions a row, and the rows
+//     that survive on all 64 bits; real matches go to the wave's record buffer.  Every (row, needle) pair belongs to
+//     one (lane, group, step), one chain and one field, so a match is emitted once.
 // (An immediate scalar re-check -- s_load + s_bcnt1 per candidate -- was built first: no VALU at all, but every event
 //  stalled the wave for a scalar-cache miss, 15.9 ms at threshold 6; NOTES 11.)
 // The wave's words: pending list (2 words per descriptor) | record buffer | item list (1 word per item).
@@ -452,23 +465,43 @@ __device__ __forceinline__ void prefilter_body(CBH_MFMA_PARAMS) {
     // all lanes' loads in flight together; a null needle (and one past nq: the padding, the partner of a lone last pair)
     // matches nothing
     const uint64_t nv = live && qi < hp.nq ? hp.q[qi] : 0;
-    const uint32_t qlo = (uint32_t)nv, qhi = (uint32_t)(nv >> 32);
-    // chain 0 = registers 0..16 (quads 0..3 and the first of quad 4), chain 1 = 17..31 (the rest of quad 4, quads 5..7)
-    const uint32_t rows = nv == 0 ? 0u : ch ? 0xfffe0000u : 0x0001ffffu;
-    const uint2* hq = s_hay + row0 + cd_row(16u * ch, L);
-    uint32_t hit = 0;
-#pragma unroll 1
-    for (uint32_t i = 0; i < 5u; ++i) {
-      const uint32_t qd = 4u * ch + i;  // chain 1 at i = 4: quad 8, masked below; clamped to stay inside s_hay
-      const uint4* h4 = reinterpret_cast<const uint4*>(hq + 8u * min(i, 4u - ch));
-      const uint4 x = h4[0], y = h4[1];
-      const uint32_t d0 = __popc(x.x ^ qlo) + __popc(x.y ^ qhi), d1 = __popc(x.z ^ qlo) + __popc(x.w ^ qhi);
-      const uint32_t d2 = __popc(y.x ^ qlo) + __popc(y.y ^ qhi), d3 = __popc(y.z ^ qlo) + __popc(y.w ^ qhi);
-      const uint32_t m4 = (d0 < hp.thresh ? 1u : 0u) | (d1 < hp.thresh ? 2u : 0u) | (d2 < hp.thresh ? 4u : 0u) |
-                          (d3 < hp.thresh ? 8u : 0u);
-      hit |= qd < 8u ? m4 << (4u * qd) : 0u;
+    const uint32_t qlo = (uint32_t)nv, qhi = (uint32_t)(nv >> 32), qfold = qlo ^ qhi;
+    // Bit k of the chain's row masks is register 16 ch + k of the group.  Chain 0 = registers 0..16 (quads 0..3 and the
+    // first of quad 4): 17 bits; chain 1 = 17..31 (the rest of quad 4, quads 5..7): bits 1..15.
+    const uint32_t rows = nv == 0 ? 0u : ch ? 0x0000fffeu : 0x0001ffffu;
+    const uint2* hq = s_hay + row0 + cd_row(16u * ch, L);  // quad i of the chain: hq[8 i .. 8 i + 3]
+    // First the FOLD of every row, all 64 bits only for the survivors: popc(fold(row) ^ fold(needle)) <= hamm64(row,
+    // needle) whichever word raised the flag, and all but about one row of a flagged chain differ from the needle in
+    // about 16 of the 32 fold bits.  Three instructions per row: the three-input xor, v_bcnt_u32_b32 onto 2^31 - thresh
+    // (bit 31 of the sum <=> popc >= thresh) and v_alignbit_b32, which shifts that bit into the mask from below -- rows
+    // go in from the last to the first, so row k ends in bit k.
+    const uint32_t far0 = 0x80000000u - hp.thresh;
+    uint32_t far = 0;  // bit k: row k is out on its fold alone
+    auto shift_in = [&](uint32_t lo, uint32_t hi) __attribute__((always_inline)) {
+      // (the builtin: written as lo ^ hi ^ qfold the compiler emits two v_xor_b32; 0x96 is the truth table of a ^ b ^ c)
+      far = __builtin_amdgcn_alignbit(far, (uint32_t)__popc(__builtin_amdgcn_bitop3_b32(lo, hi, qfold, 0x96)) + far0, 31u);
+    };
+    {  // register 16, chain 0's seventeenth row; chain 1 reads its row 0 in that place, which `rows` leaves out
+      const uint2 h = hq[ch ? 0u : 32u];
+      shift_in(h.x, h.y);
     }
-    hit &= rows;
+#pragma unroll
+    for (int i = 3; i >= 0; --i) {
+      const uint4* h4 = reinterpret_cast<const uint4*>(hq + 8 * i);
+      const uint4 x = h4[0], y = h4[1];
+      shift_in(y.z, y.w);
+      shift_in(y.x, y.y);
+      shift_in(x.z, x.w);
+      shift_in(x.x, x.y);
+    }
+    // the survivors, lane by lane: a flagged chain usually has one, a carried chain's unflagged fields none
+    uint32_t hit = 0;
+    for (uint32_t sv = ~far & rows; sv != 0; sv &= sv - 1u) {
+      const uint32_t k = (uint32_t)__builtin_ctz(sv);
+      const uint2 hv = hq[k + (k & 0x1cu)];  // 8 (k >> 2) + (k & 3)
+      if (__popc(hv.x ^ qlo) + __popc(hv.y ^ qhi) < hp.thresh) hit |= 1u << k;
+    }
+    hit <<= 16u * ch;  // as registers of the group
     // a needle can match several rows of a chain (duplicates): one record per lane and round; the loop is uniform -- the
     // record buffer ballots
     while (__builtin_amdgcn_ballot_w64(hit != 0) != 0) {
@@ -490,21 +523,22 @@ __device__ __forceinline__ void prefilter_body(CBH_MFMA_PARAMS) {
         // candidates: bit 4 c + f = field f in the rows of chain c (flag bits of chain c at 5 + c, 11 + c, 17 + c,
         // 23 + c).  A carry into the exponent (top field flagged) leaves the lower fields of that register unreadable,
         // and the OR cannot say which register it was: all four fields are candidates in that chain's rows.
+        // (the four flags, six bits apart, brought together by ONE 24-bit multiply: 1 + 2^5 + 2^10 + 2^15 lands them on
+        //  bits 15..18 and every other partial product on a bit of its own outside those, so nothing carries)
         uint32_t cm = 0;
 #pragma unroll
         for (uint32_t c = 0; c < 2; ++c) {
-          const uint32_t w = e.x >> c;
-          cm |= (((w >> 23) & 1u) ? 0xfu : (((w >> 5) & 1u) | (((w >> 11) & 1u) << 1) | (((w >> 17) & 1u) << 2))) << (4u * c);
+          const uint32_t nb = ((((e.x >> (5u + c)) & 0x41041u) * 0x8421u) >> 15) & 0xfu;
+          cm |= (nb > 7u ? 0xfu : nb) << (4u * c);
         }
         if (k0 + lane >= npend) cm = 0;
-        // item = {lane | group | step} << 3 | chain << 2 | field, listed bit by bit of cm: a ballot and an mbcnt each
-#pragma unroll
-        for (uint32_t b = 0; b < 8; ++b) {
-          const bool on = ((cm >> b) & 1u) != 0;
-          const uint64_t m = __builtin_amdgcn_ballot_w64(on);
-          if (on) s_item[wave_rank(m, nitem)] = (e.y << 3) | b;
-          nitem += (uint32_t)__popcll(m);
-        }
+        // item = {lane | group | step} << 3 | chain << 2 | field.  A lane lists its own descriptor's items, one behind
+        // the other from where the lanes below it end: one prefix sum of the per-lane counts for the wave, then a loop
+        // over the lane's set bits (one turn for most lanes, four behind a carry).
+        const uint32_t cnt = (uint32_t)__popc(cm), upto = wave_prefix_sum(cnt);
+        uint32_t* dst = s_item + nitem + (upto - cnt);
+        for (const uint32_t item0 = e.y << 3; cm != 0; cm &= cm - 1u) *dst++ = item0 | (uint32_t)__builtin_ctz(cm);
+        nitem += (uint32_t)__builtin_amdgcn_readlane((int)upto, 63);
         k0 += 64u;
         wave_order();
         continue;

@@ -341,16 +341,18 @@ constexpr size_t kMfmaMinN = 4096;
 // TRUE match (a flagged group goes through three passes of sixteen ballots, 2.7e5 ms per unit of r_true against the
 // prefilter's 0.7e5): where the candidates are mostly true matches -- a dense cluster of near-identical hashes -- the
 // prefilter wins again, at any rate.  Measured per 10^12 pairs (tools/ab/adaptive_ab.py, profiles/r07_adaptive_ab_*.jsonl):
-//   T_pre = 8.55 ms + 1.3e4 ms x r_cand  (8.8 / 9.0 / 9.7 / 12.1 ms at thresholds 4..7 of image hashes; the slope was 2.4e4
-//   while the drain took one descriptor per lane instead of one candidate field, NOTES 23 -- re-fitted at threshold 7 of
-//   profiles/r09_lib_ab_A.json; the true-match weights below are round 7's),
+//   T_pre = 8.55 ms + 1.0e4 ms x r_cand  (8.8 / 8.9 / 9.5 / 11.3 ms at thresholds 4..7 of image hashes; the slope was 2.4e4
+//   while the drain took one descriptor per lane instead of one candidate field, NOTES 23, and 1.3e4 while it walked a
+//   chain's rows on all 64 bits instead of on their fold first -- re-fitted at threshold 7 of profiles/r12_lib_ab.json,
+//   (11.315 - 8.55) / 2.7e-4, with the floor held; the true-match weights below are round 7's),
 //   T_full = 15.75 ms + 2.7e5 ms x r_true.
 // The probe counts both rates on a sample of the launch's pairs -- a few microseconds and one host round trip, against
 // launches of milliseconds -- and the prefilter is taken while
 //   r_cand - kTrueWeight x r_true <= "scan_pre_rate_e9" x 1e-9      (3.0e-4: where the prefilter tied with the three-field
-//   kernel at the old slope, kTrueWeight = (2.7e5 - 0.7e5) / 2.4e4; at the new one it reaches 12.5 ms there, which is
-//   where it ties with the 48-bit prefilter below -- the kernel that now takes the launches beyond it),
-// which puts threshold 7 of unrelated hashes on the prefilter (12.1 ms against 13.9-17.0) and leaves 8 to the others.  Launches too small to pay for the round trip, and a probe that cannot run, take the fixed rule
+//   kernel at the slope of 2.4e4, kTrueWeight = (2.7e5 - 0.7e5) / 2.4e4; at today's it reaches 11.6 ms there, 2.4 ms
+//   short of the 48-bit prefilter below -- the kernel that takes the launches beyond it; the knob keeps its value, no
+//   data set between the two was measured),
+// which puts threshold 7 of unrelated hashes on the prefilter (11.3 ms against 13.8-17.0) and leaves 8 to the others.  Launches too small to pay for the round trip, and a probe that cannot run, take the fixed rule
 // (thresholds <= 6: at 7 the prefilter's margin is 7 % on unrelated hashes and gone on anything denser).
 //
 // The 48-bit prefilter (PRE48: 16 folds + 32 plain bits, three MFMAs per four needle tiles = 3/4 of the three-field
@@ -375,15 +377,17 @@ constexpr size_t kMfmaMinN = 4096;
 // under it.  Its candidates are the pairs whose fold16 distance is < t, at the rate of uniform 16-bit words on unrelated
 // hashes: 1.5e-5 per pair at t = 1, 2.6e-4 at 2, 2.1e-3 at 3 -- the probe counts that rate r16 in the same sample -- and a
 // candidate costs it what it costs the 32-bit prefilter (the events, the drain and the re-check are the same code):
-//   T_16 = 5.85 + 1.3e4 x r16 + 0.7e5 x r_true
+//   T_16 = 5.85 + 1.0e4 x r16 + 0.7e5 x r_true
 // (6.09 ms per 10^12 pairs at threshold 1 of image hashes, r16 = 1.8e-5, against the 32-bit prefilter's 8.78 on the same
 // box, profiles/r10_lib_ab.json; the issue model 24 M + 4 V gave 6.2 + 0.24).
 // It is taken where T_16 < kPre16Margin x T_pre, at thresholds <= 8 (its bias 24 + t): threshold 1 of unrelated hashes;
-// at 2 the candidates cost 3.4 ms, more than the kernel saves.  "scan_pre16": -1 = routed like this, 0 = never, 1 = always
-// for thresholds <= 8 (larger thresholds are routed as if it were -1).  Launches on the fixed rule never take it.
+// at 2 the model has the candidates at 2.6 ms, 8.45 against 0.9 x 8.55 = 7.7 (measured, forced: 8.15 against the 32-bit
+// prefilter's 8.74 on the same box, profiles/r12_pre16_forced_t2.json -- inside the margin).  "scan_pre16": -1 = routed
+// like this, 0 = never, 1 = always for thresholds <= 8 (larger thresholds are routed as if it were -1).  Launches on the
+// fixed rule never take it.
 constexpr int kPreStatic = 6;
 constexpr double kTrueWeight = 8.0;
-constexpr double kSlopePre = 1.3e4, kBaseFull = 15.75, kTrueFull = 2.7e5, kTruePre = 0.7e5;  // ms per 10^12 pairs
+constexpr double kSlopePre = 1.0e4, kBaseFull = 15.75, kTrueFull = 2.7e5, kTruePre = 0.7e5;  // ms per 10^12 pairs
 constexpr double kBasePre = 8.55, kBase48 = 14.0, kSlope48 = 2.8e4, kTrue48 = 1.0e5, kPre48Margin = 0.9;
 constexpr double kBase16 = 5.85, kPre16Margin = 0.9;
 constexpr uint64_t kProbeMinPairs = 1ull << 31;  // ~20 us of scan: below this the probe's round trip is not worth it
@@ -414,7 +418,7 @@ Route route(size_t n, size_t nq, int thresh, bool masked) {
   // (the 16-bit prefilter at threshold 1; the 32-bit one at thresholds <= 5, at 6 and at 7 on unrelated hashes; the
   // three-field kernel)
   const double pairs = (double)n * (double)nq;
-  const double pre_ms = pairs * (thresh <= 5 ? 8.7e-12 : thresh == 6 ? 9.7e-12 : thresh == 7 ? 12.1e-12 : 15.8e-12);
+  const double pre_ms = pairs * (thresh <= 5 ? 8.7e-12 : thresh == 6 ? 9.5e-12 : thresh == 7 ? 11.3e-12 : 15.8e-12);
   r.scan_ms = thresh == 1 ? pairs * 6.1e-12 : pre_ms;
   // thresholds <= 8, "scan_mfma" 3: the join when its candidate count says it is cheaper than looking at every pair (only
   // asked where a scan on the 32-bit prefilter or the three-field kernel would take >= 1 ms: the bound weighs the call's
