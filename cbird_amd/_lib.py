@@ -189,6 +189,10 @@ _SIGS = {
                                               _vp, _sz, _vp, _vp]),
     "cbh_vidx_search_index_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.c_int, _vp, _sz, _vp, _vp]),
+    "cbh_vidx_search_index_frames_batch": (C.c_int, [_vp, _vp, _vp, _vp, _sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                     C.c_int, _vp, _sz, _vp, _vp]),
+    "cbh_vidx_find_frame_coalesced": (C.c_int, [_vp, C.c_uint64, C.c_int, C.c_int, C.c_int, _vp, _sz, C.POINTER(_sz)]),
+    "cbh_vidx_find_frames_batch": (C.c_int, [_vp, _vp, _vp, _sz, C.c_int, C.c_int, _vp, _sz, _vp]),
     "cbh_idx256_search_index_batch": (C.c_int, [_vp, _vp, _vp, _vp, _sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_int, _vp, _sz, _vp, _vp]),
     "cbh_color_search_index_batch": (C.c_int, [_vp, _vp, _vp, _sz, C.c_int, C.c_int, _vp, _sz, _vp, _vp]),

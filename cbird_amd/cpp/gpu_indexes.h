@@ -416,8 +416,9 @@ class GpuDctVideoIndex : public DctVideoIndex {
         qWarning() << "needle has no dct hash" << needle.id() << needle.path();
         return {};
       }
-      if (!CBH_QUERY(cbh_vidx_find_frame(_idx, needle.dctHash(), p.dctThresh, p.skipFrames, needle.matchRange().dstIn,
-                                         out.data(), out.size(), &n)))
+      // (callers that arrive from other pool threads during a search share one batched findFrame: combine.hip)
+      if (!CBH_QUERY(cbh_vidx_find_frame_coalesced(_idx, needle.dctHash(), p.dctThresh, p.skipFrames,
+                                                   needle.matchRange().dstIn, out.data(), out.size(), &n)))
         return {};
     } else if (needle.type() == Media::TypeVideo) {
       VideoIndex src;

@@ -416,6 +416,15 @@ int launch_video_reduce(const unsigned* d_off, const unsigned long long* d_seg, 
                         const uint32_t* d_qneedle, const int32_t* d_qframe, const uint32_t* d_needle_id, int filter_self,
                         int min_matched, int min_near, std::vector<cbh_nvmatch>* h_out, hipStream_t s);
 
+// ---- frames.hip: K9, findFrame for a chunk of image needles (nearest frame per video, one sort, no host ordering) ----
+// d_rec: `total` unordered scan records of `nq` needles, re-keyed and sorted between d_rec and d_alt (d_tmp / tmp_bytes: the
+// sort's scratch, Workspace::ensure_sort); h_src_in: NULL or nq values.  h_out: one match per (needle, video) run, in
+// (needle, video index) order; h_off[0 .. nq]: first run of every needle.  CBH_E_OVERFLOW for total >= 2^32.
+int launch_frame_reduce(unsigned long long* d_rec, unsigned long long* d_alt, size_t total, size_t nq, void* d_tmp,
+                        size_t tmp_bytes, const uint32_t* d_evidx, const int32_t* d_eframe, const uint32_t* d_vmedia,
+                        const int32_t* h_src_in, std::vector<cbh_vmatch>* h_out, std::vector<uint32_t>* h_off,
+                        hipStream_t s);
+
 // ---- dcthash.hip (whole images), kphash.hip (rectangles, keypoint squares) -------------
 // view: the images are w x h sub-rectangles at (ox, oy) of pw x ph parents starting at d_imgs -- cv::blur on a
 // cv::Mat view takes its border pixels from the parent (dctHash64 after autocrop(), src/cvutil.cpp:1397-1401)

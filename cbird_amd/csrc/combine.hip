@@ -7,7 +7,8 @@
 // CvFeaturesIndex and ColorDescIndex with one generic leader / follower queue: callers that arrive while a search is in
 // flight queue up, one of them (the leader) takes every queued request whose parameters equal those of the oldest one
 // -- up to kMaxBatch -- serves them with ONE call of the index's batch entry point (cbh_fdct_find_batch_ex /
-// cbh_vidx_find_videos_batch / cbh_idx256_find_batch / cbh_color_find_all_batch: one scan, one reduction), and hands
+// cbh_vidx_find_videos_batch, cbh_vidx_find_frames_batch for a DctVideoIndex's image needles / cbh_idx256_find_batch /
+// cbh_color_find_all_batch: one scan, one reduction), and hands
 // every caller its own result.  T blocked callers = T needles per device round trip.  Results are those of the
 // single-needle entry points, which the batch entry points already equal (tests/test_fdct.py, test_video.py,
 // test_cvfeatures.py, test_color.py).  No self-join cache here: these needles carry hundreds of hashes each and the
@@ -132,6 +133,12 @@ struct VideoReq : ReqBase {
     return thresh == o.thresh && skip == o.skip && vfm == o.vfm && vfn == o.vfn && filter_self == o.filter_self;
   }
 };
+struct FrameReq : ReqBase {  // an image needle of DctVideoIndex (findFrame)
+  uint64_t hash;
+  int thresh, skip, src_in;
+  cbh_vmatch* out;
+  bool compatible(const FrameReq& o) const { return thresh == o.thresh && skip == o.skip; }
+};
 struct OrbReq : ReqBase {
   const uint8_t* rows;
   size_t n_desc;
@@ -144,6 +151,10 @@ struct ColorReq : ReqBase {
   cbh_match* out;
   bool compatible(const ColorReq&) const { return true; }
 };
+
+// A DctVideoIndex serves two kinds of needle, each with a queue of its own: the video needles' combiner is registered
+// under the handle, the image needles' under this second key (an address inside the handle, so no other handle's)
+const void* frame_key(const void* handle) { return static_cast<const char*>(handle) + 1; }
 
 template <class Req, class M>
 void scatter(std::vector<Req*>& batch, int rc, const std::vector<M>& buf, const std::vector<uint64_t>& oo) {
@@ -163,10 +174,12 @@ void scatter(std::vector<Req*>& batch, int rc, const std::vector<M>& buf, const 
 void combiner_drop(const void* handle) {
   Registry& R = registry();
   std::lock_guard<std::mutex> lk(R.mu);
-  auto it = R.by_handle.find(handle);
-  if (it == R.by_handle.end()) return;
-  delete it->second;
-  R.by_handle.erase(it);
+  for (const void* key : {handle, frame_key(handle)}) {
+    auto it = R.by_handle.find(key);
+    if (it == R.by_handle.end()) continue;
+    delete it->second;
+    R.by_handle.erase(it);
+  }
 }
 
 }  // namespace cbh
@@ -236,6 +249,37 @@ int cbh_vidx_find_video_coalesced(cbh_vidx* v, const int32_t* frames, const uint
   return rc;
 }
 
+int cbh_vidx_find_frame_coalesced(cbh_vidx* v, uint64_t hash, int thresh, int skip_frames, int src_in, cbh_vmatch* out,
+                                  size_t cap, size_t* n_out) {
+  if (!v || !n_out || (cap && !out)) return CBH_E_INVAL;
+  *n_out = 0;
+  if (hash == 0) return CBH_OK;  // "needle has no dct hash" (src/dctvideoindex.cpp:331-335): nothing to queue
+  auto* co = combiner_of<Combiner<FrameReq>>(frame_key(v));
+  if (!co) return CBH_E_NOMEM;
+  FrameReq me;
+  me.hash = hash, me.thresh = thresh, me.skip = skip_frames, me.src_in = src_in, me.out = out, me.cap = cap;
+  int rc = co->submit(me, [&](std::vector<FrameReq*>& batch) {
+    std::vector<uint64_t> h, oo(batch.size() + 1);
+    std::vector<int32_t> si;
+    for (FrameReq* r : batch) {
+      h.push_back(r->hash);
+      si.push_back(r->src_in);
+    }
+    const FrameReq& p = *batch[0];
+    std::vector<cbh_vmatch> buf(std::max<size_t>(64, 16 * batch.size()));
+    int rc2 = cbh_vidx_find_frames_batch(v, h.data(), si.data(), batch.size(), p.thresh, p.skip, buf.data(), buf.size(),
+                                         oo.data());
+    if (rc2 == CBH_E_OVERFLOW && oo[batch.size()] > buf.size()) {
+      buf.resize((size_t)oo[batch.size()]);
+      rc2 = cbh_vidx_find_frames_batch(v, h.data(), si.data(), batch.size(), p.thresh, p.skip, buf.data(), buf.size(),
+                                       oo.data());
+    }
+    scatter(batch, rc2, buf, oo);
+  });
+  *n_out = me.n_out;
+  return rc;
+}
+
 int cbh_idx256_find_coalesced(cbh_idx256* ix, const uint8_t* needle_rows, size_t n_desc, int thresh, int k, cbh_match* out,
                               size_t cap, size_t* n_out) {
   if (!ix || !n_out || (cap && !out) || (n_desc && !needle_rows) || k <= 0) return CBH_E_INVAL;
@@ -286,11 +330,13 @@ int cbh_combine_stats(const void* handle, uint64_t* finds, uint64_t* rounds) {
   *finds = *rounds = 0;
   Registry& R = registry();
   std::lock_guard<std::mutex> lk(R.mu);
-  auto it = R.by_handle.find(handle);
-  if (it == R.by_handle.end()) return CBH_OK;
-  CombinerBase* c = it->second;
-  std::lock_guard<std::mutex> l2(c->mu);
-  *finds = c->st.finds, *rounds = c->st.rounds;
+  for (const void* key : {handle, frame_key(handle)}) {  // (a DctVideoIndex: video and image needles together)
+    auto it = R.by_handle.find(key);
+    if (it == R.by_handle.end()) continue;
+    CombinerBase* c = it->second;
+    std::lock_guard<std::mutex> l2(c->mu);
+    *finds += c->st.finds, *rounds += c->st.rounds;
+  }
   return CBH_OK;
 }
 

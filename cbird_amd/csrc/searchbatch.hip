@@ -133,6 +133,37 @@ int cbh_vidx_search_index_batch(cbh_vidx* v, const int32_t* frames, const uint64
                                          filter_self, valid_ids_sorted, n_valid, find, out, out_counts);
 }
 
+// image needles (DctVideoIndex::find -> findFrame, src/dctvideoindex.cpp:282-289): findFrame does not know filterSelf, so
+// the count that decides about another level is every row it returned; equal (score, mediaId) keep findFrame's video order
+int cbh_vidx_search_index_frames_batch(cbh_vidx* v, const uint64_t* hashes, const int32_t* src_in, const uint32_t* needle_ids,
+                                       size_t n_needles, int thresh, int max_thresh, int skip_frames, int min_matches,
+                                       int max_matches, int filter_self, const uint32_t* valid_ids_sorted, size_t n_valid,
+                                       cbh_vmatch* out, uint32_t* out_counts) {
+  if (!v || max_matches < 0 || (n_needles && (!hashes || !needle_ids || !out_counts)) ||
+      (n_needles && max_matches && !out))
+    return CBH_E_INVAL;
+  auto find = [&](const std::vector<uint32_t>& pend, int t, std::vector<std::vector<cbh_vmatch>>& res) {
+    std::vector<uint64_t> h;
+    std::vector<int32_t> si;
+    for (uint32_t j : pend) {
+      h.push_back(hashes[j]);
+      si.push_back(src_in ? src_in[j] : -1);
+    }
+    std::vector<cbh_vmatch> buf(std::max<size_t>(64, 8 * pend.size()));
+    std::vector<uint64_t> oo(pend.size() + 1);
+    int rc = cbh_vidx_find_frames_batch(v, h.data(), si.data(), pend.size(), t, skip_frames, buf.data(), buf.size(), oo.data());
+    if (rc == CBH_E_OVERFLOW && oo[pend.size()] > buf.size()) {
+      buf.resize((size_t)oo[pend.size()]);
+      rc = cbh_vidx_find_frames_batch(v, h.data(), si.data(), pend.size(), t, skip_frames, buf.data(), buf.size(), oo.data());
+    }
+    if (rc) return rc;
+    for (size_t i = 0; i < pend.size(); ++i) res[i].assign(buf.begin() + (long)oo[i], buf.begin() + (long)oo[i + 1]);
+    return (int)CBH_OK;
+  };
+  return search_index_levels<cbh_vmatch>(n_needles, needle_ids, thresh, max_thresh, 1, min_matches, max_matches,
+                                         filter_self, valid_ids_sorted, n_valid, find, out, out_counts);
+}
+
 int cbh_idx256_search_index_batch(cbh_idx256* ix, const uint8_t* rows, const uint64_t* offsets, const uint32_t* needle_ids,
                                   size_t n_needles, int thresh, int max_thresh, int k, int min_matches, int max_matches,
                                   int filter_self, const uint32_t* valid_ids_sorted, size_t n_valid, cbh_match* out,

@@ -37,6 +37,9 @@ struct cbh_vidx {
   uint32_t* d_egroup = nullptr;
   int32_t* d_eframe = nullptr;
   uint32_t* d_vmedia = nullptr;
+  // entry -> video index on the device: findFrame groups by VIDEO, not by media id (two videos of one id are two rows,
+  // :346-356).  Only the batched image-needle search reads it: uploaded by its first call after a build (ensure_evidx)
+  uint32_t* d_evidx = nullptr;
   std::mutex build_mu;           // QMutex _mutex (dctvideoindex.cpp:118)
   // 0 = exact search.  > 0 = RadixMap-compatible: a needle hash only sees the entries of its bucket
   // (hash >> 1) & (2^radix - 1) (src/tree/radix.h:135-141), like `-p.vradix N` in the reference.
@@ -79,9 +82,9 @@ int build(cbh_vidx* v, int skip) {
   {
     DeviceGuard g(v->device);
     if (!g.ok) return CBH_E_NODEVICE;
-    for (void* p : {(void*)v->d_egroup, (void*)v->d_eframe, (void*)v->d_vmedia})
+    for (void* p : {(void*)v->d_egroup, (void*)v->d_eframe, (void*)v->d_vmedia, (void*)v->d_evidx})
       if (p) (void)hipFree(p);
-    v->d_egroup = nullptr, v->d_eframe = nullptr, v->d_vmedia = nullptr;
+    v->d_egroup = nullptr, v->d_eframe = nullptr, v->d_vmedia = nullptr, v->d_evidx = nullptr;
     const size_t ne = std::max<size_t>(1, v->evidx.size()), nv = std::max<size_t>(1, v->videos.size());
     std::vector<uint32_t> vmedia(v->videos.size()), vgroup(v->videos.size()), egroup(v->evidx.size());
     std::unordered_map<uint32_t, uint32_t> first;  // media id -> its first video
@@ -284,6 +287,77 @@ int find_videos(cbh_vidx* v, const int32_t* frames, const uint64_t* hashes, cons
   return CBH_OK;
 }
 
+// the device copy of evidx for the built structure, made by the first batched image-needle search that needs it
+int ensure_evidx(cbh_vidx* v) {
+  std::lock_guard<std::mutex> lk(v->build_mu);
+  if (v->d_evidx) return CBH_OK;
+  DeviceGuard g(v->device);
+  if (!g.ok) return CBH_E_NODEVICE;
+  uint32_t* d = nullptr;
+  CBH_HIP(hipMalloc(&d, std::max<size_t>(1, v->evidx.size()) * 4));
+  if (!v->evidx.empty()) {
+    hipError_t e = hipMemcpy(d, v->evidx.data(), v->evidx.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(d);
+      CBH_HIP(e);
+    }
+  }
+  v->d_evidx = d;
+  return CBH_OK;
+}
+
+// findFrame (:291-387) for n image needles: one scan and one device reduction (frames.hip) per chunk of
+// CBH_MAX_QUERIES_PER_CALL needles.  out: the matches of needle i at [offs[i], offs[i + 1]), ascending video index.
+int find_frames(cbh_vidx* v, const uint64_t* hashes, const int32_t* src_in, size_t n, int thresh, int skip,
+                std::vector<cbh_vmatch>* out, std::vector<uint64_t>* offs) {
+  out->clear();
+  offs->assign(n + 1, 0);
+  if (n == 0) return CBH_OK;
+  int rc = build(v, skip);
+  if (rc) return rc;
+  cbh_idx64* idx = v->idx;
+  if (idx->n == 0 || thresh <= 0) return CBH_OK;
+  if ((rc = ensure_evidx(v))) return rc;
+  DeviceGuard g(idx->device);
+  if (!g.ok) return CBH_E_NODEVICE;
+  WsLease L(idx, &rc);
+  if (!L.ws) return rc;
+  Workspace* ws = L.ws;
+  hipStream_t s = ws->stream;
+  std::vector<uint64_t> masks;
+  std::vector<cbh_vmatch> part;
+  std::vector<uint32_t> poff;
+  for (size_t c0 = 0; c0 < n; c0 += CBH_MAX_QUERIES_PER_CALL) {
+    const size_t nq = std::min<size_t>(CBH_MAX_QUERIES_PER_CALL, n - c0);
+    if ((rc = Workspace::grow(&ws->d_q, &ws->q_cap, nq))) return rc;
+    CBH_HIP(hipMemcpyAsync(ws->d_q, hashes + c0, nq * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    if (v->radix) {  // equal bucket <=> equal bits 1..radix
+      masks.assign(nq, ((1ull << v->radix) - 1) << 1);
+      if ((rc = Workspace::grow(&ws->d_qmask, &ws->qmask_cap, nq))) return rc;
+      CBH_HIP(hipMemcpyAsync(ws->d_qmask, masks.data(), nq * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    }
+    // (no zero_needles: "needle has no dct hash", :333-337 -- the scan leaves a hash of 0 without records)
+    unsigned long long total = 0;
+    rc = scan_all(idx, ws, ws->d_q, nq, thresh, s, &total, ScanOpts{false, v->radix ? ws->d_qmask : nullptr, false});
+    if (rc) return rc;
+    if (total >= (1ull << 32)) return CBH_E_OVERFLOW;
+    if (total) {
+      if ((rc = ws->ensure_sort())) return rc;
+      rc = launch_frame_reduce(reinterpret_cast<unsigned long long*>(ws->d_rec),
+                               reinterpret_cast<unsigned long long*>(ws->d_alt), (size_t)total, nq, ws->d_tmp, ws->tmp_bytes,
+                               v->d_evidx, v->d_eframe, v->d_vmedia, src_in ? src_in + c0 : nullptr, &part, &poff, s);
+      if (rc) return rc;
+    } else {
+      part.clear();
+      poff.assign(nq + 1, 0);
+    }
+    const uint64_t base = out->size();
+    for (size_t j = 0; j <= nq; ++j) (*offs)[c0 + j] = base + poff[j];
+    out->insert(out->end(), part.begin(), part.end());
+  }
+  return CBH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -323,7 +397,7 @@ void cbh_vidx_destroy(cbh_vidx* v) {
   if (!v) return;
   cbh::combiner_drop(v);  // combine.hip: the queue of cbh_*_find_coalesced callers
   if (v->idx) cbh_idx64_destroy(v->idx);
-  for (void* p : {(void*)v->d_egroup, (void*)v->d_eframe, (void*)v->d_vmedia})
+  for (void* p : {(void*)v->d_egroup, (void*)v->d_eframe, (void*)v->d_vmedia, (void*)v->d_evidx})
     if (p) (void)hipFree(p);
   delete v;
 }
@@ -421,6 +495,19 @@ int cbh_vidx_find_frame(cbh_vidx* v, uint64_t hash, int thresh, int skip_frames,
     ++m;
   }
   *n_out = m;
+  return CBH_OK;
+}
+
+int cbh_vidx_find_frames_batch(cbh_vidx* v, const uint64_t* hashes, const int32_t* src_in, size_t n, int thresh,
+                               int skip_frames, cbh_vmatch* out, size_t cap, uint64_t* out_offsets) {
+  if (!v || !out_offsets || (cap && !out) || (n && !hashes)) return CBH_E_INVAL;
+  std::vector<cbh_vmatch> res;
+  std::vector<uint64_t> offs;
+  int rc = find_frames(v, hashes, src_in, n, thresh, skip_frames, &res, &offs);
+  if (rc) return rc;
+  std::copy(offs.begin(), offs.end(), out_offsets);
+  if (res.size() > cap) return CBH_E_OVERFLOW;  // (out_offsets[n] = the room needed)
+  std::copy(res.begin(), res.end(), out);
   return CBH_OK;
 }
 

@@ -128,19 +128,45 @@ def search_index_batch(index, needles, params: SearchParams, id_map: dict):
         rows = [[(int(out[j, t, 0]), int(sc[j, t]), None) for t in range(int(counts[j]))] for j in range(n)]
     elif cls == "DctVideoIndex":
         index._apply_radix(params)
-        f = np.concatenate([np.asarray(m.videoIndex.frames, np.int32) for m in needles] or [np.zeros(0, np.int32)])
-        h = np.concatenate([np.asarray(m.videoIndex.hashes, np.uint64) for m in needles] or [np.zeros(0, np.uint64)])
-        offs = np.zeros(n + 1, np.uint64)
-        np.cumsum([len(m.videoIndex.frames) for m in needles], out=offs[1:])
-        out = (_lib.cbh_vmatch * max(1, n * max(k, 1)))()
-        _lib.check(L.cbh_vidx_search_index_batch(index._h, f.ctypes.data, h.ctypes.data, offs.ctypes.data, nid.ctypes.data,
-                                                 n, int(params.dctThresh), int(params.maxThresh), int(params.skipFrames),
-                                                 int(params.minFramesMatched), int(params.minFramesNear),
-                                                 int(params.minMatches), k, fs, *vargs, out, counts.ctypes.data),
-                   "vidx_search_index_batch")
-        rows = [[(out[j * k + t].id, out[j * k + t].score,
-                  MatchRange(out[j * k + t].src_in, out[j * k + t].dst_in, out[j * k + t].len))
-                 for t in range(int(counts[j]))] for j in range(n)]
+        # DctVideoIndex::find (dctvideoindex.cpp:282-289): a needle with a video index is a video needle (findVideo), any
+        # other an image needle (findFrame); each part goes to its own entry point, the rows come back in needle order
+        is_video = [getattr(m, "videoIndex", None) is not None for m in needles]
+        rows = [None] * n
+
+        def take(part, out, cnt):
+            for i, j in enumerate(part):
+                rows[j] = [(out[i * k + t].id, out[i * k + t].score,
+                            MatchRange(out[i * k + t].src_in, out[i * k + t].dst_in, out[i * k + t].len))
+                           for t in range(int(cnt[i]))]
+
+        part = [j for j in range(n) if is_video[j]]
+        if part:
+            vn = [needles[j] for j in part]
+            f = np.concatenate([np.asarray(m.videoIndex.frames, np.int32) for m in vn])
+            h = np.concatenate([np.asarray(m.videoIndex.hashes, np.uint64) for m in vn])
+            offs = np.zeros(len(vn) + 1, np.uint64)
+            np.cumsum([len(m.videoIndex.frames) for m in vn], out=offs[1:])
+            pid = np.ascontiguousarray(nid[part])
+            cnt = np.zeros(len(vn), np.uint32)
+            out = (_lib.cbh_vmatch * max(1, len(vn) * max(k, 1)))()
+            _lib.check(L.cbh_vidx_search_index_batch(index._h, f.ctypes.data, h.ctypes.data, offs.ctypes.data,
+                                                     pid.ctypes.data, len(vn), int(params.dctThresh), int(params.maxThresh),
+                                                     int(params.skipFrames), int(params.minFramesMatched),
+                                                     int(params.minFramesNear), int(params.minMatches), k, fs, *vargs, out,
+                                                     cnt.ctypes.data), "vidx_search_index_batch")
+            take(part, out, cnt)
+        part = [j for j in range(n) if not is_video[j]]
+        if part:
+            h = np.ascontiguousarray([int(needles[j].dctHash) for j in part], np.uint64)
+            si = np.ascontiguousarray([int(getattr(needles[j], "matchRange", MatchRange()).dstIn) for j in part], np.int32)
+            pid = np.ascontiguousarray(nid[part])
+            cnt = np.zeros(len(part), np.uint32)
+            out = (_lib.cbh_vmatch * max(1, len(part) * max(k, 1)))()
+            _lib.check(L.cbh_vidx_search_index_frames_batch(index._h, h.ctypes.data, si.ctypes.data, pid.ctypes.data,
+                                                            len(part), int(params.dctThresh), int(params.maxThresh),
+                                                            int(params.skipFrames), int(params.minMatches), k, fs, *vargs,
+                                                            out, cnt.ctypes.data), "vidx_search_index_frames_batch")
+            take(part, out, cnt)
     else:
         raise TypeError(f"search_index_batch: unsupported index {cls}")
     groups = []

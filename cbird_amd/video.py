@@ -343,5 +343,29 @@ class DctVideoIndex:
         return [self._matches(buf[int(out_offs[k]):int(out_offs[k + 1])], int(out_offs[k + 1] - out_offs[k]))
                 for k in range(len(needles))]
 
+    def find_frames_batch(self, needles, p: VideoSearchParams):
+        """[findFrame(m, p) for m in needles] with one scan and one reduction on the device (cbh_vidx_find_frames_batch);
+        a needle without a dct hash gets an empty list, as findFrame gives it"""
+        self._apply_radix(p)
+        needles = list(needles)
+        for m in needles:
+            if int(m.dctHash) == 0:
+                warnings.warn(f"needle has no dct hash {m.id} {m.path}")
+        h = np.ascontiguousarray([int(m.dctHash) for m in needles], np.uint64)
+        s = np.ascontiguousarray([int(getattr(m, "matchRange", MatchRange()).dstIn) for m in needles], np.int32)
+        out_offs = np.zeros(len(needles) + 1, np.uint64)
+        cap = max(64, 8 * len(needles))
+        while True:  # the library reports the full size in out_offs[-1] when cap was too small
+            buf = (cbh_vmatch * cap)()
+            rc = self._L.cbh_vidx_find_frames_batch(self._h, h.ctypes.data, s.ctypes.data, len(needles), int(p.dctThresh),
+                                                    int(p.skipFrames), buf, cap, out_offs.ctypes.data)
+            if rc == _lib.CBH_E_OVERFLOW and int(out_offs[-1]) > cap:
+                cap = int(out_offs[-1])
+                continue
+            check(rc, "find_frames_batch")
+            break
+        return [self._matches(buf[int(out_offs[k]):int(out_offs[k + 1])], int(out_offs[k + 1] - out_offs[k]))
+                for k in range(len(needles))]
+
     def entries(self, skip_frames: int) -> int:
         return int(self._L.cbh_vidx_entries(self._h, int(skip_frames)))

@@ -731,6 +731,15 @@ int cbh_vidx_search_index_batch(struct cbh_vidx*, const int32_t* frames, const u
                                 int min_frames_matched, int min_frames_near, int min_matches, int max_matches,
                                 int filter_self, const uint32_t* valid_ids_sorted, size_t n_valid, struct cbh_vmatch* out,
                                 uint32_t* out_counts);
+/* the same for IMAGE needles of the video index (DctVideoIndex::find -> findFrame, src/dctvideoindex.cpp:282-289): needle j
+ * is hashes[j] with src_in[j] (src_in NULL: all -1); per dctThresh level one cbh_vidx_find_frames_batch of the pending
+ * needles; a needle goes on while the rows findFrame returned for it -- counted before filter_self and the idMap rule,
+ * findFrame knows neither -- are <= min_matches; order (score, mediaId, video index) */
+int cbh_vidx_search_index_frames_batch(struct cbh_vidx*, const uint64_t* hashes, const int32_t* src_in,
+                                       const uint32_t* needle_ids, size_t n_needles, int thresh, int max_thresh,
+                                       int skip_frames, int min_matches, int max_matches, int filter_self,
+                                       const uint32_t* valid_ids_sorted, size_t n_valid, struct cbh_vmatch* out,
+                                       uint32_t* out_counts);
 int cbh_idx256_search_index_batch(cbh_idx256*, const uint8_t* rows, const uint64_t* offsets, const uint32_t* needle_ids,
                                   size_t n_needles, int thresh, int max_thresh, int k, int min_matches, int max_matches,
                                   int filter_self, const uint32_t* valid_ids_sorted, size_t n_valid, cbh_match* out,
@@ -750,6 +759,10 @@ int cbh_fdct_find_coalesced(cbh_idx64*, const uint64_t* hashes, size_t n, uint32
 int cbh_vidx_find_video_coalesced(struct cbh_vidx*, const int32_t* frames, const uint64_t* hashes, size_t n,
                                   uint32_t needle_id, int thresh, int skip_frames, int min_frames_matched,
                                   int min_frames_near, int filter_self, struct cbh_vmatch* out, size_t cap, size_t* n_out);
+/* ... and cbh_vidx_find_frame for the image needles of a DctVideoIndex (a queue of its own beside the video needles';
+ * cbh_combine_stats of the handle counts both): one cbh_vidx_find_frames_batch per round */
+int cbh_vidx_find_frame_coalesced(struct cbh_vidx*, uint64_t hash, int thresh, int skip_frames, int src_in,
+                                  struct cbh_vmatch* out, size_t cap, size_t* n_out);
 int cbh_idx256_find_coalesced(cbh_idx256*, const uint8_t* needle_rows, size_t n_desc, int thresh, int k, cbh_match* out,
                               size_t cap, size_t* n_out);
 int cbh_color_find_coalesced(struct cbh_color*, const void* needle_desc, cbh_match* out, size_t cap, size_t* n_out);
@@ -854,6 +867,14 @@ size_t cbh_vidx_entries(cbh_vidx*, int skip_frames);
  * index; range = (src_in<0 ? 0 : src_in, matched frame, 1). */
 int cbh_vidx_find_frame(cbh_vidx*, uint64_t hash, int thresh, int skip_frames, int src_in,
                         cbh_vmatch* out, size_t cap, size_t* n_out);
+/* findFrame for n image needles with one scan and one reduction on the device (cbird_amd/csrc/frames.hip) per
+ * CBH_MAX_QUERIES_PER_CALL needles: the results of needle i, those of cbh_vidx_find_frame(hashes[i], .., src_in[i]), go to
+ * out[out_offsets[i] .. out_offsets[i+1]).  src_in NULL: every needle -1.  A needle whose hash is 0 gets none (:333-337).
+ * CBH_E_OVERFLOW when the total exceeds cap (out_offsets is complete, out_offsets[n] holds the required capacity, out is
+ * not written), or when one chunk's scan finds 2^32 records or more (out_offsets is not written).  Honours
+ * cbh_vidx_set_radix; plain and sharded handles. */
+int cbh_vidx_find_frames_batch(cbh_vidx*, const uint64_t* hashes, const int32_t* src_in, size_t n, int thresh,
+                               int skip_frames, cbh_vmatch* out, size_t cap, uint64_t* out_offsets);
 /* findVideo (:399-657), video needle given as its (frames, hashes) list (needle_id 0 = not in the db).
  * thresh = dctThresh, skip_frames = vtrim (skipFrames), min_frames_matched = vfm, min_frames_near = vfn. */
 int cbh_vidx_find_video(cbh_vidx*, const int32_t* frames, const uint64_t* hashes, size_t n,
