@@ -57,6 +57,18 @@ class cbh_filter_params(C.Structure):
                 ("merge_groups", C.c_int), ("expand_groups", C.c_int)]
 
 
+CBH_SORT_SIMILAR_MAX = 65536
+
+
+class cbh_sort_similar_params(C.Structure):
+    _fields_ = [("thresh", C.c_int), ("max_thresh", C.c_int), ("min_matches", C.c_int), ("max_matches", C.c_int),
+                ("filter_parent", C.c_int), ("path_mode", C.c_int), ("look_behind", C.c_int)]
+
+
+class cbh_sort_similar_result(C.Structure):
+    _fields_ = [("sorted", C.c_uint32), ("queries", C.c_uint32), ("not_found", C.c_uint32), ("behind", C.c_uint32)]
+
+
 class cbh_vmatch(C.Structure):
     _fields_ = [("id", C.c_uint32), ("score", C.c_int32), ("src_in", C.c_int32), ("dst_in", C.c_int32),
                 ("len", C.c_int32)]
@@ -205,6 +217,8 @@ _SIGS = {
     "cbh_combine_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cbh_filter_groups_ex": (C.c_int, [_vp, _vp, _vp, _sz, C.c_int, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp,
                                        _vp]),
+    "cbh_sort_similar": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int]),
+    "cbh_sort_similar_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int, _vp]),
     "cbh_vdx_verify": (C.c_int, [_vp, _sz]),
     "cbh_records_topk_dev": (C.c_int, [_vp, _sz, _sz, _sz, _sz, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
     "cbh_idx64_set_record_capacity": (C.c_int, [_vp, _sz]),

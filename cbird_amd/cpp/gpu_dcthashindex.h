@@ -209,6 +209,67 @@ class GpuDctHashIndex : public Index {
     return res;
   }
 
+  /// What filterMatch reads from paths (src/database.cpp:1217-1242), parallel to the selection, for gpuSortSimilar:
+  /// dirId[i] -- equal numbers <=> equal Media::dirPath() -- when params.filterParent, underPrefix[i] =
+  /// path().startsWith(prefix) when params.path is set (pathMode 1 = inPath, 2 = not inPath).  INTEGRATION.md fills it.
+  struct SortSimilarPaths {
+    bool filterParent = false;
+    int pathMode = 0;
+    std::vector<uint32_t> dirId;
+    std::vector<uint8_t> underPrefix;
+  };
+  /// `-sort-similar` (src/main.cpp:1523-1580) in one kernel launch instead of up to 5 (n - 1) slices and queries:
+  /// `selection` becomes the sorted list (items never reached are dropped, :1579), *queries / *notFound count what the
+  /// reference's loop counts.  AlgoDCT with mirrorMask 0 and no templateMatch; items this index does not hold are never
+  /// candidates, as in the reference's slice.  false (selection untouched, the error logged): the call failed or the
+  /// selection has more than CBH_SORT_SIMILAR_MAX items -- run the reference's loop then.
+  bool gpuSortSimilar(MediaGroup& selection, const SearchParams& p, int* queries, int* notFound,
+                      const SortSimilarPaths* paths = nullptr) const {
+    const size_t n = selection.size();
+    std::vector<uint64_t> hashes;
+    std::vector<uint32_t> ids, held, order(n ? n : 1);
+    for (const Media& m : selection) {
+      hashes.push_back(m.dctHash());
+      ids.push_back(uint32_t(m.id()));
+    }
+    // what a slice of this index can hold: every entry with an id, a hash of 0 included (mediaIds() leaves those out)
+    held.resize(cbh_idx64_count(_idx) ? cbh_idx64_count(_idx) : 1);
+    std::vector<uint64_t> heldHashes(held.size());
+    if (cbh_idx64_count(_idx) &&
+        !query("download", [&] { return cbh_idx64_download(_idx, heldHashes.data(), held.data(), cbh_idx64_count(_idx)); }))
+      return false;
+    held.resize(cbh_idx64_count(_idx));
+    std::sort(held.begin(), held.end());
+    std::vector<uint8_t> inIndex;
+    for (uint32_t id : ids) inIndex.push_back(id && std::binary_search(held.begin(), held.end(), id) ? 1 : 0);
+    cbh_sort_similar_params sp;
+    sp.thresh = p.dctThresh, sp.max_thresh = p.maxThresh, sp.min_matches = p.minMatches, sp.max_matches = p.maxMatches;
+    sp.filter_parent = paths && paths->filterParent, sp.path_mode = paths ? paths->pathMode : 0;
+    sp.look_behind = 5;  // `const int lookBehind = 5` (:1530)
+    if ((sp.filter_parent && paths->dirId.size() != n) || (sp.path_mode && paths->underPrefix.size() != n)) {
+      qCritical("GpuDctHashIndex::gpuSortSimilar: the path attributes are not parallel to the selection");
+      return false;
+    }
+    const uint64_t first[2] = {0, n};
+    cbh_sort_similar_result res = {0, 0, 0, 0};
+    if (!query("sort_similar", [&] {
+          return cbh_sort_similar(hashes.data(), ids.data(), inIndex.data(), sp.filter_parent ? paths->dirId.data() : nullptr,
+                                  sp.path_mode ? paths->underPrefix.data() : nullptr, first, 1, &sp, order.data(), &res,
+                                  _device);
+        }))
+      return false;
+    std::vector<std::pair<uint32_t, size_t>> where;  // id -> place in the selection
+    for (size_t i = 0; i < n; ++i) where.push_back({ids[i], i});
+    std::sort(where.begin(), where.end());
+    MediaGroup sorted;
+    for (uint32_t k = 0; k < res.sorted; ++k)
+      sorted.append(selection[std::lower_bound(where.begin(), where.end(), std::make_pair(order[k], size_t(0)))->second]);
+    selection = sorted;
+    if (queries) *queries = int(res.queries);
+    if (notFound) *notFound = int(res.not_found);
+    return true;
+  }
+
   cbh_idx64* handle() const { return _idx; }  // for statistics (cbh_idx64_get_stats / cbh_idx64_coalesce_stats)
 
  private:

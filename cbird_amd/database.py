@@ -450,3 +450,112 @@ def similar(index, haystack, params: SearchParams, batched: bool = True, db_path
             continue
         results.append([m] + search_index(index, m, params, id_map))
     return filter_results(params, results, db_path)
+
+
+# ---- -sort-similar (src/main.cpp:1523-1580) ---------------------------------------------------------------------------
+SORT_SIMILAR_LOOK_BEHIND = 5  # `const int lookBehind = 5` (:1530)
+
+
+def _sort_similar_loop(index, selection, params, db_path):
+    """the reference's loop with what exists: a fresh slice of unsorted + needle, one query and one insert per pass"""
+    sel = list(selection)
+    if not sel:
+        return [], 0, 0
+    id_map = {m.id: m for m in sel}
+    if len(id_map) != len(sel) or 0 in id_map:
+        raise ValueError("sort_similar: the selection needs unique non-zero ids")
+    ordered = [sel[0]]
+    unsorted = {m.id: m for m in sel[1:]}
+    queries = not_found = 0
+    for _ in range(len(sel) - 1):
+        j = 0
+        while j < min(SORT_SIMILAR_LOOK_BEHIND, len(ordered)):  # sorted.count() is read again on every pass (:1547)
+            needle = ordered[len(ordered) - 1 - j]
+            # "set must also contain needle or else we can't search for it" (:1554-1559)
+            part = index.slice(list(unsorted) + [needle.id])
+            matches = query(part, needle, params, id_map, db_path=db_path)
+            if matches:
+                hit = id_map[matches[0].id]
+                ordered.insert(len(ordered) - j, hit)
+                del unsorted[hit.id]
+            else:
+                not_found += 1
+            queries += 1
+            j += 1  # no break after an insert: the same needle is asked again one place further back
+    return ordered, queries, not_found
+
+
+def _sort_similar_on_device(index, params) -> bool:
+    from .index import DctHashIndex
+
+    return (isinstance(index, DctHashIndex) and params.algo == SearchParams.AlgoDCT and not params.mirrorMask and
+            not params.templateMatch and 1 <= int(params.maxMatches) <= 55 and 0 <= int(params.dctThresh) <= 65 and
+            int(params.maxThresh) <= 65)
+
+
+def sort_similar_batch(index, selections, params: SearchParams, db_path: str = ""):
+    """sort_similar for many selections; DctHashIndex without reflections: ONE cbh_sort_similar call, a workgroup per
+    selection (sortsimilar.hip).  Returns [sort_similar(index, s, params, True, db_path) for s in selections]."""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+
+    if not params.filterSelf:
+        raise ValueError("sort_similar: without filterSelf the reference inserts the needle again forever")
+    selections = [list(s) for s in selections]
+    if not (_sort_similar_on_device(index, params) and
+            all(len(s) <= _lib.CBH_SORT_SIMILAR_MAX for s in selections)):
+        return [_sort_similar_loop(index, s, params, db_path) for s in selections]
+    flat = [m for s in selections for m in s]
+    first = np.zeros(len(selections) + 1, np.uint64)
+    np.cumsum([len(s) for s in selections], out=first[1:])
+    ids = np.ascontiguousarray([m.id for m in flat], np.uint32)
+    hashes = np.ascontiguousarray([int(m.dctHash) for m in flat], np.uint64)
+    # the reference searches the index's slice, not the Media list: what the index does not hold is no candidate
+    # (every entry with an id, a hash of 0 included: mediaIds() leaves those out, the slice does not)
+    L = _lib.lib()
+    held = index.download()[1]
+    in_index = np.ascontiguousarray(np.isin(ids, held[held != 0]), np.uint8)
+    # paths enter as attributes, as in filter_groups_c_abi: a number per distinct dirPath(), under-the-prefix flags
+    dir_id = under = None
+    if params.filterParent:
+        dirs = {}
+        dir_id = np.ascontiguousarray([dirs.setdefault(dir_path(m.path), len(dirs)) for m in flat], np.uint32)
+    if params.path != "":
+        prefix = params.path if params.path.startswith(db_path) else db_path + "/" + params.path
+        under = np.ascontiguousarray([1 if m.path.startswith(prefix) else 0 for m in flat], np.uint8)
+    sp = _lib.cbh_sort_similar_params(int(params.dctThresh), int(params.maxThresh), int(params.minMatches),
+                                      int(params.maxMatches), int(bool(params.filterParent)),
+                                      0 if params.path == "" else (1 if params.inPath else 2), SORT_SIMILAR_LOOK_BEHIND)
+    out_ids = np.zeros(max(len(flat), 1), np.uint32)
+    res = (_lib.cbh_sort_similar_result * max(len(selections), 1))()
+    _lib.check(L.cbh_sort_similar(hashes.ctypes.data, ids.ctypes.data, in_index.ctypes.data,
+                                  None if dir_id is None else dir_id.ctypes.data,
+                                  None if under is None else under.ctypes.data, first.ctypes.data, len(selections),
+                                  C.byref(sp), out_ids.ctypes.data, res, getattr(index, "device", 0)), "sort_similar")
+    out = []
+    for s, sel in enumerate(selections):
+        by_id = {m.id: m for m in sel}
+        a = int(first[s])
+        out.append(([by_id[int(i)] for i in out_ids[a:a + res[s].sorted]], int(res[s].queries), int(res[s].not_found)))
+    return out
+
+
+def sort_similar(index, selection, params: SearchParams, batched: bool = True, db_path: str = ""):
+    """-sort-similar (src/main.cpp:1523-1580): the selection ordered so that every item is followed by its nearest
+    remaining neighbour -- for each place, up to lookBehind = 5 queries of the last placed items inside the set of
+    unplaced ones, a hit inserted behind its needle, no break after a hit, every failing query counted.  Returns
+    (sorted media, queries, notFound); items never reached are dropped, as in the reference (:1579).
+
+    batched=False: the reference's shape for any index and any params query() supports -- index.slice() of unsorted +
+    needle, query(), insert, once per pass.  batched=True (DctHashIndex, mirrorMask 0): the whole chain in one kernel
+    launch, cbh_sort_similar; the Media list stands for the index's slice (items the index does not hold are never
+    candidates), so its dctHash values have to be the index's.  Anything else takes the loop.  filterSelf must be set:
+    without it the reference inserts the needle again forever (ValueError)."""
+    if not params.filterSelf:
+        raise ValueError("sort_similar: without filterSelf the reference inserts the needle again forever")
+    if batched:
+        return sort_similar_batch(index, [selection], params, db_path)[0]
+    return _sort_similar_loop(index, selection, params, db_path)

@@ -795,6 +795,48 @@ int cbh_filter_groups_ex(const uint32_t* needle_ids, const cbh_match* matches, c
                          uint64_t* out_first, size_t cap_groups, cbh_match* out_members, size_t cap_members,
                          size_t* n_groups, size_t* n_members);
 
+/* ---- -sort-similar: src/main.cpp:1523-1580 ----------------------------------------------------------------------------
+ * Orders selections so that every item is followed by its nearest remaining neighbour, the reference's loop and its
+ * side effects restated exactly (AlgoDCT; items = 64-bit hash + unique non-zero id):
+ *   sorted = [first item], unsorted = the rest; for i in 0 .. n-2, for j in 0 .. min(look_behind, len(sorted)) - 1 --
+ *   len(sorted) read again on every pass -- the needle sorted[len-1-j] is queried inside unsorted + needle (:1552-1561);
+ *   a hit is inserted at len-j and leaves unsorted (:1563-1567), a miss counts in not_found; every pass counts in
+ *   queries; there is no break after a hit.  So after a hit at j the same needle is asked again and its next neighbour
+ *   lands in front of the previous one, passes go on failing once unsorted is empty, and items never reached are
+ *   dropped (selection = sorted, :1579).
+ * One query is Database::similarTo + searchIndex + filterMatch (src/database.cpp:1468-1503, 1691-1757, 1209-1247) and
+ * matches[0] after the sort of src/engine.cpp:441, with filterSelf on:
+ *   a needle with hash 0 finds nothing (src/dcthashindex.cpp:196-200); a haystack hash 0 is a value like any other;
+ *   candidates = unsorted items flagged in_index with popcount(needle ^ hash) < t, t from thresh; with max_thresh > 0,
+ *   while candidates + self <= min_matches, t + 1 unless that passes max_thresh (:1703-1725) -- self = 1 when t > 0 and
+ *   the needle is in_index (its slice holds it at distance 0); order by (distance, id); the first max_matches; of those,
+ *   path_mode and filter_parent as in cbh_filter_params; accepted iff 1 + kept > min_matches; the answer is the first kept.
+ * mirrorMask and templateMatch need images and have no counterpart here.
+ * The batch is ragged: set s = items set_first[s] .. set_first[s+1] of hashes / ids / in_index (NULL: all in the index) /
+ * dir_id (may be NULL without filter_parent) / under_prefix (may be NULL with path_mode 0); its first item is the start.
+ * out_ids is parallel to ids: out_ids[set_first[s] .. + out[s].sorted) is the order, the rest of the set's range is 0.
+ * out[s]: sorted = items placed, queries, not_found as the loop counts them, behind = hits at j > 0.  Sets of 0 or 1
+ * items: sorted = n, no queries.  One launch for the whole batch, one workgroup per set (sortsimilar.hip).
+ * CBH_E_INVAL: an id 0, an id twice in a set, look_behind outside 1..8, max_matches outside 1..55, thresholds outside
+ * 0..65, an attribute array the params need missing; CBH_E_UNSUPPORTED: a set above CBH_SORT_SIMILAR_MAX items.
+ * _dev: every array in device memory, work queued on `stream`; it waits for the stream twice (the set sizes, the id
+ * check) before the ordering kernel is queued, and not after it. */
+#define CBH_SORT_SIMILAR_MAX 65536
+typedef struct cbh_sort_similar_params {
+  int thresh, max_thresh, min_matches, max_matches; /* max_matches 1..55 */
+  int filter_parent, path_mode;                     /* as cbh_filter_params */
+  int look_behind;                                  /* the reference's 5 (:1530); 1..8 */
+} cbh_sort_similar_params;
+typedef struct cbh_sort_similar_result {
+  uint32_t sorted, queries, not_found, behind;
+} cbh_sort_similar_result;
+int cbh_sort_similar(const uint64_t* hashes, const uint32_t* ids, const uint8_t* in_index, const uint32_t* dir_id,
+                     const uint8_t* under_prefix, const uint64_t* set_first, size_t n_sets,
+                     const cbh_sort_similar_params* params, uint32_t* out_ids, cbh_sort_similar_result* out, int device);
+int cbh_sort_similar_dev(const void* d_hashes, const void* d_ids, const void* d_in_index, const void* d_dir_id,
+                         const void* d_under_prefix, const void* d_set_first, size_t n_sets,
+                         const cbh_sort_similar_params* params, void* d_out_ids, void* d_out, int device, void* stream);
+
 /* ---- DctFeaturesIndex: src/dctfeaturesindex.{h,cpp} over src/tree/hammingtree.h -----------------
  * The index is a cbh_idx64 whose entries are (mediaId, keypoint hash) pairs, several per media:
  *   load/add      -> cbh_idx64_load / cbh_idx64_add with one entry per hash (:229-238, :143-156)
