@@ -266,6 +266,14 @@ _SIGS = {
     "cbh_bgr2gray_ragged_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]),
     "cbh_tm_match_points_dev": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, C.c_int, C.c_int, _vp, _vp, _vp, _sz, _vp,
                                           C.c_int, _vp]),
+    "cbh_template_match_pairs": (C.c_int, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _sz, _vp, _vp, C.c_int]),
+    "cbh_template_match_pairs_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _sz, _vp, _vp, C.c_int,
+                                               _vp]),
+    "cbh_tm_match_points_pairs_dev": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, C.c_int, C.c_int, _vp, _vp,
+                                                _vp, _sz, _vp, C.c_int, _vp]),
+    "cbh_warp_affine_ragged_dev": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             C.c_int, _vp]),
+    "cbh_tm_pairs_stage_ms": (C.c_int, [C.c_int, _vp, _vp, _vp]),
     "cbh_vindexer_create": (_vp, [C.c_int, C.c_int, C.c_int]),
     "cbh_vindexer_destroy": (None, [_vp]),
     "cbh_vindexer_resume": (C.c_int, [_vp, _vp, _vp, _sz]),

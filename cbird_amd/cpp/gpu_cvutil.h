@@ -398,6 +398,46 @@ inline void gpuTemplateMatchImages(const cv::Mat& tmplImg, const std::vector<cv:
   if (rc) qFatal("gpuTemplateMatchImages: %s (%s)", cbh_strerror(rc), cbh_last_error());
 }
 
+// gpuTemplateMatchImages for a batch of result groups in ONE call: what Database::similar does once per needle when
+// params.templateMatch is set (src/database.cpp:1418: TemplateMatcher().match(needle, match, params) right after
+// searchIndex).  images: every decoded image once (the needles and their candidates; an image may be a template in some
+// pairs and a candidate in others), 8-bit, one channel count; pairs[p] = (template, candidate) as indexes of `images`, in
+// any order.  results[p] is what gpuTemplateMatchImages(images[pairs[p].first], {images[pairs[p].second]}, ...) gives as
+// results[0].  The caller keeps what is its own, per group: loading, the md5-pair cache, the threshold and the sort.
+template <class Params>
+inline void gpuTemplateMatchPairs(const std::vector<cv::Mat>& images, const std::vector<std::pair<int, int>>& pairs,
+                                  const Params& params, std::vector<cbh_tm_image_result>& results) {
+  const size_t n = pairs.size();
+  results.assign(n, cbh_tm_image_result());
+  if (n == 0) return;
+  if (images.empty()) qFatal("gpuTemplateMatchPairs: pairs without images");
+  const int cn = images[0].channels();
+  std::vector<uint64_t> off;
+  std::vector<uint32_t> w, h, step, pt, pc;
+  std::vector<uint8_t> buf;
+  for (size_t i = 0; i < images.size(); ++i) {
+    const cv::Mat& m = images[i];
+    if (m.rows <= 0 || m.cols <= 0 || m.depth() != CV_8U || m.channels() != cn)
+      qFatal("gpuTemplateMatchPairs: expected non-empty 8-bit images of one channel count");
+    const size_t row = size_t(m.cols) * size_t(cn);
+    off.push_back((buf.size() + 15) / 16 * 16);
+    buf.resize(size_t(off.back()) + row * size_t(m.rows));
+    for (int y = 0; y < m.rows; ++y) memcpy(buf.data() + off.back() + size_t(y) * row, m.ptr<uint8_t>(y), row);
+    w.push_back(uint32_t(m.cols)), h.push_back(uint32_t(m.rows)), step.push_back(uint32_t(row));
+  }
+  for (size_t p = 0; p < n; ++p) {
+    if (pairs[p].first < 0 || pairs[p].second < 0 || size_t(pairs[p].first) >= images.size() ||
+        size_t(pairs[p].second) >= images.size())
+      qFatal("gpuTemplateMatchPairs: a pair names an image that is not in the table");
+    pt.push_back(uint32_t(pairs[p].first)), pc.push_back(uint32_t(pairs[p].second));
+  }
+  const cbh_tm_params p = {int32_t(params.needleFeatures), int32_t(params.haystackFeatures), int32_t(params.cvThresh),
+                           int32_t(params.tmScalePct)};
+  const int rc = cbh_template_match_pairs(buf.data(), buf.size(), images.size(), off.data(), w.data(), h.data(), step.data(),
+                                          cn, pt.data(), pc.data(), n, &p, results.data(), hashDevice());
+  if (rc) qFatal("gpuTemplateMatchPairs: %s (%s)", cbh_strerror(rc), cbh_last_error());
+}
+
 // qualityScore(const Media&) (src/cimgops.cpp:313-596) for images that are already decoded: 8-bit cv::Mat of 1, 3 (BGR)
 // or 4 (BGRA) channels, the layout loadImage / qImageToCvImg give.  Only the red channel takes part, as in the
 // reference (its crop keeps channel 0 of qImageToCImg's planes).  INT32_MIN = no score (no edges at all, or a side of 1,

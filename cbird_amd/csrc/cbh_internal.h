@@ -475,6 +475,38 @@ int launch_orb_describe(const uint8_t* d_imgs, size_t n, const uint64_t* img_off
                         const uint32_t* kp_first, cbh_keypoint* out_kp, uint8_t* out_desc, uint32_t* out_first,
                         hipStream_t s);
 
+// ---- tmpairs.hip: the kernels the grouped template match adds, launched from tmimages.hip and tmatch.hip ---------------
+constexpr int kTmMatchBlock = 256;     // k_tm_match / k_tm_match_pairs: threads per block, one query row each
+constexpr int kTmTrainPiece = 1024;    // ... and the train rows they stage in LDS at a time (32 KB)
+struct TSet {                          // a candidate's train set: n rows from row `base` of the templates' descriptor rows
+  unsigned base, n;
+};
+struct WImage;  // warp_px.h
+struct PPatch;
+// k_tm_match's launch (grid (tiles, m), candidates cand0 ..) with the train set per candidate
+void launch_tm_match_pairs(bool emit, unsigned tiles, unsigned m, hipStream_t s, const uint8_t* d_train, const TSet* d_tsets,
+                           const uint8_t* d_desc, const uint32_t* d_counts, unsigned kp_cap, unsigned max_dist, unsigned cand0,
+                           unsigned* d_qcount, const unsigned* d_qoff, const unsigned long long* d_first,
+                           unsigned long long base, unsigned g0, unsigned long long* d_keys, unsigned long long cap);
+// grid (x, candidates): candidate blockIdx.y of the tables warps into its own patch / is masked by its own template
+void launch_warp_ragged(int channels, dim3 grid, hipStream_t s, const uint8_t* d_imgs, const WImage* d_images,
+                        const double* d_wm, const unsigned char* d_ok, const PPatch* d_patches, uint8_t* d_out);
+void launch_tm_mask_ragged(dim3 grid, hipStream_t s, const uint8_t* d_patches, const uint8_t* d_tmpl_base,
+                           const PPatch* d_tab, int channels, uint8_t* d_cand_gray, uint8_t* d_tmpl_gray);
+
+// ---- tmatch.hip: estimate -> prepare -> ragged warp -> mask -> hashes -> records for candidates that each have their own
+// template (the tail of tmimages.hip's grouped chain).  tg (host, n): candidate i's template, bytes at d_tmpl_base + off.
+// res (host, n) is complete on return; *hash_launches (optional) is advanced by the launch_dcthash calls made.
+struct TmplGeom {
+  uint64_t off;
+  uint32_t tw, th, stride;
+};
+int template_match_pairs_tail(const uint8_t* d_tmpl_base, const TmplGeom* tg, const uint8_t* d_imgs, size_t n,
+                              const uint64_t* img_off, const uint32_t* img_w, const uint32_t* img_h,
+                              const uint32_t* img_row_stride, int channels, const float* d_tmpl_xy, const float* d_match_xy,
+                              const uint64_t* first, const float* cand_scale, cbh_template_result* res, unsigned* hash_launches,
+                              hipStream_t s);
+
 // ---- prestage.hip: the fixed-point Lanczos-4 tables of cv::resize (dsize offsets, dsize x 8 weights), built on the host --
 void lanczos4_table(int ssize, int dsize, std::vector<int>* ofs, std::vector<short>* coef);
 

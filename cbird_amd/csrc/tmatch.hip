@@ -21,6 +21,8 @@
 //                 lane's store is one aligned 4 * CH byte vector store and a wave writes 256 * CH contiguous bytes); the
 //                 coordinate integers adelta / bdelta are recomputed per pixel in double, X0 / Y0 per lane and row, four taps
 //                 of CH bytes are gathered.  Gather-bound: a wave's taps follow a line through the candidate image.
+// The grouped chain's tail (template_match_pairs_tail, a template per candidate) launches the same kernels and, for the
+// warp and the mask, tmpairs.hip's ragged forms; warp_px.h holds the pixel both warps share.
 // The file is built with -ffp-contract=off (Makefile): every float / double operation rounds once, as in the model.
 #include <cfloat>
 #include <climits>
@@ -33,6 +35,7 @@
 #include "cbh_index.h"
 #include "cbh_runs.h"
 #include "cbh_staging.h"
+#include "warp_px.h"
 
 namespace cbh {
 namespace {
@@ -48,10 +51,6 @@ struct RProblem {
   unsigned long long first;  // first pair of the list in a_xy / b_xy
   unsigned count;
   float b_div;               // B is divided by this in float (1: as it is; x / 1.0f == x)
-};
-struct WImage {
-  unsigned long long off;
-  unsigned w, h, stride, pad;
 };
 
 // ---- getRTMatrix(fullAffine = false): x = V diag(1 / lambda) V^T b by cyclic Jacobi ---------------------------------
@@ -273,9 +272,11 @@ __global__ __launch_bounds__(64) void k_ransac(const float2* __restrict__ a_xy, 
 __global__ __launch_bounds__(64) void k_tm_prepare(const double* __restrict__ m_in, const unsigned char* __restrict__ found,
                                                    unsigned m_step, unsigned n, int tw, int th,
                                                    const float* __restrict__ scale, double* __restrict__ wm,
-                                                   unsigned char* __restrict__ ok, int* __restrict__ roi) {
+                                                   unsigned char* __restrict__ ok, int* __restrict__ roi,
+                                                   const PPatch* __restrict__ ragged) {
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if (ragged) tw = (int)ragged[i].tw, th = (int)ragged[i].th;  // the grouped chain: every candidate has its own template
   const double* M = m_in + (size_t)i * m_step * 6;
   double w[6] = {0, 0, 0, 0, 0, 0};
   bool good = found[(size_t)i * m_step] != 0;
@@ -315,38 +316,6 @@ __global__ __launch_bounds__(64) void k_tm_prepare(const double* __restrict__ m_
       roi[(size_t)i * 8 + 2 * c + 1] = good ? (int)qy : 0;
     }
   }
-}
-
-template <int CH>
-__device__ __forceinline__ void warp_pixel(const unsigned char* __restrict__ imgs, const WImage& im,
-                                           const double* __restrict__ M, int x, int X0, int Y0, unsigned (&px)[CH]) {
-  // adelta[x], bdelta[x] (AB_BITS 10, INTER_BITS 5); cvRound = round half to even; X0 / Y0 are the row's (row_start)
-  const int adx = (int)rint(M[0] * (double)x * 1024.0), bdx = (int)rint(M[3] * (double)x * 1024.0);
-  const int X = (X0 + adx) >> 5, Y = (Y0 + bdx) >> 5;
-  const int sx = min(max(X >> 5, -32768), 32767), sy = min(max(Y >> 5, -32768), 32767);  // saturate_cast<short>
-  const int fx = X & 31, fy = Y & 31;
-  const int wgt[4] = {(32 - fx) * (32 - fy) * 32, fx * (32 - fy) * 32, (32 - fx) * fy * 32, fx * fy * 32};
-  int acc[CH];
-#pragma unroll
-  for (int c = 0; c < CH; ++c) acc[c] = 16384;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int xx = sx + (t & 1), yy = sy + (t >> 1);
-    const bool inside = xx >= 0 && xx < (int)im.w && yy >= 0 && yy < (int)im.h;
-    const unsigned char* p = imgs + im.off + (unsigned long long)(inside ? yy : 0) * im.stride + (size_t)(inside ? xx : 0) * CH;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      const int border = (CH == 4 && c == 3) ? 255 : 0;  // Scalar(0, 0, 0, 255)
-      acc[c] += wgt[t] * (inside ? (int)p[c] : border);
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < CH; ++c) px[c] = (unsigned)(acc[c] >> 15);
-}
-
-// X0 / Y0 of a patch row
-__device__ __forceinline__ void row_start(const double* __restrict__ M, int y, int& X0, int& Y0) {
-  X0 = (int)rint((M[1] * (double)y + M[2]) * 1024.0) + 16, Y0 = (int)rint((M[4] * (double)y + M[5]) * 1024.0) + 16;
 }
 
 // out: packed patches of candidates i0 .. (flat bytes, 4 * CH per lane); total = pixels of this launch
@@ -484,7 +453,116 @@ int queue_warp(Scratch& scratch, std::vector<WImage>& images, const uint8_t* d_i
 
 size_t tmatch_budget() { return (size_t)std::max(g_tmatch_chunk_mb, 1) << 20; }
 
+// the ragged warp of n candidates; images / patches are host memory: the caller synchronises
+int queue_warp_ragged(Scratch& scratch, std::vector<WImage>& images, const std::vector<PPatch>& patches,
+                      const PPatch* d_patches_tab, const uint8_t* d_imgs, const uint64_t* img_off, const uint32_t* img_w,
+                      const uint32_t* img_h, const uint32_t* img_row_stride, int channels, const double* d_wm,
+                      const unsigned char* d_ok, uint8_t* d_out, hipStream_t s) {
+  const size_t n = patches.size();
+  images.resize(n);
+  for (size_t i = 0; i < n; ++i) images[i] = {img_off[i], img_w[i], img_h[i], img_row_stride[i], 0u};
+  WImage* d_images = nullptr;
+  const hipError_t e = upload(scratch, &d_images, images, s);
+  if (e != hipSuccess) return fail("warp tables", e);
+  for (size_t i0 = 0; i0 < n; i0 += 65535) {
+    const size_t m = std::min<size_t>(65535, n - i0);
+    unsigned long long most = 1;
+    for (size_t i = i0; i < i0 + m; ++i) most = std::max(most, (unsigned long long)patches[i].tw * patches[i].th);
+    const dim3 grid((unsigned)std::min<unsigned long long>((most + 4 * kWarpBlock - 1) / (4 * kWarpBlock), 4096), (unsigned)m);
+    launch_warp_ragged(channels, grid, s, d_imgs, d_images + i0, d_wm + i0 * 6, d_ok + i0, d_patches_tab + i0, d_out);
+  }
+  return CBH_OK;
+}
+
 }  // namespace
+
+// cbh_template_match_dev for candidates that each have a template of their own (tmimages.hip's grouped chain): candidate i
+// is matched against the tg[i].tw x tg[i].th template at d_tmpl_base + tg[i].off.  One RANSAC launch, one prepare, one
+// ragged warp and one ragged mask for all of them; the hashes keep their per-geometry launch plan -- one launch_dcthash
+// pair per run of consecutive candidates with the same template size, queued back to back (launch_dcthash takes arena
+// scratch per call but neither synchronises nor reaches the driver once a geometry's tables exist).  res is host memory
+// and complete on return: the one wait of this function.
+int template_match_pairs_tail(const uint8_t* d_tmpl_base, const TmplGeom* tg, const uint8_t* d_imgs, size_t n,
+                              const uint64_t* img_off, const uint32_t* img_w, const uint32_t* img_h,
+                              const uint32_t* img_row_stride, int channels, const float* d_tmpl_xy, const float* d_match_xy,
+                              const uint64_t* first, const float* cand_scale, cbh_template_result* res, unsigned* hash_launches,
+                              hipStream_t s) {
+  if (n == 0) return CBH_OK;
+  if (!lists_ok(first, n)) return CBH_E_INVAL;
+  std::vector<PPatch> patches(n);
+  size_t patch_bytes = 0, gray_bytes = 0;
+  for (size_t i = 0; i < n; ++i) {
+    patches[i] = {patch_bytes, tg[i].off, gray_bytes, tg[i].tw, tg[i].th, tg[i].stride, 0u};
+    patch_bytes += ((size_t)tg[i].tw * tg[i].th * channels + 15) & ~(size_t)15;
+    gray_bytes += (size_t)tg[i].tw * tg[i].th;  // (packed: a run of one size is what launch_dcthash takes)
+  }
+  Scratch scratch(s), tables(s);
+  std::vector<RProblem> probs;
+  std::vector<WImage> images;
+  double *d_m = nullptr, *d_wm = nullptr;
+  unsigned char *d_found = nullptr, *d_ok = nullptr, *d_gray = nullptr;
+  cbh_rigid_detail* d_detail = nullptr;
+  int* d_roi = nullptr;
+  float* d_scale = nullptr;
+  unsigned long long* d_hash = nullptr;
+  uint8_t* d_p = nullptr;
+  cbh_template_result* d_res = nullptr;
+  PPatch* d_tab = nullptr;
+  hipError_t e = scratch.get(&d_m, n * 12 * sizeof(double));
+  if (e == hipSuccess) e = scratch.get(&d_wm, n * 6 * sizeof(double));
+  if (e == hipSuccess) e = scratch.get(&d_found, n * 2);
+  if (e == hipSuccess) e = scratch.get(&d_ok, n);
+  if (e == hipSuccess) e = scratch.get(&d_detail, n * 2 * sizeof(cbh_rigid_detail));
+  if (e == hipSuccess) e = scratch.get(&d_roi, n * 8 * sizeof(int));
+  if (e == hipSuccess) e = scratch.get(&d_hash, n * 2 * sizeof(unsigned long long));
+  if (e == hipSuccess) e = scratch.get(&d_p, patch_bytes);
+  if (e == hipSuccess) e = scratch.get(&d_gray, 2 * gray_bytes);
+  if (e == hipSuccess) e = scratch.get(&d_res, n * sizeof(cbh_template_result));
+  if (e == hipSuccess) e = upload(tables, &d_scale, cand_scale, n, s);
+  if (e == hipSuccess) e = upload(tables, &d_tab, patches, s);
+  int rc = e == hipSuccess ? CBH_OK : fail("template match pairs scratch", e);
+  if (rc == CBH_OK)
+    rc = queue_ransac(tables, probs, d_tmpl_xy, d_match_xy, first, n, 2, cand_scale, d_m, d_found, d_detail, s);
+  if (rc == CBH_OK) {
+    hipLaunchKernelGGL(k_tm_prepare, dim3(((unsigned)n + 63) / 64), dim3(64), 0, s, d_m, d_found, 2u, (unsigned)n, 0, 0,
+                       d_scale, d_wm, d_ok, d_roi, (const PPatch*)d_tab);
+    rc = queue_warp_ragged(tables, images, patches, d_tab, d_imgs, img_off, img_w, img_h, img_row_stride, channels, d_wm, d_ok,
+                           d_p, s);
+  }
+  if (rc == CBH_OK) {
+    unsigned char *cg = d_gray, *tgray = d_gray + gray_bytes;
+    for (size_t i0 = 0; i0 < n; i0 += 65535) {
+      const size_t m = std::min<size_t>(65535, n - i0);
+      unsigned long long most = 1;
+      for (size_t i = i0; i < i0 + m; ++i) most = std::max(most, (unsigned long long)patches[i].tw * patches[i].th);
+      launch_tm_mask_ragged(dim3((unsigned)std::min<unsigned long long>(1024, (most + 255) / 256), (unsigned)m), s, d_p,
+                            d_tmpl_base, d_tab + i0, channels, cg, tgray);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) rc = fail("template match pairs", e);
+    for (size_t i0 = 0; i0 < n && rc == CBH_OK;) {
+      const size_t px = (size_t)tg[i0].tw * tg[i0].th;
+      const size_t per = std::max<size_t>(1, std::min<size_t>(65535, ((size_t)1 << 30) / px));  // (cbh_template_hashes_dev's)
+      size_t i1 = i0 + 1;
+      while (i1 < n && i1 - i0 < per && tg[i1].tw == tg[i0].tw && tg[i1].th == tg[i0].th) ++i1;
+      const size_t g0 = (size_t)patches[i0].gray_off;
+      rc = launch_dcthash(cg + g0, i1 - i0, (int)tg[i0].tw, (int)tg[i0].th, tg[i0].tw, px, (uint64_t*)d_hash + i0, s);
+      if (rc == CBH_OK)
+        rc = launch_dcthash(tgray + g0, i1 - i0, (int)tg[i0].tw, (int)tg[i0].th, tg[i0].tw, px, (uint64_t*)d_hash + n + i0, s);
+      if (hash_launches) *hash_launches += 2;
+      i0 = i1;
+    }
+  }
+  if (rc == CBH_OK) {
+    hipLaunchKernelGGL(k_tm_finish, dim3(((unsigned)n + 63) / 64), dim3(64), 0, s, d_m, d_found, d_detail, d_ok, d_roi, d_hash,
+                       d_hash + n, (unsigned)n, d_res);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(res, d_res, n * sizeof(cbh_template_result), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) rc = fail("template match pairs", e);
+  }
+  e = hipStreamSynchronize(s);  // the results; and the host tables are leaving
+  if (rc == CBH_OK && e != hipSuccess) rc = fail("template match pairs", e);
+  return rc;
+}
 
 void set_tmatch_chunk_mb(int v) {
   if (v > 0) g_tmatch_chunk_mb = v;
@@ -565,7 +643,8 @@ int cbh_warp_affine_dev(const void* d_imgs, size_t n, const uint64_t* img_off, c
   if (e == hipSuccess) e = scratch.get(&d_ok, n);
   if (e != hipSuccess) return cbh::fail("warp scratch", e);
   hipLaunchKernelGGL(cbh::k_tm_prepare, dim3(((unsigned)n + 63) / 64), dim3(64), 0, s, (const double*)d_m,
-                     (const unsigned char*)d_found, 1u, (unsigned)n, tw, th, (const float*)nullptr, d_wm, d_ok, (int*)nullptr);
+                     (const unsigned char*)d_found, 1u, (unsigned)n, tw, th, (const float*)nullptr, d_wm, d_ok, (int*)nullptr,
+                     (const cbh::PPatch*)nullptr);
   std::vector<cbh::WImage> images;
   int rc = cbh::queue_warp(scratch, images, (const uint8_t*)d_imgs, n, img_off, img_w, img_h, img_row_stride, channels, d_wm,
                            d_ok, tw, th, (uint8_t*)d_patches, s);
@@ -574,6 +653,50 @@ int cbh_warp_affine_dev(const void* d_imgs, size_t n, const uint64_t* img_off, c
   if (e == hipSuccess && d_warped) e = hipMemcpyAsync(d_warped, d_ok, n, hipMemcpyDeviceToDevice, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);  // the host table must outlive its copy
   return e == hipSuccess ? CBH_OK : cbh::fail("warp", e);
+}
+
+int cbh_warp_affine_ragged_dev(const void* d_imgs, size_t n, const uint64_t* img_off, const uint32_t* img_w,
+                               const uint32_t* img_h, const uint32_t* img_row_stride, int channels, const void* d_m,
+                               const void* d_found, const uint32_t* tw, const uint32_t* th, const uint64_t* patch_off,
+                               void* d_patches, void* d_warped, int device, void* stream) {
+  if (!cbh::device_usable(device)) return CBH_E_NODEVICE;
+  if (n == 0) return CBH_OK;
+  if (!d_imgs || !img_off || !img_w || !img_h || !img_row_stride || !d_m || !d_found || !tw || !th || !patch_off ||
+      !d_patches || !cbh::channels_ok(channels) || n > (1u << 24) || ((uintptr_t)d_patches & 15))
+    return CBH_E_INVAL;
+  std::vector<cbh::PPatch> patches(n);
+  for (size_t i = 0; i < n; ++i) {
+    if (!cbh::image_ok(img_w[i], img_h[i], img_row_stride[i], channels) || tw[i] < 1 || th[i] < 1 || tw[i] > 32767 ||
+        th[i] > 32767 || (patch_off[i] & 15))
+      return CBH_E_INVAL;
+    patches[i] = {patch_off[i], 0ull, 0ull, tw[i], th[i], 0u, 0u};
+  }
+  cbh::DeviceGuard g(device);
+  if (!g.ok) return CBH_E_NODEVICE;
+  hipStream_t s = (hipStream_t)stream;
+  cbh::Scratch scratch(s);
+  double* d_wm = nullptr;
+  unsigned char* d_ok = nullptr;
+  cbh::PPatch* d_tab = nullptr;
+  hipError_t e = scratch.get(&d_wm, n * 6 * sizeof(double));
+  if (e == hipSuccess) e = scratch.get(&d_ok, n);
+  if (e == hipSuccess) e = cbh::upload(scratch, &d_tab, patches, s);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(s);  // the table's copy may be queued
+    return cbh::fail("warp scratch", e);
+  }
+  hipLaunchKernelGGL(cbh::k_tm_prepare, dim3(((unsigned)n + 63) / 64), dim3(64), 0, s, (const double*)d_m,
+                     (const unsigned char*)d_found, 1u, (unsigned)n, 0, 0, (const float*)nullptr, d_wm, d_ok, (int*)nullptr,
+                     (const cbh::PPatch*)d_tab);
+  std::vector<cbh::WImage> images;
+  int rc = cbh::queue_warp_ragged(scratch, images, patches, d_tab, (const uint8_t*)d_imgs, img_off, img_w, img_h, img_row_stride,
+                                  channels, d_wm, d_ok, (uint8_t*)d_patches, s);
+  e = hipGetLastError();
+  if (rc == CBH_OK && e == hipSuccess && d_warped) e = hipMemcpyAsync(d_warped, d_ok, n, hipMemcpyDeviceToDevice, s);
+  const hipError_t e2 = hipStreamSynchronize(s);  // the host tables must outlive their copies
+  if (rc != CBH_OK) return rc;
+  if (e == hipSuccess) e = e2;
+  return e == hipSuccess ? CBH_OK : cbh::fail("ragged warp", e);
 }
 
 int cbh_template_match_dev(const void* d_tmpl, int tw, int th, size_t tmpl_row_stride, int tmpl_channels, const void* d_imgs,
@@ -631,7 +754,7 @@ int cbh_template_match_dev(const void* d_tmpl, int tw, int th, size_t tmpl_row_s
       return rc;
     }
     hipLaunchKernelGGL(cbh::k_tm_prepare, dim3(((unsigned)m + 63) / 64), dim3(64), 0, s, d_m, d_found, 2u, (unsigned)m, tw, th,
-                       d_scale, d_wm, d_ok, d_roi);
+                       d_scale, d_wm, d_ok, d_roi, (const cbh::PPatch*)nullptr);
     rc = cbh::queue_warp(scratch, images, (const uint8_t*)d_imgs, m, img_off + i0, img_w + i0, img_h + i0, img_row_stride + i0,
                          channels, d_wm, d_ok, tw, th, d_p, s);
     if (rc == CBH_OK && (e = hipGetLastError()) != hipSuccess) rc = cbh::fail("template match", e);

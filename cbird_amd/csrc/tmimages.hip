@@ -17,6 +17,9 @@
 //                        guessed and nothing is retried.
 //   k_tm_gather          :241-250 from the ordered keys and the kp_after tables: the tmplPoints / matchPoints lists
 // and cbh_template_match_images(_dev), the chain resize -> grey -> ORB -> match -> gather -> cbh_template_match_dev.
+// cbh_template_match_pairs(_dev) is the same chain for (template image, candidate image) pairs over one image table --
+// Database::similar's call of the matcher once per needle (src/database.cpp:1418) as one call: run_pairs below, with
+// tmpairs.hip's kernels where a candidate has a template of its own and tmatch.hip's template_match_pairs_tail.
 //
 // UNPINNED, as tmatch.hip and orb.hip are: OpenCV is not available to this repository; the estimate, the warp and ORB are
 // restated as recalled.  The resize, the grey conversion and the match are integer arithmetic checked against the oracle.
@@ -36,8 +39,8 @@
 namespace cbh {
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kTrainPiece = 1024;  // train rows in LDS at a time (32 KB); any number of rows, piece by piece
+constexpr int kBlock = kTmMatchBlock;
+constexpr int kTrainPiece = kTmTrainPiece;  // train rows in LDS at a time (32 KB); any number of rows, piece by piece
 constexpr int kQueryBits = 23;     // of a key's query field (the record layout of hamm256_scan.hip)
 constexpr unsigned long long kGroupKeys = 1ull << 26;  // keys sorted at a time (512 MB), unless one candidate has more
 
@@ -281,13 +284,13 @@ __global__ __launch_bounds__(kBlock) void k_tm_gather(const unsigned long long* 
                                                       unsigned long long base, unsigned g0, unsigned kp_cap,
                                                       const float2* __restrict__ tmpl_xy, const float2* __restrict__ cand_xy,
                                                       float2* __restrict__ tmpl_pts, float2* __restrict__ match_pts,
-                                                      cbh_dmatch* __restrict__ records) {
+                                                      cbh_dmatch* __restrict__ records, const TSet* __restrict__ tsets) {
   const unsigned long long r = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
   if (r >= cnt) return;
   const unsigned long long key = keys[r];
   const unsigned q = (unsigned)(key >> 41), d = (unsigned)(key >> 32) & 0x1ffu, t = (unsigned)key;
   const unsigned cand = g0 + q / kp_cap, row = q % kp_cap;
-  tmpl_pts[base + r] = tmpl_xy[t];
+  tmpl_pts[base + r] = tmpl_xy[(tsets ? (size_t)tsets[cand].base : 0) + t];  // (the grouped chain: its own template's)
   match_pts[base + r] = cand_xy[(size_t)cand * kp_cap + row];
   if (records) {
     cbh_dmatch m;
@@ -389,7 +392,8 @@ bool match_shape_ok(size_t n_train, size_t n, int kp_cap, int max_dist) {
 
 // counting pass + scans; `first` (host, n + 1) is complete when this returns (it synchronises the stream)
 int match_count(Scratch& scratch, MatchState& st, const uint8_t* d_train, size_t n_train, const uint8_t* d_desc,
-                const uint32_t* d_counts, size_t n, int kp_cap, int max_dist, uint64_t* first, hipStream_t s) {
+                const uint32_t* d_counts, size_t n, int kp_cap, int max_dist, uint64_t* first, hipStream_t s,
+                const TSet* d_tsets = nullptr) {
   if (n_train == 0) {
     std::fill(first, first + n + 1, (uint64_t)0);
     return CBH_OK;
@@ -403,10 +407,14 @@ int match_count(Scratch& scratch, MatchState& st, const uint8_t* d_train, size_t
   const unsigned tiles = ((unsigned)kp_cap + kBlock - 1) / kBlock;
   for (size_t i0 = 0; i0 < n; i0 += 65535) {
     const unsigned m = (unsigned)std::min<size_t>(65535, n - i0);
-    hipLaunchKernelGGL(k_tm_match<false>, dim3(tiles, m), dim3(kBlock), 0, s, (const uint4*)d_train, (unsigned)n_train,
-                       (const uint4*)d_desc, d_counts, (unsigned)kp_cap, (unsigned)max_dist, (unsigned)i0, st.d_qcount,
-                       (const unsigned*)nullptr, (const unsigned long long*)nullptr, 0ull, 0u, (unsigned long long*)nullptr,
-                       0ull);
+    if (d_tsets)  // the grouped chain: a train set per candidate (tmpairs.hip)
+      launch_tm_match_pairs(false, tiles, m, s, d_train, d_tsets, d_desc, d_counts, (unsigned)kp_cap, (unsigned)max_dist,
+                            (unsigned)i0, st.d_qcount, nullptr, nullptr, 0ull, 0u, nullptr, 0ull);
+    else
+      hipLaunchKernelGGL(k_tm_match<false>, dim3(tiles, m), dim3(kBlock), 0, s, (const uint4*)d_train, (unsigned)n_train,
+                         (const uint4*)d_desc, d_counts, (unsigned)kp_cap, (unsigned)max_dist, (unsigned)i0, st.d_qcount,
+                         (const unsigned*)nullptr, (const unsigned long long*)nullptr, 0ull, 0u,
+                         (unsigned long long*)nullptr, 0ull);
   }
   for (size_t i0 = 0; i0 < n; i0 += 1u << 20)
     hipLaunchKernelGGL(k_tm_scan_queries, dim3((unsigned)std::min<size_t>(1u << 20, n - i0)), dim3(kBlock), 0, s, st.d_qcount,
@@ -421,7 +429,8 @@ int match_count(Scratch& scratch, MatchState& st, const uint8_t* d_train, size_t
 // emitting pass, the sort and the gather for first[n] pairs (the lists have room for them)
 int match_emit(const MatchState& st, const uint8_t* d_train, size_t n_train, const float* d_tmpl_xy, const uint8_t* d_desc,
                const float* d_xy, const uint32_t* d_counts, size_t n, int kp_cap, int max_dist, const uint64_t* first,
-               cbh_dmatch* d_records, float* d_tmpl_pts, float* d_match_pts, hipStream_t s) {
+               cbh_dmatch* d_records, float* d_tmpl_pts, float* d_match_pts, hipStream_t s,
+               const TSet* d_tsets = nullptr) {
   if (first[n] == 0) return CBH_OK;
   const unsigned tiles = ((unsigned)kp_cap + kBlock - 1) / kBlock;
   const size_t most = std::min<size_t>(65535, ((size_t)1 << kQueryBits) / (size_t)kp_cap);
@@ -434,10 +443,15 @@ int match_emit(const MatchState& st, const uint8_t* d_train, size_t n_train, con
       unsigned long long* d_keys = nullptr;
       hipError_t e = scratch.get(&d_keys, cnt * sizeof(unsigned long long));
       if (e != hipSuccess) return fail("descriptor match keys", e);
-      hipLaunchKernelGGL(k_tm_match<true>, dim3(tiles, (unsigned)(g1 - g0)), dim3(kBlock), 0, s, (const uint4*)d_train,
-                         (unsigned)n_train, (const uint4*)d_desc, d_counts, (unsigned)kp_cap, (unsigned)max_dist, (unsigned)g0,
-                         (unsigned*)nullptr, (const unsigned*)st.d_qoff, (const unsigned long long*)st.d_first,
-                         (unsigned long long)first[g0], (unsigned)g0, d_keys, cnt);
+      if (d_tsets)
+        launch_tm_match_pairs(true, tiles, (unsigned)(g1 - g0), s, d_train, d_tsets, d_desc, d_counts, (unsigned)kp_cap,
+                              (unsigned)max_dist, (unsigned)g0, nullptr, st.d_qoff, st.d_first, (unsigned long long)first[g0],
+                              (unsigned)g0, d_keys, cnt);
+      else
+        hipLaunchKernelGGL(k_tm_match<true>, dim3(tiles, (unsigned)(g1 - g0)), dim3(kBlock), 0, s, (const uint4*)d_train,
+                           (unsigned)n_train, (const uint4*)d_desc, d_counts, (unsigned)kp_cap, (unsigned)max_dist, (unsigned)g0,
+                           (unsigned*)nullptr, (const unsigned*)st.d_qoff, (const unsigned long long*)st.d_first,
+                           (unsigned long long)first[g0], (unsigned)g0, d_keys, cnt);
       if ((e = hipGetLastError()) != hipSuccess) return fail("descriptor match", e);
       int bits = 0;
       while (((size_t)1 << bits) < (g1 - g0) * (size_t)kp_cap) ++bits;
@@ -445,7 +459,7 @@ int match_emit(const MatchState& st, const uint8_t* d_train, size_t n_train, con
       if (rc != CBH_OK) return rc;
       hipLaunchKernelGGL(k_tm_gather, dim3((unsigned)((cnt + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, d_keys, cnt,
                          (unsigned long long)first[g0], (unsigned)g0, (unsigned)kp_cap, (const float2*)d_tmpl_xy,
-                         (const float2*)d_xy, (float2*)d_tmpl_pts, (float2*)d_match_pts, d_records);
+                         (const float2*)d_xy, (float2*)d_tmpl_pts, (float2*)d_match_pts, d_records, d_tsets);
       if ((e = hipGetLastError()) != hipSuccess) return fail("point gather", e);
     }
     g0 = g1;
@@ -689,10 +703,386 @@ std::vector<Run> candidate_runs(size_t n, const uint64_t* off, const uint32_t* w
   return make_runs(n, off, end.data(), (uint64_t)std::max(get_tmatch_chunk_mb(), 1) << 20, 32768);
 }
 
+// ---- the grouped chain: (template image, candidate image) pairs over one image table --------------------------------
+// Device-event times of the stages of the last grouped call, kept only while cbh_tm_pairs_stage_ms has asked for them.
+struct StageClock {
+  bool on = false;
+  double ms[5] = {0, 0, 0, 0, 0};  // grey, ORB of the templates, ORB of the candidates, match + gather, estimate to score
+  unsigned sizes = 0, hash_launches = 0;
+};
+StageClock g_clock;
+struct StageTimer {  // brackets one stage with two events; read (a host wait) only when the clock is on
+  hipStream_t s;
+  int stage;
+  hipEvent_t a = nullptr, b = nullptr;
+  StageTimer(hipStream_t stream, int st) : s(stream), stage(st) {
+    if (g_clock.on && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) (void)hipEventRecord(a, s);
+  }
+  void stop() {
+    if (!a || !b) return;
+    float ms = 0.f;
+    if (hipEventRecord(b, s) == hipSuccess && hipEventSynchronize(b) == hipSuccess &&
+        hipEventElapsedTime(&ms, a, b) == hipSuccess)
+      g_clock.ms[stage] += ms;
+  }
+  ~StageTimer() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+};
+
+struct PairRef {
+  uint32_t tmpl, cand, out;  // indexes of the image table; results[out]
+};
+
+// m pairs whose equal templates are adjacent: the distinct templates go through grey and ONE ragged ORB, the candidates
+// through resize / grey / ONE ragged ORB, then one grouped match and template_match_pairs_tail.  The host waits are the
+// two ORB counts, `first` and the results, whatever the number of templates.  Returns with the stream synchronised.
+int run_pairs(const uint8_t* d_imgs, const uint64_t* img_off, const uint32_t* img_w, const uint32_t* img_h,
+              const uint32_t* img_row_stride, int ch, const PairRef* pairs, size_t m, const cbh_tm_params* p,
+              cbh_tm_image_result* results, hipStream_t s) {
+  // 1. the distinct templates
+  std::vector<uint32_t> slot(m);
+  std::vector<uint64_t> toff, tgoff;
+  std::vector<uint32_t> tw, th, tst, tgst;
+  size_t tgray_bytes = 0;
+  for (size_t j = 0; j < m; ++j) {
+    if (j == 0 || pairs[j].tmpl != pairs[j - 1].tmpl) {
+      const uint32_t t = pairs[j].tmpl;
+      toff.push_back(img_off[t]), tw.push_back(img_w[t]), th.push_back(img_h[t]), tst.push_back(img_row_stride[t]);
+      tgoff.push_back(tgray_bytes), tgst.push_back(img_w[t]);
+      tgray_bytes += align16((size_t)img_w[t] * img_h[t]);
+    }
+    slot[j] = (uint32_t)toff.size() - 1;
+  }
+  const size_t G = toff.size();
+  Scratch tscratch(s);
+  std::vector<RImage> tkeep;
+  std::vector<std::unique_ptr<Scratch>> theld;
+  std::vector<uint32_t> tcounts(G);
+  OrbOut torb;
+  int rc = CBH_OK;
+  hipError_t e = hipSuccess;
+  {
+    uint8_t* d_tgray = nullptr;
+    StageTimer grey(s, 0);
+    if (ch != 1) {
+      if ((e = tscratch.get(&d_tgray, tgray_bytes)) != hipSuccess) return fail("template match pairs grey", e);
+      rc = queue_gray(tscratch, tkeep, d_imgs, G, toff.data(), tw.data(), th.data(), tst.data(), ch, tgoff.data(), d_tgray, s);
+    }
+    grey.stop();
+    StageTimer orb(s, 1);
+    if (rc == CBH_OK)
+      rc = orb_until_it_fits(theld, torb, ch == 1 ? d_imgs : d_tgray, G, ch == 1 ? toff.data() : tgoff.data(), tw.data(),
+                             th.data(), ch == 1 ? tst.data() : tgst.data(), p->needle_features, tcounts.data(), s);
+    orb.stop();
+    if (rc != CBH_OK) {
+      (void)hipStreamSynchronize(s);  // `tkeep` is leaving
+      return rc;
+    }
+  }
+  // 2. scales and target sizes per pair; `live` = the pairs that go on
+  std::vector<uint32_t> live;
+  std::vector<uint64_t> src_off, woff, goff;
+  std::vector<uint32_t> sw, sh, sst, ww, wh, wst;
+  std::vector<uint8_t> copy;
+  std::vector<float> scale;
+  std::vector<TSet> tsets;
+  std::vector<TmplGeom> geom;
+  size_t work_bytes = 0, gray_bytes = 0, n_train = 0;
+  for (size_t j = 0; j < m; ++j) {
+    cbh_tm_image_result& r = results[pairs[j].out];
+    const uint32_t c = pairs[j].cand, g = slot[j];
+    r = blank_result();
+    int dw, dh;
+    bool resized;
+    cand_target((int)tw[g], (int)th[g], (int)img_w[c], (int)img_h[c], p->tm_scale_pct, &r.cand_scale, &dw, &dh, &resized);
+    r.w = dw, r.h = dh;
+    if (tcounts[g] == 0) {
+      r.status = CBH_TM_NO_TEMPLATE_KEYPOINTS;
+      r.cand_scale = 1.f, r.w = (int)img_w[c], r.h = (int)img_h[c];
+      continue;
+    }
+    if (dw <= 0 || dh <= 0) {
+      r.status = CBH_TM_EMPTY_RESIZE;
+      continue;
+    }
+    if (dw > 8192 || dh > 8192) return CBH_E_INVAL;  // ORB's limit (the stream is idle: orb_until_it_fits waited)
+    live.push_back((uint32_t)j);
+    src_off.push_back(img_off[c]), sw.push_back(img_w[c]), sh.push_back(img_h[c]), sst.push_back(img_row_stride[c]);
+    ww.push_back((uint32_t)dw), wh.push_back((uint32_t)dh), wst.push_back((uint32_t)dw * ch);
+    copy.push_back(resized ? 0 : 1), scale.push_back(r.cand_scale);
+    woff.push_back(work_bytes), goff.push_back(gray_bytes);
+    work_bytes += align16((size_t)dw * dh * ch), gray_bytes += align16((size_t)dw * dh);
+    tsets.push_back({(unsigned)(g * (size_t)torb.kp_cap), tcounts[g]});
+    geom.push_back({toff[g], tw[g], th[g], tst[g]});
+    n_train = std::max<size_t>(n_train, tcounts[g]);
+  }
+  const size_t k = live.size();
+  if (k == 0) return CBH_OK;
+  if (G * (size_t)torb.kp_cap >= (1ull << 32)) return CBH_E_INVAL;  // (a TSet's base is 32 bits)
+  Scratch scratch(s);
+  ResizeTables rkeep;
+  std::vector<RImage> gkeep;
+  std::vector<std::unique_ptr<Scratch>> held;
+  std::vector<uint32_t> counts(k);
+  std::vector<uint64_t> first(k + 1);
+  std::vector<cbh_template_result> res(k);
+  uint8_t *d_work = nullptr, *d_gray = nullptr;
+  float *d_tp = nullptr, *d_mp = nullptr;
+  TSet* d_tsets = nullptr;
+  OrbOut orb;
+  MatchState st;
+  e = scratch.get(&d_work, work_bytes);
+  if (e == hipSuccess && ch != 1) e = scratch.get(&d_gray, gray_bytes);
+  if (e == hipSuccess) e = upload(scratch, &d_tsets, tsets, s);
+  if (e != hipSuccess) rc = fail("template match pairs scratch", e);
+  {
+    StageTimer grey(s, 0);
+    if (rc == CBH_OK)
+      rc = queue_resize(scratch, rkeep, d_imgs, k, src_off.data(), sw.data(), sh.data(), sst.data(), ch, woff.data(), ww.data(),
+                        wh.data(), copy.data(), d_work, s);
+    if (rc == CBH_OK && ch != 1)
+      rc = queue_gray(scratch, gkeep, d_work, k, woff.data(), ww.data(), wh.data(), wst.data(), ch, goff.data(), d_gray, s);
+    grey.stop();
+  }
+  {
+    StageTimer t(s, 2);
+    if (rc == CBH_OK)
+      rc = orb_until_it_fits(held, orb, ch == 1 ? d_work : d_gray, k, ch == 1 ? woff.data() : goff.data(), ww.data(), wh.data(),
+                             ww.data(), p->haystack_features, counts.data(), s);
+    t.stop();
+  }
+  {
+    StageTimer t(s, 3);
+    if (rc == CBH_OK) rc = match_shape_ok(n_train, k, orb.kp_cap, p->cv_thresh) ? CBH_OK : CBH_E_INVAL;
+    if (rc == CBH_OK)
+      rc = match_count(scratch, st, torb.d_desc, n_train, orb.d_desc, orb.d_counts, k, orb.kp_cap, p->cv_thresh, first.data(), s,
+                       d_tsets);
+    if (rc == CBH_OK) {
+      const size_t pts = std::max<uint64_t>(first[k], 1) * 2 * sizeof(float);
+      if ((e = scratch.get(&d_tp, pts)) != hipSuccess || (e = scratch.get(&d_mp, pts)) != hipSuccess)
+        rc = fail("template match pairs point lists", e);
+    }
+    if (rc == CBH_OK)
+      rc = match_emit(st, torb.d_desc, n_train, torb.d_after, orb.d_desc, orb.d_after, orb.d_counts, k, orb.kp_cap, p->cv_thresh,
+                      first.data(), nullptr, d_tp, d_mp, s, d_tsets);
+    t.stop();
+  }
+  {
+    StageTimer t(s, 4);
+    if (rc == CBH_OK)
+      rc = template_match_pairs_tail(d_imgs, geom.data(), d_work, k, woff.data(), ww.data(), wh.data(), wst.data(), ch, d_tp,
+                                     d_mp, first.data(), scale.data(), res.data(), g_clock.on ? &g_clock.hash_launches : nullptr,
+                                     s);
+    t.stop();
+  }
+  e = hipStreamSynchronize(s);  // the host tables of this chunk are leaving
+  if (rc == CBH_OK && e != hipSuccess) rc = fail("template match pairs", e);
+  if (rc != CBH_OK) return rc;
+  if (g_clock.on)
+    for (size_t j = 0; j < k; ++j)
+      if (j == 0 || geom[j].tw != geom[j - 1].tw || geom[j].th != geom[j - 1].th) ++g_clock.sizes;
+  for (size_t j = 0; j < k; ++j) {
+    cbh_tm_image_result& r = results[pairs[live[j]].out];
+    r.r = res[j];
+    r.n_keypoints = counts[j];
+    r.n_matches = (uint32_t)std::min<uint64_t>(first[j + 1] - first[j], 0xffffffffu);
+    r.status = counts[j] == 0      ? CBH_TM_NO_KEYPOINTS
+               : r.n_matches == 0  ? CBH_TM_NO_MATCHES
+               : r.n_matches < 3   ? CBH_TM_FEW_POINTS
+               : !r.r.found        ? CBH_TM_NO_TRANSFORM
+                                   : CBH_TM_SCORED;
+  }
+  return CBH_OK;
+}
+
+bool pairs_args_ok(const void* imgs, size_t n_imgs, const uint64_t* off, const uint32_t* w, const uint32_t* h,
+                   const uint32_t* stride, int channels, const uint32_t* pt, const uint32_t* pc, size_t n_pairs,
+                   const cbh_tm_params* p, const void* results) {
+  if (!imgs || !off || !w || !h || !stride || !pt || !pc || !results || !channels_ok(channels) || !params_ok(p) ||
+      n_imgs > (1u << 24) || n_pairs > (1u << 24))
+    return false;
+  for (size_t i = 0; i < n_imgs; ++i)
+    if (!image_ok(w[i], h[i], stride[i], channels)) return false;
+  for (size_t j = 0; j < n_pairs; ++j)
+    if (pt[j] >= n_imgs || pc[j] >= n_imgs || w[pt[j]] > 8192 || h[pt[j]] > 8192) return false;  // ORB's limit: the template
+  return true;
+}
+
+// The caller's pairs in the order the chain works in -- by template size (runs of one hash geometry), then template, then
+// the caller's order -- cut into chunks whose working set (the templates once, each pair's candidate image and its
+// patch) stays within "tmatch_chunk_mb": make_runs over the running sum of those bytes.
+struct PairPlan {
+  std::vector<PairRef> pairs;
+  std::vector<Run> runs;
+};
+PairPlan plan_pairs(const uint32_t* w, const uint32_t* h, const uint32_t* stride, int channels, const uint32_t* pt,
+                    const uint32_t* pc, size_t n_pairs) {
+  PairPlan plan;
+  plan.pairs.resize(n_pairs);
+  for (size_t j = 0; j < n_pairs; ++j) plan.pairs[j] = {pt[j], pc[j], (uint32_t)j};
+  std::sort(plan.pairs.begin(), plan.pairs.end(), [&](const PairRef& a, const PairRef& b) {
+    if (w[a.tmpl] != w[b.tmpl]) return w[a.tmpl] < w[b.tmpl];
+    if (h[a.tmpl] != h[b.tmpl]) return h[a.tmpl] < h[b.tmpl];
+    if (a.tmpl != b.tmpl) return a.tmpl < b.tmpl;
+    return a.out < b.out;
+  });
+  std::vector<uint64_t> lo(n_pairs), hi(n_pairs);
+  uint64_t at = 0;
+  for (size_t j = 0; j < n_pairs; ++j) {
+    const PairRef& r = plan.pairs[j];
+    lo[j] = at;
+    at += (uint64_t)h[r.cand] * stride[r.cand] + (uint64_t)w[r.tmpl] * h[r.tmpl] * channels;
+    if (j == 0 || plan.pairs[j - 1].tmpl != r.tmpl) at += (uint64_t)h[r.tmpl] * stride[r.tmpl];
+    hi[j] = at;
+  }
+  plan.runs = make_runs(n_pairs, lo.data(), hi.data(), (uint64_t)std::max(get_tmatch_chunk_mb(), 1) << 20, 32768);
+  return plan;
+}
+
 }  // namespace
 }  // namespace cbh
 
 extern "C" {
+
+int cbh_tm_pairs_stage_ms(int on, double* ms5, uint32_t* sizes, uint32_t* hash_launches) {
+  if (ms5) std::copy(cbh::g_clock.ms, cbh::g_clock.ms + 5, ms5);
+  if (sizes) *sizes = cbh::g_clock.sizes;
+  if (hash_launches) *hash_launches = cbh::g_clock.hash_launches;
+  cbh::g_clock = cbh::StageClock();
+  cbh::g_clock.on = on != 0;
+  return CBH_OK;
+}
+
+int cbh_template_match_pairs_dev(const void* d_imgs, size_t n_imgs, const uint64_t* img_off, const uint32_t* img_w,
+                                 const uint32_t* img_h, const uint32_t* img_row_stride, int channels,
+                                 const uint32_t* pair_tmpl, const uint32_t* pair_cand, size_t n_pairs,
+                                 const cbh_tm_params* params, cbh_tm_image_result* results, int device, void* stream) {
+  if (!cbh::device_usable(device)) return CBH_E_NODEVICE;
+  if (n_pairs == 0) return CBH_OK;
+  if (!cbh::pairs_args_ok(d_imgs, n_imgs, img_off, img_w, img_h, img_row_stride, channels, pair_tmpl, pair_cand, n_pairs,
+                          params, results))
+    return CBH_E_INVAL;
+  cbh::DeviceGuard g(device);
+  if (!g.ok) return CBH_E_NODEVICE;
+  hipStream_t s = (hipStream_t)stream;
+  const cbh::PairPlan plan = cbh::plan_pairs(img_w, img_h, img_row_stride, channels, pair_tmpl, pair_cand, n_pairs);
+  for (const cbh::Run& r : plan.runs) {
+    const int rc = cbh::run_pairs((const uint8_t*)d_imgs, img_off, img_w, img_h, img_row_stride, channels,
+                                  plan.pairs.data() + r.i0, r.m, params, results, s);
+    if (rc != CBH_OK) return rc;
+  }
+  return CBH_OK;
+}
+
+int cbh_template_match_pairs(const uint8_t* imgs, size_t imgs_bytes, size_t n_imgs, const uint64_t* img_off,
+                             const uint32_t* img_w, const uint32_t* img_h, const uint32_t* img_row_stride, int channels,
+                             const uint32_t* pair_tmpl, const uint32_t* pair_cand, size_t n_pairs,
+                             const cbh_tm_params* params, cbh_tm_image_result* results, int device) {
+  if (!cbh::device_usable(device)) return CBH_E_NODEVICE;
+  if (n_pairs == 0) return CBH_OK;
+  if (!cbh::pairs_args_ok(imgs, n_imgs, img_off, img_w, img_h, img_row_stride, channels, pair_tmpl, pair_cand, n_pairs, params,
+                          results))
+    return CBH_E_INVAL;
+  for (size_t i = 0; i < n_imgs; ++i)
+    if (cbh::image_end(img_off[i], img_w[i], img_h[i], img_row_stride[i], channels) > imgs_bytes) return CBH_E_INVAL;
+  cbh::DeviceGuard g(device);
+  if (!g.ok) return CBH_E_NODEVICE;
+  const cbh::PairPlan plan = cbh::plan_pairs(img_w, img_h, img_row_stride, channels, pair_tmpl, pair_cand, n_pairs);
+  // What a chunk uploads: the images its pairs name, each once.  They go up in ascending host order, and neighbours
+  // (the next one starts within 64 bytes of the bytes taken so far: a packed table) in ONE copy that keeps their distances;
+  // the copies are packed at 16-byte offsets.  `upload` false: only the bytes the chunk needs on the device.
+  std::vector<uint64_t> off(n_imgs);
+  std::vector<uint32_t> seen(n_imgs, 0xffffffffu), ids;
+  auto span = [&](uint32_t i) {
+    return (size_t)(cbh::image_end(img_off[i], img_w[i], img_h[i], img_row_stride[i], channels) - img_off[i]);
+  };
+  cbh::Staging st("template match pairs");
+  uint8_t* d_imgs = nullptr;
+  auto lay_out = [&](size_t k, bool upload) {
+    const cbh::Run& r = plan.runs[k];
+    const uint32_t mark = (uint32_t)(2 * k + (upload ? 1 : 0));
+    ids.clear();
+    for (size_t j = r.i0; j < r.i0 + r.m; ++j)
+      for (uint32_t i : {plan.pairs[j].tmpl, plan.pairs[j].cand})
+        if (seen[i] != mark) seen[i] = mark, ids.push_back(i);
+    std::sort(ids.begin(), ids.end(), [&](uint32_t x, uint32_t y) { return img_off[x] < img_off[y]; });
+    size_t at = 0;
+    for (size_t a = 0; a < ids.size();) {
+      const uint64_t lo = img_off[ids[a]];
+      uint64_t hi = lo + span(ids[a]);
+      size_t b = a + 1;
+      while (b < ids.size() && img_off[ids[b]] <= hi + 64) hi = std::max<uint64_t>(hi, img_off[ids[b]] + span(ids[b])), ++b;
+      if (upload) {
+        for (size_t c = a; c < b; ++c) off[ids[c]] = at + (img_off[ids[c]] - lo);
+        st.up(d_imgs + at, imgs + lo, (size_t)(hi - lo));
+      }
+      at += cbh::align16((size_t)(hi - lo));
+      a = b;
+    }
+    return at;
+  };
+  size_t most = 0;
+  for (size_t k = 0; k < plan.runs.size(); ++k) most = std::max(most, lay_out(k, false));
+  st.alloc(&d_imgs, most);
+  int rc = st.status();
+  for (size_t k = 0; k < plan.runs.size() && rc == CBH_OK; ++k) {
+    const cbh::Run& r = plan.runs[k];
+    // (the chunk before has finished: run_pairs returns with the stream synchronised)
+    lay_out(k, true);
+    if ((rc = st.status()) != CBH_OK) break;
+    rc = cbh::run_pairs(d_imgs, off.data(), img_w, img_h, img_row_stride, channels, plan.pairs.data() + r.i0, r.m, params,
+                        results, st.s);
+  }
+  return rc;
+}
+
+int cbh_tm_match_points_pairs_dev(const void* d_tmpl_desc, const void* d_tmpl_xy, const uint64_t* tmpl_first, size_t n_tmpl,
+                                  const uint32_t* tmpl_of, const void* d_desc, const void* d_xy, const void* d_counts,
+                                  size_t n, int kp_cap, int max_dist, void* d_records, void* d_tmpl_pts, void* d_match_pts,
+                                  size_t points_cap, uint64_t* first, int device, void* stream) {
+  if (!cbh::device_usable(device)) return CBH_E_NODEVICE;
+  if (n == 0) {
+    if (first) first[0] = 0;
+    return CBH_OK;
+  }
+  if (!first || !d_desc || !d_xy || !d_counts || !tmpl_first || !tmpl_of || n_tmpl == 0 || n_tmpl > (1u << 24) ||
+      (points_cap && (!d_tmpl_pts || !d_match_pts)) || tmpl_first[0] != 0)
+    return CBH_E_INVAL;
+  size_t n_train = 0;
+  for (size_t g = 0; g < n_tmpl; ++g) {
+    if (tmpl_first[g + 1] < tmpl_first[g] || tmpl_first[g + 1] >= (1ull << 32)) return CBH_E_INVAL;
+    n_train = std::max<size_t>(n_train, tmpl_first[g + 1] - tmpl_first[g]);
+  }
+  if ((tmpl_first[n_tmpl] && (!d_tmpl_desc || !d_tmpl_xy)) || !cbh::match_shape_ok(n_train, n, kp_cap, max_dist))
+    return CBH_E_INVAL;
+  std::vector<cbh::TSet> tsets(n);
+  for (size_t i = 0; i < n; ++i) {
+    if (tmpl_of[i] >= n_tmpl) return CBH_E_INVAL;
+    tsets[i] = {(unsigned)tmpl_first[tmpl_of[i]], (unsigned)(tmpl_first[tmpl_of[i] + 1] - tmpl_first[tmpl_of[i]])};
+  }
+  cbh::DeviceGuard g(device);
+  if (!g.ok) return CBH_E_NODEVICE;
+  hipStream_t s = (hipStream_t)stream;
+  cbh::Scratch scratch(s);
+  cbh::MatchState st;
+  cbh::TSet* d_tsets = nullptr;
+  hipError_t e = cbh::upload(scratch, &d_tsets, tsets, s);
+  int rc = e == hipSuccess ? CBH_OK : cbh::fail("descriptor match tables", e);
+  // (n_train = 0 fills `first` with zeros without a launch: every train set is empty)
+  if (rc == CBH_OK)
+    rc = cbh::match_count(scratch, st, (const uint8_t*)d_tmpl_desc, n_train, (const uint8_t*)d_desc, (const uint32_t*)d_counts, n,
+                          kp_cap, max_dist, first, s, d_tsets);
+  if (rc == CBH_OK && first[n] > points_cap) rc = CBH_E_OVERFLOW;  // `first` is complete; nothing has been written
+  if (rc == CBH_OK)
+    rc = cbh::match_emit(st, (const uint8_t*)d_tmpl_desc, n_train, (const float*)d_tmpl_xy, (const uint8_t*)d_desc,
+                         (const float*)d_xy, (const uint32_t*)d_counts, n, kp_cap, max_dist, first, (cbh_dmatch*)d_records,
+                         (float*)d_tmpl_pts, (float*)d_match_pts, s, d_tsets);
+  e = hipStreamSynchronize(s);  // the host table must outlive its copy
+  if (rc == CBH_OK && e != hipSuccess) rc = cbh::fail("descriptor match", e);
+  return rc;
+}
 
 int cbh_resize_lanczos4_ragged_dev(const void* d_src, size_t n, const uint64_t* img_off, const uint32_t* img_w,
                                    const uint32_t* img_h, const uint32_t* img_row_stride, int channels,

@@ -409,9 +409,15 @@ def query_batch(index, needles, views, params: SearchParams, id_map: dict, db_pa
     return out
 
 
-def similar(index, haystack, params: SearchParams, batched: bool = True, db_path: str = ""):
+def similar(index, haystack, params: SearchParams, batched: bool = True, db_path: str = "", matcher=None):
     """Database::similar for an in-memory haystack (list of Media with unique ids): every item is searched
     as a needle; returns the accepted groups [needle, match1, ...].
+
+    params.templateMatch: every needle's searchIndex result goes through the template matcher (the needle is the template,
+    its result the candidates) before the needle is prepended and before filterMatch (src/database.cpp:1418-1421) --
+    matcher.match per needle on the batched=False route, ONE matcher.match_groups call for all the groups on the batched
+    route; both give the same groups.  The media then need templatematcher.py's ``image`` / ``md5``; matcher=None makes a
+    TemplateMatcher().
 
     batched (DctHashIndex): the whole job behind the C-ABI -- cbh_search_index_batch (scans, escalation and the
     per-needle cut on the device, no per-needle loop here) and cbh_filter_groups_ex (path / parent filters, acceptance,
@@ -419,6 +425,11 @@ def similar(index, haystack, params: SearchParams, batched: bool = True, db_path
     if getattr(params, "mirrorMask", 0):
         warnings.warn("reflected images unsupported, use -similar-to")  # database.cpp:1283; ignored, as there
     id_map = {m.id: m for m in haystack}
+    tm = bool(getattr(params, "templateMatch", False))
+    if tm and matcher is None:
+        from .templatematcher import TemplateMatcher
+
+        matcher = TemplateMatcher()
     if batched and hasattr(index, "search_index_batch") and params.algo == SearchParams.AlgoDCT:
         import ctypes as C
 
@@ -433,12 +444,34 @@ def similar(index, haystack, params: SearchParams, batched: bool = True, db_path
         k = int(params.maxMatches)
         pairs = np.zeros((len(hay), max(k, 1), 2), np.uint32)
         pairs[:, :k, 0], pairs[:, :k, 1] = mi, ms.view(np.uint32) if ms.size else ms
+        matched = {}  # (needle id, media id) -> the media the matcher scored (its roi / transform are on it)
+        if tm:
+            mc = np.array(mc, np.uint32)
+            tmpls, cands = [], []
+            for i, m in enumerate(hay):
+                if mc[i]:
+                    group = []
+                    for t in range(int(mc[i])):
+                        media = copy.copy(id_map[int(mi[i, t])])
+                        media.score = int(ms[i, t])
+                        group.append(media)
+                    tmpls.append((i, m)), cands.append(group)
+            # the surviving (id, score) rows go back in front of the filters
+            for (i, m), group in zip(tmpls, matcher.match_groups([m for _, m in tmpls], cands, params)):
+                mc[i] = len(group)
+                for t, media in enumerate(group):
+                    pairs[i, t, 0] = media.id
+                    pairs[i, t, 1] = np.int32(media.score).view(np.uint32)
+                    matched[(m.id, media.id)] = media
         # paths enter the C-ABI as per-media attributes (rank of the path, directory number, under-the-prefix flag)
         groups = []
         for g in filter_groups_c_abi(params, ids, pairs, mc, hay, db_path):
             out = []
             for t, (mid, score) in enumerate(g):
-                media = id_map[mid] if (t == 0 and score == -1) else copy.copy(id_map[mid])
+                if t == 0 and score == -1:
+                    media = id_map[mid]
+                else:
+                    media = matched.get((g[0][0], mid)) or copy.copy(id_map[mid])
                 if not (t == 0 and score == -1):
                     media.score = score
                 out.append(media)
@@ -448,7 +481,10 @@ def similar(index, haystack, params: SearchParams, batched: bool = True, db_path
     for m in haystack:
         if params.algo == SearchParams.AlgoDCT and not m.dctHash:
             continue
-        results.append([m] + search_index(index, m, params, id_map))
+        group = search_index(index, m, params, id_map)
+        if tm and group:
+            group = matcher.match(m, group, params)
+        results.append([m] + group)
     return filter_results(params, results, db_path)
 
 

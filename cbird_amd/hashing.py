@@ -331,3 +331,32 @@ def template_match_images(tmpl, cands, params=None, patches: bool = False, devic
                                                p.ctypes.data, res.ctypes.data, out.ctypes.data if patches else None,
                                                device), "template_match_images")
     return (res, out) if patches else res
+
+
+def template_match_pairs(images, pair_tmpl, pair_cand, params=None, device: int = 0):
+    """template_match_images for a batch of result groups in ONE call (Database::similar with params.templateMatch): `images`
+    is one table of uint8 images of one channel count, pair p matches template images[pair_tmpl[p]] against candidate
+    images[pair_cand[p]].  An image may be a template in some pairs and a candidate in others, the pairs of one template
+    need not be adjacent.  Returns TEMPLATE_IMAGE_RESULT_DTYPE [n_pairs] in the caller's order, entry p equal to
+    template_match_images(images[pair_tmpl[p]], [images[pair_cand[p]]], params)[0].  Needs orb.set_pattern."""
+    from .quality import pack_images
+
+    pt = np.ascontiguousarray(pair_tmpl, np.uint32).reshape(-1)
+    pc = np.ascontiguousarray(pair_cand, np.uint32).reshape(-1)
+    if len(pt) != len(pc):
+        raise ValueError("one template and one candidate index per pair")
+    res = np.zeros(len(pt), TEMPLATE_IMAGE_RESULT_DTYPE)
+    if len(pt) == 0:
+        return res
+    imgs = [np.ascontiguousarray(im, np.uint8) for im in images]
+    chs = {1 if im.ndim == 2 else im.shape[2] for im in imgs}
+    if len(chs) != 1 or not chs <= {1, 3, 4} or any(im.size == 0 or im.ndim not in (2, 3) for im in imgs):
+        raise ValueError("expected non-empty uint8 images of one channel count: [h, w], [h, w, 3] or [h, w, 4]")
+    if max(int(pt.max()), int(pc.max())) >= len(imgs):
+        raise ValueError("a pair names an image that is not in the table")
+    p = tm_params(params)
+    buf, off, w, h, stride = pack_images(imgs)
+    check(_lib.lib().cbh_template_match_pairs(buf.ctypes.data, buf.size, len(imgs), off.ctypes.data, w.ctypes.data,
+                                              h.ctypes.data, stride.ctypes.data, chs.pop(), pt.ctypes.data, pc.ctypes.data,
+                                              len(pt), p.ctypes.data, res.ctypes.data, device), "template_match_pairs")
+    return res

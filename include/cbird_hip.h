@@ -1110,6 +1110,50 @@ int cbh_tm_match_points_dev(const void* d_tmpl_desc, const void* d_tmpl_xy, size
                             void* d_tmpl_pts, void* d_match_pts, size_t points_cap, uint64_t* first, int device,
                             void* stream);
 
+/* ---- TemplateMatcher::match for a batch of result groups (Database::similar with params.templateMatch,
+ * src/database.cpp:1418: once per needle there) ------------------------------------------------------------------------
+ * One ragged image table (img_off / img_w / img_h / img_row_stride, one channel count per call) and n_pairs (template
+ * image, candidate image) pairs that index it; an image may be a template in some pairs and a candidate in others,
+ * pair_tmpl[p] == pair_cand[p] is legal, and the pairs of one template need not be adjacent (the entry groups them itself).
+ * results[p], in the caller's pair order, is byte for byte what cbh_template_match_images returns for template = image
+ * pair_tmpl[p], candidates = [image pair_cand[p]] and the same params -- every status, CBH_TM_NO_TEMPLATE_KEYPOINTS for
+ * every pair of a template without keypoints, cand_scale, w, h, n_keypoints, n_matches.  There are no patches.
+ * The distinct templates of a chunk go through grey and ORB once, the candidates once per pair (the resize target depends
+ * on the pair's template; ORB is not shared between unresized occurrences of one image); the host waits for the two sets
+ * of ORB counts, the match counts and the results per chunk, however many templates it holds.  Chunks: pairs whose
+ * working set (templates once, candidate images, patches) stays within "tmatch_chunk_mb".
+ * n_imgs, n_pairs <= 2^24; an index >= n_imgs, a template side above 8192 or a candidate that reaches ORB above 8192:
+ * CBH_E_INVAL; zero pairs: CBH_OK with nothing read.  cbird_amd/csrc/tmimages.hip. */
+int cbh_template_match_pairs(const uint8_t* imgs, size_t imgs_bytes, size_t n_imgs, const uint64_t* img_off,
+                             const uint32_t* img_w, const uint32_t* img_h, const uint32_t* img_row_stride, int channels,
+                             const uint32_t* pair_tmpl, const uint32_t* pair_cand, size_t n_pairs,
+                             const cbh_tm_params* params, cbh_tm_image_result* results, int device);
+/* images in device memory; every table and the results are host memory.  Returns with the stream synchronised. */
+int cbh_template_match_pairs_dev(const void* d_imgs, size_t n_imgs, const uint64_t* img_off, const uint32_t* img_w,
+                                 const uint32_t* img_h, const uint32_t* img_row_stride, int channels,
+                                 const uint32_t* pair_tmpl, const uint32_t* pair_cand, size_t n_pairs,
+                                 const cbh_tm_params* params, cbh_tm_image_result* results, int device, void* stream);
+/* Its two own stages.  cbh_tm_match_points_dev with a train set per candidate: template g owns rows tmpl_first[g] ..
+ * tmpl_first[g + 1] (host, n_tmpl + 1, ascending from 0, below 2^32) of d_tmpl_desc / d_tmpl_xy, candidate i is matched
+ * against template tmpl_of[i] (host, n); train_idx counts inside the candidate's own set.  Otherwise that entry's
+ * contract, CBH_E_OVERFLOW included; the n_train limits apply to the largest set. */
+int cbh_tm_match_points_pairs_dev(const void* d_tmpl_desc, const void* d_tmpl_xy, const uint64_t* tmpl_first, size_t n_tmpl,
+                                  const uint32_t* tmpl_of, const void* d_desc, const void* d_xy, const void* d_counts,
+                                  size_t n, int kp_cap, int max_dist, void* d_records, void* d_tmpl_pts, void* d_match_pts,
+                                  size_t points_cap, uint64_t* first, int device, void* stream);
+/* cbh_warp_affine_dev with a patch size per candidate: candidate i warps into tw[i] x th[i] pixels (pitch tw[i] *
+ * channels) at d_patches + patch_off[i] (host tables; offsets 16-byte aligned, patches must not overlap).  No byte outside
+ * a patch is written. */
+int cbh_warp_affine_ragged_dev(const void* d_imgs, size_t n, const uint64_t* img_off, const uint32_t* img_w,
+                               const uint32_t* img_h, const uint32_t* img_row_stride, int channels, const void* d_m,
+                               const void* d_found, const uint32_t* tw, const uint32_t* th, const uint64_t* patch_off,
+                               void* d_patches, void* d_warped, int device, void* stream);
+/* Measurement (tools/template_pairs_bench.py): reads the device-event times the grouped entry has summed since the last
+ * call -- ms5: grey and resize, ORB of the templates, ORB of the candidates, match + gather, estimate to score; sizes:
+ * runs of one template size; hash_launches: launch_dcthash calls -- then clears them and switches the clock on or off.
+ * While it is on every stage ends in a host wait of its own: never leave it on outside a measurement. */
+int cbh_tm_pairs_stage_ms(int on, double* ms5, uint32_t* sizes, uint32_t* hash_launches);
+
 /* ---- CvFeaturesIndex: src/cvfeaturesindex.{h,cpp} ---------------------------------------------------
  * N x 32-byte ORB/BRIEF descriptor rows (cv::Mat CV_8U, cvfeaturesindex.h:73) + the first-row -> mediaId
  * map (_indexMap/_idMap, :77-81).  Searches are exact brute force (the reference asks a FLANN LSH index,
