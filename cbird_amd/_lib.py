@@ -143,6 +143,8 @@ _SIGS = {
                                    _vp, _vp, _vp, C.c_int]),
     "cbh_index_images_views": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "cbh_index_images_views_ex": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),
     "cbh_orb_set_pattern": (C.c_int, [_vp]),
     "cbh_orb_retain_best_dev": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
     "cbh_orb": (C.c_int, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int]),
@@ -153,6 +155,7 @@ _SIGS = {
     "cbh_resize_lanczos4_dev": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int, _vp, C.c_int, _vp]),
     "cbh_bgr2gray_dev": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, _vp, C.c_int, _vp]),
     "cbh_gray_views_dev": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
+    "cbh_turn_views_dev": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
     "cbh_autocrop_dev": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, _vp, C.c_int, _vp]),
     "cbh_process_images": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int, _vp, _vp, C.c_int]),
     "cbh_process_images_ex": (C.c_int, [_vp, _sz, C.c_int, C.c_int, _sz, _sz, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp,

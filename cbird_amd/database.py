@@ -347,6 +347,7 @@ def _filtered(needle, group, params, db_path):
 
 
 _MIRROR_FLAGS = (SearchParams.MirrorHorizontal, SearchParams.MirrorVertical, SearchParams.MirrorBoth)
+_TURN_FLAGS = (SearchParams.TurnRight, SearchParams.TurnLeft, SearchParams.Transpose, SearchParams.AntiTranspose)
 
 
 def mirrored(needle, view):
@@ -364,13 +365,15 @@ def mirrored(needle, view):
 
 
 def _needle_views(needle, params, views):
-    """the needle and its reflections in the order Engine::query searches them (engine.cpp:429-436)"""
+    """the needle and its reflections in the order Engine::query searches them (engine.cpp:429-436), then its quarter
+    turns and transposes (params.turnMask) in flag order"""
     out = [needle]
-    for flag in _MIRROR_FLAGS:
-        if params.mirrorMask & flag:
-            if views is None or views.get(flag) is None:
-                raise ValueError(f"mirrorMask has bit {flag} but no view {flag} of {needle.path!r} was given")
-            out.append(mirrored(needle, views[flag]))
+    for name, flags in (("mirrorMask", _MIRROR_FLAGS), ("turnMask", _TURN_FLAGS)):
+        for flag in flags:
+            if getattr(params, name, 0) & flag:
+                if views is None or views.get(flag) is None:
+                    raise ValueError(f"{name} has bit {flag} but no view {flag} of {needle.path!r} was given")
+                out.append(mirrored(needle, views[flag]))
     return out
 
 
@@ -385,7 +388,8 @@ def _compose(lists):
 def query(index, needle, params: SearchParams, id_map: dict, views=None, db_path: str = ""):
     """Engine::query from similarTo on (src/engine.cpp:421-438), without the template matcher: similarTo of the needle,
     then for each bit of params.mirrorMask (1 left-right, 2 top-bottom, 4 both, in that order) similarTo of the mirrored
-    needle appended, each list filtered on its own; the whole sorted by score.  views = the {flag: IndexResult} that
+    needle appended, then the same for each bit of params.turnMask (8 / 16 turned right / left, 32 / 64 transposed /
+    anti-transposed), each list filtered on its own; the whole sorted by score.  views = the {flag: IndexResult} that
     scanner.process_images_views returned for this needle; a set bit without its view raises ValueError."""
     needles = _needle_views(needle, params, views)
     return _compose([similar_to(index, m, params, id_map, db_path) for m in needles])
@@ -424,6 +428,8 @@ def similar(index, haystack, params: SearchParams, batched: bool = True, db_path
     duplicate groups, merge / expand, order); this function only turns the surviving rows back into Media objects."""
     if getattr(params, "mirrorMask", 0):
         warnings.warn("reflected images unsupported, use -similar-to")  # database.cpp:1283; ignored, as there
+    if getattr(params, "turnMask", 0):
+        warnings.warn("turned images unsupported, use -similar-to")  # ignored like mirrorMask
     id_map = {m.id: m for m in haystack}
     tm = bool(getattr(params, "templateMatch", False))
     if tm and matcher is None:
@@ -525,8 +531,8 @@ def _sort_similar_on_device(index, params) -> bool:
     from .index import DctHashIndex
 
     return (isinstance(index, DctHashIndex) and params.algo == SearchParams.AlgoDCT and not params.mirrorMask and
-            not params.templateMatch and 1 <= int(params.maxMatches) <= 55 and 0 <= int(params.dctThresh) <= 65 and
-            int(params.maxThresh) <= 65)
+            not getattr(params, "turnMask", 0) and not params.templateMatch and 1 <= int(params.maxMatches) <= 55 and
+            0 <= int(params.dctThresh) <= 65 and int(params.maxThresh) <= 65)
 
 
 def sort_similar_batch(index, selections, params: SearchParams, db_path: str = ""):

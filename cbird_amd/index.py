@@ -72,6 +72,12 @@ class SearchParams:
     MirrorHorizontal = 1
     MirrorVertical = 2
     MirrorBoth = 4
+    # the views that swap width and height (no reference counterpart: "DCT hashes do not support rotation",
+    # src/dctfeaturesindex.h:34); the values continue Mirror*, so mirrorMask | turnMask is the C ABI's view_mask
+    TurnRight = 8        # quarter turn clockwise, QTransform().rotate(90)
+    TurnLeft = 16        # quarter turn counter-clockwise
+    Transpose = 32
+    AntiTranspose = 64
 
     algo: int = 0
     dctThresh: int = 5
@@ -89,6 +95,7 @@ class SearchParams:
     expandGroups: bool = False
     mergeGroups: int = 0
     mirrorMask: int = 0       # Mirror* flags: also search the needle's reflections (-p.refl; database.query)
+    turnMask: int = 0         # Turn* / *Transpose flags: also search the needle's quarter turns and transposes
     # the template matcher (src/index.h:79-91, defaults identical; cbird_amd/templatematcher.py reads them)
     needleFeatures: int = 100     # number of needle / template features
     haystackFeatures: int = 1000  # number of haystack / candidate features

@@ -42,6 +42,7 @@ class IndexResult:
 
 
 MirrorFlags = (1, 2, 4)  # SearchParams::MirrorHorizontal, MirrorVertical, MirrorBoth (src/index.h:51-59)
+TurnFlags = (8, 16, 32, 64)  # SearchParams.TurnRight, TurnLeft, Transpose, AntiTranspose
 
 
 def process_images(imgs: np.ndarray, params: IndexParams | None = None, device: int = 0) -> list[IndexResult]:
@@ -50,22 +51,28 @@ def process_images(imgs: np.ndarray, params: IndexParams | None = None, device: 
 
 
 def process_images_views(imgs: np.ndarray, mirror_mask: int, params: IndexParams | None = None,
-                         device: int = 0) -> list[dict]:
+                         device: int = 0, turn_mask: int = 0) -> list[dict]:
     """processImage of each image and of its reflections for a reflection search (Engine::mirrored / Engine::query,
     src/engine.cpp:357-365, 423-436) over cbh_index_images_views: one upload per image feeds every view.  Returns one
     {flag: IndexResult} per image: 0 = the image as given, 1 / 2 / 4 = mirrored left-right / top-bottom / both, for the
-    bits of mirror_mask (SearchParams.mirrorMask); rects and keypoints are in the coordinates of their own view."""
-    mirror_mask = int(mirror_mask)
+    bits of mirror_mask (SearchParams.mirrorMask); rects and keypoints are in the coordinates of their own view.
+    turn_mask (SearchParams.turnMask, bits 8 / 16 / 32 / 64) adds the quarter turn clockwise, the quarter turn
+    counter-clockwise, the transpose and the anti-transpose under those keys (cbh_index_images_views_ex); they are h wide
+    and w high."""
+    mirror_mask, turn_mask = int(mirror_mask), int(turn_mask)
     if not 0 <= mirror_mask <= 7:
         raise ValueError(f"mirror_mask {mirror_mask}: expected 0..7")
-    flags = [0] + [f for f in MirrorFlags if mirror_mask & f]
-    res = _index(imgs, mirror_mask, params, device)
+    if turn_mask < 0 or turn_mask & ~120:
+        raise ValueError(f"turn_mask {turn_mask}: expected bits 8, 16, 32, 64")
+    flags = [0] + [f for f in MirrorFlags + TurnFlags if (mirror_mask | turn_mask) & f]
+    res = _index(imgs, mirror_mask | turn_mask, params, device)
     V = len(flags)
     return [dict(zip(flags, res[i * V:(i + 1) * V])) for i in range(len(res) // V)]
 
 
 def _index(imgs, mirror_mask, params, device):
-    """cbh_index_images (mirror_mask None) or cbh_index_images_views: one IndexResult per result row"""
+    """cbh_index_images (mirror_mask None), cbh_index_images_views or, with turn bits in the mask,
+    cbh_index_images_views_ex: one IndexResult per result row"""
     p = params or IndexParams()
     imgs = np.asarray(imgs)
     if imgs.dtype != np.uint8 or imgs.ndim not in (3, 4):
@@ -102,6 +109,9 @@ def _index(imgs, mirror_mask, params, device):
                 desc.ctypes.data, khc.ctypes.data, kh.ctypes.data, cd.ctypes.data, cok.ctypes.data, device)
         if mirror_mask is None:
             check(L.cbh_index_images(imgs.ctypes.data, n, w, h, w * ch, w * h * ch, ch, C.byref(cp), *outs), "index_images")
+        elif mirror_mask > 7:
+            check(L.cbh_index_images_views_ex(imgs.ctypes.data, n, w, h, w * ch, w * h * ch, ch, mirror_mask, C.byref(cp),
+                                              *outs), "index_images_views_ex")
         else:
             check(L.cbh_index_images_views(imgs.ctypes.data, n, w, h, w * ch, w * h * ch, ch, mirror_mask, C.byref(cp),
                                            *outs), "index_images_views")

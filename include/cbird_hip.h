@@ -466,6 +466,14 @@ int cbh_bgr2gray_dev(const void* d_src, size_t n, int w, int h, size_t row_strid
  * ColorDescriptor::create reads for that view; the identity view is the input itself.  Channels 1 / 3 / 4. */
 int cbh_gray_views_dev(const void* d_src, size_t n, int w, int h, size_t row_stride, size_t img_stride, int channels,
                        int mirror_mask, void* d_gray, void* d_color, int device, void* stream);
+/* The views that swap width and height, the other four symmetries of a rectangle, from one read of each image.
+ * turn_mask: bit 8 quarter turn clockwise (QTransform().rotate(90): out[y][x] = in[h-1-x][y]), 16 quarter turn
+ * counter-clockwise (in[x][w-1-y]), 32 transpose (in[x][y]), 64 anti-transpose (in[h-1-x][w-1-y]); bits 8 / 16 / 32 / 64
+ * only, at least one (else CBH_E_INVAL); T = popcount.  d_gray: n*T packed planes of w rows x h columns, plane i*T + t,
+ * set bits in rising order; each equals cbh_bgr2gray_dev of the turned image (channels 1: the turned bytes).
+ * d_color: NULL, or n*T packed images of w x h x channels, the turned colour images.  Channels 1 / 3 / 4. */
+int cbh_turn_views_dev(const void* d_src, size_t n, int w, int h, size_t row_stride, size_t img_stride, int channels,
+                       int turn_mask, void* d_gray, void* d_color, int device, void* stream);
 /* autocrop(gray, range) (src/cvutil.cpp:1285-1402): d_rects[i] = {left, top, right, bottom} (int32 x4) of the
  * region kept (the whole image when nothing is cropped). */
 int cbh_autocrop_dev(const void* d_gray, size_t n, int w, int h, size_t row_stride, size_t img_stride, int range,
@@ -515,6 +523,16 @@ int cbh_index_images_views(const uint8_t* imgs, size_t n, int w, int h, size_t r
                            int channels, int mirror_mask, const cbh_index_params* p, uint64_t* dct_hashes, int32_t* rects,
                            int32_t* resized_dims, uint32_t* kp_counts, cbh_keypoint* kp, uint8_t* desc,
                            uint32_t* kph_counts, uint64_t* kp_hashes, uint8_t* color_descs, uint8_t* color_ok, int device);
+/* cbh_index_images_views for all eight views of an image: view_mask = the reflection bits 1 / 2 / 4 and the bits of
+ * cbh_turn_views_dev, 8 / 16 / 32 / 64 (0..127, else CBH_E_INVAL); V = 1 + popcount(view_mask), views in the order
+ * identity, then the set bits rising.  Every output array is sized n*V, row i*V + v = exactly what cbh_index_images
+ * gives for view v of image i, rects / keypoints / resized dims in that view's own coordinates (turned views are h wide
+ * and w high).  One upload per chunk; the stages after the grey step run once per geometry present. */
+int cbh_index_images_views_ex(const uint8_t* imgs, size_t n, int w, int h, size_t row_stride, size_t img_stride,
+                              int channels, int view_mask, const cbh_index_params* p, uint64_t* dct_hashes,
+                              int32_t* rects, int32_t* resized_dims, uint32_t* kp_counts, cbh_keypoint* kp, uint8_t* desc,
+                              uint32_t* kph_counts, uint64_t* kp_hashes, uint8_t* color_descs, uint8_t* color_ok,
+                              int device);
 
 /* sizeLongestSide(cv::Mat& img, int size, int filter = INTER_LANCZOS4) -- src/cvutil.cpp:1932-1950, the resize in
  * front of ORB detection (src/scanner.cpp:876, size = IndexParams::resizeLongestSide = 400): target size from the
