@@ -65,6 +65,14 @@ class cbh_sort_similar_params(C.Structure):
                 ("filter_parent", C.c_int), ("path_mode", C.c_int), ("look_behind", C.c_int)]
 
 
+CBH_COLOR_SORT_SIMILAR_MAX = 32768
+
+
+class cbh_sort_table_params(C.Structure):
+    _fields_ = [("min_matches", C.c_int), ("max_matches", C.c_int), ("filter_parent", C.c_int), ("path_mode", C.c_int),
+                ("look_behind", C.c_int)]
+
+
 class cbh_sort_similar_result(C.Structure):
     _fields_ = [("sorted", C.c_uint32), ("queries", C.c_uint32), ("not_found", C.c_uint32), ("behind", C.c_uint32)]
 
@@ -222,6 +230,9 @@ _SIGS = {
                                        _vp]),
     "cbh_sort_similar": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int]),
     "cbh_sort_similar_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int, _vp]),
+    "cbh_sort_similar_table": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int]),
+    "cbh_sort_similar_table_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int, _vp]),
+    "cbh_color_sort_similar": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "cbh_vdx_verify": (C.c_int, [_vp, _sz]),
     "cbh_records_topk_dev": (C.c_int, [_vp, _sz, _sz, _sz, _sz, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
     "cbh_idx64_set_record_capacity": (C.c_int, [_vp, _sz]),

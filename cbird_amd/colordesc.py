@@ -141,6 +141,32 @@ class ColorDescIndex:
         check(self._L.cbh_color_distances(self._h, d.ctypes.data, len(d), out.ctypes.data), "color_distances")
         return out
 
+    def sort_similar(self, ids, needle_descs, params: SearchParams, set_first=None, dir_id=None, under=None,
+                     path_mode: int = 0, look_behind: int = 5):
+        """-sort-similar with -p.alg color for selections given as ids (cbh_color_sort_similar: the score tables filled
+        and walked on the device, one workgroup per selection).  ids: the items of all selections, set s =
+        ids[set_first[s]:set_first[s + 1]] (None: one selection); needle_descs: COLOR_DTYPE parallel to ids, or None for
+        the index's own; dir_id (with params.filterParent) / under + path_mode (1 = inPath, 2 = not inPath) are the path
+        attributes of cbh_filter_params.  Returns [(ids in sorted order, queries, notFound, behind)] per selection; raises
+        CbhError -- CBH_E_UNSUPPORTED for a selection above CBH_COLOR_SORT_SIMILAR_MAX or an index holding an id twice."""
+        ids = np.ascontiguousarray(ids, np.uint32)
+        first = np.ascontiguousarray([0, len(ids)] if set_first is None else set_first, np.uint64)
+        n_sets = len(first) - 1
+        d = None if needle_descs is None else np.ascontiguousarray(np.asarray(needle_descs, COLOR_DTYPE).reshape(-1))
+        if d is not None and len(d) != len(ids):
+            raise ValueError("needle_descs is not parallel to ids")
+        dir_id = None if dir_id is None else np.ascontiguousarray(dir_id, np.uint32)
+        under = None if under is None else np.ascontiguousarray(under, np.uint8)
+        sp = _lib.cbh_sort_table_params(int(params.minMatches), int(params.maxMatches), int(bool(params.filterParent)),
+                                        int(path_mode), int(look_behind))
+        out_ids = np.zeros(max(len(ids), 1), np.uint32)
+        res = (_lib.cbh_sort_similar_result * max(n_sets, 1))()
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        check(self._L.cbh_color_sort_similar(self._h, ptr(ids), ptr(d), ptr(dir_id), ptr(under), ptr(first), n_sets,
+                                             C.byref(sp), ptr(out_ids), res), "color_sort_similar")
+        return [([int(i) for i in out_ids[int(first[s]):int(first[s]) + res[s].sorted]], int(res[s].queries),
+                 int(res[s].not_found), int(res[s].behind)) for s in range(n_sets)]
+
     def find_batch(self, descs, k: int):
         d = np.ascontiguousarray(np.asarray(descs, COLOR_DTYPE).reshape(-1))
         nq = len(d)

@@ -346,6 +346,55 @@ class GpuColorDescIndex : public ColorDescIndex {
     return new GpuColorDescIndex(sub, _device);
   }
 
+  /// What filterMatch reads from paths (src/database.cpp:1217-1242), parallel to the selection, for gpuSortSimilar:
+  /// as GpuDctHashIndex::SortSimilarPaths.
+  struct SortSimilarPaths {
+    bool filterParent = false;
+    int pathMode = 0;
+    std::vector<uint32_t> dirId;
+    std::vector<uint8_t> underPrefix;
+  };
+  /// `-sort-similar` with `-p.alg color` (src/main.cpp:1523-1580) in one call instead of up to 5 (n - 1) slices and
+  /// queries: `selection` becomes the sorted list (items never reached are dropped, :1579), *queries / *notFound count
+  /// what the reference's loop counts.  The Media's descriptors are the needles (the index's where a Media has none),
+  /// the index's the candidates; no mirrorMask, no templateMatch.  false (selection untouched, the error logged): the
+  /// call failed, the selection has more than CBH_COLOR_SORT_SIMILAR_MAX items or the index holds one of its ids
+  /// twice -- run the reference's loop then.
+  bool gpuSortSimilar(MediaGroup& selection, const SearchParams& p, int* queries, int* notFound,
+                      const SortSimilarPaths* paths = nullptr) const {
+    const size_t n = selection.size();
+    std::vector<uint32_t> ids, order(n ? n : 1);
+    std::vector<ColorDescriptor> descs;
+    for (const Media& m : selection) {
+      ids.push_back(uint32_t(m.id()));
+      descs.push_back(m.colorDescriptor());
+    }
+    cbh_sort_table_params sp;
+    sp.min_matches = p.minMatches, sp.max_matches = p.maxMatches;
+    sp.filter_parent = paths && paths->filterParent, sp.path_mode = paths ? paths->pathMode : 0;
+    sp.look_behind = 5;  // `const int lookBehind = 5` (:1530)
+    if ((sp.filter_parent && paths->dirId.size() != n) || (sp.path_mode && paths->underPrefix.size() != n)) {
+      qCritical("GpuColorDescIndex::gpuSortSimilar: the path attributes are not parallel to the selection");
+      return false;
+    }
+    const uint64_t first[2] = {0, n};
+    cbh_sort_similar_result res = {0, 0, 0, 0};
+    if (!CBH_QUERY(cbh_color_sort_similar(_idx, ids.data(), descs.data(), sp.filter_parent ? paths->dirId.data() : nullptr,
+                                          sp.path_mode ? paths->underPrefix.data() : nullptr, first, 1, &sp, order.data(),
+                                          &res)))
+      return false;
+    std::vector<std::pair<uint32_t, size_t>> where;  // id -> place in the selection
+    for (size_t i = 0; i < n; ++i) where.push_back({ids[i], i});
+    std::sort(where.begin(), where.end());
+    MediaGroup sorted;
+    for (uint32_t k = 0; k < res.sorted; ++k)
+      sorted.append(selection[std::lower_bound(where.begin(), where.end(), std::make_pair(order[k], size_t(0)))->second]);
+    selection = sorted;
+    if (queries) *queries = int(res.queries);
+    if (notFound) *notFound = int(res.not_found);
+    return true;
+  }
+
   cbh_color* handle() const { return _idx; }  // for statistics (cbh_combine_stats)
   uint32_t scratchMask() const { return 1u << _device; }
 

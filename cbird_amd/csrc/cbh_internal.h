@@ -360,6 +360,25 @@ int set_color_chunk_scores(int v);  // color.hip "color_chunk_scores": most scor
 int get_color_chunk_scores();
 long long get_color_full_sorts();   // "color_full_sorts": needles cbh_color_find_batch has sent through color_full_sort_one
 long long get_color_window_cuts();  // "color_window_cuts": needles it has answered from the candidate list
+int set_color_sort_table_kb(int v);  // color.hip "color_sort_table_kb": KiB of score tables one group of cbh_color_sort_similar may hold, 0 (default) = 2 GiB; < 0: CBH_E_INVAL
+int get_color_sort_table_kb();
+void set_color_sort_timing(int on);  // "color_sort_timing": 1 = cbh_color_sort_similar times its table fill and its chain with events
+long long get_color_sort_stat(int which);  // 0 "color_sort_groups", 1 "color_sort_fill_us", 2 "color_sort_chain_us": the last call's
+
+// ---- sortsimilar_table.hip: the -sort-similar chain over tables of scores -------------------------------------------
+// A set of n items in ascending id order has its table as n rows of sort_table_row_stride(n) scores (16-byte rows, the
+// padding is never a candidate); sort_table_layout gives every set's first score in one block (multiples of 8 from 0)
+// and returns the block's size in scores (at least 8).
+__host__ __device__ inline uint32_t sort_table_row_stride(uint32_t n) { return (n + 7u) & ~7u; }
+uint64_t sort_table_layout(const uint64_t* h_first, size_t n_sets, uint64_t* h_sorted_first);
+int sort_table_params_ok(const cbh_sort_table_params* p, const void* dir_id, const void* under_prefix);
+// the chain alone: tables, ids, attributes (bit 0 in the index, bit 1 under the prefix) and dir ids already in ascending
+// id order per set, item i of set s at d_first[s] - base + i; first_pos[s] = where the set's first item went;
+// d_out_ids / d_out as cbh_sort_similar_dev.  d_sorted 16-byte aligned.
+int launch_sort_table_chain(const uint16_t* d_sorted, const uint64_t* d_sorted_first, const uint32_t* s_id,
+                            const uint8_t* s_attr, const uint32_t* s_dir, const uint32_t* first_pos, const uint64_t* d_first,
+                            uint64_t base, size_t n_sets, uint32_t largest, const cbh_sort_table_params* p,
+                            uint32_t* d_out_ids, cbh_sort_similar_result* d_out, hipStream_t s);
 
 // ---- records.hip ----------------------------------------------------------------------
 // Ascending u64 sort of n records in place (uses d_alt as the ping-pong buffer and d_tmp as

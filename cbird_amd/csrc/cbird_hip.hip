@@ -1361,6 +1361,8 @@ int cbh_set_tuning(const char* key, int value) {
   if (!strcmp(key, "join_resident_mb")) return set_join_resident_mb(value);
   if (!strcmp(key, "color_create_group")) return set_cd_group(value);
   if (!strcmp(key, "color_chunk_scores")) return set_color_chunk_scores(value);
+  if (!strcmp(key, "color_sort_table_kb")) return set_color_sort_table_kb(value);
+  if (!strcmp(key, "color_sort_timing")) return set_color_sort_timing(value), CBH_OK;
   if (!strcmp(key, "scan256_kernels")) {  // a read-back, not a knob: writing 0 clears it, nothing else can be written
     if (value != 0) return CBH_E_INVAL;
     clear_scan256_kernels();
@@ -1392,6 +1394,10 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strcmp(key, "color_chunk_scores")) return *value = get_color_chunk_scores(), CBH_OK;
   if (!strcmp(key, "color_full_sorts")) return *value = get_color_full_sorts(), CBH_OK;
   if (!strcmp(key, "color_window_cuts")) return *value = get_color_window_cuts(), CBH_OK;
+  if (!strcmp(key, "color_sort_table_kb")) return *value = get_color_sort_table_kb(), CBH_OK;
+  if (!strcmp(key, "color_sort_groups")) return *value = get_color_sort_stat(0), CBH_OK;
+  if (!strcmp(key, "color_sort_fill_us")) return *value = get_color_sort_stat(1), CBH_OK;
+  if (!strcmp(key, "color_sort_chain_us")) return *value = get_color_sort_stat(2), CBH_OK;
   if (!strcmp(key, "quality_chunk_mb")) return *value = get_quality_chunk_mb(), CBH_OK;
   if (!strcmp(key, "quality_strip_rows")) return *value = get_quality_strip_rows(), CBH_OK;
   if (!strcmp(key, "tmatch_chunk_mb")) return *value = get_tmatch_chunk_mb(), CBH_OK;

@@ -368,6 +368,36 @@ std::atomic<int> g_color_chunk_scores{0};
 // answered from the candidate list (needles without a match, and k == 0, count as neither)
 std::atomic<long long> g_color_full_sorts{0}, g_color_window_cuts{0};
 
+// ---- cbh_color_sort_similar ---------------------------------------------------------------------------------------------
+// "color_sort_table_kb": KiB of score tables one group of sets may hold, 0 (default) = kSortTableBytes.  Forced (tests):
+// several groups on small sets, and a set that does not fit.  Results do not depend on it.
+constexpr uint64_t kSortTableBytes = 2ull << 30;
+static_assert((uint64_t)CBH_COLOR_SORT_SIMILAR_MAX * CBH_COLOR_SORT_SIMILAR_MAX * 2 <= kSortTableBytes,
+              "the largest set's table has to fit the default budget");
+static_assert(CBH_COLOR_SORT_SIMILAR_MAX <= CBH_SORT_SIMILAR_MAX, "the chain's limit");
+std::atomic<int> g_color_sort_table_kb{0}, g_color_sort_timing{0};
+std::atomic<long long> g_color_sort_stat[3];  // the last call's groups, table fill in us, chain in us (timing on)
+
+// int scores of rows [r0, r0 + m) of one set (k_color_dist*: [m][n], -1 = no match) into the set's table: uint16_t rows of
+// `stride` scores (a multiple of 8), 0xFFFF = no match and in the padding.  A score is (int)(1.0f + up to 32 distances of
+// at most sqrt(100^2 + 354^2 + 262^2) = 451.7 between decompressed colours, src/cvutil.h:83-87) <= 14 454 < 0xFFFF.
+__global__ __launch_bounds__(256) void k_color_table(const int* __restrict__ score, uint32_t m, uint32_t n, uint32_t stride,
+                                                     uint32_t* __restrict__ rows /* [m][stride / 2] */) {
+  const uint32_t half = stride / 2;
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)m * half) return;
+  const uint32_t r = (uint32_t)(t / half), c = (uint32_t)(t % half) * 2;
+  const int a = c < n ? score[(size_t)r * n + c] : -1, b = c + 1 < n ? score[(size_t)r * n + c + 1] : -1;
+  rows[t] = (a < 0 ? 0xffffu : (uint32_t)a) | (b < 0 ? 0xffffu : (uint32_t)b) << 16;
+}
+
+// an item without a live entry in the index: no colours, so that no needle matches it (its in_index flag is 0 as well)
+__global__ __launch_bounds__(256) void k_color_absent(const uint8_t* __restrict__ attr, uint32_t n,
+                                                      unsigned char* __restrict__ num) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n && !(attr[i] & 1)) num[i] = 0;
+}
+
 // needles per chunk of a loop whose default budget is `dflt` score elements
 size_t color_chunk(size_t nq, size_t n, size_t dflt) {
   const int forced = g_color_chunk_scores.load();
@@ -386,6 +416,14 @@ int set_color_chunk_scores(int v) {
 int get_color_chunk_scores() { return g_color_chunk_scores.load(); }
 long long get_color_full_sorts() { return g_color_full_sorts.load(); }
 long long get_color_window_cuts() { return g_color_window_cuts.load(); }
+int set_color_sort_table_kb(int v) {
+  if (v < 0) return CBH_E_INVAL;
+  g_color_sort_table_kb.store(v);
+  return CBH_OK;
+}
+int get_color_sort_table_kb() { return g_color_sort_table_kb.load(); }
+void set_color_sort_timing(int on) { g_color_sort_timing.store(on ? 1 : 0); }
+long long get_color_sort_stat(int which) { return which >= 0 && which < 3 ? g_color_sort_stat[which].load() : 0; }
 }  // namespace cbh
 
 struct cbh_color {
@@ -495,17 +533,15 @@ int ensure_scratch(cbh_color* c, size_t nq, bool keys) {
 
 // scores of nq needles against the whole index -> c->d_scores [nq][n] (enqueued on c->stream); d_raw: also the float
 // distances (k_color_dist3 only)
-int run_dist(cbh_color* c, const uint8_t* needle_descs, size_t nq, float* d_raw = nullptr) {
-  std::vector<NeedleF> nf(nq);
-  for (size_t q = 0; q < nq; ++q) decompress(needle_descs + q * kDescBytes, &nf[q]);
-  CBH_HIP(hipMemcpyAsync(c->d_needles, nf.data(), nq * sizeof(NeedleF), hipMemcpyHostToDevice, c->stream));
-  CBH_HIP(hipStreamSynchronize(c->stream));  // nf is a stack-lifetime buffer
+// the distance kernel the knobs choose, nq needles against n descriptors in planes of `cap` entries (cap even, padded)
+int launch_dist(const float* dL, const float* dU, const float* dV, const unsigned char* d_num, size_t cap, size_t n,
+                const NeedleF* d_needles, size_t nq, int* d_scores, float* d_raw, hipStream_t stream) {
   if (d_raw || g_color_fma) {
-    const unsigned tiles = (unsigned)((c->n + 255) / 256);
+    const unsigned tiles = (unsigned)((n + 255) / 256);
     dim3 grid((unsigned)nq, std::min(tiles, 32768u), (tiles + 32767u) / 32768u), block(256);
-#define CBH_DIST3(RAW_, FMA_)                                                                                       \
-  hipLaunchKernelGGL((k_color_dist3<RAW_, FMA_>), grid, block, 0, c->stream, c->dL, c->dU, c->dV, c->d_num, c->cap, \
-                     (uint32_t)c->n, c->d_needles, c->d_scores, d_raw)
+#define CBH_DIST3(RAW_, FMA_)                                                                                         \
+  hipLaunchKernelGGL((k_color_dist3<RAW_, FMA_>), grid, block, 0, stream, dL, dU, dV, d_num, cap, (uint32_t)n, d_needles, \
+                     d_scores, d_raw)
     if (g_color_fma) {
       if (d_raw) CBH_DIST3(true, true); else CBH_DIST3(false, true);
     } else {
@@ -513,13 +549,20 @@ int run_dist(cbh_color* c, const uint8_t* needle_descs, size_t nq, float* d_raw 
     }
 #undef CBH_DIST3
   } else {  // (cap is always even: ensure_cap)
-    const unsigned tiles = (unsigned)((c->n + 511) / 512);
+    const unsigned tiles = (unsigned)((n + 511) / 512);
     dim3 grid((unsigned)nq, std::min(tiles, 32768u), (tiles + 32767u) / 32768u), block(256);
-    hipLaunchKernelGGL(k_color_dist2, grid, block, 0, c->stream, c->dL, c->dU, c->dV, c->d_num, c->cap,
-                       (uint32_t)c->n, c->d_needles, c->d_scores);
+    hipLaunchKernelGGL(k_color_dist2, grid, block, 0, stream, dL, dU, dV, d_num, cap, (uint32_t)n, d_needles, d_scores);
   }
   CBH_HIP(hipGetLastError());
   return CBH_OK;
+}
+
+int run_dist(cbh_color* c, const uint8_t* needle_descs, size_t nq, float* d_raw = nullptr) {
+  std::vector<NeedleF> nf(nq);
+  for (size_t q = 0; q < nq; ++q) decompress(needle_descs + q * kDescBytes, &nf[q]);
+  CBH_HIP(hipMemcpyAsync(c->d_needles, nf.data(), nq * sizeof(NeedleF), hipMemcpyHostToDevice, c->stream));
+  CBH_HIP(hipStreamSynchronize(c->stream));  // nf is a stack-lifetime buffer
+  return launch_dist(c->dL, c->dU, c->dV, c->d_num, c->cap, c->n, c->d_needles, nq, c->d_scores, d_raw, c->stream);
 }
 
 }  // namespace
@@ -857,3 +900,233 @@ int cbh_color_find_batch(cbh_color* c, const void* needle_descs, size_t nq, int 
 }
 
 }  // extern "C"
+
+// ---- -sort-similar with AlgoColor: the tables on the device, then sortsimilar_table.hip's chain ------------------------
+namespace {
+
+int cs_fail(int code, const char* why) {
+  cbh::set_last_error_text(why);
+  return code;
+}
+
+struct StreamDrain {  // host vectors feed asynchronous copies: no way out of the call before the stream has run dry
+  hipStream_t s;
+  ~StreamDrain() { (void)hipStreamSynchronize(s); }
+};
+
+constexpr uint32_t kNoPos = 0xffffffffu;
+
+// under c->mu.  first0: set_first rebased to 0; perm[g]: the caller's place (from the batch's first item) of the item
+// that is g-th when every set is in ascending id order
+int color_sort_similar(cbh_color* c, const uint32_t* ids, const uint8_t* needle_descs, const uint32_t* dir_id,
+                       const uint8_t* under, const std::vector<uint64_t>& first0, const std::vector<uint32_t>& perm,
+                       uint64_t budget_scores, const cbh_sort_table_params* p, uint32_t* out_ids,
+                       cbh_sort_similar_result* out) {
+  const size_t n_sets = first0.size() - 1, total = perm.size();
+  // where the index holds the listed ids: one pass over the index, as slice() makes it
+  std::vector<uint32_t> want(ids, ids + total);
+  std::sort(want.begin(), want.end());
+  want.erase(std::unique(want.begin(), want.end()), want.end());
+  std::vector<uint32_t> where(want.size(), kNoPos);
+  for (size_t i = 0; i < c->n; ++i) {
+    const uint32_t id = c->host_ids[i];
+    if (id == 0) continue;  // removed (:272-273)
+    const auto it = std::lower_bound(want.begin(), want.end(), id);
+    if (it == want.end() || *it != id) continue;
+    if (where[it - want.begin()] != kNoPos) return cs_fail(CBH_E_UNSUPPORTED, "color sort similar: the index holds an id twice");
+    where[it - want.begin()] = (uint32_t)i;
+  }
+  // every set in id order: ids, attributes, index positions (sets start at multiples of 4: the gather's loads), needles
+  std::vector<uint32_t> s_id(total), s_dir(p->filter_parent ? total : 0), first_pos(n_sets);
+  std::vector<uint64_t> pos_first(n_sets + 1, 0), sorted_first(n_sets);
+  for (size_t s = 0; s < n_sets; ++s) pos_first[s + 1] = pos_first[s] + ((first0[s + 1] - first0[s] + 3) & ~(uint64_t)3);
+  std::vector<uint32_t> pos(std::max<uint64_t>(pos_first[n_sets], 4), 0);
+  std::vector<uint8_t> s_attr(total);
+  std::vector<NeedleF> nf(total);
+  static const uint8_t kNoDesc[kDescBytes] = {0};
+  for (size_t s = 0; s < n_sets; ++s)
+    for (uint64_t g = first0[s]; g < first0[s + 1]; ++g) {
+      const uint32_t src = perm[g], id = ids[src];
+      const uint32_t at = where[std::lower_bound(want.begin(), want.end(), id) - want.begin()];
+      s_id[g] = id;
+      s_attr[g] = (uint8_t)((at != kNoPos ? 1 : 0) | (under && under[src] ? 2 : 0));
+      if (p->filter_parent) s_dir[g] = dir_id[src];
+      if (src == first0[s]) first_pos[s] = (uint32_t)(g - first0[s]);
+      pos[pos_first[s] + (g - first0[s])] = at != kNoPos ? at : 0;
+      const uint8_t* own = needle_descs ? needle_descs + (size_t)src * kDescBytes : nullptr;
+      decompress(own && own[256] > 0 ? own : at != kNoPos ? c->host_desc.data() + (size_t)at * kDescBytes : kNoDesc, &nf[g]);
+    }
+
+  if (!c->stream) CBH_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  hipStream_t st = c->stream;
+  StreamDrain drain{st};
+  cbh::Scratch scratch(st);
+  uint32_t *d_id, *d_dir = nullptr, *d_first_pos, *d_pos, *d_out_ids;
+  uint8_t* d_attr;
+  uint64_t *d_first, *d_sorted_first;
+  NeedleF* d_needles;
+  cbh_sort_similar_result* d_out;
+  CBH_HIP(scratch.get(&d_id, total * 4));
+  CBH_HIP(scratch.get(&d_attr, total));
+  if (p->filter_parent) CBH_HIP(scratch.get(&d_dir, total * 4));
+  CBH_HIP(scratch.get(&d_first_pos, n_sets * 4));
+  CBH_HIP(scratch.get(&d_first, (n_sets + 1) * 8));
+  CBH_HIP(scratch.get(&d_sorted_first, n_sets * 8));
+  CBH_HIP(scratch.get(&d_pos, pos.size() * 4));
+  CBH_HIP(scratch.get(&d_needles, total * sizeof(NeedleF)));
+  CBH_HIP(scratch.get(&d_out_ids, total * 4));
+  CBH_HIP(scratch.get(&d_out, n_sets * sizeof(cbh_sort_similar_result)));
+  // groups of consecutive sets whose tables fit the budget; sorted_first counts from each group's own block
+  std::vector<size_t> group_end;
+  for (size_t g0 = 0; g0 < n_sets;) {
+    size_t g1 = g0;
+    uint64_t scores = 0;
+    while (g1 < n_sets) {
+      const uint64_t n = first0[g1 + 1] - first0[g1], t = n * cbh::sort_table_row_stride((uint32_t)n);
+      if (g1 > g0 && scores + t > budget_scores) break;
+      scores += t, ++g1;
+    }
+    (void)cbh::sort_table_layout(first0.data() + g0, g1 - g0, sorted_first.data() + g0);
+    group_end.push_back(g1);
+    g0 = g1;
+  }
+  CBH_HIP(hipMemcpyAsync(d_id, s_id.data(), total * 4, hipMemcpyHostToDevice, st));
+  CBH_HIP(hipMemcpyAsync(d_attr, s_attr.data(), total, hipMemcpyHostToDevice, st));
+  if (d_dir) CBH_HIP(hipMemcpyAsync(d_dir, s_dir.data(), total * 4, hipMemcpyHostToDevice, st));
+  CBH_HIP(hipMemcpyAsync(d_first_pos, first_pos.data(), n_sets * 4, hipMemcpyHostToDevice, st));
+  CBH_HIP(hipMemcpyAsync(d_first, first0.data(), (n_sets + 1) * 8, hipMemcpyHostToDevice, st));
+  CBH_HIP(hipMemcpyAsync(d_sorted_first, sorted_first.data(), n_sets * 8, hipMemcpyHostToDevice, st));
+  CBH_HIP(hipMemcpyAsync(d_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, st));
+  CBH_HIP(hipMemcpyAsync(d_needles, nf.data(), total * sizeof(NeedleF), hipMemcpyHostToDevice, st));
+
+  const bool timing = g_color_sort_timing.load() != 0;
+  float fill_ms = 0.f, chain_ms = 0.f;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  if (timing)
+    for (hipEvent_t& e : ev) CBH_HIP(hipEventCreate(&e));
+  int rc = CBH_OK;
+  size_t g0 = 0;
+  for (size_t g1 : group_end) {
+    uint32_t largest = 0;
+    uint64_t chunk_scores = 1;
+    for (size_t s = g0; s < g1; ++s) {
+      const uint32_t n = (uint32_t)(first0[s + 1] - first0[s]);
+      largest = std::max(largest, n);
+      if (n) chunk_scores = std::max<uint64_t>(chunk_scores, (uint64_t)color_chunk(n, n, (size_t)1 << 24) * n);
+    }
+    const uint64_t group_scores = cbh::sort_table_layout(first0.data() + g0, g1 - g0, sorted_first.data() + g0);
+    const size_t cap = ((size_t)largest + 3) & ~(size_t)3;
+    cbh::Scratch gs(st);
+    uint16_t* table;
+    float *pl, *pu, *pv;
+    unsigned char* pnum;
+    uint32_t* pids;
+    int* d_scores;
+    hipError_t e = gs.get(&table, group_scores * 2);
+    if (e == hipSuccess) e = gs.get(&pl, std::max<size_t>(cap, 4) * kNC * 4);
+    if (e == hipSuccess) e = gs.get(&pu, std::max<size_t>(cap, 4) * kNC * 4);
+    if (e == hipSuccess) e = gs.get(&pv, std::max<size_t>(cap, 4) * kNC * 4);
+    if (e == hipSuccess) e = gs.get(&pnum, std::max<size_t>(cap, 4));
+    if (e == hipSuccess) e = gs.get(&pids, std::max<size_t>(cap, 4) * 4);
+    if (e == hipSuccess) e = gs.get(&d_scores, chunk_scores * 4);
+    if (e == hipSuccess && timing) e = hipEventRecord(ev[0], st);
+    if (e != hipSuccess) {
+      rc = cbh::fail("color sort similar: a group's scratch", e);
+      break;
+    }
+    for (size_t s = g0; s < g1 && rc == CBH_OK && c->n > 0; ++s) {
+      const uint32_t n = (uint32_t)(first0[s + 1] - first0[s]);
+      if (n < 2) continue;  // no queries
+      const uint32_t stride = cbh::sort_table_row_stride(n);
+      const size_t cap_s = ((size_t)n + 3) & ~(size_t)3;
+      rc = cbh::launch_slice_color(c->dL, c->dU, c->dV, c->d_num, c->d_ids, c->cap, d_pos + pos_first[s], n, pl, pu, pv,
+                                   pnum, pids, cap_s, st);
+      if (rc) break;
+      hipLaunchKernelGGL(k_color_absent, dim3((n + 255) / 256), dim3(256), 0, st, d_attr + first0[s], n, pnum);
+      const size_t chunk = color_chunk(n, n, (size_t)1 << 24);
+      for (size_t r0 = 0; r0 < n && rc == CBH_OK; r0 += chunk) {
+        const size_t m = std::min<size_t>(chunk, n - r0);
+        rc = launch_dist(pl, pu, pv, pnum, cap_s, n, d_needles + first0[s] + r0, m, d_scores, nullptr, st);
+        if (rc) break;
+        const size_t words = m * (stride / 2);
+        hipLaunchKernelGGL(k_color_table, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, d_scores, (uint32_t)m, n,
+                           stride, reinterpret_cast<uint32_t*>(table + sorted_first[s] + r0 * stride));
+      }
+    }
+    if (rc == CBH_OK && (e = hipGetLastError()) != hipSuccess) rc = cbh::fail("color sort similar: the table fill", e);
+    if (rc != CBH_OK) break;
+    if (timing) (void)hipEventRecord(ev[1], st);
+    rc = cbh::launch_sort_table_chain(table, d_sorted_first + g0, d_id, d_attr, d_dir, d_first_pos + g0, d_first + g0, 0,
+                                      g1 - g0, largest, p, d_out_ids, d_out + g0, st);
+    if (rc != CBH_OK) break;
+    if (timing) {
+      float a = 0.f, b = 0.f;
+      (void)hipEventRecord(ev[2], st);
+      if (hipEventSynchronize(ev[2]) == hipSuccess && hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess &&
+          hipEventElapsedTime(&b, ev[1], ev[2]) == hipSuccess)
+        fill_ms += a, chain_ms += b;
+    }
+    g0 = g1;
+  }
+  for (hipEvent_t e : ev)
+    if (e) (void)hipEventDestroy(e);
+  if (rc != CBH_OK) return rc;
+  if (total) CBH_HIP(hipMemcpyAsync(out_ids, d_out_ids, total * 4, hipMemcpyDeviceToHost, st));
+  CBH_HIP(hipMemcpyAsync(out, d_out, n_sets * sizeof(cbh_sort_similar_result), hipMemcpyDeviceToHost, st));
+  CBH_HIP(hipStreamSynchronize(st));
+  g_color_sort_stat[0].store((long long)group_end.size());
+  g_color_sort_stat[1].store(timing ? (long long)(fill_ms * 1000.f) : 0);
+  g_color_sort_stat[2].store(timing ? (long long)(chain_ms * 1000.f) : 0);
+  return CBH_OK;
+}
+
+}  // namespace
+
+extern "C" int cbh_color_sort_similar(cbh_color* c, const uint32_t* ids, const void* needle_descs, const uint32_t* dir_id,
+                                      const uint8_t* under_prefix, const uint64_t* set_first, size_t n_sets,
+                                      const cbh_sort_table_params* params, uint32_t* out_ids,
+                                      cbh_sort_similar_result* out) {
+  if (!c) return CBH_E_INVAL;
+  int rc = cbh::sort_table_params_ok(params, dir_id, under_prefix);
+  if (rc != CBH_OK) return rc;
+  if (n_sets == 0) return CBH_OK;
+  if (!set_first || !out) return cs_fail(CBH_E_INVAL, "color sort similar: a required pointer is NULL");
+  const int kb = g_color_sort_table_kb.load();
+  const uint64_t budget_scores = (kb > 0 ? (uint64_t)kb * 1024 : kSortTableBytes) / 2;
+  for (size_t s = 0; s < n_sets; ++s) {
+    if (set_first[s + 1] < set_first[s]) return cs_fail(CBH_E_INVAL, "color sort similar: set_first is not ascending");
+    const uint64_t n = set_first[s + 1] - set_first[s];
+    if (n > CBH_COLOR_SORT_SIMILAR_MAX)
+      return cs_fail(CBH_E_UNSUPPORTED, "color sort similar: a set above CBH_COLOR_SORT_SIMILAR_MAX items");
+    if (n * cbh::sort_table_row_stride((uint32_t)n) > budget_scores)
+      return cs_fail(CBH_E_UNSUPPORTED, "color sort similar: a set's table does not fit \"color_sort_table_kb\"");
+  }
+  const uint64_t base = set_first[0], total = set_first[n_sets] - base;
+  if (n_sets > 0xfffffff0ull || total > 0xfffffff0ull)
+    return cs_fail(CBH_E_INVAL, "color sort similar: more than 2^32 sets or items in one call");
+  if (total && (!ids || !out_ids)) return cs_fail(CBH_E_INVAL, "color sort similar: a required pointer is NULL");
+  if (total == 0) {
+    memset(out, 0, n_sets * sizeof(cbh_sort_similar_result));
+    return CBH_OK;
+  }
+  // every set in ascending id order, on the host: positions then order like ids
+  std::vector<uint64_t> first0(n_sets + 1);
+  for (size_t s = 0; s <= n_sets; ++s) first0[s] = set_first[s] - base;
+  std::vector<uint32_t> perm(total);
+  for (uint64_t i = 0; i < total; ++i) perm[i] = (uint32_t)i;
+  const uint32_t* id0 = ids + base;
+  for (size_t s = 0; s < n_sets; ++s) {
+    std::sort(perm.begin() + first0[s], perm.begin() + first0[s + 1], [&](uint32_t a, uint32_t b) { return id0[a] < id0[b]; });
+    for (uint64_t g = first0[s]; g < first0[s + 1]; ++g) {
+      if (id0[perm[g]] == 0) return cs_fail(CBH_E_INVAL, "color sort similar: an item has id 0");
+      if (g > first0[s] && id0[perm[g]] == id0[perm[g - 1]])
+        return cs_fail(CBH_E_INVAL, "color sort similar: an id occurs twice in one set");
+    }
+  }
+  cbh::DeviceGuard g(c->device);
+  if (!g.ok) return CBH_E_NODEVICE;
+  std::lock_guard<std::mutex> lk(c->mu);
+  return color_sort_similar(c, id0, needle_descs ? (const uint8_t*)needle_descs + base * kDescBytes : nullptr,
+                            dir_id ? dir_id + base : nullptr, under_prefix ? under_prefix + base : nullptr, first0, perm,
+                            budget_scores, params, out_ids + base, out);
+}

@@ -37,35 +37,14 @@
 namespace cbh {
 namespace {
 
+#include "sortsimilar_common.h"  // kNone, kMostKeys, kTail, k_ss_keys, wave_min, ss_inval, sets_ok
+
 constexpr uint32_t kLdsItems = 16384;  // largest set whose hashes stay in LDS
-constexpr uint32_t kNone = 0xffffffffu;
-constexpr int kMostKeys = 56;          // max(max_matches <= 55, min_matches + 1 <= 56)
-constexpr int kTail = 8;               // look_behind <= 8: the entries of `sorted` a pass can still read or move
 
 struct SsParams {
   int thresh, max_thresh, min_matches, max_matches, filter_parent, path_mode, look_behind;
   int never;  // min_matches > max_matches: 1 + kept > min_matches cannot hold, every query fails
 };
-
-__global__ __launch_bounds__(256) void k_ss_keys(const uint32_t* __restrict__ ids, const uint64_t* __restrict__ set_first,
-                                                 uint32_t n_sets, uint64_t base, uint32_t total,
-                                                 unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals,
-                                                 uint32_t* __restrict__ status) {
-  const uint32_t g = blockIdx.x * 256 + threadIdx.x;
-  if (g >= total) return;
-  uint32_t lo = 0, hi = n_sets;  // last set whose first is <= base + g (empty sets in front of it share that first)
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (set_first[mid] <= base + g)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  const uint32_t id = ids[base + g];
-  if (id == 0) atomicOr(status, 1u);
-  keys[g] = (unsigned long long)lo << 32 | id;
-  vals[g] = g;
-}
 
 // attr: bit 0 = in the index, bit 1 = under the path prefix
 __global__ __launch_bounds__(256) void k_ss_gather(const unsigned long long* __restrict__ keys,
@@ -86,19 +65,6 @@ __global__ __launch_bounds__(256) void k_ss_gather(const unsigned long long* __r
   s_attr[g] = (uint8_t)((in_index ? (in_index[base + src] != 0) : 1) | (under ? (under[base + src] != 0) << 1 : 0));
   if (s_dir) s_dir[g] = dir_id[base + src];
   if (base + src == set_first[set]) first_pos[set] = g - (uint32_t)(set_first[set] - base);
-}
-
-// minimum over the 64 lanes, in every lane.  row_shr:n = 0x110 + n inside each row of 16 lanes, then row_bcast:15
-// (0x142) onto rows 1 | 3 and row_bcast:31 (0x143) onto rows 2 and 3 (wave_prefix_sum in hamm64_mfma.hip has the same
-// ladder); lanes without a source take `old`, the identity.  Lane 63 ends with the whole wave's minimum.
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)kNone, (int)v, 0x111, 0xf, 0xf, false));
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)kNone, (int)v, 0x112, 0xf, 0xf, false));
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)kNone, (int)v, 0x114, 0xf, 0xf, false));
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)kNone, (int)v, 0x118, 0xf, 0xf, false));
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)kNone, (int)v, 0x142, 0xa, 0xf, false));
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)kNone, (int)v, 0x143, 0xc, 0xf, false));
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
 // out_ids doubles as the list of positions while the workgroup runs; the last step turns positions into ids.
@@ -247,11 +213,6 @@ __global__ __launch_bounds__(1024) void k_sort_similar(const uint64_t* __restric
   for (uint32_t k = tid; k < n; k += T) order[k] = k < sorted ? g_id[off + order[k]] : 0u;
 }
 
-int ss_inval(const char* why) {
-  set_last_error_text(why);
-  return CBH_E_INVAL;
-}
-
 int params_ok(const cbh_sort_similar_params* p, const void* dir_id, const void* under_prefix) {
   if (!p) return ss_inval("sort similar: params is NULL");
   if (p->look_behind < 1 || p->look_behind > kTail) return ss_inval("sort similar: look_behind outside 1..8");
@@ -260,23 +221,6 @@ int params_ok(const cbh_sort_similar_params* p, const void* dir_id, const void* 
   if (p->path_mode < 0 || p->path_mode > 2) return ss_inval("sort similar: path_mode outside 0..2");
   if (p->filter_parent && !dir_id) return ss_inval("sort similar: filter_parent without dir_id");
   if (p->path_mode && !under_prefix) return ss_inval("sort similar: path_mode without under_prefix");
-  return CBH_OK;
-}
-
-// set_first on the host: ascending, every set within CBH_SORT_SIMILAR_MAX, the batch within 32-bit positions
-int sets_ok(const uint64_t* set_first, size_t n_sets, uint32_t* largest) {
-  *largest = 0;
-  for (size_t s = 0; s < n_sets; ++s) {
-    if (set_first[s + 1] < set_first[s]) return ss_inval("sort similar: set_first is not ascending");
-    const uint64_t n = set_first[s + 1] - set_first[s];
-    if (n > CBH_SORT_SIMILAR_MAX) {
-      set_last_error_text("sort similar: a set above CBH_SORT_SIMILAR_MAX items");
-      return CBH_E_UNSUPPORTED;
-    }
-    *largest = std::max(*largest, (uint32_t)n);
-  }
-  if (n_sets > 0xfffffff0ull || set_first[n_sets] - set_first[0] > 0xfffffff0ull)
-    return ss_inval("sort similar: more than 2^32 sets or items in one call");
   return CBH_OK;
 }
 

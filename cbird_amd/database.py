@@ -528,16 +528,69 @@ def _sort_similar_loop(index, selection, params, db_path):
 
 
 def _sort_similar_on_device(index, params) -> bool:
+    from .colordesc import ColorDescIndex
     from .index import DctHashIndex
 
-    return (isinstance(index, DctHashIndex) and params.algo == SearchParams.AlgoDCT and not params.mirrorMask and
-            not getattr(params, "turnMask", 0) and not params.templateMatch and 1 <= int(params.maxMatches) <= 55 and
+    if (params.mirrorMask or getattr(params, "turnMask", 0) or params.templateMatch or
+            not 1 <= int(params.maxMatches) <= 55):
+        return False
+    if isinstance(index, ColorDescIndex):  # no threshold and no escalation level (src/database.cpp:1707-1718)
+        return params.algo == SearchParams.AlgoColor
+    return (isinstance(index, DctHashIndex) and params.algo == SearchParams.AlgoDCT and
             0 <= int(params.dctThresh) <= 65 and int(params.maxThresh) <= 65)
+
+
+def _sort_similar_color(index, selections, params, db_path):
+    """the colour route of sort_similar_batch: ONE cbh_color_sort_similar call with the Media's descriptors as needles;
+    None when the call refuses the batch (CBH_E_UNSUPPORTED: the loop takes it)"""
+    import numpy as np
+
+    from . import _lib
+    from .colordesc import COLOR_DTYPE
+
+    flat = [m for s in selections for m in s]
+    first = np.zeros(len(selections) + 1, np.uint64)
+    np.cumsum([len(s) for s in selections], out=first[1:])
+    descs = np.zeros(len(flat), COLOR_DTYPE)
+    for k, m in enumerate(flat):
+        d = getattr(m, "colorDescriptor", None)
+        if d is not None:
+            descs[k] = np.asarray(d, COLOR_DTYPE)
+    dir_id, under, mode = _path_attributes(flat, params, db_path)
+    try:
+        got = index.sort_similar([m.id for m in flat], descs, params, first, dir_id, under, mode,
+                                 SORT_SIMILAR_LOOK_BEHIND)
+    except _lib.CbhError as e:
+        if e.code != _lib.CBH_E_UNSUPPORTED:
+            raise
+        return None
+    out = []
+    for sel, (order, queries, not_found, _) in zip(selections, got):
+        by_id = {m.id: m for m in sel}
+        out.append(([by_id[i] for i in order], queries, not_found))
+    return out
+
+
+def _path_attributes(flat, params, db_path):
+    """paths as attributes, as in filter_groups_c_abi: a number per distinct dirPath(), under-the-prefix flags, path_mode"""
+    import numpy as np
+
+    dir_id = under = None
+    if params.filterParent:
+        dirs = {}
+        dir_id = np.ascontiguousarray([dirs.setdefault(dir_path(m.path), len(dirs)) for m in flat], np.uint32)
+    if params.path != "":
+        prefix = params.path if params.path.startswith(db_path) else db_path + "/" + params.path
+        under = np.ascontiguousarray([1 if m.path.startswith(prefix) else 0 for m in flat], np.uint8)
+    return dir_id, under, 0 if params.path == "" else (1 if params.inPath else 2)
 
 
 def sort_similar_batch(index, selections, params: SearchParams, db_path: str = ""):
     """sort_similar for many selections; DctHashIndex without reflections: ONE cbh_sort_similar call, a workgroup per
-    selection (sortsimilar.hip).  Returns [sort_similar(index, s, params, True, db_path) for s in selections]."""
+    selection (sortsimilar.hip); ColorDescIndex with AlgoColor: ONE cbh_color_sort_similar call -- the score tables
+    filled on the device from the index's descriptors and the Media's colorDescriptor as needles, then walked by a
+    workgroup per selection (sortsimilar_table.hip); what that call refuses as unsupported (an id twice in the index)
+    takes the loop.  Returns [sort_similar(index, s, params, True, db_path) for s in selections]."""
     import ctypes as C
 
     import numpy as np
@@ -547,9 +600,15 @@ def sort_similar_batch(index, selections, params: SearchParams, db_path: str = "
     if not params.filterSelf:
         raise ValueError("sort_similar: without filterSelf the reference inserts the needle again forever")
     selections = [list(s) for s in selections]
-    if not (_sort_similar_on_device(index, params) and
-            all(len(s) <= _lib.CBH_SORT_SIMILAR_MAX for s in selections)):
+    from .colordesc import ColorDescIndex
+
+    colour = isinstance(index, ColorDescIndex)
+    most = _lib.CBH_COLOR_SORT_SIMILAR_MAX if colour else _lib.CBH_SORT_SIMILAR_MAX
+    if not (_sort_similar_on_device(index, params) and all(len(s) <= most for s in selections)):
         return [_sort_similar_loop(index, s, params, db_path) for s in selections]
+    if colour:
+        got = _sort_similar_color(index, selections, params, db_path)
+        return got if got is not None else [_sort_similar_loop(index, s, params, db_path) for s in selections]
     flat = [m for s in selections for m in s]
     first = np.zeros(len(selections) + 1, np.uint64)
     np.cumsum([len(s) for s in selections], out=first[1:])
@@ -560,17 +619,10 @@ def sort_similar_batch(index, selections, params: SearchParams, db_path: str = "
     L = _lib.lib()
     held = index.download()[1]
     in_index = np.ascontiguousarray(np.isin(ids, held[held != 0]), np.uint8)
-    # paths enter as attributes, as in filter_groups_c_abi: a number per distinct dirPath(), under-the-prefix flags
-    dir_id = under = None
-    if params.filterParent:
-        dirs = {}
-        dir_id = np.ascontiguousarray([dirs.setdefault(dir_path(m.path), len(dirs)) for m in flat], np.uint32)
-    if params.path != "":
-        prefix = params.path if params.path.startswith(db_path) else db_path + "/" + params.path
-        under = np.ascontiguousarray([1 if m.path.startswith(prefix) else 0 for m in flat], np.uint8)
+    dir_id, under, mode = _path_attributes(flat, params, db_path)
     sp = _lib.cbh_sort_similar_params(int(params.dctThresh), int(params.maxThresh), int(params.minMatches),
-                                      int(params.maxMatches), int(bool(params.filterParent)),
-                                      0 if params.path == "" else (1 if params.inPath else 2), SORT_SIMILAR_LOOK_BEHIND)
+                                      int(params.maxMatches), int(bool(params.filterParent)), mode,
+                                      SORT_SIMILAR_LOOK_BEHIND)
     out_ids = np.zeros(max(len(flat), 1), np.uint32)
     res = (_lib.cbh_sort_similar_result * max(len(selections), 1))()
     _lib.check(L.cbh_sort_similar(hashes.ctypes.data, ids.ctypes.data, in_index.ctypes.data,
@@ -594,7 +646,9 @@ def sort_similar(index, selection, params: SearchParams, batched: bool = True, d
     batched=False: the reference's shape for any index and any params query() supports -- index.slice() of unsorted +
     needle, query(), insert, once per pass.  batched=True (DctHashIndex, mirrorMask 0): the whole chain in one kernel
     launch, cbh_sort_similar; the Media list stands for the index's slice (items the index does not hold are never
-    candidates), so its dctHash values have to be the index's.  Anything else takes the loop.  filterSelf must be set:
+    candidates), so its dctHash values have to be the index's; ColorDescIndex with AlgoColor: cbh_color_sort_similar, the
+    candidates' descriptors are the index's and the Media's own are the needles, as in the loop.  Anything else -- the
+    keypoint-hash, ORB and video indexes, reflections, the template matcher -- takes the loop.  filterSelf must be set:
     without it the reference inserts the needle again forever (ValueError)."""
     if not params.filterSelf:
         raise ValueError("sort_similar: without filterSelf the reference inserts the needle again forever")

@@ -855,6 +855,35 @@ int cbh_sort_similar_dev(const void* d_hashes, const void* d_ids, const void* d_
                          const void* d_under_prefix, const void* d_set_first, size_t n_sets,
                          const cbh_sort_similar_params* params, void* d_out_ids, void* d_out, int device, void* stream);
 
+/* The same loop over a TABLE of pair scores, for an index whose score of a pair does not depend on what else is in the
+ * slice (sortsimilar_table.hip).  Everything said above holds -- sorted / unsorted, look_behind passes whose bound is read
+ * again on every pass, no break after a hit, failing passes counted, items never reached dropped -- except the rule for
+ * candidates: the score of (needle r, candidate c) is the set's table[r * n + c], a uint16_t, 0xFFFF = no match.  A
+ * candidate is an item that is unsorted, flagged in_index (NULL: all) and has a score other than 0xFFFF; there are no
+ * thresholds and no escalation.  Candidates order by (score, id); the first max_matches; of those, path_mode and
+ * filter_parent as in cbh_filter_params; accepted iff 1 + kept > min_matches; the answer is the first kept.  The needle
+ * is not unsorted, so it never takes one of the max_matches places.
+ * set s = items set_first[s] .. set_first[s+1]; its table = scores + table_first[s], n_s * n_s entries in the CALLER's
+ * item order, row = needle, column = candidate (the table need not be symmetric).
+ * Outputs and error codes are cbh_sort_similar's: out_ids parallel to ids with the rest of a set's range 0; out[s] =
+ * {sorted, queries, not_found, behind}; sets of 0 or 1 items make no queries.  CBH_E_INVAL: an id 0, an id twice in a
+ * set, look_behind outside 1..8, max_matches outside 1..55, path_mode outside 0..2, an attribute array the params need
+ * missing; CBH_E_UNSUPPORTED: a set above CBH_SORT_SIMILAR_MAX items.  The device holds a second copy of the tables
+ * (rows and columns in id order, rows padded to 16 bytes).  _dev: every array in device memory, work queued on `stream`;
+ * it waits for the stream twice before the ordering kernel is queued, and not after it. */
+typedef struct cbh_sort_table_params {
+  int min_matches, max_matches; /* max_matches 1..55 */
+  int filter_parent, path_mode; /* as cbh_filter_params */
+  int look_behind;              /* 1..8; the reference's 5 */
+} cbh_sort_table_params;
+int cbh_sort_similar_table(const uint16_t* scores, const uint64_t* table_first, const uint32_t* ids,
+                           const uint8_t* in_index, const uint32_t* dir_id, const uint8_t* under_prefix,
+                           const uint64_t* set_first, size_t n_sets, const cbh_sort_table_params* params,
+                           uint32_t* out_ids, cbh_sort_similar_result* out, int device);
+int cbh_sort_similar_table_dev(const void* d_scores, const void* d_table_first, const void* d_ids, const void* d_in_index,
+                               const void* d_dir_id, const void* d_under_prefix, const void* d_set_first, size_t n_sets,
+                               const cbh_sort_table_params* params, void* d_out_ids, void* d_out, int device, void* stream);
+
 /* ---- DctFeaturesIndex: src/dctfeaturesindex.{h,cpp} over src/tree/hammingtree.h -----------------
  * The index is a cbh_idx64 whose entries are (mediaId, keypoint hash) pairs, several per media:
  *   load/add      -> cbh_idx64_load / cbh_idx64_add with one entry per hash (:229-238, :143-156)
@@ -1268,8 +1297,29 @@ int cbh_color_distances(cbh_color*, const void* needle_descs, size_t nq, float* 
 /* many needles + the sort/cut of Database::searchIndex: first min(counts[q], k) matches by (score, id) */
 int cbh_color_find_batch(cbh_color*, const void* needle_descs, size_t nq, int k, cbh_match* out,
                          uint32_t* counts);
+/* -sort-similar with -p.alg color for a ragged batch of selections (cbh_sort_similar_table has the loop's rules and the
+ * outputs): per selection the table the loop's queries would see is filled on the device and walked by one workgroup.
+ *   in_index[c]  this index holds id c as a live entry (removed entries have id 0 and are no candidates, :272-273)
+ *   candidate c  the index's own descriptor, gathered on the device as cbh_color_slice does
+ *   needle r     the caller's descriptor (needle_descs, n x 258 bytes parallel to ids) when its numColors > 0, else the
+ *                index's entry for that id when held (findIndexData, :257-266), else none: the row is all 0xFFFF;
+ *                needle_descs NULL: the index's for every item
+ *   table[r][c]  (int) ColorDescriptor::distance(needle_r, entry_c), the needle as the first argument -- the distance is
+ *                not symmetric when both sides have equal numColors (src/cvutil.cpp:702-708); FLT_MAX (a side without
+ *                colours, counts that differ by more than 2) is 0xFFFF.  The arithmetic is cbh_color_find's, "color_fma"
+ *                included: the scores are its scores bit for bit.  A score is at most 1 + 32 * sqrt(100^2 + 354^2 +
+ *                262^2) < 14 454 (src/cvutil.h:83-87), so a uint16_t holds it.
+ * The tables are filled in row chunks ("color_chunk_scores") and a batch goes in groups of consecutive sets whose tables
+ * (n rows of n rounded up to 8 scores, 2 bytes each) fit "color_sort_table_kb" (default 2 GiB).  CBH_E_UNSUPPORTED: a set
+ * above CBH_COLOR_SORT_SIMILAR_MAX items or whose own table does not fit that budget, or the index holds a listed id
+ * more than once; CBH_E_INVAL as cbh_sort_similar_table; CBH_E_NOMEM when an allocation is refused (nothing is kept,
+ * the handle stays usable).  Takes the index's search lock, like cbh_color_slice. */
+#define CBH_COLOR_SORT_SIMILAR_MAX 32768
+int cbh_color_sort_similar(cbh_color*, const uint32_t* ids, const void* needle_descs, const uint32_t* dir_id,
+                           const uint8_t* under_prefix, const uint64_t* set_first, size_t n_sets,
+                           const cbh_sort_table_params* params, uint32_t* out_ids, cbh_sort_similar_result* out);
 
-/* Knobs (29).  Results never change with any of them except "color_fma".  Unknown keys return CBH_E_INVAL.
+/* Knobs (31).  Results never change with any of them except "color_fma".  Unknown keys return CBH_E_INVAL.
  * Which kernel serves a call:
  *   "scan_mfma"     64-bit scan on the matrix cores (k_hamm64_mfma*): 0 = never (the popcount kernel k_hamm64_scan), 1 = calls
  *                   with >= 256 needles and >= 4096 slots (default), 2 = always; 3 = as 1, and calls with thresholds <= 8 and
@@ -1338,6 +1388,11 @@ int cbh_color_find_batch(cbh_color*, const void* needle_descs, size_t nq, int k,
  *                   cbh_color_find_batch, cbh_color_find_all_batch and cbh_color_distances may hold: 0 (default) = 2^28 /
  *                   2^27 / 2^27; at least one needle per chunk (tests: the later chunks on a small index).  Negative
  *                   values return CBH_E_INVAL and leave the knob as it was
+ *   "color_sort_table_kb" KiB of score tables one group of sets of cbh_color_sort_similar may hold: 0 (default) = 2 GiB; a
+ *                   set whose own table does not fit is CBH_E_UNSUPPORTED (tests: several groups on small sets).
+ *                   Negative values return CBH_E_INVAL and leave the knob as it was
+ *   "color_sort_timing" 1 = cbh_color_sort_similar times its table fill and its chain apart with events and waits for
+ *                   each group (tools/sort_similar_color_bench.py); read "color_sort_fill_us" / "color_sort_chain_us"
  *   "quality_chunk_mb" what one upload of cbh_quality_scores, and the working planes of one group of launches of
  *                   cbh_quality_scores_dev, may take, in MB (default 1024; at least one image each)
  *   "tmatch_chunk_mb" what one upload of cbh_template_match, and the patches of one group of candidates of
@@ -1384,7 +1439,10 @@ int cbh_set_tuning(const char* key, int value);
  * a sharded handle notes one launch per shard, a buffer that had to grow one per attempt); "slices_on_device" (the
  * cbh_idx256_slice and cbh_color_slice calls so far that succeeded on the device route, the one that
  * runs the kernels of slice.hip; a call that had nothing to move -- an empty list, an empty index, nothing kept --
- * counts too, although it launches none of them); "color_chunk_scores" (the knob's value); "color_full_sorts" / "color_window_cuts" (needles of
+ * counts too, although it launches none of them); "color_chunk_scores" (the knob's value); "color_sort_table_kb" (the
+ * knob's value); "color_sort_groups" / "color_sort_fill_us" / "color_sort_chain_us" (of the last cbh_color_sort_similar
+ * call that succeeded: the groups its sets went in and, with "color_sort_timing" 1, the microseconds its table fills and
+ * its chains took on the device, else 0; read-only); "color_full_sorts" / "color_window_cuts" (needles of
  * cbh_color_find_batch sent through the full sort -- k above 4096, or more than 4096 candidates at or under the k-th score
  * -- / answered from the candidate list, since the library loaded; needles without a match, and k = 0, count as neither;
  * read-only); "quality_chunk_mb" (the knob's value); "quality_strip_rows" (rows of
