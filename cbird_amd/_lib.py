@@ -57,6 +57,11 @@ class cbh_filter_params(C.Structure):
                 ("merge_groups", C.c_int), ("expand_groups", C.c_int)]
 
 
+class cbh_cluster_stats(C.Structure):
+    _fields_ = [("nodes", C.c_uint64), ("records", C.c_uint64), ("clusters", C.c_uint64), ("members", C.c_uint64),
+                ("chunks", C.c_uint32), ("rescans", C.c_uint32)]
+
+
 CBH_SORT_SIMILAR_MAX = 65536
 
 
@@ -228,6 +233,9 @@ _SIGS = {
     "cbh_combine_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cbh_filter_groups_ex": (C.c_int, [_vp, _vp, _vp, _sz, C.c_int, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp,
                                        _vp]),
+    "cbh_idx64_cluster_labels": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
+    "cbh_idx64_cluster_labels_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp, _vp]),
+    "cbh_idx64_clusters": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _sz, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz), _vp]),
     "cbh_sort_similar": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int]),
     "cbh_sort_similar_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int, _vp]),
     "cbh_sort_similar_table": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int]),

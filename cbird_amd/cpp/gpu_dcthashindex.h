@@ -270,6 +270,38 @@ class GpuDctHashIndex : public Index {
     return true;
   }
 
+  /// The partition `-similar` cannot give: every connected component of this index's match graph at p.dctThresh with more
+  /// than p.minMatches members (filterMatch's rule, src/database.cpp:1244; never fewer than two), as Match(mediaId, distance
+  /// to the nearest other member) -- members in ascending id, clusters in ascending first id (cbh_idx64_clusters).  One
+  /// device pass over the edges; Media::mergeGroupList on -similar's groups is neither transitive nor better than
+  /// quadratic.  The caller maps the ids to Media and orders by path.  Empty (the error logged): the call
+  /// failed, or nothing clusters.
+  QVector<QVector<Index::Match>> gpuClusters(const SearchParams& p) const {
+    QVector<QVector<Index::Match>> res;
+    std::vector<uint64_t> first(1);
+    std::vector<cbh_match> members(1);
+    size_t nc = 0, nm = 0;
+    if (!query("clusters", [&] {
+          const int minMembers = std::max(2, p.minMatches + 1);
+          int rc = cbh_idx64_clusters(_idx, p.dctThresh, minMembers, first.data(), first.size() - 1, members.data(),
+                                      members.size(), &nc, &nm, nullptr);
+          if (rc == CBH_E_OVERFLOW && (nc > first.size() - 1 || nm > members.size())) {  // the room needed: once more
+            first.resize(nc + 1);
+            members.resize(std::max<size_t>(nm, 1));
+            rc = cbh_idx64_clusters(_idx, p.dctThresh, minMembers, first.data(), nc, members.data(), members.size(), &nc, &nm,
+                                    nullptr);
+          }
+          return rc;
+        }))
+      return res;
+    for (size_t g = 0; g < nc; ++g) {
+      QVector<Index::Match> group;
+      for (uint64_t t = first[g]; t < first[g + 1]; ++t) group.append(Index::Match(members[t].id, members[t].score));
+      res.append(group);
+    }
+    return res;
+  }
+
   cbh_idx64* handle() const { return _idx; }  // for statistics (cbh_idx64_get_stats / cbh_idx64_coalesce_stats)
 
  private:

@@ -295,6 +295,9 @@ namespace cbh {
 int sharded_scan_all(cbh_idx64* idx, Workspace* ws, const uint64_t* d_q, size_t nq, int thresh, hipStream_t stream,
                      unsigned long long* total, const ScanOpts& opts, size_t max_records);
 int sharded_download(const cbh_idx64* idx, uint64_t* hashes, uint32_t* ids, size_t cap);
+// the same gather onto the handle's root device (clusters.hip): d_hashes / d_ids hold idx->n slots in the global slot order
+// when `stream` gets to its end
+int sharded_gather_dev(const cbh_idx64* idx, uint64_t* d_hashes, uint32_t* d_ids, hipStream_t stream);
 }  // namespace cbh
 
 // what scan_all and sharded_scan_all share: the size of the first record block of a call, ...

@@ -364,6 +364,12 @@ int set_color_sort_table_kb(int v);  // color.hip "color_sort_table_kb": KiB of 
 int get_color_sort_table_kb();
 void set_color_sort_timing(int on);  // "color_sort_timing": 1 = cbh_color_sort_similar times its table fill and its chain with events
 long long get_color_sort_stat(int which);  // 0 "color_sort_groups", 1 "color_sort_fill_us", 2 "color_sort_chain_us": the last call's
+int set_cluster_chunk(int v);  // clusters.hip "cluster_chunk": needle nodes per scan of cbh_idx64_clusters, 1..2^25 (default 2^20); else CBH_E_INVAL
+int get_cluster_chunk();
+int set_cluster_max_records(int v);  // "cluster_max_records": records one of its scans may materialise (default 2^26); < 1: CBH_E_INVAL
+int get_cluster_max_records();
+void set_cluster_timing(int on);  // "cluster_timing": 1 = the cluster calls time their stages apart with events
+long long get_cluster_stat(int which);  // 0 "cluster_table_us", 1 "cluster_hook_us", 2 "cluster_emit_us": the last call's
 
 // ---- sortsimilar_table.hip: the -sort-similar chain over tables of scores -------------------------------------------
 // A set of n items in ascending id order has its table as n rows of sort_table_row_stride(n) scores (16-byte rows, the

@@ -1363,6 +1363,9 @@ int cbh_set_tuning(const char* key, int value) {
   if (!strcmp(key, "color_chunk_scores")) return set_color_chunk_scores(value);
   if (!strcmp(key, "color_sort_table_kb")) return set_color_sort_table_kb(value);
   if (!strcmp(key, "color_sort_timing")) return set_color_sort_timing(value), CBH_OK;
+  if (!strcmp(key, "cluster_chunk")) return set_cluster_chunk(value);
+  if (!strcmp(key, "cluster_max_records")) return set_cluster_max_records(value);
+  if (!strcmp(key, "cluster_timing")) return set_cluster_timing(value), CBH_OK;
   if (!strcmp(key, "scan256_kernels")) {  // a read-back, not a knob: writing 0 clears it, nothing else can be written
     if (value != 0) return CBH_E_INVAL;
     clear_scan256_kernels();
@@ -1398,6 +1401,11 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strcmp(key, "color_sort_groups")) return *value = get_color_sort_stat(0), CBH_OK;
   if (!strcmp(key, "color_sort_fill_us")) return *value = get_color_sort_stat(1), CBH_OK;
   if (!strcmp(key, "color_sort_chain_us")) return *value = get_color_sort_stat(2), CBH_OK;
+  if (!strcmp(key, "cluster_chunk")) return *value = get_cluster_chunk(), CBH_OK;
+  if (!strcmp(key, "cluster_max_records")) return *value = get_cluster_max_records(), CBH_OK;
+  if (!strcmp(key, "cluster_table_us")) return *value = get_cluster_stat(0), CBH_OK;
+  if (!strcmp(key, "cluster_hook_us")) return *value = get_cluster_stat(1), CBH_OK;
+  if (!strcmp(key, "cluster_emit_us")) return *value = get_cluster_stat(2), CBH_OK;
   if (!strcmp(key, "quality_chunk_mb")) return *value = get_quality_chunk_mb(), CBH_OK;
   if (!strcmp(key, "quality_strip_rows")) return *value = get_quality_strip_rows(), CBH_OK;
   if (!strcmp(key, "tmatch_chunk_mb")) return *value = get_tmatch_chunk_mb(), CBH_OK;

@@ -628,6 +628,25 @@ int sharded_download(const cbh_idx64* idx, uint64_t* hashes, uint32_t* ids, size
   return CBH_OK;
 }
 
+int sharded_gather_dev(const cbh_idx64* idx, uint64_t* d_hashes, uint32_t* d_ids, hipStream_t stream) {
+  const ShardSet* S = idx->shards;
+  bool drained = false;
+  for (const ShardSet::Seg& g : S->segs) {
+    const cbh_idx64* c = S->child[g.shard];
+    if (c->device == idx->device) {
+      CBH_HIP(hipMemcpyAsync(d_hashes + g.global, c->d_hashes + g.local, g.len * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+      CBH_HIP(hipMemcpyAsync(d_ids + g.global, c->d_ids + g.local, g.len * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    } else {
+      // (the copy does not run on `stream`: whatever `stream` still does with the destination blocks comes first)
+      if (!drained) CBH_HIP(hipStreamSynchronize(stream));
+      drained = true;
+      CBH_HIP(hipMemcpyPeer(d_hashes + g.global, idx->device, c->d_hashes + g.local, c->device, g.len * sizeof(uint64_t)));
+      CBH_HIP(hipMemcpyPeer(d_ids + g.global, idx->device, c->d_ids + g.local, c->device, g.len * sizeof(uint32_t)));
+    }
+  }
+  return CBH_OK;
+}
+
 // load: shard s of R takes [s*n/R, (s+1)*n/R) (cbird_amd/dist.py shard_range); src on the host, or on the
 // root device (load_dev)
 int sharded_load(cbh_idx64* idx, const void* hashes, const void* ids, size_t n, bool on_device, hipStream_t stream) {

@@ -494,6 +494,31 @@ def similar(index, haystack, params: SearchParams, batched: bool = True, db_path
     return filter_results(params, results, db_path)
 
 
+# ---- clusters: the components of the match graph (no reference counterpart; include/cbird_hip.h) ---------------------
+def clusters(index, haystack, params: SearchParams, db_path: str = ""):
+    """The partition -similar cannot give: every connected component of the index's match graph at params.dctThresh
+    that has more than params.minMatches members (filterMatch's rule, src/database.cpp:1244; never fewer than two), as
+    a group of copies of the haystack's Media with score = the distance to the nearest other member.  A group is ordered
+    by path and the groups by their first path (:1463).  One device call (DctHashIndex.clusters); a is-similar-to chain
+    a ~ c ~ b is ONE group here, where similar(mergeGroups=1) leaves b and c in two.  AlgoDCT only; the path, parent
+    and negative-match filters do not apply.  (db_path: accepted for the signature of similar(); paths are compared as
+    they are.)"""
+    if params.algo != SearchParams.AlgoDCT or not hasattr(index, "clusters"):
+        raise ValueError("clusters: only AlgoDCT on a DctHashIndex")
+    id_map = {m.id: m for m in haystack}
+    groups = []
+    for g in index.clusters(int(params.dctThresh), max(2, int(params.minMatches) + 1)):
+        out = []
+        for mid, score in g:
+            if mid not in id_map:
+                raise ValueError(f"clusters: the index holds id {mid}, the haystack does not")
+            media = copy.copy(id_map[mid])
+            media.score = score
+            out.append(media)
+        groups.append(sorted(out, key=lambda m: m.path))
+    return sorted(groups, key=lambda g: g[0].path)
+
+
 # ---- -sort-similar (src/main.cpp:1523-1580) ---------------------------------------------------------------------------
 SORT_SIMILAR_LOOK_BEHIND = 5  # `const int lookBehind = 5` (:1530)
 

@@ -240,6 +240,38 @@ class DctHashIndex:
             return np.zeros((nq, 0), np.uint32), np.zeros((nq, 0), np.int32), counts
         return out[:, :k, 0].copy(), out[:, :k, 1].astype(np.int32), counts
 
+    def cluster_labels(self, thresh: int):
+        """The connected components of the match graph at `thresh` (cbh_idx64_cluster_labels): per live entry, in
+        ascending id order, (ids u32, label u32 = the smallest id of its component, nearest u8 = the distance to its
+        nearest neighbour under thresh, 0xFF without one).  `last_cluster_stats` holds the call's cbh_cluster_stats."""
+        st, n = _lib.cbh_cluster_stats(), C.c_size_t(0)
+        cap = self.count()
+        ids, label, near = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint8)
+        check(self._L.cbh_idx64_cluster_labels(self._h, int(thresh), ids.ctypes.data, label.ctypes.data, near.ctypes.data,
+                                               cap, C.byref(n), C.byref(st)), "cluster_labels")
+        self.last_cluster_stats = st
+        return ids[: n.value], label[: n.value], near[: n.value]
+
+    def clusters(self, thresh: int, min_members: int = 2):
+        """The components with at least `min_members` entries (cbh_idx64_clusters) as lists of (mediaId, score): members
+        in ascending id, clusters in ascending first id, score = the distance to the nearest other member."""
+        st = _lib.cbh_cluster_stats()
+        cap_c = cap_m = 0
+        while True:
+            first = np.zeros(cap_c + 1, np.uint64)
+            members = np.zeros((max(cap_m, 1), 2), np.uint32)
+            nc, nm = C.c_size_t(0), C.c_size_t(0)
+            rc = self._L.cbh_idx64_clusters(self._h, int(thresh), int(min_members), first.ctypes.data, cap_c,
+                                            members.ctypes.data, cap_m, C.byref(nc), C.byref(nm), C.byref(st))
+            if rc == _lib.CBH_E_OVERFLOW and (nc.value > cap_c or nm.value > cap_m):
+                cap_c, cap_m = nc.value, nm.value
+                continue
+            check(rc, "clusters")
+            self.last_cluster_stats = st
+            sc = members[:, 1].view(np.int32)
+            return [[(int(members[t, 0]), int(sc[t])) for t in range(int(first[g]), int(first[g + 1]))]
+                    for g in range(nc.value)]
+
     def tree_masks(self, hashes: Sequence[int]) -> np.ndarray:
         """HammingTree leaf masks of needle hashes for the current contents (cbh_idx64_tree_masks)"""
         q = _as_u64(hashes)

@@ -813,6 +813,47 @@ int cbh_filter_groups_ex(const uint32_t* needle_ids, const cbh_match* matches, c
                          uint64_t* out_first, size_t cap_groups, cbh_match* out_members, size_t cap_members,
                          size_t* n_groups, size_t* n_members);
 
+/* ---- clusters: the connected components of a DctHashIndex's match graph (cbird_amd/csrc/clusters.hip) ------------------
+ * "Which of my files are the same picture?" as a partition of the library.  The reference has no counterpart: -similar
+ * gives one group per needle, and Media::mergeGroupList (src/media.cpp:300-324), its only tool for making sets of them,
+ * is not transitive (a ~ c, c ~ b, a !~ b leaves b and c in two groups, and which two depends on the path order) and
+ * quadratic in the number of groups.  Here: single-linkage clusters at dctThresh, exact.
+ *   nodes     the live entries: slots with id != 0 and hash != 0 -- what mediaIds() counts; a null hash finds nothing
+ *             (src/dcthashindex.cpp:196-200).  Live ids must be unique, else CBH_E_UNSUPPORTED (a keypoint-hash handle is
+ *             not a DctHashIndex).
+ *   edges     nodes i != j with popcount(h_i ^ h_j) < thresh, find()'s predicate (:210-217).  thresh 0..65, else
+ *             CBH_E_INVAL; at 0 there are no edges, at 1 edges join equal hashes only.
+ *   clusters  connected components with at least min_members nodes; min_members >= 2, else CBH_E_INVAL (callers pass
+ *             minMatches + 1, the rule of filterMatch, src/database.cpp:1244).
+ *   order     members in ascending id, clusters in ascending first id.  Nothing depends on the slot order, the shard layout
+ *             or the chunking below.
+ *   score     of a member = its distance to its nearest other member, 0..thresh-1.
+ * The live (id, hash) pairs are put in id order once per call; ranges of "cluster_chunk" of them (cbh_set_tuning) are
+ * the needles of one scan each, whose records are consumed and dropped before the next.  A scan with more than
+ * "cluster_max_records" records is not materialised: its range is halved and scanned again (stats.rescans); a single
+ * entry with more matches than that is CBH_E_OVERFLOW.  The call takes the handle as a reader, like
+ * cbh_search_index_batch.  CBH_E_NOMEM when an allocation is refused: nothing is kept, the handle stays usable.
+ * stats (may be NULL): nodes, records consumed, clusters / members found (cbh_idx64_clusters), scans that delivered
+ * (chunks) and scans given up for their size (rescans). */
+typedef struct cbh_cluster_stats {
+  uint64_t nodes, records, clusters, members;
+  uint32_t chunks, rescans;
+} cbh_cluster_stats;
+/* Per node, in ascending id order: ids[], label[] (the smallest id of its component), nearest[] (the distance to its
+ * nearest neighbour under thresh, 0xFF for a node without one).  Writes min(n, cap) entries; *n_out = the node count. */
+int cbh_idx64_cluster_labels(cbh_idx64*, int thresh, uint32_t* ids, uint32_t* label, uint8_t* nearest, size_t cap,
+                             size_t* n_out, cbh_cluster_stats* stats);
+/* The same into arrays on the handle's device; the work is queued on `stream` (NULL: a stream of the handle's), which
+ * the call has synchronised when it returns. */
+int cbh_idx64_cluster_labels_dev(cbh_idx64*, int thresh, void* d_ids, void* d_label, void* d_nearest, size_t cap,
+                                 size_t* n_out, cbh_cluster_stats* stats, void* stream);
+/* The clusters: cluster g = out_members[out_first[g] .. out_first[g+1]) as cbh_match{id, score}.  CBH_E_OVERFLOW with
+ * *n_clusters / *n_members = the room needed when cap_clusters (+1 entries in out_first) or cap_members is too small,
+ * exactly as cbh_filter_groups_ex. */
+int cbh_idx64_clusters(cbh_idx64*, int thresh, int min_members, uint64_t* out_first, size_t cap_clusters,
+                       cbh_match* out_members, size_t cap_members, size_t* n_clusters, size_t* n_members,
+                       cbh_cluster_stats* stats);
+
 /* ---- -sort-similar: src/main.cpp:1523-1580 ----------------------------------------------------------------------------
  * Orders selections so that every item is followed by its nearest remaining neighbour, the reference's loop and its
  * side effects restated exactly (AlgoDCT; items = 64-bit hash + unique non-zero id):
@@ -1319,7 +1360,7 @@ int cbh_color_sort_similar(cbh_color*, const uint32_t* ids, const void* needle_d
                            const uint8_t* under_prefix, const uint64_t* set_first, size_t n_sets,
                            const cbh_sort_table_params* params, uint32_t* out_ids, cbh_sort_similar_result* out);
 
-/* Knobs (31).  Results never change with any of them except "color_fma".  Unknown keys return CBH_E_INVAL.
+/* Knobs (34). Results never change with any of them except "color_fma".  Unknown keys return CBH_E_INVAL.
  * Which kernel serves a call:
  *   "scan_mfma"     64-bit scan on the matrix cores (k_hamm64_mfma*): 0 = never (the popcount kernel k_hamm64_scan), 1 = calls
  *                   with >= 256 needles and >= 4096 slots (default), 2 = always; 3 = as 1, and calls with thresholds <= 8 and
@@ -1393,6 +1434,12 @@ int cbh_color_sort_similar(cbh_color*, const uint32_t* ids, const void* needle_d
  *                   Negative values return CBH_E_INVAL and leave the knob as it was
  *   "color_sort_timing" 1 = cbh_color_sort_similar times its table fill and its chain apart with events and waits for
  *                   each group (tools/sort_similar_color_bench.py); read "color_sort_fill_us" / "color_sort_chain_us"
+ *   "cluster_chunk" needle entries per scan of cbh_idx64_clusters / cbh_idx64_cluster_labels: 1 .. 2^25 (default 2^20; tests:
+ *                   several chunks on a small index).  Other values return CBH_E_INVAL and leave the knob as it was
+ *   "cluster_max_records" records one of those scans may materialise (default 2^26 = 512 MB): a range with more is halved
+ *                   and scanned again.  Values below 1 return CBH_E_INVAL and leave the knob as it was
+ *   "cluster_timing" 1 = the cluster calls time their stages apart with events and wait for each
+ *                   (tools/clusters_bench.py); read "cluster_table_us" / "cluster_hook_us" / "cluster_emit_us"
  *   "quality_chunk_mb" what one upload of cbh_quality_scores, and the working planes of one group of launches of
  *                   cbh_quality_scores_dev, may take, in MB (default 1024; at least one image each)
  *   "tmatch_chunk_mb" what one upload of cbh_template_match, and the patches of one group of candidates of
@@ -1447,6 +1494,9 @@ int cbh_set_tuning(const char* key, int value);
  * -- / answered from the candidate list, since the library loaded; needles without a match, and k = 0, count as neither;
  * read-only); "quality_chunk_mb" (the knob's value); "quality_strip_rows" (rows of
  * the working plane one thread of the quality kernels walks: their strips start at every multiple of it; read-only);
+ * "cluster_chunk" / "cluster_max_records" (the knobs' values); "cluster_table_us" / "cluster_hook_us" / "cluster_emit_us"
+ * (of the last cluster call that succeeded, with "cluster_timing" 1: the microseconds its node table, its k_cl_hook +
+ * k_cl_flatten launches and its output stage took on the device, else 0; read-only);
  * "tmatch_chunk_mb" (the knob's value); "diff_block_pixels" (consecutive pixels of one image a workgroup of the
  * difference-image passes takes: an image above it spans several workgroups; read-only). */
 int cbh_get_tuning(const char* key, long long* value);
