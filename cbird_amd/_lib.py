@@ -71,6 +71,12 @@ class cbh_sort_similar_params(C.Structure):
 
 
 CBH_COLOR_SORT_SIMILAR_MAX = 32768
+CBH_MERGE_PLACED, CBH_MERGE_NO_MATCH, CBH_MERGE_MATCH_UNPLACED = 0, 1, 2
+
+
+class cbh_merge_params(C.Structure):
+    _fields_ = [("thresh", C.c_int), ("max_thresh", C.c_int), ("min_matches", C.c_int), ("max_matches", C.c_int),
+                ("filter_parent", C.c_int), ("path_mode", C.c_int)]
 
 
 class cbh_sort_table_params(C.Structure):
@@ -241,6 +247,8 @@ _SIGS = {
     "cbh_sort_similar_table": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int]),
     "cbh_sort_similar_table_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_int, _vp]),
     "cbh_color_sort_similar": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "cbh_merge_find": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, C.c_int]),
+    "cbh_merge_place": (C.c_int, [_vp, _sz, _sz, _vp, _vp, _vp, C.POINTER(C.c_size_t)]),
     "cbh_vdx_verify": (C.c_int, [_vp, _sz]),
     "cbh_records_topk_dev": (C.c_int, [_vp, _sz, _sz, _sz, _sz, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
     "cbh_idx64_set_record_capacity": (C.c_int, [_vp, _sz]),

@@ -227,21 +227,13 @@ class GpuDctHashIndex : public Index {
                       const SortSimilarPaths* paths = nullptr) const {
     const size_t n = selection.size();
     std::vector<uint64_t> hashes;
-    std::vector<uint32_t> ids, held, order(n ? n : 1);
+    std::vector<uint32_t> ids, order(n ? n : 1);
     for (const Media& m : selection) {
       hashes.push_back(m.dctHash());
       ids.push_back(uint32_t(m.id()));
     }
-    // what a slice of this index can hold: every entry with an id, a hash of 0 included (mediaIds() leaves those out)
-    held.resize(cbh_idx64_count(_idx) ? cbh_idx64_count(_idx) : 1);
-    std::vector<uint64_t> heldHashes(held.size());
-    if (cbh_idx64_count(_idx) &&
-        !query("download", [&] { return cbh_idx64_download(_idx, heldHashes.data(), held.data(), cbh_idx64_count(_idx)); }))
-      return false;
-    held.resize(cbh_idx64_count(_idx));
-    std::sort(held.begin(), held.end());
     std::vector<uint8_t> inIndex;
-    for (uint32_t id : ids) inIndex.push_back(id && std::binary_search(held.begin(), held.end(), id) ? 1 : 0);
+    if (!heldFlags(ids, &inIndex)) return false;
     cbh_sort_similar_params sp;
     sp.thresh = p.dctThresh, sp.max_thresh = p.maxThresh, sp.min_matches = p.minMatches, sp.max_matches = p.maxMatches;
     sp.filter_parent = paths && paths->filterParent, sp.path_mode = paths ? paths->pathMode : 0;
@@ -267,6 +259,90 @@ class GpuDctHashIndex : public Index {
     selection = sorted;
     if (queries) *queries = int(res.queries);
     if (notFound) *notFound = int(res.not_found);
+    return true;
+  }
+
+  /// The AlgoDCT stage of `-merge A B` (src/main.cpp:1582-1652) for every needle of B in one kernel launch instead of one
+  /// slice and one query per needle: needle b_k is searched inside setA followed by b_0 .. b_k (:1619-1625) with
+  /// multiSearch's maxMatches = 2 (:1591).  (*match)[k] = the place of its matches[0] in setA + setB (setA.size() + j for
+  /// b_j), 0xFFFFFFFF without one; (*score)[k] = its distance, -1 without one.  `paths` is parallel to setA then setB.
+  /// Items this index does not hold are never candidates, as in the reference's slice.  false (the error logged): the
+  /// call failed.
+  bool gpuMergeFind(const MediaGroup& setA, const MediaGroup& setB, const SearchParams& p, std::vector<uint32_t>* match,
+                    std::vector<int32_t>* score, const SortSimilarPaths* paths = nullptr) const {
+    const size_t nA = setA.size(), nB = setB.size(), n = nA + nB;
+    std::vector<uint64_t> hashes;
+    std::vector<uint32_t> ids;
+    for (const MediaGroup* g : {&setA, &setB})
+      for (const Media& m : *g) {
+        hashes.push_back(m.dctHash());
+        ids.push_back(uint32_t(m.id()));
+      }
+    std::vector<uint8_t> inIndex;
+    if (!heldFlags(ids, &inIndex)) return false;
+    cbh_merge_params mp;
+    mp.thresh = p.dctThresh, mp.max_thresh = p.maxThresh, mp.min_matches = p.minMatches;
+    mp.max_matches = 2;  // `search.params.maxMatches = 2` (:1591)
+    mp.filter_parent = paths && paths->filterParent, mp.path_mode = paths ? paths->pathMode : 0;
+    if ((mp.filter_parent && paths->dirId.size() != n) || (mp.path_mode && paths->underPrefix.size() != n)) {
+      qCritical("GpuDctHashIndex::gpuMergeFind: the path attributes are not parallel to A then B");
+      return false;
+    }
+    match->assign(nB ? nB : 1, 0xffffffffu);
+    score->assign(nB ? nB : 1, -1);
+    const bool ok = query("merge_find", [&] {
+      return cbh_merge_find(hashes.data(), ids.data(), inIndex.data(), mp.filter_parent ? paths->dirId.data() : nullptr,
+                            mp.path_mode ? paths->underPrefix.data() : nullptr, nA, nB, &mp, match->data(), score->data(),
+                            _device);
+    });
+    match->resize(nB);
+    score->resize(nB);
+    return ok;
+  }
+  /// The placement of `-merge` (:1628-1650) for match[k] as gpuMergeFind writes it, from whichever stage of the cascade
+  /// answered: setA becomes the merged list.  (*status)[k] (may be NULL) = CBH_MERGE_PLACED, CBH_MERGE_NO_MATCH ("no
+  /// match", the needle is dropped) or CBH_MERGE_MATCH_UNPLACED (its match is a needle that was dropped: the reference's
+  /// Q_ASSERT at :1640; here the needle is dropped too).  false (setA untouched, the error logged): a match outside A, B.
+  static bool mergePlace(MediaGroup& setA, const MediaGroup& setB, const std::vector<uint32_t>& match,
+                         std::vector<uint8_t>* status = nullptr) {
+    const size_t nA = setA.size(), nB = setB.size();
+    std::vector<uint64_t> hashes;
+    for (const MediaGroup* g : {static_cast<const MediaGroup*>(&setA), &setB})
+      for (const Media& m : *g) hashes.push_back(m.dctHash());
+    std::vector<uint32_t> order(nA + nB + 1);
+    std::vector<uint8_t> st(nB + 1);
+    size_t len = 0;
+    if (match.size() != nB ||
+        cbh_merge_place(hashes.data(), nA, nB, match.data(), order.data(), st.data(), &len) != CBH_OK) {
+      qCritical("GpuDctHashIndex::mergePlace: one match per needle, each a place in A then B");
+      return false;
+    }
+    MediaGroup merged;
+    for (size_t k = 0; k < len; ++k) merged.append(order[k] < nA ? setA[order[k]] : setB[order[k] - nA]);
+    setA = merged;
+    st.resize(nB);
+    if (status) *status = st;
+    return true;
+  }
+  /// `-merge` with AlgoDCT: gpuMergeFind, then mergePlace with every needle the stage answered at a score under 12
+  /// (multiSearch's threshold for algo 0, :1594-1607).  *unanswered = the needles of setB, in B's order, that it did not
+  /// answer so -- they are NOT placed: the caller's own cascade (fdct, ORB, colour through Engine::query) still has to try
+  /// them before placing them.  The result is the reference's whenever *unanswered comes back empty; a caller that wants
+  /// it for the other needles too completes `match` itself between the two halves, because a place
+  /// depends on what was placed before.  false (setA untouched, the error logged): the call failed.
+  bool gpuMerge(MediaGroup& setA, const MediaGroup& setB, const SearchParams& p, QVector<int>* unanswered,
+                const SortSimilarPaths* paths = nullptr) const {
+    std::vector<uint32_t> match;
+    std::vector<int32_t> score;
+    if (!gpuMergeFind(setA, setB, p, &match, &score, paths)) return false;
+    QVector<int> open;
+    for (size_t k = 0; k < match.size(); ++k)
+      if (match[k] == 0xffffffffu || score[k] >= 12) {
+        match[k] = 0xffffffffu;
+        open.append(int(k));
+      }
+    if (!mergePlace(setA, setB, match)) return false;
+    if (unanswered) *unanswered = open;
     return true;
   }
 
@@ -317,6 +393,19 @@ class GpuDctHashIndex : public Index {
   template <class Call>
   bool query(const char* what, Call&& call) const {
     return gpuidx::run(gpuidx::Query, (std::string("GpuDctHashIndex::") + what).c_str(), call, cbh_idx64_device_mask(_idx));
+  }
+  // (*inIndex)[i] = a slice of this index can hold ids[i]: every entry with an id, a hash of 0 included (mediaIds()
+  // leaves those out)
+  bool heldFlags(const std::vector<uint32_t>& ids, std::vector<uint8_t>* inIndex) const {
+    std::vector<uint32_t> held(cbh_idx64_count(_idx) ? cbh_idx64_count(_idx) : 1);
+    std::vector<uint64_t> heldHashes(held.size());
+    if (cbh_idx64_count(_idx) &&
+        !query("download", [&] { return cbh_idx64_download(_idx, heldHashes.data(), held.data(), cbh_idx64_count(_idx)); }))
+      return false;
+    held.resize(cbh_idx64_count(_idx));
+    std::sort(held.begin(), held.end());
+    for (uint32_t id : ids) inIndex->push_back(id && std::binary_search(held.begin(), held.end(), id) ? 1 : 0);
+    return true;
   }
   int _device;
   cbh_idx64* _idx;

@@ -680,3 +680,173 @@ def sort_similar(index, selection, params: SearchParams, batched: bool = True, d
     if batched:
         return sort_similar_batch(index, [selection], params, db_path)[0]
     return _sort_similar_loop(index, selection, params, db_path)
+
+
+# ---- -merge (src/main.cpp:1582-1652) ------------------------------------------------------------------------------------
+MERGE_THRESHOLDS = (12, 1000, 1000, 2 ** 31 - 1)  # "if match.score is >= threshold, use the next algorithm" (:1593-1599)
+MERGE_PLACED, MERGE_NO_MATCH, MERGE_MATCH_UNPLACED = 0, 1, 2  # CBH_MERGE_* of include/cbird_hip.h
+
+
+def _media_ready(needle, algo) -> bool:
+    """SearchParams::mediaReady (src/index.cpp:31-52) for algos 0..3"""
+    if algo == SearchParams.AlgoDCT:
+        return int(needle.dctHash) != 0
+    if needle.id != 0:
+        return True
+    if algo == SearchParams.AlgoDCTFeatures:
+        return len(getattr(needle, "keyPointHashes", None) or []) > 0
+    if algo == SearchParams.AlgoCVFeatures:
+        d = getattr(needle, "keyPointDescriptors", None)
+        return d is not None and len(d) > 0
+    return getattr(needle, "colorDescriptor", None) is not None
+
+
+def _merge_indexes(indexes, params):
+    if params.algo > SearchParams.AlgoColor:
+        raise ValueError("merge: the cascade's threshold table ends at AlgoColor (src/main.cpp:1594-1599)")
+    return indexes if isinstance(indexes, dict) else {params.algo: indexes}
+
+
+def multi_search(indexes, needle, params: SearchParams, id_map: dict, set_ids, db_path: str = ""):
+    """the lambda multiSearch of -merge (src/main.cpp:1587-1615) with what exists: maxMatches = 2; from params.algo on,
+    query() inside indexes[algo].slice(set_ids) -- the inSet slice of Database::similarTo (src/database.cpp:1475-1486) --
+    accepted when there is a match and matches[0].score < MERGE_THRESHOLDS[algo]; otherwise the next algo, up to
+    AlgoColor.  An algo without an index, or whose needle is not mediaReady, finds nothing.  Returns (matches, algo), or
+    ([], -1) when no stage answered.  indexes maps algo -> index; a bare index stands for {params.algo: index}."""
+    indexes = _merge_indexes(indexes, params)
+    p = copy.copy(params)
+    p.maxMatches = 2
+    set_ids = list(set_ids)
+    for algo in range(params.algo, SearchParams.AlgoColor + 1):
+        p.algo = algo
+        index = indexes.get(algo)
+        if index is None or not _media_ready(needle, algo):
+            continue
+        matches = query(index.slice(set_ids), needle, p, id_map, db_path=db_path)
+        if matches and matches[0].score < MERGE_THRESHOLDS[algo]:
+            return matches, algo
+    return [], -1
+
+
+def _merge_on_device(index, params) -> bool:
+    from .index import DctHashIndex
+
+    return (isinstance(index, DctHashIndex) and params.algo == SearchParams.AlgoDCT and not params.templateMatch and
+            0 <= int(params.dctThresh) <= 65 and 0 <= int(params.maxThresh) <= 65)
+
+
+def _merge_find(index, media, n_a, params, db_path):
+    """cbh_merge_find for all needles: (match place or -1, score) per needle"""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+
+    n_b = len(media) - n_a
+    ids = np.ascontiguousarray([m.id for m in media], np.uint32)
+    hashes = np.ascontiguousarray([int(m.dctHash) for m in media], np.uint64)
+    # the reference searches the index's slice, not the Media list: what the index does not hold is no candidate
+    held = index.download()[1]
+    in_index = np.ascontiguousarray(np.isin(ids, held[held != 0]), np.uint8)
+    dir_id, under, mode = _path_attributes(media, params, db_path)
+    mp = _lib.cbh_merge_params(int(params.dctThresh), int(params.maxThresh), int(params.minMatches), 2,
+                               int(bool(params.filterParent)), mode)
+    match = np.zeros(max(n_b, 1), np.uint32)
+    score = np.zeros(max(n_b, 1), np.int32)
+    _lib.check(_lib.lib().cbh_merge_find(hashes.ctypes.data, ids.ctypes.data, in_index.ctypes.data,
+                                         None if dir_id is None else dir_id.ctypes.data,
+                                         None if under is None else under.ctypes.data, n_a, n_b, C.byref(mp),
+                                         match.ctypes.data, score.ctypes.data, getattr(index, "device", 0)), "merge_find")
+    return [(-1 if int(m) == 0xFFFFFFFF else int(m), int(s)) for m, s in zip(match[:n_b], score[:n_b])]
+
+
+def _merge_place_loop(media, n_a, match):
+    """the placement of -merge (src/main.cpp:1628-1650) on a Python list of places"""
+    order, status = list(range(n_a)), []
+    for k, m in enumerate(match):
+        if m < 0:
+            status.append(MERGE_NO_MATCH)  # qCritical("no match") (:1631-1634)
+            continue
+        if m not in order:
+            status.append(MERGE_MATCH_UNPLACED)  # the reference's Q_ASSERT (:1640)
+            continue
+        pos = order.index(m)
+        if 0 < pos < len(order) - 1:
+            h = int(media[n_a + k].dctHash)
+            before = bin(h ^ int(media[order[pos - 1]].dctHash)).count("1")
+            after = bin(h ^ int(media[order[pos + 1]].dctHash)).count("1")
+            if after < before:
+                pos += 1
+        order.insert(pos, n_a + k)
+        status.append(MERGE_PLACED)
+    return order, status
+
+
+def _merge_place(media, n_a, match):
+    """the same through cbh_merge_place"""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+
+    n_b = len(media) - n_a
+    hashes = np.ascontiguousarray([int(m.dctHash) for m in media], np.uint64)
+    m32 = np.ascontiguousarray([0xFFFFFFFF if m < 0 else m for m in match] or [0], np.uint32)
+    order = np.zeros(max(len(media), 1), np.uint32)
+    status = np.zeros(max(n_b, 1), np.uint8)
+    n_out = C.c_size_t(0)
+    _lib.check(_lib.lib().cbh_merge_place(hashes.ctypes.data, n_a, n_b, m32.ctypes.data, order.ctypes.data,
+                                          status.ctypes.data, C.byref(n_out)), "merge_place")
+    return [int(i) for i in order[:n_out.value]], [int(s) for s in status[:n_b]]
+
+
+def merge(indexes, set_a, set_b, params: SearchParams, batched: bool = True, db_path: str = ""):
+    """-merge A B (src/main.cpp:1582-1652): every item of set_b put into set_a next to its closest match.  Needle b_k, in
+    B's order, is searched with multi_search inside the original A followed by b_0 .. b_k (:1619-1625); a needle with a
+    match goes in front of it in the list built so far -- behind it when the match has neighbours on both sides and the
+    needle's dctHash is strictly nearer to the one behind (:1643-1648) -- and a needle without one is dropped.  A needle
+    whose match is an earlier needle that was dropped aborts the reference (Q_ASSERT, :1640); here it is dropped too,
+    with a status of its own.  Returns (merged list of Media, report), report[k] = (status MERGE_*, the algo that
+    answered or -1, the score or -1, the match's id or 0) of needle k.
+
+    batched=False: multi_search per needle and the placement in Python -- the reference's shape, for any index.
+    batched=True: a DctHashIndex as algo 0 (thresholds within 0..65, no templateMatch) answers ALL needles in one
+    cbh_merge_find call (merge.hip; the Media's dctHash stands for the index's, items the index does not hold are never
+    candidates); needles it leaves unanswered or answers at a score >= 12 take the later stages through multi_search's
+    slice and query; the placement is cbh_merge_place.  Anything else takes multi_search for every needle.
+    ValueError: filterSelf off (every needle would find itself), mirrorMask or turnMask set (there are no images here),
+    params.algo above AlgoColor, an id 0 or an id twice in A and B."""
+    if not params.filterSelf:
+        raise ValueError("merge: without filterSelf every needle finds itself in its own set")
+    if params.mirrorMask or getattr(params, "turnMask", 0):
+        raise ValueError("merge: reflections and turns need the needles' images")
+    indexes = _merge_indexes(indexes, params)
+    set_a, set_b = list(set_a), list(set_b)
+    media, n_a = set_a + set_b, len(set_a)
+    id_map = {m.id: m for m in media}
+    if len(id_map) != len(media) or 0 in id_map:
+        raise ValueError("merge: A and B together need unique non-zero ids")
+    ids = [m.id for m in media]
+    place_of = {m.id: k for k, m in enumerate(media)}
+    found = [None] * len(set_b)  # (place, algo, score)
+    rest, later = range(len(set_b)), params
+    if batched and set_b and _merge_on_device(indexes.get(SearchParams.AlgoDCT), params):
+        first = _merge_find(indexes[SearchParams.AlgoDCT], media, n_a, params, db_path)
+        rest = []
+        for k, (m, s) in enumerate(first):
+            if m >= 0 and s < MERGE_THRESHOLDS[0]:
+                found[k] = (m, SearchParams.AlgoDCT, s)
+            else:
+                rest.append(k)
+        later = copy.copy(params)
+        later.algo = SearchParams.AlgoDCTFeatures
+    for k in rest:
+        matches, algo = multi_search(indexes, set_b[k], later, id_map, ids[:n_a + k + 1], db_path)
+        if matches:
+            found[k] = (place_of[matches[0].id], algo, int(matches[0].score))
+    match = [-1 if f is None else f[0] for f in found]
+    order, status = (_merge_place if batched else _merge_place_loop)(media, n_a, match)
+    report = [(st, -1, -1, 0) if f is None else (st, f[1], f[2], media[f[0]].id) for st, f in zip(status, found)]
+    return [media[i] for i in order], report

@@ -925,6 +925,51 @@ int cbh_sort_similar_table_dev(const void* d_scores, const void* d_table_first, 
                                const void* d_dir_id, const void* d_under_prefix, const void* d_set_first, size_t n_sets,
                                const cbh_sort_table_params* params, void* d_out_ids, void* d_out, int device, void* stream);
 
+/* ---- -merge A B: src/main.cpp:1582-1652 --------------------------------------------------------------------------------
+ * Puts every item of selection B into selection A next to its closest match.  The reference, restated:
+ *   sets: for needle b_k, in B's order, params.set = the original A followed by b_0 .. b_k, with inSet (:1619-1625); the
+ *   set grows by appended needles only and never holds the mutated A, so the searches do not depend on one another.
+ *   one search, the lambda multiSearch (:1587-1615): maxMatches = 2; from params.algo on, Engine::query, accepted when
+ *   there is a match and matches[0].score < thresholds[algo], thresholds = {12, 1000, 1000, INT_MAX} for algos 0..3;
+ *   otherwise algo + 1, until algo > 3, then no matches.  (A start at AlgoVideo reads past the table: refused here.)
+ *   placement (:1628-1650), sequential in B's order on the list L = A with every needle placed so far: no match --
+ *   qCritical("no match"), the needle is dropped; else pos = the place of matches[0] in L; if 0 < pos < len - 1 and
+ *   hamm64(needle, L[pos+1]) < hamm64(needle, L[pos-1]) then pos + 1; L.insert(pos, needle).  A needle lands in front of
+ *   its match, and behind it only when the match has neighbours on both sides and the needle is strictly nearer to the
+ *   one behind.  The two distances are of the dctHash, whichever algorithm answered.
+ *   A match may be an earlier needle that was itself dropped: the reference's Q_ASSERT (:1640) aborts the process.  Here
+ *   that needle is dropped with CBH_MERGE_MATCH_UNPLACED and the merge goes on -- a chosen deviation; any match on an
+ *   empty A is such a case.
+ * cbh_merge_find is the AlgoDCT stage for all needles in one launch (merge.hip): the arrays hold A (n_a items) then B
+ * (n_b items); items = 64-bit hash + unique non-zero id.  One query is exactly the one cbh_sort_similar defines above --
+ * a needle hash of 0, escalation with self, the order by (distance, id), the first max_matches, path_mode and
+ * filter_parent, accepted iff 1 + kept > min_matches, filterSelf on -- with one difference: the candidates of needle b_k
+ * are not "unsorted items" but the items of A and b_0 .. b_{k-1} flagged in_index (the slice of its set, Database::similarTo
+ * with inSet, src/database.cpp:1475-1486, without the needle).  in_index (NULL: all in the index), dir_id (may be NULL
+ * without filter_parent), under_prefix (may be NULL with path_mode 0) are parallel to hashes.  multiSearch's own
+ * parameters are max_matches = 2 and the caller's thresholds; the score limit 12 is the caller's to apply.
+ * out_match[k] = the place of needle k's answer in the caller's arrays (0 .. n_a + n_b - 1), 0xFFFFFFFF without one;
+ * out_score[k] = its distance, -1 without one.
+ * CBH_E_INVAL: an id 0, an id twice in A and B, max_matches outside 1..55, thresholds outside 0..65, path_mode outside
+ * 0..2, an attribute array the params need missing; CBH_E_UNSUPPORTED: n_a + n_b >= 2^24 (a query's key holds the
+ * position in 24 bits); CBH_E_NOMEM when an allocation is refused: nothing is kept.
+ * cbh_merge_place is the placement above, on the host with no device use: match[k] as cbh_merge_find writes it, from
+ * whichever stage of the cascade answered (0xFFFFFFFF: none).  out_order (room for n_a + n_b) = the places in the
+ * caller's arrays in merged order, *n_out of them; out_status[k] = CBH_MERGE_* of needle k.  CBH_E_INVAL: a match
+ * outside the arrays. */
+#define CBH_MERGE_PLACED 0
+#define CBH_MERGE_NO_MATCH 1
+#define CBH_MERGE_MATCH_UNPLACED 2
+typedef struct cbh_merge_params {
+  int thresh, max_thresh, min_matches, max_matches; /* max_matches 1..55; multiSearch's is 2 */
+  int filter_parent, path_mode;                     /* as cbh_filter_params */
+} cbh_merge_params;
+int cbh_merge_find(const uint64_t* hashes, const uint32_t* ids, const uint8_t* in_index, const uint32_t* dir_id,
+                   const uint8_t* under_prefix, size_t n_a, size_t n_b, const cbh_merge_params* params, uint32_t* out_match,
+                   int32_t* out_score, int device);
+int cbh_merge_place(const uint64_t* hashes, size_t n_a, size_t n_b, const uint32_t* match, uint32_t* out_order,
+                    uint8_t* out_status, size_t* n_out);
+
 /* ---- DctFeaturesIndex: src/dctfeaturesindex.{h,cpp} over src/tree/hammingtree.h -----------------
  * The index is a cbh_idx64 whose entries are (mediaId, keypoint hash) pairs, several per media:
  *   load/add      -> cbh_idx64_load / cbh_idx64_add with one entry per hash (:229-238, :143-156)
