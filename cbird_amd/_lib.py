@@ -93,6 +93,17 @@ class cbh_vmatch(C.Structure):
                 ("len", C.c_int32)]
 
 
+class cbh_vcover(C.Structure):
+    _fields_ = [("src_frames_total", C.c_int64), ("src_frames_covered", C.c_int64), ("gap_len", C.c_int64),
+                ("gap_begin", C.c_int32), ("n_src", C.c_int32), ("n_dst", C.c_int32), ("n_covered", C.c_int32),
+                ("n_low_detail", C.c_int32), ("near_percent", C.c_int32), ("src_in", C.c_int32), ("dst_in", C.c_int32),
+                ("len", C.c_int32), ("dst_min", C.c_int32), ("dst_max", C.c_int32), ("reserved", C.c_int32)]
+
+
+class cbh_vcover_frame(C.Structure):
+    _fields_ = [("src_frame", C.c_int32), ("dst_frame", C.c_int32), ("distance", C.c_int32)]
+
+
 class cbh_quality_detail(C.Structure):
     _fields_ = [("h_sum", C.c_uint64), ("v_sum", C.c_uint64), ("h_mean", C.c_float), ("v_mean", C.c_float),
                 ("h_long", C.c_int32), ("v_long", C.c_int32), ("num_edges", C.c_int32), ("qw", C.c_int32),
@@ -271,6 +282,8 @@ _SIGS = {
                                       C.c_int, _vp, _sz, C.POINTER(_sz)]),
     "cbh_vidx_find_videos_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, C.c_int, C.c_int, C.c_int, C.c_int,
                                              C.c_int, _vp, _sz, _vp]),
+    "cbh_video_coverage": (C.c_int, [C.c_int, _vp, _vp, _vp, _sz, _vp, _sz, C.c_int, C.c_int, _vp, _vp, _sz, _vp]),
+    "cbh_vidx_coverage": (C.c_int, [_vp, _vp, _vp, _sz, C.c_int, C.c_int, _vp, _vp, _sz, _vp]),
     "cbh_vdx_encode": (_sz, [_vp, _vp, _sz, C.c_char_p, _vp, _sz]),
     "cbh_vdx_decode": (C.c_longlong, [_vp, _sz, _vp, _vp, _sz]),
     "cbh_vdx_version": (C.c_int, [_vp, _sz]),

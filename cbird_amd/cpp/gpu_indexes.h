@@ -520,6 +520,51 @@ class GpuDctVideoIndex : public DctVideoIndex {
     return copy;
   }
 
+  /// One pair of gpuCoverage: the summary (cbh_vcover, include/cbird_hip.h) and, with maps, one entry per considered frame
+  /// of the source -- its frame number, the nearest frame of the destination and its distance.
+  struct Coverage {
+    cbh_vcover summary;
+    std::vector<cbh_vcover_frame> frames;
+    /// the destination holds at least minPercent of the source, counted in the source's own frame numbers
+    bool contains(int minPercent = 100) const {
+      return summary.src_frames_covered * 100 >= int64_t(minPercent) * summary.src_frames_total;
+    }
+  };
+  /// Which frames of one video another contains -- the list findVideo builds per matched video and drops
+  /// (dctvideoindex.cpp:468-509), kept: pair k is the video of media id pairs[k].first (the source) against that of
+  /// pairs[k].second, both held by this index; (*out)[k] answers it.  One call for all pairs, every distinct video
+  /// uploaded once; p.dctThresh and p.skipFrames as in find(); exact, whatever radixCompat says.  maps = false fetches
+  /// the summaries only.  false (the error logged, *out empty): an id the index does not hold, or the call failed.
+  bool gpuCoverage(const std::vector<std::pair<uint32_t, uint32_t>>& pairs, const SearchParams& p, std::vector<Coverage>* out,
+                   bool maps = true) const {
+    out->clear();
+    const size_t n = pairs.size();
+    std::vector<uint32_t> src, dst;
+    for (const auto& pr : pairs) src.push_back(pr.first), dst.push_back(pr.second);
+    std::vector<cbh_vcover> sums(n ? n : 1);
+    std::vector<uint64_t> offs(n + 1, 0);
+    std::vector<cbh_vcover_frame> map(1);
+    if (maps) {  // the sizes are known before anything runs: a call without room reports them and does nothing else
+      cbh_clear_error();
+      const int rc = cbh_vidx_coverage(_idx, src.data(), dst.data(), n, p.dctThresh, p.skipFrames, sums.data(), map.data(), 0,
+                                       offs.data());
+      if (rc != CBH_OK && rc != CBH_E_OVERFLOW) {
+        qCritical("GpuDctVideoIndex::gpuCoverage: %s (%s)", cbh_strerror(rc), cbh_last_error());
+        return false;
+      }
+      map.resize(size_t(offs[n]) ? size_t(offs[n]) : 1);
+    }
+    if (!CBH_QUERY(cbh_vidx_coverage(_idx, src.data(), dst.data(), n, p.dctThresh, p.skipFrames, sums.data(),
+                                     maps ? map.data() : nullptr, maps ? size_t(offs[n]) : 0, offs.data())))
+      return false;
+    out->resize(n);
+    for (size_t k = 0; k < n; ++k) {
+      (*out)[k].summary = sums[k];
+      if (maps) (*out)[k].frames.assign(map.begin() + offs[k], map.begin() + offs[k + 1]);
+    }
+    return true;
+  }
+
   cbh_vidx* handle() const { return _idx; }  // for statistics (cbh_combine_stats)
 
  private:

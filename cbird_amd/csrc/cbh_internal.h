@@ -370,6 +370,10 @@ int set_cluster_max_records(int v);  // "cluster_max_records": records one of it
 int get_cluster_max_records();
 void set_cluster_timing(int on);  // "cluster_timing": 1 = the cluster calls time their stages apart with events
 long long get_cluster_stat(int which);  // 0 "cluster_table_us", 1 "cluster_hook_us", 2 "cluster_emit_us": the last call's
+int set_vcover_chunk(int v);  // vcoverage.hip "vcover_chunk": destination entries per workgroup of cbh_video_coverage, 0 (default) = by the batch, 1..2^24; else CBH_E_INVAL
+int get_vcover_chunk();
+int set_vcover_tile(int v);  // "vcover_tile": source frames per workgroup, 256 / 512 / 1024 (default) / 2048; else CBH_E_INVAL
+int get_vcover_tile();
 
 // ---- sortsimilar_table.hip: the -sort-similar chain over tables of scores -------------------------------------------
 // A set of n items in ascending id order has its table as n rows of sort_table_row_stride(n) scores (16-byte rows, the

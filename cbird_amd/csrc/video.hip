@@ -552,6 +552,46 @@ int cbh_vidx_find_videos_batch(cbh_vidx* v, const int32_t* frames, const uint64_
   return pos > cap ? CBH_E_OVERFLOW : CBH_OK;
 }
 
+/* The coverage maps (vcoverage.hip) of videos the handle holds: the lists of the named media, each distinct video once,
+ * handed to cbh_video_coverage.  Host code over v->videos, the same on a plain and on a sharded handle; the search
+ * structure is not touched.  Of two videos with one media id the first is taken, as cbh_vidx_slice does. */
+int cbh_vidx_coverage(cbh_vidx* v, const uint32_t* src_ids, const uint32_t* dst_ids, size_t n_pairs, int thresh,
+                      int skip_frames, cbh_vcover* summaries, cbh_vcover_frame* map, size_t map_cap,
+                      uint64_t* map_offsets) {
+  if (!v || (n_pairs && (!src_ids || !dst_ids))) return CBH_E_INVAL;
+  std::vector<int32_t> frames;
+  std::vector<uint64_t> hashes, offsets(1, 0);
+  std::vector<uint32_t> pairs;
+  try {
+    std::lock_guard<std::mutex> lk(v->build_mu);
+    std::unordered_map<uint32_t, size_t> at;  // media id -> its first video
+    for (size_t i = 0; i < v->videos.size(); ++i) at.emplace(v->videos[i].media_id, i);
+    std::unordered_map<size_t, uint32_t> row;  // video -> its row of this call's table
+    pairs.reserve(2 * n_pairs);
+    for (size_t k = 0; k < n_pairs; ++k)
+      for (uint32_t id : {src_ids[k], dst_ids[k]}) {
+        auto it = at.find(id);
+        if (it == at.end()) {
+          set_last_error_text("cbh_vidx_coverage: a media id the index does not hold");
+          return CBH_E_INVAL;
+        }
+        auto put = row.emplace(it->second, (uint32_t)row.size());
+        if (put.second) {
+          const cbh_vidx::Video& vid = v->videos[it->second];
+          frames.insert(frames.end(), vid.frames.begin(), vid.frames.end());
+          hashes.insert(hashes.end(), vid.hashes.begin(), vid.hashes.end());
+          offsets.push_back(hashes.size());
+        }
+        pairs.push_back(put.first->second);
+      }
+  } catch (const std::bad_alloc&) {
+    set_last_error_text("cbh_vidx_coverage: host allocation failed");
+    return CBH_E_NOMEM;
+  }
+  return cbh_video_coverage(v->device, frames.data(), hashes.data(), offsets.data(), offsets.size() - 1, pairs.data(),
+                            n_pairs, thresh, skip_frames, summaries, map, map_cap, map_offsets);
+}
+
 /* ---- .vdx v2 codec (host) ------------------------------------------------------------------- */
 
 // Layout (src/videoindex.cpp:271-337 fixes the bytes, nothing else): text header line, u32 length of the frame-number

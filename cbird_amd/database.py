@@ -519,6 +519,33 @@ def clusters(index, haystack, params: SearchParams, db_path: str = ""):
     return sorted(groups, key=lambda g: g[0].path)
 
 
+# ---- video coverage: which frames of one clip another contains (no reference counterpart; include/cbird_hip.h) -------
+def video_coverage(index, groups, params: SearchParams):
+    """For result groups [needle, match1, ...] as similar() returns them for AlgoVideo: needle -> match and match ->
+    needle for every member, all in ONE DctVideoIndex.coverage call (summaries only).  Sets on each match
+        coverage    the percent of the needle's frames the match contains
+        coveredBy   the percent of the match's frames the needle contains
+    (whole percents of frame numbers, VideoCoverage.percent) and touches no other attribute; the needle is left alone.
+    100 / below 100 reads "the needle is a cut of this match, it is safe to drop the needle".  A member that is no
+    video (an image needle of findFrame) is skipped.  Returns the groups."""
+    if params.algo != SearchParams.AlgoVideo or not hasattr(index, "coverage"):
+        raise ValueError("video_coverage: only AlgoVideo on a DctVideoIndex")
+    pairs, where = [], []
+    for g in groups:
+        if not g or getattr(g[0], "videoIndex", None) is None:
+            continue
+        for m in g[1:]:
+            if getattr(m, "videoIndex", None) is None:
+                continue
+            where.append(m)
+            pairs += [(g[0].id, m.id), (m.id, g[0].id)]
+    if pairs:
+        res = index.coverage(pairs, params, maps=False)
+        for k, m in enumerate(where):
+            m.coverage, m.coveredBy = res[2 * k].percent(), res[2 * k + 1].percent()
+    return groups
+
+
 # ---- -sort-similar (src/main.cpp:1523-1580) ---------------------------------------------------------------------------
 SORT_SIMILAR_LOOK_BEHIND = 5  # `const int lookBehind = 5` (:1530)
 

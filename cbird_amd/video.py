@@ -169,6 +169,118 @@ class VideoSearchParams(SearchParams):
     videoRadix: int = 10  # `-p.vradix`; only honoured by DctVideoIndex(radix_compat=True), else the search is exact
 
 
+# ---- coverage maps (cbird_amd/csrc/vcoverage.hip; the rules are in include/cbird_hip.h) ------------------------------
+VCOVER_DTYPE = np.dtype([("src_frames_total", "<i8"), ("src_frames_covered", "<i8"), ("gap_len", "<i8"),
+                         ("gap_begin", "<i4"), ("n_src", "<i4"), ("n_dst", "<i4"), ("n_covered", "<i4"),
+                         ("n_low_detail", "<i4"), ("near_percent", "<i4"), ("src_in", "<i4"), ("dst_in", "<i4"),
+                         ("len", "<i4"), ("dst_min", "<i4"), ("dst_max", "<i4"), ("reserved", "<i4")])  # cbh_vcover
+VCOVER_FRAME_DTYPE = np.dtype([("src_frame", "<i4"), ("dst_frame", "<i4"), ("distance", "<i4")])  # cbh_vcover_frame
+VCOVER_FIELDS = tuple(n for n in VCOVER_DTYPE.names if n != "reserved")
+
+
+@dataclass
+class VideoCoverage:
+    """Which frames of a source video a destination video contains: cbh_vcover, and with maps the nearest destination
+    frame and its distance for every considered source frame (``frames`` / ``dst_frames`` / ``distances``, None without)"""
+    thresh: int = 0
+    src_frames_total: int = 0
+    src_frames_covered: int = 0
+    gap_len: int = 0
+    gap_begin: int = 0
+    n_src: int = 0
+    n_dst: int = 0
+    n_covered: int = 0
+    n_low_detail: int = 0
+    near_percent: int = 0
+    src_in: int = -1
+    dst_in: int = -1
+    len: int = 0
+    dst_min: int = -1
+    dst_max: int = -1
+    frames: np.ndarray | None = None
+    dst_frames: np.ndarray | None = None
+    distances: np.ndarray | None = None
+
+    def contains(self, min_percent: float = 100) -> bool:
+        """the destination holds at least min_percent of the source, counted in frames of the source's own numbering"""
+        return self.src_frames_covered * 100 >= min_percent * self.src_frames_total
+
+    def percent(self) -> int:
+        return self.src_frames_covered * 100 // self.src_frames_total if self.src_frames_total else 0
+
+    def spans(self) -> np.ndarray:
+        """the span of every considered frame: up to the next one, and for the last what src_frames_total leaves"""
+        if self.frames is None:
+            raise ValueError("this VideoCoverage was made without maps")
+        f = self.frames.astype(np.int64)
+        if len(f) == 0:
+            return f
+        return np.append(np.diff(f), self.src_frames_total - (f[-1] - f[0]))
+
+    def ranges(self, covered: bool = True) -> list:
+        """the runs of consecutive considered frames that are covered (or are not) as (first_frame, length) in source
+        frame numbers; the length is the sum of the run's spans"""
+        spans = self.spans()
+        flag = (self.distances < self.thresh) == bool(covered)
+        out = []
+        i, n = 0, len(flag)
+        while i < n:
+            if not flag[i]:
+                i += 1
+                continue
+            j = i
+            while j < n and flag[j]:
+                j += 1
+            out.append((int(self.frames[i]), int(spans[i:j].sum())))
+            i = j
+        return out
+
+
+def _coverage_results(summaries, fmap, offs, thresh):
+    out = []
+    for k, s in enumerate(summaries):
+        c = VideoCoverage(int(thresh), **{n: int(s[n]) for n in VCOVER_FIELDS})
+        if fmap is not None:
+            m = fmap[int(offs[k]):int(offs[k + 1])]
+            c.frames, c.dst_frames, c.distances = m["src_frame"].copy(), m["dst_frame"].copy(), m["distance"].copy()
+        out.append(c)
+    return out
+
+
+def _coverage_call(call, n_pairs, maps, what):
+    """the capacity protocol of cbh_video_coverage: the sizes come back with CBH_E_OVERFLOW, the second call fills"""
+    summaries = np.zeros(max(1, n_pairs), VCOVER_DTYPE)
+    offs = np.zeros(n_pairs + 1, np.uint64)
+    if not maps:
+        check(call(summaries.ctypes.data, None, 0, offs.ctypes.data), what)
+        return summaries[:n_pairs], None, offs
+    fmap = np.zeros(1, VCOVER_FRAME_DTYPE)
+    rc = call(summaries.ctypes.data, fmap.ctypes.data, 0, offs.ctypes.data)
+    if rc == _lib.CBH_E_OVERFLOW:
+        fmap = np.zeros(int(offs[-1]), VCOVER_FRAME_DTYPE)
+        rc = call(summaries.ctypes.data, fmap.ctypes.data, len(fmap), offs.ctypes.data)
+    check(rc, what)
+    return summaries[:n_pairs], fmap, offs
+
+
+def video_coverage(videos, pairs, thresh: int, skip_frames: int = 0, maps: bool = True, device: int = 0):
+    """cbh_video_coverage for explicit lists: videos = [(frames, hashes), ...], pairs = [(source, destination), ...] as
+    indexes into it.  One VideoCoverage per pair.  No index is involved: a needle outside the database works as well."""
+    L = _lib.lib()
+    videos = list(videos)
+    f = np.concatenate([np.asarray(v[0], np.int32) for v in videos] or [np.zeros(0, np.int32)])
+    h = np.concatenate([np.asarray(v[1], np.uint64) for v in videos] or [np.zeros(0, np.uint64)])
+    o = np.zeros(len(videos) + 1, np.uint64)
+    np.cumsum([len(v[0]) for v in videos], out=o[1:])
+    p = np.ascontiguousarray(np.asarray(list(pairs), np.uint32).reshape(-1, 2))
+
+    def call(s, m, cap, offs):
+        return L.cbh_video_coverage(int(device), f.ctypes.data, h.ctypes.data, o.ctypes.data, len(videos), p.ctypes.data,
+                                    len(p), int(thresh), int(skip_frames), s, m, cap, offs)
+
+    return _coverage_results(*_coverage_call(call, len(p), maps, "video_coverage"), thresh)
+
+
 class DctVideoIndex:
     """Detect similar videos with full-frame dct hashes (src/dctvideoindex.h:66-70)."""
 
@@ -366,6 +478,21 @@ class DctVideoIndex:
             break
         return [self._matches(buf[int(out_offs[k]):int(out_offs[k + 1])], int(out_offs[k + 1] - out_offs[k]))
                 for k in range(len(needles))]
+
+    def coverage(self, pairs, p: VideoSearchParams, maps: bool = True):
+        """Which frames of one video another contains (cbh_vidx_coverage): pairs = [(source media id, destination media
+        id), ...] of videos the index holds, one VideoCoverage per pair, from one call -- every distinct video uploaded
+        once.  p.dctThresh and p.skipFrames as in findVideo; the map is exact, videoRadix does not apply.  maps=False
+        fetches the summaries only."""
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        s = np.ascontiguousarray([a for a, _ in pairs], np.uint32)
+        d = np.ascontiguousarray([b for _, b in pairs], np.uint32)
+
+        def call(sums, m, cap, offs):
+            return self._L.cbh_vidx_coverage(self._h, s.ctypes.data, d.ctypes.data, len(pairs), int(p.dctThresh),
+                                             int(p.skipFrames), sums, m, cap, offs)
+
+        return _coverage_results(*_coverage_call(call, len(pairs), maps, "vidx_coverage"), int(p.dctThresh))
 
     def entries(self, skip_frames: int) -> int:
         return int(self._L.cbh_vidx_entries(self._h, int(skip_frames)))

@@ -1060,6 +1060,63 @@ int cbh_vidx_find_videos_batch(cbh_vidx*, const int32_t* frames, const uint64_t*
                                const uint64_t* offsets, const uint32_t* needle_ids, size_t n_needles,
                                int thresh, int skip_frames, int min_frames_matched, int min_frames_near,
                                int filter_self, cbh_vmatch* out, size_t cap, uint64_t* out_offsets);
+/* ---- the coverage map of video pairs (cbird_amd/csrc/vcoverage.hip) -------------------------------------------------------
+ * Which frames of one video another contains: the list "needle frame -> closest frame" that findVideo (:399-657) builds
+ * per matched video and drops, kept, for a batch of ordered pairs (source video, destination video), with a summary per
+ * pair.  The reference's wish list names it (doc/cbird-devel.md, Search: "video coverage map to tell if one clip includes
+ * all frames of another clip").  A video is the (frames, hashes) list of its .vdx, frame numbers rising.
+ *   source frames considered  the stored frames findVideo searches (:431): frame f is dropped when f < skip_frames or
+ *                 f > last - skip_frames, unconditionally; last = the last stored frame number
+ *   destination entries       the frames insertHashes stores (:61-111): not a hash with fewer than 5 set or fewer than 5
+ *                 clear bits; the same trim, but only when skip_frames && last / 2 > skip_frames -- with the skip_frames
+ *                 of THIS call, whatever a handle's search structure was built with
+ *   nearest       for considered frame i the entry j with the smallest hamm64, the lowest j among equals: the unsigned
+ *                 minimum of distance << 24 | j.  Reported whether or not it is under thresh; a destination without
+ *                 entries gives frame -1 and distance 65
+ *   covered       distance < thresh, the comparison of every find of this library
+ *   span          of a stored source frame: the next stored frame number of the untrimmed list minus its own, 1 for the
+ *                 last one -- the indexer only drops a frame that is near every frame since the last stored one
+ *                 (src/media.cpp:998-1012), so a stored frame stands for that stretch */
+typedef struct cbh_vcover {
+  int64_t src_frames_total;   /* sum of the spans of the considered frames */
+  int64_t src_frames_covered; /* ... of the covered ones */
+  int64_t gap_len;            /* the longest run of consecutive uncovered considered frames, as the sum of its spans: the */
+  int32_t gap_begin;          /* run with the largest sum, the earliest among equals, and its first frame number; 0, 0   */
+                              /* without an uncovered frame                                                              */
+  int32_t n_src, n_dst;       /* considered frames, destination entries */
+  int32_t n_covered;
+  int32_t n_low_detail;       /* considered frames whose own hash fails the 5-bit rule (searched all the same, as findVideo does) */
+  int32_t near_percent;       /* findVideo's percentNear over the covered frames in frame order (frameMargin 15, lastFrame */
+                              /* starting at 0, integer division); 0 when nothing is covered                               */
+  int32_t src_in, dst_in, len; /* the MatchRange findVideo reports for the pair; -1, -1, 0 when nothing is covered */
+  int32_t dst_min, dst_max;   /* lowest and highest destination frame a covered frame matched; -1, -1 when none */
+  int32_t reserved;           /* 0 */
+} cbh_vcover;
+typedef struct cbh_vcover_frame {
+  int32_t src_frame, dst_frame, distance;
+} cbh_vcover_frame;
+/* Video v of the table is frames / hashes [video_offsets[v], video_offsets[v + 1]); pair k is source video pairs[2 k]
+ * against destination video pairs[2 k + 1], both indexes into the table (equal ones allowed).  Every video is uploaded
+ * once, however many pairs name it; no handle is involved, so a needle outside the database is served as well.
+ * summaries[n_pairs] is always written.  map == NULL: nothing else comes back from the device (map_offsets, if given,
+ * is still filled).  Otherwise the map of pair k, one entry per considered source frame in frame order, goes to
+ * map[map_offsets[k] .. map_offsets[k + 1]); the sizes are known before anything is launched, and when they exceed
+ * map_cap (in entries) the call returns CBH_E_OVERFLOW with map_offsets complete, map_offsets[n_pairs] the capacity
+ * needed, and nothing else written -- the protocol of cbh_vidx_find_frames_batch.
+ * n_pairs == 0 returns CBH_OK.  CBH_E_INVAL: a NULL required pointer, a map without map_offsets, a pair outside the table,
+ * falling offsets, skip_frames < 0.  CBH_E_UNSUPPORTED: a video of more than 2^24 stored frames.  CBH_E_NOMEM when an
+ * allocation is refused: nothing is kept.  The result does not depend on "vcover_chunk" / "vcover_tile" (cbh_set_tuning). */
+int cbh_video_coverage(int device, const int32_t* frames, const uint64_t* hashes, const uint64_t* video_offsets,
+                       size_t n_videos, const uint32_t* pairs, size_t n_pairs, int thresh, int skip_frames,
+                       cbh_vcover* summaries, cbh_vcover_frame* map, size_t map_cap, uint64_t* map_offsets);
+/* The same for videos the handle holds: pair k is the video of media id src_ids[k] against that of dst_ids[k].  The lists
+ * are gathered from the handle (they live on the host, on a plain and on a sharded handle alike), each distinct video
+ * once, and go through cbh_video_coverage on the handle's device; the search structure is neither needed nor built, and
+ * cbh_vidx_set_radix does not apply (the map is exact).  Of two videos that carry one media id the FIRST is used.  An id
+ * the handle does not hold: CBH_E_INVAL, nothing written. */
+int cbh_vidx_coverage(cbh_vidx*, const uint32_t* src_ids, const uint32_t* dst_ids, size_t n_pairs, int thresh,
+                      int skip_frames, cbh_vcover* summaries, cbh_vcover_frame* map, size_t map_cap,
+                      uint64_t* map_offsets);
 /* .vdx v2 (VideoIndex::save_v2/load_v2/verify_v2, src/videoindex.cpp:248-429).  encode returns the file
  * size (0 = invalid input: first frame must be 0, frames strictly increasing) and writes it when it fits;
  * decode = load_v2: the frame count or a negative CBH_E_* (bad header, short data); like the reference's loader it
@@ -1485,6 +1542,11 @@ int cbh_color_sort_similar(cbh_color*, const uint32_t* ids, const void* needle_d
  *                   and scanned again.  Values below 1 return CBH_E_INVAL and leave the knob as it was
  *   "cluster_timing" 1 = the cluster calls time their stages apart with events and wait for each
  *                   (tools/clusters_bench.py); read "cluster_table_us" / "cluster_hook_us" / "cluster_emit_us"
+ *   "vcover_chunk"  destination entries one workgroup of cbh_video_coverage takes: 0 (default) = 4096, halved down to 256
+ *                   while the batch has fewer than 2048 workgroups; 1 .. 2^24 = that many (tests: several chunks on short
+ *                   videos).  Other values return CBH_E_INVAL and leave the knob as it was
+ *   "vcover_tile"   source frames one workgroup of it takes: 256, 512, 1024 (default) or 2048, that is 1, 2, 4 or 8 per
+ *                   lane.  Other values return CBH_E_INVAL and leave the knob as it was
  *   "quality_chunk_mb" what one upload of cbh_quality_scores, and the working planes of one group of launches of
  *                   cbh_quality_scores_dev, may take, in MB (default 1024; at least one image each)
  *   "tmatch_chunk_mb" what one upload of cbh_template_match, and the patches of one group of candidates of
