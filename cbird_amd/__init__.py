@@ -7,7 +7,7 @@ missing.
 """
 from ._lib import CbhError, lib, require_device  # noqa: F401
 from .alignment import align_spatial, align_temporal, alignment_transform  # noqa: F401
-from .database import clusters, merge, multi_search, sort_similar, sort_similar_batch, video_coverage  # noqa: F401
+from .database import clusters, merge, multi_search, sort_similar, sort_similar_batch, video_coverage, video_segments  # noqa: F401
 from .demosaic import demosaic, edge_maps, grid_lines, grid_tiles  # noqa: F401
 from .difference import auto_contrast, difference_images  # noqa: F401
 from .hashing import dct_hash64, dct_hash64_batch, estimate_rigid, template_match, warp_affine  # noqa: F401
@@ -18,5 +18,5 @@ __all__ = ["CbhError", "lib", "require_device", "dct_hash64", "dct_hash64_batch"
            "DctFeaturesIndex", "quality_scores", "quality_planes", "estimate_rigid", "warp_affine", "template_match",
            "auto_contrast", "difference_images", "align_spatial", "align_temporal", "alignment_transform",
            "demosaic", "edge_maps", "grid_lines", "grid_tiles", "sort_similar", "sort_similar_batch", "clusters",
-           "merge", "multi_search", "video_coverage",
+           "merge", "multi_search", "video_coverage", "video_segments",
            "Match", "MatchRange", "Media", "SearchParams"]

@@ -104,6 +104,21 @@ class cbh_vcover_frame(C.Structure):
     _fields_ = [("src_frame", C.c_int32), ("dst_frame", C.c_int32), ("distance", C.c_int32)]
 
 
+class cbh_vsegment(C.Structure):
+    _fields_ = [("span_sum", C.c_int64), ("offset", C.c_int32), ("n_frames", C.c_int32), ("src_first", C.c_int32),
+                ("src_last", C.c_int32), ("dst_first", C.c_int32), ("dst_last", C.c_int32)]
+
+
+class cbh_vsegments(C.Structure):
+    _fields_ = [("src_frames_total", C.c_int64), ("src_frames_aligned", C.c_int64), ("n_src", C.c_int32),
+                ("n_dst", C.c_int32), ("n_segments", C.c_int32), ("n_aligned", C.c_int32), ("monotone", C.c_int32),
+                ("src_in", C.c_int32), ("dst_in", C.c_int32), ("len", C.c_int32)]
+
+
+class cbh_vsegment_frame(C.Structure):
+    _fields_ = [("src_frame", C.c_int32), ("dst_frame", C.c_int32), ("distance", C.c_int32), ("segment", C.c_int32)]
+
+
 class cbh_quality_detail(C.Structure):
     _fields_ = [("h_sum", C.c_uint64), ("v_sum", C.c_uint64), ("h_mean", C.c_float), ("v_mean", C.c_float),
                 ("h_long", C.c_int32), ("v_long", C.c_int32), ("num_edges", C.c_int32), ("qw", C.c_int32),
@@ -284,6 +299,10 @@ _SIGS = {
                                              C.c_int, _vp, _sz, _vp]),
     "cbh_video_coverage": (C.c_int, [C.c_int, _vp, _vp, _vp, _sz, _vp, _sz, C.c_int, C.c_int, _vp, _vp, _sz, _vp]),
     "cbh_vidx_coverage": (C.c_int, [_vp, _vp, _vp, _sz, C.c_int, C.c_int, _vp, _vp, _sz, _vp]),
+    "cbh_video_segments": (C.c_int, [C.c_int, _vp, _vp, _vp, _sz, _vp, _sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     _vp, _vp, _vp, _sz, _vp]),
+    "cbh_vidx_segments": (C.c_int, [_vp, _vp, _vp, _sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _sz,
+                                    _vp]),
     "cbh_vdx_encode": (_sz, [_vp, _vp, _sz, C.c_char_p, _vp, _sz]),
     "cbh_vdx_decode": (C.c_longlong, [_vp, _sz, _vp, _vp, _sz]),
     "cbh_vdx_version": (C.c_int, [_vp, _sz]),

@@ -565,6 +565,55 @@ class GpuDctVideoIndex : public DctVideoIndex {
     return true;
   }
 
+  /// One pair of gpuSegments: the summary (cbh_vsegments, include/cbird_hip.h), its segments in the order found and, with
+  /// maps, one entry per considered frame of the source -- the destination frame it chose, its distance and its segment.
+  struct Segments {
+    cbh_vsegments summary;
+    std::vector<cbh_vsegment> segments;
+    std::vector<cbh_vsegment_frame> frames;
+    /// segment 0 as the range VideoCompareWidget seeks both players by; an empty range without a segment
+    MatchRange matchRange() const { return MatchRange(summary.src_in, summary.dst_in, summary.len); }
+  };
+  /// At which frame-number offsets one video lies in another (cbh_vidx_segments): pairs as in gpuCoverage, (*out)[k]
+  /// answers pairs[k].  p.dctThresh and p.skipFrames as in find(); tol = frames of slack (findVideo's frameMargin),
+  /// minFrames < 1 means p.minFramesMatched.  maps = false fetches summaries and segments only.  false (the error
+  /// logged, *out empty): an id the index does not hold, or the call failed.
+  bool gpuSegments(const std::vector<std::pair<uint32_t, uint32_t>>& pairs, const SearchParams& p, std::vector<Segments>* out,
+                   int tol = 15, int minFrames = 0, int maxSegments = 4, bool maps = true) const {
+    out->clear();
+    const size_t n = pairs.size();
+    if (maxSegments < 1 || maxSegments > CBH_VSEGMENTS_MAX) return false;
+    const int least = minFrames < 1 ? p.minFramesMatched : minFrames;
+    std::vector<uint32_t> src, dst;
+    for (const auto& pr : pairs) src.push_back(pr.first), dst.push_back(pr.second);
+    std::vector<cbh_vsegments> sums(n ? n : 1);
+    std::vector<cbh_vsegment> segs(n ? n * size_t(maxSegments) : 1);
+    std::vector<uint64_t> offs(n + 1, 0);
+    std::vector<cbh_vsegment_frame> map(1);
+    if (maps) {  // the sizes are known before anything runs: a call without room reports them and does nothing else
+      cbh_clear_error();
+      const int rc = cbh_vidx_segments(_idx, src.data(), dst.data(), n, p.dctThresh, p.skipFrames, tol, least, maxSegments,
+                                       sums.data(), segs.data(), map.data(), 0, offs.data());
+      if (rc != CBH_OK && rc != CBH_E_OVERFLOW) {
+        qCritical("GpuDctVideoIndex::gpuSegments: %s (%s)", cbh_strerror(rc), cbh_last_error());
+        return false;
+      }
+      map.resize(size_t(offs[n]) ? size_t(offs[n]) : 1);
+    }
+    if (!CBH_QUERY(cbh_vidx_segments(_idx, src.data(), dst.data(), n, p.dctThresh, p.skipFrames, tol, least, maxSegments,
+                                     sums.data(), segs.data(), maps ? map.data() : nullptr, maps ? size_t(offs[n]) : 0,
+                                     offs.data())))
+      return false;
+    out->resize(n);
+    for (size_t k = 0; k < n; ++k) {
+      Segments& r = (*out)[k];
+      r.summary = sums[k];
+      r.segments.assign(segs.begin() + k * maxSegments, segs.begin() + k * maxSegments + sums[k].n_segments);
+      if (maps) r.frames.assign(map.begin() + offs[k], map.begin() + offs[k + 1]);
+    }
+    return true;
+  }
+
   cbh_vidx* handle() const { return _idx; }  // for statistics (cbh_combine_stats)
 
  private:

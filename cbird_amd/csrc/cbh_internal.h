@@ -374,6 +374,8 @@ int set_vcover_chunk(int v);  // vcoverage.hip "vcover_chunk": destination entri
 int get_vcover_chunk();
 int set_vcover_tile(int v);  // "vcover_tile": source frames per workgroup, 256 / 512 / 1024 (default) / 2048; else CBH_E_INVAL
 int get_vcover_tile();
+int set_vseg_budget_mb(int v);  // vsegments.hip "vseg_budget_mb": what the difference arrays of one group of pairs of cbh_video_segments may take, 1..4096 (default 256); else CBH_E_INVAL
+int get_vseg_budget_mb();
 
 // ---- sortsimilar_table.hip: the -sort-similar chain over tables of scores -------------------------------------------
 // A set of n items in ascending id order has its table as n rows of sort_table_row_stride(n) scores (16-byte rows, the

@@ -1368,6 +1368,7 @@ int cbh_set_tuning(const char* key, int value) {
   if (!strcmp(key, "cluster_timing")) return set_cluster_timing(value), CBH_OK;
   if (!strcmp(key, "vcover_chunk")) return set_vcover_chunk(value);
   if (!strcmp(key, "vcover_tile")) return set_vcover_tile(value);
+  if (!strcmp(key, "vseg_budget_mb")) return set_vseg_budget_mb(value);
   if (!strcmp(key, "scan256_kernels")) {  // a read-back, not a knob: writing 0 clears it, nothing else can be written
     if (value != 0) return CBH_E_INVAL;
     clear_scan256_kernels();
@@ -1410,6 +1411,7 @@ int cbh_get_tuning(const char* key, long long* value) {
   if (!strcmp(key, "cluster_emit_us")) return *value = get_cluster_stat(2), CBH_OK;
   if (!strcmp(key, "vcover_chunk")) return *value = get_vcover_chunk(), CBH_OK;
   if (!strcmp(key, "vcover_tile")) return *value = get_vcover_tile(), CBH_OK;
+  if (!strcmp(key, "vseg_budget_mb")) return *value = get_vseg_budget_mb(), CBH_OK;
   if (!strcmp(key, "quality_chunk_mb")) return *value = get_quality_chunk_mb(), CBH_OK;
   if (!strcmp(key, "quality_strip_rows")) return *value = get_quality_strip_rows(), CBH_OK;
   if (!strcmp(key, "tmatch_chunk_mb")) return *value = get_tmatch_chunk_mb(), CBH_OK;

@@ -30,6 +30,7 @@
 
 #include "cbh_index.h"
 #include "cbh_staging.h"
+#include "cbh_vviews.h"
 
 namespace cbh {
 namespace {
@@ -37,7 +38,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kStage = 256;                // destination hashes per LDS stage: one per thread
 constexpr uint32_t kNoKey = 0xffffffffu;   // no destination entry seen (a real key is at most 64 << 24 | 2^24 - 1)
-constexpr uint32_t kMostEntries = 1u << 24;  // the entry field of a key; MAX_FRAMES_PER_VIDEO of the reference
+constexpr uint32_t kMostEntries = kMostVideoEntries;  // the entry field of a key (cbh_vviews.h)
 constexpr int kFrameMargin = 15;           // findVideo's frameMargin (:593)
 
 std::atomic<int> g_vcover_chunk{0};     // "vcover_chunk": destination entries per block, 0 = by the size of the batch
@@ -231,11 +232,6 @@ void launch_map(unsigned blocks, hipStream_t s, const uint64_t* sh, const uint64
 
 size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 
-// the views of one video for this call's skip: which of its stored frames are searched, which are entries
-struct Views {
-  uint32_t s_begin = 0, s_n = 0, d_begin = 0, d_n = 0;
-};
-
 int video_coverage(int device, const int32_t* frames, const uint64_t* hashes, const uint64_t* voff, size_t n_videos,
                    const uint32_t* pairs, size_t n_pairs, int thresh, int skip, cbh_vcover* summaries,
                    cbh_vcover_frame* map, size_t map_cap, uint64_t* map_offsets) {
@@ -244,62 +240,24 @@ int video_coverage(int device, const int32_t* frames, const uint64_t* hashes, co
     if (pairs[2 * k] >= n_videos || pairs[2 * k + 1] >= n_videos) return vc_inval("video coverage: a pair names a video outside the table");
     as_src[pairs[2 * k]] = 1, as_dst[pairs[2 * k + 1]] = 1;
   }
-  std::vector<Views> views(n_videos);
-  std::vector<uint64_t> sh, dh;
-  std::vector<int32_t> sf, ss, df;
+  VideoViews vv;
   {
-    size_t most_s = 0, most_d = 0;  // room for every frame, so that the views below never move
-    for (size_t v = 0; v < n_videos; ++v) {
-      if (voff[v + 1] < voff[v]) return vc_inval("video coverage: video_offsets fall");
-      if (as_src[v]) most_s += (size_t)(voff[v + 1] - voff[v]);
-      if (as_dst[v]) most_d += (size_t)(voff[v + 1] - voff[v]);
-    }
-    sh.reserve(most_s), sf.reserve(most_s), ss.reserve(most_s), dh.reserve(most_d), df.reserve(most_d);
-  }
-  for (size_t v = 0; v < n_videos; ++v) {
-    const size_t b = (size_t)voff[v], n = (size_t)(voff[v + 1] - voff[v]);
-    if (n == 0 || !(as_src[v] | as_dst[v])) continue;
-    if (n > kMostEntries) {
-      set_last_error_text("video coverage: a video with more than 2^24 stored frames");
-      return CBH_E_UNSUPPORTED;
-    }
-    const long long last = frames[b + n - 1];
-    Views& w = views[v];
-    if (as_src[v]) {  // findVideo's needle frames (:431): the trim is unconditional
-      w.s_begin = (uint32_t)sh.size();
-      for (size_t i = 0; i < n; ++i) {
-        const long long f = frames[b + i];
-        if (f < skip || f > last - skip) continue;
-        sh.push_back(hashes[b + i]);
-        sf.push_back((int32_t)f);
-        ss.push_back(i + 1 < n ? (int32_t)((long long)frames[b + i + 1] - f) : 1);
-      }
-      w.s_n = (uint32_t)(sh.size() - w.s_begin);
-    }
-    if (as_dst[v]) {  // insertHashes (:61-111): the detail rule, and the trim only on a video long enough for it
-      w.d_begin = (uint32_t)dh.size();
-      const bool trim = skip && last / 2 > skip;
-      for (size_t i = 0; i < n; ++i) {
-        const int pc = __builtin_popcountll(hashes[b + i]);
-        if (pc < 5 || 64 - pc < 5) continue;
-        const long long f = frames[b + i];
-        if (trim && (f < skip || f > last - skip)) continue;
-        dh.push_back(hashes[b + i]);
-        df.push_back((int32_t)f);
-      }
-      w.d_n = (uint32_t)(dh.size() - w.d_begin);
-    }
-    if (sh.size() >= 0xffffffffull || dh.size() >= 0xffffffffull) {
-      set_last_error_text("video coverage: the videos of one call hold 2^32 frames or more");
-      return CBH_E_UNSUPPORTED;
+    std::string why;
+    const int rc = build_video_views("video coverage", frames, hashes, voff, n_videos, as_src, as_dst, skip, false, &vv, &why);
+    if (rc != CBH_OK) {
+      set_last_error_text(why.c_str());
+      return rc;
     }
   }
+  const std::vector<VideoView>& views = vv.views;
+  const std::vector<uint64_t>&sh = vv.sh, &dh = vv.dh;
+  const std::vector<int32_t>&sf = vv.sf, &ss = vv.ss, &df = vv.df;
 
   // the map's layout is known before anything runs: one entry per considered source frame
   std::vector<VcPair> ptab(n_pairs);
   uint64_t need = 0;
   for (size_t k = 0; k < n_pairs; ++k) {
-    const Views &a = views[pairs[2 * k]], &b = views[pairs[2 * k + 1]];
+    const VideoView &a = views[pairs[2 * k]], &b = views[pairs[2 * k + 1]];
     ptab[k] = VcPair{a.s_begin, a.s_n, b.d_begin, b.d_n, need};
     if (map_offsets) map_offsets[k] = need;
     need += a.s_n;

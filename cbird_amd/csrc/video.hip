@@ -552,44 +552,69 @@ int cbh_vidx_find_videos_batch(cbh_vidx* v, const int32_t* frames, const uint64_
   return pos > cap ? CBH_E_OVERFLOW : CBH_OK;
 }
 
-/* The coverage maps (vcoverage.hip) of videos the handle holds: the lists of the named media, each distinct video once,
- * handed to cbh_video_coverage.  Host code over v->videos, the same on a plain and on a sharded handle; the search
- * structure is not touched.  Of two videos with one media id the first is taken, as cbh_vidx_slice does. */
-int cbh_vidx_coverage(cbh_vidx* v, const uint32_t* src_ids, const uint32_t* dst_ids, size_t n_pairs, int thresh,
-                      int skip_frames, cbh_vcover* summaries, cbh_vcover_frame* map, size_t map_cap,
-                      uint64_t* map_offsets) {
-  if (!v || (n_pairs && (!src_ids || !dst_ids))) return CBH_E_INVAL;
+/* The lists of the named media for cbh_video_coverage / cbh_video_segments: each distinct video once, in a table of this
+ * call's own.  Host code over v->videos, the same on a plain and on a sharded handle; the search structure is not
+ * touched.  Of two videos with one media id the first is taken, as cbh_vidx_slice does. */
+namespace {
+struct PairTable {
   std::vector<int32_t> frames;
-  std::vector<uint64_t> hashes, offsets(1, 0);
+  std::vector<uint64_t> hashes, offsets;
   std::vector<uint32_t> pairs;
+};
+int gather_pairs(cbh_vidx* v, const uint32_t* src_ids, const uint32_t* dst_ids, size_t n_pairs, const char* what,
+                 PairTable* t) {
+  t->offsets.assign(1, 0);
   try {
     std::lock_guard<std::mutex> lk(v->build_mu);
     std::unordered_map<uint32_t, size_t> at;  // media id -> its first video
     for (size_t i = 0; i < v->videos.size(); ++i) at.emplace(v->videos[i].media_id, i);
     std::unordered_map<size_t, uint32_t> row;  // video -> its row of this call's table
-    pairs.reserve(2 * n_pairs);
+    t->pairs.reserve(2 * n_pairs);
     for (size_t k = 0; k < n_pairs; ++k)
       for (uint32_t id : {src_ids[k], dst_ids[k]}) {
         auto it = at.find(id);
         if (it == at.end()) {
-          set_last_error_text("cbh_vidx_coverage: a media id the index does not hold");
+          cbh::set_last_error_text((std::string(what) + ": a media id the index does not hold").c_str());
           return CBH_E_INVAL;
         }
         auto put = row.emplace(it->second, (uint32_t)row.size());
         if (put.second) {
           const cbh_vidx::Video& vid = v->videos[it->second];
-          frames.insert(frames.end(), vid.frames.begin(), vid.frames.end());
-          hashes.insert(hashes.end(), vid.hashes.begin(), vid.hashes.end());
-          offsets.push_back(hashes.size());
+          t->frames.insert(t->frames.end(), vid.frames.begin(), vid.frames.end());
+          t->hashes.insert(t->hashes.end(), vid.hashes.begin(), vid.hashes.end());
+          t->offsets.push_back(t->hashes.size());
         }
-        pairs.push_back(put.first->second);
+        t->pairs.push_back(put.first->second);
       }
   } catch (const std::bad_alloc&) {
-    set_last_error_text("cbh_vidx_coverage: host allocation failed");
+    cbh::set_last_error_text((std::string(what) + ": host allocation failed").c_str());
     return CBH_E_NOMEM;
   }
-  return cbh_video_coverage(v->device, frames.data(), hashes.data(), offsets.data(), offsets.size() - 1, pairs.data(),
-                            n_pairs, thresh, skip_frames, summaries, map, map_cap, map_offsets);
+  return CBH_OK;
+}
+}  // namespace
+
+int cbh_vidx_coverage(cbh_vidx* v, const uint32_t* src_ids, const uint32_t* dst_ids, size_t n_pairs, int thresh,
+                      int skip_frames, cbh_vcover* summaries, cbh_vcover_frame* map, size_t map_cap,
+                      uint64_t* map_offsets) {
+  if (!v || (n_pairs && (!src_ids || !dst_ids))) return CBH_E_INVAL;
+  PairTable t;
+  const int rc = gather_pairs(v, src_ids, dst_ids, n_pairs, "cbh_vidx_coverage", &t);
+  if (rc != CBH_OK) return rc;
+  return cbh_video_coverage(v->device, t.frames.data(), t.hashes.data(), t.offsets.data(), t.offsets.size() - 1,
+                            t.pairs.data(), n_pairs, thresh, skip_frames, summaries, map, map_cap, map_offsets);
+}
+
+int cbh_vidx_segments(cbh_vidx* v, const uint32_t* src_ids, const uint32_t* dst_ids, size_t n_pairs, int thresh,
+                      int skip_frames, int tol, int min_frames, int max_segments, cbh_vsegments* summaries,
+                      cbh_vsegment* segments, cbh_vsegment_frame* map, size_t map_cap, uint64_t* map_offsets) {
+  if (!v || (n_pairs && (!src_ids || !dst_ids))) return CBH_E_INVAL;
+  PairTable t;
+  const int rc = gather_pairs(v, src_ids, dst_ids, n_pairs, "cbh_vidx_segments", &t);
+  if (rc != CBH_OK) return rc;
+  return cbh_video_segments(v->device, t.frames.data(), t.hashes.data(), t.offsets.data(), t.offsets.size() - 1,
+                            t.pairs.data(), n_pairs, thresh, skip_frames, tol, min_frames, max_segments, summaries, segments,
+                            map, map_cap, map_offsets);
 }
 
 /* ---- .vdx v2 codec (host) ------------------------------------------------------------------- */

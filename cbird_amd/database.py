@@ -546,6 +546,32 @@ def video_coverage(index, groups, params: SearchParams):
     return groups
 
 
+# ---- video segments: at which offsets one clip lies in another (no reference counterpart; include/cbird_hip.h) -------
+def video_segments(index, groups, params: SearchParams, tol: int = 15, min_frames=None, max_segments: int = 4):
+    """For result groups [needle, match1, ...] as similar() returns them for AlgoVideo: needle -> match for every member,
+    all in ONE DctVideoIndex.segments call (no maps).  Sets on each match
+        segments    the VideoSegments of the needle inside the match
+        aligned     the percent of the needle's frames the match holds at a consistent position (VideoSegments.percent)
+    and touches no other attribute -- the match's own range stays findVideo's; segments.match_range() is the precise one.
+    A member that is no video (an image needle of findFrame) is skipped.  Returns the groups."""
+    if params.algo != SearchParams.AlgoVideo or not hasattr(index, "segments"):
+        raise ValueError("video_segments: only AlgoVideo on a DctVideoIndex")
+    pairs, where = [], []
+    for g in groups:
+        if not g or getattr(g[0], "videoIndex", None) is None:
+            continue
+        for m in g[1:]:
+            if getattr(m, "videoIndex", None) is None:
+                continue
+            where.append(m)
+            pairs.append((g[0].id, m.id))
+    if pairs:
+        res = index.segments(pairs, params, tol=tol, min_frames=min_frames, max_segments=max_segments, maps=False)
+        for m, r in zip(where, res):
+            m.segments, m.aligned = r, r.percent()
+    return groups
+
+
 # ---- -sort-similar (src/main.cpp:1523-1580) ---------------------------------------------------------------------------
 SORT_SIMILAR_LOOK_BEHIND = 5  # `const int lookBehind = 5` (:1530)
 

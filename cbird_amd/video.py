@@ -281,6 +281,114 @@ def video_coverage(videos, pairs, thresh: int, skip_frames: int = 0, maps: bool 
     return _coverage_results(*_coverage_call(call, len(p), maps, "video_coverage"), thresh)
 
 
+# ---- offsets and segments (cbird_amd/csrc/vsegments.hip; the rules are in include/cbird_hip.h) ------------------------
+VSEGMENT_DTYPE = np.dtype([("span_sum", "<i8"), ("offset", "<i4"), ("n_frames", "<i4"), ("src_first", "<i4"),
+                           ("src_last", "<i4"), ("dst_first", "<i4"), ("dst_last", "<i4")])  # cbh_vsegment
+VSEGMENTS_DTYPE = np.dtype([("src_frames_total", "<i8"), ("src_frames_aligned", "<i8"), ("n_src", "<i4"), ("n_dst", "<i4"),
+                            ("n_segments", "<i4"), ("n_aligned", "<i4"), ("monotone", "<i4"), ("src_in", "<i4"),
+                            ("dst_in", "<i4"), ("len", "<i4")])  # cbh_vsegments
+VSEGMENT_FRAME_DTYPE = np.dtype([("src_frame", "<i4"), ("dst_frame", "<i4"), ("distance", "<i4"),
+                                 ("segment", "<i4")])  # cbh_vsegment_frame
+VSEGMENTS_MAX = 16  # CBH_VSEGMENTS_MAX
+
+
+@dataclass
+class VideoSegment:
+    """One stretch of the source that lies in the destination at one frame-number offset (cbh_vsegment)"""
+    span_sum: int = 0
+    offset: int = 0
+    n_frames: int = 0
+    src_first: int = 0
+    src_last: int = 0
+    dst_first: int = 0
+    dst_last: int = 0
+
+
+@dataclass
+class VideoSegments:
+    """Where a source video lies in a destination video: cbh_vsegments, the segments in the order found (the best
+    supported first), and with maps the chosen destination frame, its distance and the segment (-1, 65, -1 for a frame in
+    none) of every considered source frame (``frames`` / ``dst_frames`` / ``distances`` / ``segment_of``, None without)"""
+    src_frames_total: int = 0
+    src_frames_aligned: int = 0
+    n_src: int = 0
+    n_dst: int = 0
+    n_segments: int = 0
+    n_aligned: int = 0
+    monotone: int = 1
+    src_in: int = -1
+    dst_in: int = -1
+    len: int = 0
+    segments: list = field(default_factory=list)
+    frames: np.ndarray | None = None
+    dst_frames: np.ndarray | None = None
+    distances: np.ndarray | None = None
+    segment_of: np.ndarray | None = None
+
+    def match_range(self):
+        """segment 0's (src_in, dst_in, len) -- what seeks two players to the same picture; (-1, -1, 0) without one"""
+        return self.src_in, self.dst_in, self.len
+
+    def cut_list(self) -> list:
+        """the segments in source order: where each stretch of the source starts, and by its offset where it went"""
+        return sorted(self.segments, key=lambda g: g.src_first)
+
+    def percent(self) -> int:
+        """whole percent of the source's frames that lie in the destination at a consistent position"""
+        return self.src_frames_aligned * 100 // self.src_frames_total if self.src_frames_total else 0
+
+
+def _segments_results(summaries, segs, fmap, offs, max_segments):
+    out = []
+    for k, s in enumerate(summaries):
+        r = VideoSegments(**{n: int(s[n]) for n in VSEGMENTS_DTYPE.names})
+        r.segments = [VideoSegment(**{n: int(g[n]) for n in VSEGMENT_DTYPE.names})
+                      for g in segs[k * max_segments:k * max_segments + r.n_segments]]
+        if fmap is not None:
+            m = fmap[int(offs[k]):int(offs[k + 1])]
+            r.frames, r.dst_frames = m["src_frame"].copy(), m["dst_frame"].copy()
+            r.distances, r.segment_of = m["distance"].copy(), m["segment"].copy()
+        out.append(r)
+    return out
+
+
+def _segments_call(call, n_pairs, max_segments, maps, what):
+    """the capacity protocol of cbh_video_coverage with one more array"""
+    summaries = np.zeros(max(1, n_pairs), VSEGMENTS_DTYPE)
+    segs = np.zeros(max(1, n_pairs * max_segments), VSEGMENT_DTYPE)
+    offs = np.zeros(n_pairs + 1, np.uint64)
+    if not maps:
+        check(call(summaries.ctypes.data, segs.ctypes.data, None, 0, offs.ctypes.data), what)
+        return summaries[:n_pairs], segs, None, offs
+    fmap = np.zeros(1, VSEGMENT_FRAME_DTYPE)
+    rc = call(summaries.ctypes.data, segs.ctypes.data, fmap.ctypes.data, 0, offs.ctypes.data)
+    if rc == _lib.CBH_E_OVERFLOW:
+        fmap = np.zeros(int(offs[-1]), VSEGMENT_FRAME_DTYPE)
+        rc = call(summaries.ctypes.data, segs.ctypes.data, fmap.ctypes.data, len(fmap), offs.ctypes.data)
+    check(rc, what)
+    return summaries[:n_pairs], segs, fmap, offs
+
+
+def video_segments(videos, pairs, thresh: int, skip_frames: int = 0, tol: int = 15, min_frames: int = 1,
+                   max_segments: int = 4, maps: bool = True, device: int = 0):
+    """cbh_video_segments for explicit lists: videos = [(frames, hashes), ...], pairs = [(source, destination), ...] as
+    indexes into it.  One VideoSegments per pair."""
+    L = _lib.lib()
+    videos = list(videos)
+    f = np.concatenate([np.asarray(v[0], np.int32) for v in videos] or [np.zeros(0, np.int32)])
+    h = np.concatenate([np.asarray(v[1], np.uint64) for v in videos] or [np.zeros(0, np.uint64)])
+    o = np.zeros(len(videos) + 1, np.uint64)
+    np.cumsum([len(v[0]) for v in videos], out=o[1:])
+    p = np.ascontiguousarray(np.asarray(list(pairs), np.uint32).reshape(-1, 2))
+
+    def call(s, g, m, cap, offs):
+        return L.cbh_video_segments(int(device), f.ctypes.data, h.ctypes.data, o.ctypes.data, len(videos), p.ctypes.data,
+                                    len(p), int(thresh), int(skip_frames), int(tol), int(min_frames), int(max_segments),
+                                    s, g, m, cap, offs)
+
+    return _segments_results(*_segments_call(call, len(p), int(max_segments), maps, "video_segments"), int(max_segments))
+
+
 class DctVideoIndex:
     """Detect similar videos with full-frame dct hashes (src/dctvideoindex.h:66-70)."""
 
@@ -493,6 +601,23 @@ class DctVideoIndex:
                                              int(p.skipFrames), sums, m, cap, offs)
 
         return _coverage_results(*_coverage_call(call, len(pairs), maps, "vidx_coverage"), int(p.dctThresh))
+
+    def segments(self, pairs, p: VideoSearchParams, tol: int = 15, min_frames: int | None = None, max_segments: int = 4,
+                 maps: bool = True):
+        """At which frame-number offsets one video lies in another (cbh_vidx_segments): pairs as in coverage(), one
+        VideoSegments per pair, from one call.  p.dctThresh and p.skipFrames as in findVideo; tol is the slack in frames
+        (findVideo's frameMargin), min_frames=None means p.minFramesMatched."""
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        s = np.ascontiguousarray([a for a, _ in pairs], np.uint32)
+        d = np.ascontiguousarray([b for _, b in pairs], np.uint32)
+        least = int(p.minFramesMatched if min_frames is None else min_frames)
+
+        def call(sums, g, m, cap, offs):
+            return self._L.cbh_vidx_segments(self._h, s.ctypes.data, d.ctypes.data, len(pairs), int(p.dctThresh),
+                                             int(p.skipFrames), int(tol), least, int(max_segments), sums, g, m, cap, offs)
+
+        return _segments_results(*_segments_call(call, len(pairs), int(max_segments), maps, "vidx_segments"),
+                                 int(max_segments))
 
     def entries(self, skip_frames: int) -> int:
         return int(self._L.cbh_vidx_entries(self._h, int(skip_frames)))

@@ -1117,6 +1117,61 @@ int cbh_video_coverage(int device, const int32_t* frames, const uint64_t* hashes
 int cbh_vidx_coverage(cbh_vidx*, const uint32_t* src_ids, const uint32_t* dst_ids, size_t n_pairs, int thresh,
                       int skip_frames, cbh_vcover* summaries, cbh_vcover_frame* map, size_t map_cap,
                       uint64_t* map_offsets);
+/* ---- where one video lies inside another: offsets and segments (cbird_amd/csrc/vsegments.hip) ------------------------------
+ * The coverage map gives a frame its nearest frame ANYWHERE in the destination; a black frame or a static scene matches
+ * wherever there is one.  This finds, for an ordered pair (source, destination), the frame-number offsets at which the
+ * source lies in the destination and returns one segment per offset (doc/cbird-devel.md, Search: "refine video search
+ * matches using neighboring hashes").  Considered source frames fs_i / hs_i, destination entries fd_j / hd_j, span and the
+ * predicate hamm64 < thresh are cbh_video_coverage's, unchanged.  A match is (i, j) with hamm64(hs_i, hd_j) < thresh; its
+ * offset is fd_j - fs_i.  Integers only:
+ *   1 support     for a set L of live source frames, support(o) = the number of i in L with a match whose offset lies
+ *                 within tol of o; a frame counts once per offset however many entries it matches.  o ranges over
+ *                 [min fd - max fs - tol, max fd - min fs + tol]
+ *   2 offset      m = the maximum support; of the maximal runs [lo, hi] of consecutive offsets with support m the one
+ *                 whose centre c = floor((lo + hi) / 2) (toward minus infinity) has the smallest |c|, the negative c of
+ *                 two; the round's offset is that c -- the centre of the plateau, not its edge
+ *   3 members     every live i with a match within tol of c joins the segment and leaves L; its destination frame is the
+ *                 match with the smallest |fd_j - fs_i - c|, then the smallest distance, then the lowest j
+ *   4 rounds      L starts as every considered frame; 1 - 3 repeat until m < min_frames, max_segments segments exist or L
+ *                 has no match left.  Segments come in the order found; their n_frames (= m) never rise
+ *   5 empty       no considered frame, no entry or no match: no segment
+ * The result does not depend on launch shapes, on "vseg_budget_mb" or on any order of accumulation. */
+#define CBH_VSEGMENTS_MAX 16
+typedef struct cbh_vsegment {
+  int64_t span_sum;            /* sum of the members' spans */
+  int32_t offset, n_frames;    /* rule 2, rule 3 */
+  int32_t src_first, src_last; /* frame numbers of the first and last member */
+  int32_t dst_first, dst_last; /* the destination frames those two members chose */
+} cbh_vsegment;
+typedef struct cbh_vsegments {
+  int64_t src_frames_total, src_frames_aligned; /* span sums: considered / members of any segment */
+  int32_t n_src, n_dst, n_segments, n_aligned;
+  int32_t monotone;       /* 1: sorted by src_first (the earlier found of two equals first), src_first + offset never */
+                          /* falls -- no scenes swapped; 0 or 1 segments: 1                                           */
+  int32_t src_in, dst_in, len;  /* of segment 0: src_first, dst_first, dst_last - dst_first + 1; -1, -1, 0 without */
+} cbh_vsegments;
+typedef struct cbh_vsegment_frame {
+  int32_t src_frame, dst_frame, distance, segment;
+} cbh_vsegment_frame;
+/* The video table, the pairs, the map, map_cap / map_offsets and the CBH_E_OVERFLOW protocol are cbh_video_coverage's.
+ * summaries[n_pairs] and segments[n_pairs * max_segments] are always written: the segments of pair k from
+ * segments[k * max_segments] on, unused records zero.  The map has one entry per considered source frame in frame order;
+ * a frame in no segment holds dst_frame -1, distance 65, segment -1.  tol >= 0 frames of slack (stored frames are sparse:
+ * two encodes of one clip rarely store the same frame numbers; findVideo's frameMargin is 15), min_frames >= 1,
+ * max_segments 1 .. CBH_VSEGMENTS_MAX.
+ * Errors: those of cbh_video_coverage; CBH_E_INVAL also for tol < 0, min_frames < 1, max_segments outside 1..16, and for a
+ * named video whose frame numbers fall -- this is how no input reaches an index outside an array: the first and last
+ * frame of a view are its extremes.  CBH_E_UNSUPPORTED also for an offset outside 32 bits.  Every pair has an array of one
+ * word per offset of its domain; pairs are processed in groups whose arrays fit "vseg_budget_mb" together, and a pair
+ * whose array alone exceeds it (a huge tol) returns CBH_E_NOMEM with nothing kept. */
+int cbh_video_segments(int device, const int32_t* frames, const uint64_t* hashes, const uint64_t* video_offsets,
+                       size_t n_videos, const uint32_t* pairs, size_t n_pairs, int thresh, int skip_frames, int tol,
+                       int min_frames, int max_segments, cbh_vsegments* summaries, cbh_vsegment* segments,
+                       cbh_vsegment_frame* map, size_t map_cap, uint64_t* map_offsets);
+/* The same for videos the handle holds, plain or sharded, gathered as cbh_vidx_coverage gathers them. */
+int cbh_vidx_segments(cbh_vidx*, const uint32_t* src_ids, const uint32_t* dst_ids, size_t n_pairs, int thresh,
+                      int skip_frames, int tol, int min_frames, int max_segments, cbh_vsegments* summaries,
+                      cbh_vsegment* segments, cbh_vsegment_frame* map, size_t map_cap, uint64_t* map_offsets);
 /* .vdx v2 (VideoIndex::save_v2/load_v2/verify_v2, src/videoindex.cpp:248-429).  encode returns the file
  * size (0 = invalid input: first frame must be 0, frames strictly increasing) and writes it when it fits;
  * decode = load_v2: the frame count or a negative CBH_E_* (bad header, short data); like the reference's loader it
@@ -1547,6 +1602,8 @@ int cbh_color_sort_similar(cbh_color*, const uint32_t* ids, const void* needle_d
  *                   videos).  Other values return CBH_E_INVAL and leave the knob as it was
  *   "vcover_tile"   source frames one workgroup of it takes: 256, 512, 1024 (default) or 2048, that is 1, 2, 4 or 8 per
  *                   lane.  Other values return CBH_E_INVAL and leave the knob as it was
+ *   "vseg_budget_mb" what the difference arrays of one group of pairs of cbh_video_segments may take together, in MB:
+ *                   1 .. 4096 (default 256).  Other values return CBH_E_INVAL and leave the knob as it was
  *   "quality_chunk_mb" what one upload of cbh_quality_scores, and the working planes of one group of launches of
  *                   cbh_quality_scores_dev, may take, in MB (default 1024; at least one image each)
  *   "tmatch_chunk_mb" what one upload of cbh_template_match, and the patches of one group of candidates of
