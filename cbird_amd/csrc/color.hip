@@ -598,10 +598,10 @@ int cbh_color_add(cbh_color* c, const uint32_t* ids, const void* descs, size_t n
   if (!g.ok) return CBH_E_NODEVICE;
   std::lock_guard<std::mutex> lk(c->mu);
   const size_t first = c->n;
+  int rc = grow_index(c, first + n);
+  if (rc) return rc;  // (before the host copies grow: a refused add leaves nothing behind for the next one to upload)
   c->host_desc.insert(c->host_desc.end(), (const uint8_t*)descs, (const uint8_t*)descs + n * kDescBytes);
   c->host_ids.insert(c->host_ids.end(), ids, ids + n);
-  int rc = grow_index(c, first + n);
-  if (rc) return rc;
   c->n = first + n;
   return upload(c, first, n);
 }
